@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the refpoint -> epipolar match -> triangulate hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--workload auto|c2|c3|c4|c3real]
+  python bench.py --gpus N --steps K --warmup W [--workload auto|c2|c3|c4|c3real] [--full] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path (eg3d_match_resident: K1..K4) over one batch of synthetic
 seeds whose scene and tracks are already resident in HBM.
@@ -30,6 +30,11 @@ algorithmic bytes of SURVEY 8(d) / that kernel's HIP-event time with ONE step on
 roofline.in_flight); traffic = PMC bytes from the committed rocprofv3 passes of this workload, with
 provenance. `roofline_valu` = the same kernel against the vector-ALU issue peak (what actually
 bounds the path). `cpu_baseline` = the CPU oracle, 1 thread, on this box (N=1 only).
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, stage_ms, the
+roofline from the in-flight kernel times); everything else above — one step at a time, end to end, time
+to solution, cpu_baseline + parity, scaling_base, c5 — runs only with --full. --dump-outputs DIR writes
+the cloud of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -59,6 +64,8 @@ DOM_NAME, DOM_KEY = "k3b_expand", "ms_expand"  # the dominant kernel on every wo
 WORKLOADS = {"c2": 2, "c3": 3, "c4": 4}
 CLOUD_BYTES_PER_POINT = 12 + 8 + 16    # X, obs_off, key
 CLOUD_BYTES_PER_OBS = 4 + 4 + 4 + 8    # view, polyline, segment, xy
+DUMP_BUDGET = 64 << 20                 # --dump-outputs: bytes written at most
+DUMP_SEED = 20240611                   # ... and the seed of the point sample when the cloud is larger
 
 
 class _RealEdges:
@@ -458,6 +465,45 @@ def _rooflines(wkey, bytes_alg, excl_ms, inflight_ms):
     return roof, valu
 
 
+def _dump_outputs(ctx, out_dir):
+    """--dump-outputs: the edge-point cloud of ctx's last call (what eg3d_match_resident hands a caller) as .npy files,
+    integer fields widened to float64 (exact). A cloud larger than DUMP_BUDGET bytes is cut to a sample of its points,
+    drawn with a fixed seed from the point and observation counts alone, so that two builds with the same cloud dump
+    the same points."""
+    import numpy as np
+    d = ctx.fetch_device_output()
+    n, m = d["n_points"], d["n_obs"]
+    off = d["obs_off"].astype(np.int64)
+    per_point = 12 + 32 + 8 + 8          # X f32, key 4 x f64, obs_count f64, point_index f64
+    per_obs = 3 * 8 + 8                  # view / polyline / segment f64, xy 2 x f32
+    idx = np.arange(n, dtype=np.int64)
+    if n * per_point + m * per_obs > DUMP_BUDGET:
+        k = int(DUMP_BUDGET / (per_point + per_obs * (m / n)) * 0.9)
+        rng = np.random.default_rng(DUMP_SEED)
+        while True:
+            idx = np.sort(rng.choice(n, size=k, replace=False))
+            cnt = off[idx + 1] - off[idx]
+            if k * per_point + int(cnt.sum()) * per_obs <= DUMP_BUDGET:
+                break
+            k //= 2
+            rng = np.random.default_rng(DUMP_SEED)
+    cnt = off[idx + 1] - off[idx]
+    obs = np.arange(int(cnt.sum()), dtype=np.int64) + np.repeat(off[idx] - (np.cumsum(cnt) - cnt), cnt)
+    arrays = {"X": d["X"][idx].astype(np.float32), "key": d["key"][idx].astype(np.float64),
+              "obs_count": cnt.astype(np.float64), "point_index": idx.astype(np.float64),
+              "obs_view": d["obs_view"][obs].astype(np.float64), "obs_polyline": d["obs_pl"][obs].astype(np.float64),
+              "obs_segment": d["obs_seg"][obs].astype(np.float64), "obs_xy": d["obs_xy"][obs].astype(np.float32),
+              "totals": np.array([n, m], np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in arrays), "points_total": n, "obs_total": m,
+            "points_written": int(len(idx)), "sampled": bool(len(idx) < n),
+            "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "what": "the cloud of the last timed step on rank 0: X, key (4 ids), obs_count and point_index per point, "
+                    "obs_view / obs_polyline / obs_segment / obs_xy per observation, totals = [points, observations]"}
+
+
 def _c5_subline(device):
     """BASELINE configs[4]: gaussNewtonFiltering over 1 M synthetic points (k5_gn_filter), kernel HIP-event time,
     bit-exact parity of ALL points against the oracle, the oracle timed beside it on a sample."""
@@ -542,7 +588,19 @@ def main():
     ap.add_argument("--cpu-runs", type=int, default=0, help="timed CPU baseline runs after the warm-up (default 5, median; ~5 s each on the C3' sample)")
     ap.add_argument("--cpu-seeds", type=int, default=0,
                     help="bound the CPU baseline to the first K seeds of the first step's batch (default: all; c4: 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: one step at a time, end to end, time to solution, "
+                         "the CPU baseline with its parity check, and the C4 and C5 sub-lines (each can still be dropped with "
+                         "the --no-* options above); without it a run only sets up, warms up, times the steps and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the cloud of the last timed step (rank 0) as DIR/<name>.npy "
+                         "(float32 / float64, at most %d MB: a fixed, seeded sample of the points when larger)" % (DUMP_BUDGET >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py --steps must be >= 1")
+    extras = args.full and not args.no_extras
+    cpu_baseline = args.full and not args.no_cpu_baseline
+    sublines = extras and not args.no_sublines
 
     # stdout carries exactly ONE line (the JSON): libraries that print to file descriptor 1 (RCCL's
     # "Librccl path : ..." banner, for one) are sent to stderr; the line itself goes to the saved descriptor
@@ -617,6 +675,10 @@ def main():
     leg = Leg(env, wl, args.path, args.seeds, args.batch_seeds, args.inflight)
     sets, synth, inflight = leg.sets, leg.synth, leg.inflight
     elapsed, results = leg.timed(args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on context (steps - 1) % inflight, and nothing has run on it since
+        dumped = _dump_outputs(leg.workers[(args.steps - 1) % len(leg.workers)].ctx, args.dump_outputs)
     stage_ms = {k: [r["times"][k] for r, _ in results] for _, k in STAGES}
     points_done = sum(tot for _, tot in results)
     last, _ = results[-1]
@@ -624,11 +686,11 @@ def main():
     gstats = leg.gather_stats()
     # untimed side measurements reported beside the value
     single = e2e = tts = setup = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         single, e2e = leg.serial_and_e2e(args.steps)
         if sets is None:
             setup = leg.setup_and_time_to_solution()
-    if wl == "c4" and not args.no_extras and sets is None:
+    if wl == "c4" and extras and sets is None:
         tts = leg.time_to_solution()   # every rank takes part (collectives)
 
     if rank == 0:
@@ -707,7 +769,9 @@ def main():
             line["setup_ms"] = {"eg3d_create": setup["create_ms"], "eg3d_create_again": setup["create_again_ms"],
                                 "eg3d_upload_seeds": setup["upload_seeds_ms"], "first_context_of_the_process": leg.setup_ms}
             line["time_to_solution_one_shot"] = setup
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            line["dump_outputs"] = dumped
+        if world == 1 and cpu_baseline:
             from oracle import binding as ob   # cpu_baseline leg: the checker timed as the CPU port
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             from parity_util import compare_edgepoints
@@ -772,7 +836,7 @@ def main():
                               "tolerance": 1e-4}
     leg.close()
     # ---- sub-measurements of the default single-GPU run: the scaling workload's N = 1 point, and config 5
-    if rank == 0 and world == 1 and wl == "c3" and sets is None and not (args.no_extras or args.no_sublines) and not args.seeds:
+    if rank == 0 and world == 1 and wl == "c3" and sets is None and sublines and not args.seeds:
         try:
             l4 = Leg(env, "c4", inflight=args.inflight)
             el4, rs4 = l4.timed(3, 0)

@@ -2,8 +2,7 @@
 (external/manifoldReconstructor/src/OpenMvgParser.cpp:39-301) and writes it with rapidjson's PrettyWriter
 (src/edgegraph3d/io/output/output_sfm_data.cpp:186-229); the product has its own reader / writer
 (edgegraph3d_amd/host/sfm_json.cpp, json_text.hpp). These tests compile a small driver (tests/rapidjson/rj_driver.cpp,
-this repo's code) against the header-only rapidjson the reference tree vendors — in the build container only: they
-are SKIPPED where /root/reference does not exist, and nothing of that tree is copied here — and check that
+this repo's code) against the header-only rapidjson the reference tree vendors — and check that
   * the product prints doubles exactly as rapidjson's Writer does (Grisu2 + notation), on 200 000 values,
   * its computed table of Grisu's cached powers equals the library's,
   * a number literal copied through from the input file is re-printed as the reference's reader + writer re-print it,
@@ -11,8 +10,15 @@ are SKIPPED where /root/reference does not exist, and nothing of that tree is co
   * the product's reader indexes a hand-written OpenMVG file (ptr_wrapper / polymorphic_id, pose keys that are not
     positions, a view order that differs from the pose order) exactly as OpenMvgParser.cpp does.
 (The reference's OpenMvgParser.cpp / output_sfm_data.cpp themselves cannot be compiled here: their headers pull
-CGAL and Eigen — SURVEY F3.)"""
+CGAL and Eigen — SURVEY F3.)
+
+The driver's outputs are recorded in tests/golden/rapidjson_driver_v2.npz, one entry per call, keyed by the mode and
+the SHA-256 of the call's input files: small outputs whole, large ones as SHA-256 digests of 1000-line chunks (see
+_Driver). The tests replay them, so they need neither the reference tree nor a compiler. The entries are data the
+library printed, not a copy of its code. To re-record (after changing a test's inputs), point
+EG3D_RAPIDJSON_INCLUDE at a directory holding the vendored rapidjson/ headers and run this module."""
 import ctypes as C
+import hashlib
 import json
 import os
 import struct
@@ -24,17 +30,106 @@ import pytest
 from edgegraph3d_amd import _cdefs as D
 from edgegraph3d_amd import host
 
-RJ = "/root/reference/external"
 HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(RJ, "rapidjson", "prettywriter.h")),
-                                reason="the reference tree (vendored rapidjson) is not present on this machine")
+GOLD = os.path.join(HERE, "golden", "rapidjson_driver_v2.npz")
+FULL_MAX = 8192     # outputs up to this size are recorded whole; larger ones as SHA-256 digests of CHUNK-line chunks
+CHUNK = 1000
+
+
+def _call_key(mode, inputs):
+    h = hashlib.sha256(mode.encode())
+    for p in inputs:
+        h.update(b"\0" + open(p, "rb").read())
+    return "%s_%s" % (mode, h.hexdigest()[:40])
+
+
+def _chunk_digests(text):
+    lines = text.splitlines(keepends=True)
+    return np.array([np.frombuffer(hashlib.sha256(b"".join(lines[i:i + CHUNK])).digest(), np.uint8)
+                     for i in range(0, len(lines), CHUNK)], np.uint8).reshape(-1, 32)
+
+
+def _first_diff(got, want):
+    g, w = got.splitlines(), want.splitlines()
+    for n, (a, b) in enumerate(zip(g, w)):
+        if a != b:
+            return "line %d: %r vs %r" % (n, a, b)
+    return "%d lines vs %d" % (len(g), len(w))
+
+
+class _Driver:
+    """What tests/rapidjson/rj_driver.cpp, built against the reference's vendored rapidjson, writes for a call, replayed
+    from GOLD. A call is keyed by its mode and the SHA-256 of its input files. Outputs up to FULL_MAX bytes are recorded
+    whole (output()); a larger one as its byte size and the SHA-256 of every chunk of CHUNK lines, against which check()
+    compares the product's text: equal digests throughout = the same bytes. With EG3D_RAPIDJSON_INCLUDE set, the driver
+    is built against that rapidjson and run instead, and GOLD is re-recorded at the end of the module."""
+
+    def __init__(self, tmp):
+        self.inc = os.environ.get("EG3D_RAPIDJSON_INCLUDE")
+        self.recorded = {}
+        self.tmp = tmp
+        if self.inc:
+            self.exe = str(tmp / "rj_driver")
+            subprocess.check_call(["g++", "-std=c++11", "-O1", "-I", self.inc, "-o", self.exe,
+                                   os.path.join(HERE, "rapidjson", "rj_driver.cpp")])
+        else:
+            with np.load(GOLD) as z:
+                self.recorded = {k: z[k] for k in z.files}
+
+    def _live(self, mode, inputs):
+        out = str(self.tmp / ("out_" + mode))
+        subprocess.check_call([self.exe, mode] + list(inputs) + [out])
+        text = open(out, "rb").read()
+        key = _call_key(mode, inputs)
+        if len(text) <= FULL_MAX:
+            self.recorded[key] = np.frombuffer(text, np.uint8)
+        else:
+            self.recorded[key + "__size"] = np.array([len(text)], np.int64)
+            self.recorded[key + "__chunks"] = _chunk_digests(text)
+        return text
+
+    def _missing(self, mode, key):
+        return ("no recorded rapidjson output for these `%s` inputs (%s): the test's inputs changed; re-record with "
+                "EG3D_RAPIDJSON_INCLUDE" % (mode, key))
+
+    def output(self, mode, *inputs):
+        """The driver's whole output (recorded whole: small outputs only)."""
+        if self.inc:
+            return self._live(mode, inputs)
+        key = _call_key(mode, inputs)
+        assert key in self.recorded, self._missing(mode, key)
+        return self.recorded[key].tobytes()
+
+    def check(self, mode, inputs, got):
+        """Asserts that `got` (bytes) is byte for byte what the driver writes for `inputs`."""
+        if self.inc:
+            want = self._live(mode, inputs)
+            assert got == want, "%s: %s" % (mode, _first_diff(got, want))
+            return
+        key = _call_key(mode, inputs)
+        if key in self.recorded:
+            want = self.recorded[key].tobytes()
+            assert got == want, "%s: %s" % (mode, _first_diff(got, want))
+            return
+        assert key + "__chunks" in self.recorded, self._missing(mode, key)
+        want = self.recorded[key + "__chunks"]
+        have = _chunk_digests(got)
+        assert have.shape == want.shape, "%s: %d chunks of %d lines vs %d" % (mode, have.shape[0], CHUNK, want.shape[0])
+        bad = np.flatnonzero((have != want).any(axis=1))
+        assert bad.size == 0, "%s: %d of %d chunks differ, first = lines %d..%d" % (
+            mode, bad.size, want.shape[0], bad[0] * CHUNK, bad[0] * CHUNK + CHUNK - 1)
+        assert len(got) == int(self.recorded[key + "__size"][0]), mode
+
+    def save(self):
+        if self.inc:
+            np.savez_compressed(GOLD, **dict(sorted(self.recorded.items())))
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("rj") / "rj_driver")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-I", RJ, "-o", exe, os.path.join(HERE, "rapidjson", "rj_driver.cpp")])
-    return exe
+    d = _Driver(tmp_path_factory.mktemp("rj"))
+    yield d
+    d.save()
 
 
 def _lib():
@@ -60,9 +155,7 @@ def _lib():
 
 def test_cached_powers_of_grisu_equal_the_librarys(driver, tmp_path):
     L = _lib()
-    out = str(tmp_path / "pw.txt")
-    subprocess.check_call([driver, "powers", out])
-    ref = [tuple(int(x) for x in ln.split()) for ln in open(out)]
+    ref = [tuple(int(x) for x in ln.split()) for ln in driver.output("powers").decode().splitlines()]
     assert len(ref) == 87
     for i in range(87):
         f, e = C.c_uint64(), C.c_int()
@@ -83,12 +176,12 @@ def test_doubles_print_exactly_as_the_librarys_writer(driver, tmp_path):
                   float(np.float32(0.1)), 1.0, -1.0, 0.0, -0.0, 123456792.0, 1e15, 1e16, 1e17, 0.5, 2.5e-7])])
     vals = vals[np.isfinite(vals)]
     vals.tofile(str(tmp_path / "d.bin"))
-    subprocess.check_call([driver, "doubles", str(tmp_path / "d.bin"), str(tmp_path / "d.txt")])
-    want = open(str(tmp_path / "d.txt")).read().split("\n")
     b = C.create_string_buffer(64)
-    for v, w in zip(vals, want):
-        assert L.eg3d_host_json_double_text(float(v), b, 64) > 0
-        assert b.value.decode() == w, repr(v)
+    got = []
+    for v in vals:
+        assert L.eg3d_host_json_double_text(float(v), b, 64) > 0, repr(v)
+        got.append(b.value + b"\n")
+    driver.check("doubles", [str(tmp_path / "d.bin")], b"".join(got))   # (line i = vals[i])
 
 
 def test_number_literals_are_reprinted_as_reader_plus_writer_do(driver, tmp_path):
@@ -118,12 +211,12 @@ def test_number_literals_are_reprinted_as_reader_plus_writer_do(driver, tmp_path
              "123456789012345678901234567890", "0.000001", "1e-6", "1e21", "1e22", "2892.3295898437500",
              "1.7976931348623157e308", "1.0e3", "12E-2", "0.1e1", "2147483649", "1073741824"]
     open(str(tmp_path / "l.txt"), "w").write("\n".join(lits) + "\n")
-    subprocess.check_call([driver, "literals", str(tmp_path / "l.txt"), str(tmp_path / "lo.txt")])
-    want = open(str(tmp_path / "lo.txt")).read().split("\n")
     b = C.create_string_buffer(64)
-    for s, w in zip(lits, want):
+    got = []
+    for s in lits:
         n = L.eg3d_host_json_number_text(s.encode(), b, 64)
-        assert (b.value.decode() if n >= 0 else "ERROR") == w, s
+        got.append((b.value if n >= 0 else b"ERROR") + b"\n")
+    driver.check("literals", [str(tmp_path / "l.txt")], b"".join(got))   # (line i = lits[i])
 
 
 def _hand_written_openmvg():
@@ -180,9 +273,8 @@ def test_written_file_is_byte_identical_to_the_reference_writers_and_reader_inde
     h = L.eg3d_sfm_read_json(p_in.encode())
     assert h
     # ---- (b) the reader: the fields as OpenMvgParser.cpp indexes them (driver `index`, same accessors)
-    subprocess.check_call([driver, "index", p_in, str(tmp_path / "idx.txt")])
     K, E, Vw, P = {}, [], [], []
-    for ln in open(str(tmp_path / "idx.txt")):
+    for ln in driver.output("index", p_in).decode().splitlines():
         t = ln.split()
         fl = lambda hx: np.array([int(hx, 16)], np.uint32).view(np.float32)[0]
         if t[0] == "K":
@@ -261,12 +353,7 @@ def test_written_file_is_byte_identical_to_the_reference_writers_and_reader_inde
         for cam, (x, y) in zip(vws, pts):
             blob += struct.pack("<iff", int(cam), float(x), float(y))
     open(str(tmp_path / "sfm.bin"), "wb").write(blob)
-    p_ref = str(tmp_path / "ref.json")
-    subprocess.check_call([driver, "rewrite", p_in, str(tmp_path / "sfm.bin"), p_ref])
-    got, want = open(p_out, "rb").read(), open(p_ref, "rb").read()
-    if got != want:
-        for n, (a, b) in enumerate(zip(got.split(b"\n"), want.split(b"\n"))):
-            assert a == b, (n, a, b)
-    assert got == want
+    got = open(p_out, "rb").read()
+    driver.check("rewrite", [p_in, str(tmp_path / "sfm.bin")], got)
     assert json.loads(got)["control_points"][0]["value"]["weight"] == 18446744073709551616.0
     L.eg3d_sfm_destroy(h)

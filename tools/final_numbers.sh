@@ -12,7 +12,7 @@ try:
 except Exception as e: print(sys.argv[1], "FAILED", e)
 P
 }
-run c3 python bench.py --gpus 1 --steps 20 --warmup 5
-run c2 python bench.py --workload c2 --steps 20 --warmup 5
-run c3real python bench.py --workload c3real --steps 20 --warmup 5
-run c4 python bench.py --workload c4 --steps 4 --warmup 1
+run c3 python bench.py --gpus 1 --steps 20 --warmup 5 --full
+run c2 python bench.py --workload c2 --steps 20 --warmup 5 --full
+run c3real python bench.py --workload c3real --steps 20 --warmup 5 --full
+run c4 python bench.py --workload c4 --steps 4 --warmup 1 --full

@@ -4,7 +4,7 @@
 # gpurun_out/<tag>_*: one --kernel-trace --stats pass, and SEPARATE --pmc passes (FETCH_SIZE,
 # WRITE_SIZE, two SQ sets) each with --kernel-trace only, as the profiling guide prescribes.
 tag=${1:-r01}; shift
-args=${@:---steps 5 --warmup 1 --no-cpu-baseline}
+args=${@:---steps 5 --warmup 1 --full --no-cpu-baseline}
 out=$PWD/gpurun_out
 mkdir -p $out
 export TMPDIR=$out/tmp; mkdir -p $TMPDIR

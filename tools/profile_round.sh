@@ -17,7 +17,7 @@ out=$PWD/gpurun_out; mkdir -p $out/tmp; export TMPDIR=$out/tmp
 [ "$wl" = c4 ] && export EG3D_CHAIN_CAP0=768 EG3D_POOL_CAP0=196608
 case $wl in
   c4) kt_args="--workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-extras"; pmc_args="--workload c4 --steps 2 --warmup 1 --inflight 1 --no-cpu-baseline --no-extras"; pmc_steps=3;;
-  *)  kt_args="--workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-sublines"; pmc_args="--workload $wl --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-extras"; pmc_steps=4;;
+  *)  kt_args="--workload $wl --steps 20 --warmup 5 --full --no-cpu-baseline --no-sublines"; pmc_args="--workload $wl --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-extras"; pmc_steps=4;;
 esac
 run() { # name, bench args, rocprof flags...
   local name=$1; local args=$2; shift 2
