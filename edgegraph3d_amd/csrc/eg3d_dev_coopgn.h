@@ -37,6 +37,9 @@ namespace eg3d {
 #ifndef EG3D_GN_PRECHECK_IT
 #define EG3D_GN_PRECHECK_IT 2
 #endif
+#ifndef EG3D_MANY_KEEP
+#define EG3D_MANY_KEEP 1 /* chunks of a long solve whose rows stay in registers between the passes of an iteration, many-views build (gn_round<KEEP>; eg3d_kernels.hip k3b_expand_many): 0 / 1 / 2 -> C4 step 1810 / 1774 / 1823 ms at 27 / 60 / 263 spilled VGPRs (round 5; round 4 had only measured 4 chunks at 2 waves per SIMD: slower) */
+#endif
 #ifndef EG3D_K3B_HOIST
 #define EG3D_K3B_HOIST 1 /* k3b_expand's one-chunk rounds load a lane's observation once, before the iterations (gn_round's HOIST) instead of per iteration (0: rounds 4-5, when it measured as a loss; on the round-6 kernel: C3' 38.6 -> 38.2 ms, C2 4.23 -> 4.16, three runs each) */
 #endif
@@ -276,7 +279,7 @@ static_assert(sizeof(CoopLds) <= 12800, "CoopLds must fit 10 LDS allocation unit
 // group's first lanes add them to the request's accumulators in observation order, carrying the
 // accumulators from chunk to chunk — every accumulator sees exactly the additions, in exactly the
 // order, of the sequential solver (eg3d_dev_tri.h gauss_newton_f64) => bit-identical results
-// whatever the grouping.
+// whatever the grouping (tests/test_gpu_coop_gn.py holds every instantiation to the oracle, request by request).
 //   * requests of <= 64 rows: G = the request's row count (one chunk; the rows stay in registers
 //     between the two passes of an iteration), requests packed side by side in lane order until
 //     the 64 lanes are full;

@@ -58,6 +58,8 @@ def lib():
         L.orc_project.argtypes = [D.f32p, D.f32p, D.f32p]
         L.orc_triangulate.argtypes = [D.f32p, C.POINTER(C.c_int), D.f32p, C.c_int, D.f32p, C.POINTER(C.c_int)]
         L.orc_gn_add.argtypes = [D.f32p, C.POINTER(C.c_int), D.f32p, C.c_int, D.f32p, D.f32p]
+        L.orc_gn_add_batch.argtypes = [D.f32p, C.c_int, C.c_uint64, D.u32p, C.POINTER(C.c_int), D.f32p, D.f32p, C.c_int,
+                                       D.u8p, D.f32p, D.i32p]
         L.orc_dlt.argtypes = [D.f32p, D.f32p, D.f32p, D.f32p, D.f64p]
         L.orc_next_by_distance.argtypes = [D.f32p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                                            C.c_uint32, C.c_float, D.u32p, D.f32p]
@@ -85,6 +87,27 @@ def plg_from_mask(mask):
     d = D.plg_view_to_dict(v)
     lib().orc_free_plg_view(C.byref(v))
     return d
+
+
+def gn_add_batch(cam_P, row_off, view, xy, X0, nthreads=None):
+    """em_add_new_observation_to_3Dpositions (the Gauss-Newton solve from a float start, no DLT) of many requests at once,
+    in the default conventions: request r = rows row_off[r] .. row_off[r + 1] - 1 of view / xy, its extra observation last,
+    start X0[r]. Returns (valid [n] uint8, X [n, 3] float32: the last iterate, the result where valid, iterations run [n]
+    int32: the `it` at which em_GaussNewton stopped, or 30)."""
+    P = np.ascontiguousarray(np.asarray(cam_P, np.float32).reshape(-1, 16))
+    row_off = np.ascontiguousarray(row_off, np.uint32)
+    view = np.ascontiguousarray(view, np.int32)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    X0 = np.ascontiguousarray(X0, np.float32).reshape(-1, 3)
+    n = len(row_off) - 1
+    assert len(X0) == n and len(view) == len(xy) == int(row_off[-1])
+    valid, X, iters = np.zeros(n, np.uint8), np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+    rc = lib().orc_gn_add_batch(D.np_ptr(P, C.c_float), len(P), n, D.np_ptr(row_off, C.c_uint32),
+                                view.ctypes.data_as(C.POINTER(C.c_int)), D.np_ptr(xy, C.c_float), D.np_ptr(X0, C.c_float),
+                                int(nthreads or min(16, os.cpu_count() or 1)), D.np_ptr(valid, C.c_uint8),
+                                D.np_ptr(X, C.c_float), D.np_ptr(iters, C.c_int32))
+    assert rc == 0, "orc_gn_add_batch: bad arguments"
+    return valid, X, iters
 
 
 class Oracle:

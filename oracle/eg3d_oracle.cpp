@@ -697,6 +697,37 @@ extern "C" int orc_gn_add(const float* P, const int* view_ids, const float* xy, 
   }
   return valid;
 }
+extern "C" int orc_gn_add_batch(const float* P, int n_views, uint64_t n_req, const uint32_t* row_off, const int* view_ids,
+                                const float* xy, const float* X0, int nthreads, uint8_t* valid, float* X, int32_t* iters) {
+  for (uint64_t r = 0; r < n_req; r++)
+    if (row_off[r + 1] < row_off[r] + 1) return -1;
+  for (uint64_t k = 0; k < row_off[n_req]; k++)
+    if (view_ids[k] < 0 || view_ids[k] >= n_views) return -1;
+  const unsigned conv = g_conv;
+  g_conv = 0;  // the default conventions, whatever a test hook set
+#pragma omp parallel for schedule(dynamic, 16) num_threads(nthreads > 1 ? nthreads : 1)
+  for (int64_t r = 0; r < (int64_t)n_req; r++) {
+    std::vector<GNObs> obs(row_off[r + 1] - row_off[r]);
+    for (size_t i = 0; i < obs.size(); i++) {
+      const uint32_t k = row_off[r] + (uint32_t)i;
+      obs[i].P = P + (size_t)view_ids[k] * 16;
+      obs[i].x = xy[2 * (size_t)k];
+      obs[i].y = xy[2 * (size_t)k + 1];
+    }
+    // em_add_new_observation_to_3Dpositions: Gauss-Newton from the stored float point, no DLT
+    const double init[3] = {(double)X0[3 * r], (double)X0[3 * r + 1], (double)X0[3 * r + 2]};
+    double opt[3], last[3];
+    int it = 0;
+    const int res = em_GaussNewton(obs, init, opt, &it, last);
+    valid[r] = res != -1 ? 1 : 0;
+    iters[r] = it;
+    X[3 * r] = (float)last[0];
+    X[3 * r + 1] = (float)last[1];
+    X[3 * r + 2] = (float)last[2];
+  }
+  g_conv = conv;
+  return 0;
+}
 extern "C" void orc_dlt(const float* P1, const float* xy1, const float* P2, const float* xy2, double* X0) {
   dlt2_init(P1, vec2(xy1[0], xy1[1]), P2, vec2(xy2[0], xy2[1]), X0);
 }

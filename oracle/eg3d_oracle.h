@@ -85,6 +85,12 @@ void orc_batch_mindist(uint64_t n, const float* pvw /*[n][6]*/, float* out /*[n]
 void orc_batch_anglecos(uint64_t n, const float* seg_line /*[n][7]: x1 y1 x2 y2 a b c*/, float* out /*[n]*/);
 int orc_triangulate(const float* P /*[n][16]*/, const int* view_ids, const float* xy, int n, float* X, int* degenerate);
 int orc_gn_add(const float* P, const int* view_ids, const float* xy, int n, const float* X0, float* X);
+/* many em_add_new_observation_to_3Dpositions solves at once (default conventions, nthreads threads): request r = rows
+ * row_off[r] .. row_off[r + 1] - 1 of view_ids / xy (its extra observation last), start X0[r]; out: valid[r], X[r] (the
+ * last iterate, as float — the result where valid) and the iterations em_GaussNewton ran (the `it` it stopped at, or 30).
+ * Returns 0, -1 on bad arguments. */
+int orc_gn_add_batch(const float* P, int n_views, uint64_t n_req, const uint32_t* row_off, const int* view_ids, const float* xy,
+                     const float* X0, int nthreads, uint8_t* valid, float* X, int32_t* iters);
 void orc_dlt(const float* P1, const float* xy1, const float* P2, const float* xy2, double* X0);
 /* polyline walking probes: vtx = [n][2], start/end node ids */
 int orc_next_by_distance(const float* vtx, int n, uint32_t start, uint32_t end, uint32_t seg, float x, float y,

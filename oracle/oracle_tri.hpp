@@ -240,7 +240,10 @@ struct GNObs {
 // GEMM orders restated from OpenCV matmul.cpp: 4x4*4x1 products sum left to right;
 // H = J^T J sums over the 2n rows in order from 0; (H^-1 * J^T) is formed first, then
 // multiplied by r summing over the 2n columns in order.
-static inline int em_GaussNewton(const std::vector<GNObs>& obs, const double init[3], double out[3]) {
+// iters (optional): the iterations run — the `it` at which the loop stopped (converged, or singular normal equations), or 30;
+// last (optional): the iterate at that point, accepted or not.
+static inline int em_GaussNewton(const std::vector<GNObs>& obs, const double init[3], double out[3], int* iters = nullptr,
+                                 double* last = nullptr) {
   const int n = (int)obs.size();
   // scratch of the solve, per thread and reused (the values are overwritten before they are read: same arithmetic; a
   // std::vector pair per call was ~50 M malloc / free per C3' step, serialising the threads of an all-core run)
@@ -251,7 +254,8 @@ static inline int em_GaussNewton(const std::vector<GNObs>& obs, const double ini
   double* const J = J_tl.data();
   double X[3] = {init[0], init[1], init[2]};
   double last_mse = 0;
-  for (int it = 0; it < 30; it++) {
+  int it = 0;
+  for (; it < 30; it++) {
     double mse = 0;
     for (int m = 0; m < n; m++) {
       const float* P = obs[m].P;
@@ -293,7 +297,11 @@ static inline int em_GaussNewton(const std::vector<GNObs>& obs, const double ini
     // cv::determinant 3x3 (det3 macro)
     double d = H[0][0] * (H[1][1] * H[2][2] - H[1][2] * H[2][1]) - H[0][1] * (H[1][0] * H[2][2] - H[1][2] * H[2][0]) +
                H[0][2] * (H[1][0] * H[2][1] - H[1][1] * H[2][0]);
-    if (d < 0.00001) return -1;
+    if (d < 0.00001) {
+      if (iters) *iters = it;
+      if (last) last[0] = X[0], last[1] = X[1], last[2] = X[2];
+      return -1;
+    }
     // Mat::inv() DECOMP_LU, n==3 closed form (lapack.cpp cv::invert)
     double Hi[3][3];
     {
@@ -322,6 +330,8 @@ static inline int em_GaussNewton(const std::vector<GNObs>& obs, const double ini
       X[i] += s;
     }
   }
+  if (iters) *iters = it;
+  if (last) last[0] = X[0], last[1] = X[1], last[2] = X[2];
   if (last_mse < 9) {
     out[0] = X[0];
     out[1] = X[1];

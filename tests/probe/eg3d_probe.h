@@ -29,6 +29,18 @@ int eg3d_probe_gn_rows(uint64_t n, const float* P16, const float* oxy, const dou
  * seven identical ADD requests of n <= 9 rows; *ms = kernel time; X_ok = {mean solution x of block 0, its accepted solves} */
 int eg3d_probe_gn_dense(const float* cam_P, int n_views, const int32_t* obs_view, const float* obs_xy, int n,
                         const float* X0, int n_blocks, int rounds, float* ms, float* X_ok);
+/* the lane-group Gauss-Newton solver (coop_gn_groups, eg3d_dev_coopgn.h) on windows of up to 32 requests, one single-wave
+ * block per window, as the expand kernel calls it (tests/test_gpu_coop_gn.py). variant: 0 small <0, false, 30>, 1 general
+ * <0, true, 30>, 2 many views <EG3D_MANY_KEEP, true, EG3D_GN_PRECHECK_IT> (the product's three instantiations), 3 <2, true,
+ * EG3D_GN_PRECHECK_IT> (KEEP = 2), 4 <0, true, EG3D_GN_PRECHECK_IT> and 5 <0, false, EG3D_GN_PRECHECK_IT>
+ * (EG3D_GN_PRECHECK_ALL). Request j of window w = entry w * 32 + j: req_i = {want, offset, nblock, has_extra, extra view},
+ * req_f = {extra x, extra y, X0[3]}; rows offset .. offset + nblock - 1 of obs_view / obs_xy, then the extra one.
+ * Out per entry: valid, X[3] and the group size G its request was solved with (0 = not solved: not wanted, or a long
+ * request refused), per window long_refused. Returns 0, -1 on bad arguments, -2 on a HIP error. */
+int eg3d_probe_coop_gn(int variant, const float* cam_P, int n_views, const int32_t* obs_view, const float* obs_xy,
+                       uint64_t n_obs, int n_windows, const int32_t* req_i, const float* req_f, int cams_mid_range,
+                       uint8_t* valid, float* X, int32_t* G, uint8_t* long_refused);
+int eg3d_probe_coop_gn_variants(void); /* number of variants */
 /* 2-D geometry primitives on the GPU (tests/test_glm_pin.py): mode 0 project_f32 (in [n][19] = P16 + X -> [n][2]),
  * 1 seg_line_cos (in [n][7] = segment + line -> [n]), 2 seg_closest (in [n][6] = p, v, w -> [n][3] = d2, closest point) */
 int eg3d_probe_geom(uint64_t n, int mode, const float* in, float* out);

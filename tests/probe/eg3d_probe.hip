@@ -316,6 +316,177 @@ extern "C" int eg3d_probe_gn_dense(const float* cam_P, int n_views, const int32_
   return 0;
 }
 
+// ---- the lane-group Gauss-Newton solver, request by request (tests/test_gpu_coop_gn.py): one single-wave block per window of
+// up to EG3D_COOP_REQ requests (request j on lane j, lanes without one pass want = false), coop_gn_groups called exactly as
+// k3b_expand calls it, with the template arguments of the product's instantiations (TeamWaveT, eg3d_kernels.hip) taken from
+// the same macros. Verdict and solution of every request, and the window's long_refused, go back to the host.
+template <int KEEP, bool LONG_GN, int PRE_IT>
+__global__ void __launch_bounds__(64) k_probe_coop_gn(const float* cam_P, const Obs* obs, const int32_t* req_i, const float* req_f,
+                                                      int cams_mid_range, uint8_t* valid, float* Xo, uint8_t* refused) {
+  __shared__ CoopLds L;
+  const int lane = (int)threadIdx.x;
+  const size_t e = (size_t)blockIdx.x * EG3D_COOP_REQ + (size_t)lane;
+  if (lane == 0) {
+    L.cams_mid_range = cams_mid_range ? 1 : 0;
+    L.long_refused = 0;
+  }
+  __syncthreads();
+  bool want = false, has_extra = false;
+  const Obs* base = obs;
+  int nblock = 0;
+  int32_t ex_view = 0;
+  float ex_x = 0.f, ex_y = 0.f;
+  float X0[3] = {0.f, 0.f, 0.f};
+  if (lane < EG3D_COOP_REQ) {
+    const int32_t* q = req_i + 5 * e;
+    const float* f = req_f + 5 * e;
+    want = q[0] != 0;
+    if (want) {
+      base = obs + q[1];
+      nblock = q[2];
+      has_extra = q[3] != 0;
+      ex_view = q[4];
+      ex_x = f[0];
+      ex_y = f[1];
+    }
+    X0[0] = f[2];
+    X0[1] = f[3];
+    X0[2] = f[4];
+  }
+  float X[3] = {0.f, 0.f, 0.f};
+  const bool ok = coop_gn_groups<KEEP, LONG_GN, PRE_IT>(cam_P, L, want, base, nblock, has_extra, ex_view, ex_x, ex_y, X0, X);
+  if (lane < EG3D_COOP_REQ) {
+    valid[e] = ok ? 1 : 0;
+    Xo[3 * e] = X[0];
+    Xo[3 * e + 1] = X[1];
+    Xo[3 * e + 2] = X[2];
+  }
+  __syncthreads();
+  if (lane == 0) refused[blockIdx.x] = L.long_refused;
+}
+
+// The group size coop_gn_run gives each request of a window, its rules restated: a short request (<= EG3D_GN_PACK_MAX rows) is
+// one group of its own row count; the long ones go in lane order, round after round, the first 64 >> lg of those left
+// getting groups of 2^lg lanes, lg chosen by the cost model over the longest request left. 0 = not solved.
+static void coop_gn_group_sizes(int keep, bool long_gn, const int* n_req, int32_t* G) {
+  std::vector<int> todo;
+  for (int j = 0; j < EG3D_COOP_REQ; j++) {
+    G[j] = 0;
+    if (n_req[j] > 0 && n_req[j] <= EG3D_GN_PACK_MAX) G[j] = n_req[j];
+    if (n_req[j] > EG3D_GN_PACK_MAX) todo.push_back(j);
+  }
+  if (!long_gn) return;
+  while (!todo.empty()) {
+    const int Bl = (int)todo.size();
+    int mxl = 0;
+    for (int j : todo) mxl = n_req[j] > mxl ? n_req[j] : mxl;
+    int lg = 6;
+    unsigned best = 0xffffffffu;
+    for (int cand = 1; cand <= 6; cand++) {
+      const int Gc = 1 << cand;
+      const int k = (mxl + Gc - 1) >> cand;
+      const int rounds = (Bl + (64 >> cand) - 1) / (64 >> cand);
+      const int krow = keep == 0 ? (k > 1 ? 2 * k : k) : k + (k > keep ? k - keep : 0);
+      const unsigned cost = (unsigned)rounds * ((unsigned)krow * EG3D_GN_ROW_CYCLES + (unsigned)k * EG3D_GN_SUM_CYCLES * Gc);
+      if (cost < best) {
+        best = cost;
+        lg = cand;
+      }
+    }
+    const int per_round = 64 >> lg;
+    const int take = Bl < per_round ? Bl : per_round;
+    for (int t = 0; t < take; t++) G[todo[t]] = 1 << lg;
+    todo.erase(todo.begin(), todo.begin() + take);
+  }
+}
+
+extern "C" int eg3d_probe_coop_gn_variants(void) { return 6; }
+
+extern "C" int eg3d_probe_coop_gn(int variant, const float* cam_P, int n_views, const int32_t* obs_view, const float* obs_xy,
+                                  uint64_t n_obs, int n_windows, const int32_t* req_i, const float* req_f, int cams_mid_range,
+                                  uint8_t* valid, float* X, int32_t* G, uint8_t* long_refused) {
+  static const int keep_of[6] = {0, 0, EG3D_MANY_KEEP, 2, 0, 0};
+  static const bool long_of[6] = {false, true, true, true, true, false};
+  if (variant < 0 || variant > 5 || !cam_P || n_views < 1 || n_views >= (1 << EG3D_VIEW_BITS) || !obs_view || !obs_xy ||
+      n_obs < 1 || n_obs > 0x7fffffffull || n_windows < 1)
+    return -1;
+  for (uint64_t i = 0; i < n_obs; i++)
+    if (obs_view[i] < 0 || obs_view[i] >= n_views) return -1;
+  const size_t ne = (size_t)n_windows * EG3D_COOP_REQ;
+  std::vector<int> n_req(ne, 0);
+  for (size_t e = 0; e < ne; e++) {
+    const int32_t* q = req_i + 5 * e;
+    if (!q[0]) continue;
+    if (q[1] < 0 || q[2] < 0 || (uint64_t)q[1] + (uint64_t)q[2] > n_obs) return -1;
+    if (q[3] && (q[4] < 0 || q[4] >= n_views)) return -1;
+    n_req[e] = q[2] + (q[3] ? 1 : 0);
+    if (n_req[e] < 2 || n_req[e] > 0x7fff) return -1;  // every request >= 2 rows; n16 holds 15 bits of row count
+  }
+  for (int w = 0; w < n_windows; w++)
+    coop_gn_group_sizes(keep_of[variant], long_of[variant], &n_req[(size_t)w * EG3D_COOP_REQ], G + (size_t)w * EG3D_COOP_REQ);
+  std::vector<Obs> h((size_t)n_obs);
+  for (uint64_t i = 0; i < n_obs; i++) {
+    h[i].view = (uint32_t)obs_view[i];
+    h[i].pl = 0;
+    h[i].seg = 0;
+    h[i].x = obs_xy[2 * i];
+    h[i].y = obs_xy[2 * i + 1];
+  }
+  float *dP, *df, *dX;
+  Obs* dobs;
+  int32_t* di;
+  uint8_t *dval, *dref;
+  PT(hipMalloc(&dP, (size_t)n_views * 64));
+  PT(hipMalloc(&dobs, sizeof(Obs) * (size_t)n_obs));
+  PT(hipMalloc(&di, ne * 5 * 4));
+  PT(hipMalloc(&df, ne * 5 * 4));
+  PT(hipMalloc(&dval, ne));
+  PT(hipMalloc(&dX, ne * 12));
+  PT(hipMalloc(&dref, (size_t)n_windows));
+  PT(hipMemcpy(dP, cam_P, (size_t)n_views * 64, hipMemcpyHostToDevice));
+  PT(hipMemcpy(dobs, h.data(), sizeof(Obs) * (size_t)n_obs, hipMemcpyHostToDevice));
+  PT(hipMemcpy(di, req_i, ne * 5 * 4, hipMemcpyHostToDevice));
+  PT(hipMemcpy(df, req_f, ne * 5 * 4, hipMemcpyHostToDevice));
+  const dim3 grid((unsigned)n_windows), block(64);
+  switch (variant) {
+    case 0:  // small scenes (TeamWaveT<0, 0>)
+      hipLaunchKernelGGL((k_probe_coop_gn<0, false, 30>), grid, block, 0, 0, dP, dobs, di, df, cams_mid_range, dval, dX, dref);
+      break;
+    case 1:  // general (TeamWaveT<0, 1>)
+      hipLaunchKernelGGL((k_probe_coop_gn<0, true, 30>), grid, block, 0, 0, dP, dobs, di, df, cams_mid_range, dval, dX, dref);
+      break;
+    case 2:  // many views (TeamWaveT<EG3D_MANY_KEEP, 2>)
+      hipLaunchKernelGGL((k_probe_coop_gn<EG3D_MANY_KEEP, true, EG3D_GN_PRECHECK_IT>), grid, block, 0, 0, dP, dobs, di, df,
+                         cams_mid_range, dval, dX, dref);
+      break;
+    case 3:  // the many-views build with two kept chunks (EG3D_MANY_KEEP=2)
+      hipLaunchKernelGGL((k_probe_coop_gn<2, true, EG3D_GN_PRECHECK_IT>), grid, block, 0, 0, dP, dobs, di, df, cams_mid_range,
+                         dval, dX, dref);
+      break;
+    case 4:  // the general build with the pre-check (EG3D_GN_PRECHECK_ALL=1)
+      hipLaunchKernelGGL((k_probe_coop_gn<0, true, EG3D_GN_PRECHECK_IT>), grid, block, 0, 0, dP, dobs, di, df, cams_mid_range,
+                         dval, dX, dref);
+      break;
+    default:  // the small build with the pre-check (EG3D_GN_PRECHECK_ALL=1)
+      hipLaunchKernelGGL((k_probe_coop_gn<0, false, EG3D_GN_PRECHECK_IT>), grid, block, 0, 0, dP, dobs, di, df, cams_mid_range,
+                         dval, dX, dref);
+      break;
+  }
+  PT(hipGetLastError());
+  PT(hipDeviceSynchronize());
+  PT(hipMemcpy(valid, dval, ne, hipMemcpyDeviceToHost));
+  PT(hipMemcpy(X, dX, ne * 12, hipMemcpyDeviceToHost));
+  PT(hipMemcpy(long_refused, dref, (size_t)n_windows, hipMemcpyDeviceToHost));
+  (void)hipFree(dP);
+  (void)hipFree(dobs);
+  (void)hipFree(di);
+  (void)hipFree(df);
+  (void)hipFree(dval);
+  (void)hipFree(dX);
+  (void)hipFree(dref);
+  return 0;
+}
+
 // ---- the 2-D geometry primitives the glm pin test checks (tests/test_glm_pin.py): project_f32, seg_line_cos,
 // seg_closest of the product's headers on the GPU. in = [n][19] / [n][7] / [n][6] floats as tests/glm/glm_driver.cpp takes.
 __global__ void k_probe_geom(uint64_t n, int mode, const float* in, float* out) {

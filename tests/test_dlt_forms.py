@@ -183,3 +183,35 @@ def test_gauss_newton_reaches_the_least_squares_point_from_either_start(dlt_rows
             assert rel <= 1e-4, (trial, rows, k, bool(deg.value), X, best, rel)
             checked += 1
     assert checked >= 150
+
+
+def test_gauss_newton_of_long_requests_reaches_the_least_squares_point():
+    """The same pin for the solves the expand stage's lane-group solver makes (tests/coop_gn_cases.py: the 16-view C5 rig
+    and a 256-view rig, 2 .. 4096 rows, views repeating beyond the rig's count, near and far float starts): wherever the
+    oracle's em_GaussNewton accepts, its point agrees with scipy's Levenberg-Marquardt minimiser of the same residuals
+    to 1e-4 relative. The GPU test holds the device to the oracle bit for bit; this holds both to the mathematics, so
+    that a mistake they share cannot hide behind bit-equality."""
+    import coop_gn_cases as cg
+    from scipy.optimize import least_squares
+    rng = np.random.default_rng(29)
+    seen = set()
+    for rig in cg.rigs()[:2]:
+        reqs = [cg.make_request(rig, n, kind, rng, has_extra=(i % 2 == 0)) for n in cg.ROWS + cg.ROWS_LONG_ONLY
+                for i, kind in enumerate(("near", "far", "far"))]
+        off = np.cumsum([0] + [len(r["view"]) for r in reqs]).astype(np.uint32)
+        valid, X, iters = ob.gn_add_batch(rig.P, off, np.concatenate([r["view"] for r in reqs]),
+                                          np.concatenate([r["xy"] for r in reqs]), np.array([r["X0"] for r in reqs]))
+        assert valid.all(), [len(r["view"]) for r, v in zip(reqs, valid) if not v]
+        assert (iters >= 2).all() and (iters < 30).all()
+        for r, x in zip(reqs, X):
+            xy, M = r["xy"].astype(np.float64), rig.M[r["view"]]
+
+            def resid(Xp):
+                h = M @ np.append(Xp, 1.0)
+                return (xy - h[:, :2] / h[:, 2:3]).ravel()
+
+            best = least_squares(resid, np.float64(r["X0"]), method="lm", xtol=1e-14, ftol=1e-14).x
+            rel = np.linalg.norm(np.float64(x) - best) / max(np.linalg.norm(best), 1e-9)
+            assert rel <= 1e-4, (rig.name, len(r["view"]), r["kind"], x, best, rel)
+            seen.add(len(r["view"]))
+    assert seen == set(cg.ROWS + cg.ROWS_LONG_ONLY)

@@ -169,6 +169,64 @@ def test_gn_filter_parity(have_gpu):
     ctx.close()
 
 
+def _k5_lists(s, rng, lengths_per_block):
+    """Points of the rig of `s` with the given list lengths, 256 points (one k5_gn_filter block) per entry: views drawn
+    without repetition while the rig has enough, observations = projection + noise of 0.3 .. 2.5 px (a point's own level:
+    both sides of the mse threshold), start = true point + 1.5 per axis."""
+    P = s.scene_np()["cam_P"].reshape(-1, 4, 4)[:, :3, :].astype(np.float64)
+    V = len(P)
+    Xt, _, _, _ = s.points(256 * len(lengths_per_block))
+    Xt = Xt.astype(np.float64)
+    ks = np.concatenate([np.resize(np.asarray(b), 256) for b in lengths_per_block]).astype(np.int64)
+    views = []
+    for k in ks:
+        v = rng.choice(V, min(int(k), V), replace=False)
+        views.append(np.concatenate([v, rng.integers(0, V, int(k) - len(v))]) if k > V else v)
+    off = np.concatenate([[0], np.cumsum(ks)]).astype(np.uint32)
+    view = np.concatenate(views).astype(np.int32)
+    pid = np.repeat(np.arange(len(ks)), ks)
+    h = np.einsum("nij,nj->ni", P[view], np.concatenate([Xt[pid], np.ones((len(pid), 1))], 1))
+    sigma = rng.uniform(0.3, 2.5, len(ks))[pid][:, None]
+    xy = (h[:, :2] / h[:, 2:3] + rng.normal(0, 1, (len(pid), 2)) * sigma).astype(np.float32)
+    X0 = (Xt + rng.normal(0, 1.5, Xt.shape)).astype(np.float32)
+    return X0, off, view, xy
+
+
+@pytest.mark.parametrize("n_views", [256, 257])
+def test_gn_filter_parity_beyond_the_staging_limits(have_gpu, n_views):
+    """k5_gn_filter stages a block's cameras and observations in LDS only for rigs of at most K5_VIEW_CAP = 256 views and
+    blocks of at most K5_OBS_CAP observations, and sorts a block's points into 64 buckets by list length, the last one
+    holding every list of 64 or more. Here: rigs of exactly 256 views (staged where the block's lists fit) and 257 (no
+    block staged), lists of 2 .. 257 observations with the >= 64 bucket mixed with short lists in one block, both abs()
+    behaviours of Q9 — inlier flags and X bit-exact against the oracle."""
+    cfg = host.default_config(4)
+    cfg.n_views, cfg.n_seeds, cfg.n_curves = n_views, 10, 20
+    s = host.Synth(cfg)
+    assert s.n_views == n_views
+    rng = np.random.default_rng(n_views)
+    blocks = [
+        [2, 3, 2, 63, 2, 64, 2, 65, 3, 2, 257, 2] + [2, 3] * 40,   # light block: < 2816 observations (staged at 256 views)
+        [2, 63, 64, 65, 257, 5, 10, 128],                         # heavy block: > 2816 observations (never staged)
+        [64, 2, 64, 3, 100, 63],
+        [2, 3, 4, 5, 6, 7, 8, 9, 10, 63, 64, 65] + [3] * 60 + [257],
+    ]
+    X0, off, view, xy = _k5_lists(s, rng, blocks)
+    m = np.diff(off.astype(np.int64))
+    per_block = np.add.reduceat(m, np.arange(0, len(m), 256))
+    assert (per_block <= 2816).any() and (per_block > 2816).any()
+    for k in (2, 63, 64, 65, 257):
+        assert (m == k).sum() >= 4, k
+    ctx = api.Context(s.scene)
+    o = _oracle(s.scene)
+    for legacy in (False, True):
+        Xo, inl, ms = ctx.gn_filter(X0, off, view, xy, 2.25, legacy_abs=legacy)
+        Xr, ir = o.gn_filter(X0, off, view, xy, 2.25, legacy_abs=legacy, nthreads=8)
+        assert np.array_equal(inl, ir) and np.array_equal(Xo.view(np.uint32), Xr.view(np.uint32)), (n_views, legacy)
+        for k in (2, 63, 64, 65, 257):   # both verdicts at every list length
+            assert inl[m == k].any() and not inl[m == k].all(), (k, legacy)
+    ctx.close()
+
+
 def test_gn_filter_full_config5_one_million_points(have_gpu):
     """BASELINE configs[4] at its FULL size: 1 000 000 edge-points of the 16-view rig (k in 3..10, 5.76 M
     observations), both abs() behaviours of Q9 — X and the inlier flags of every point bit-exact."""
