@@ -51,6 +51,7 @@ def lib():
                                           C.POINTER(D.StageTimes)]
         L.eg3d_match_polyline_sets.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32, C.c_int,
                                                C.POINTER(D.EdgePoints), C.POINTER(D.StageTimes)]
+        L.eg3d_check_polyline_sets.argtypes = [C.POINTER(D.PolylineSets), C.c_int32]
         L.eg3d_last_device_output.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints)]
         L.eg3d_set_pipelining.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.eg3d_gn_filter.argtypes = [C.c_void_p, D.f32p, D.u32p, D.i32p, D.f32p, C.c_uint64, C.c_float, C.c_int,
@@ -63,13 +64,22 @@ def lib():
 EXPORTED_SYMBOLS = [
     "eg3d_last_error", "eg3d_device_count", "eg3d_dlt_rows", "eg3d_create", "eg3d_clone", "eg3d_destroy", "eg3d_get_grid", "eg3d_candidates_run",
     "eg3d_free_candidates", "eg3d_match_refpoints", "eg3d_free_edgepoints", "eg3d_upload_seeds",
-    "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_set_pipelining",
+    "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
 ]
 
 
 def _check(rc, what):
     if rc != 0:
         raise Eg3dError("%s failed (rc=%d): %s" % (what, rc, lib().eg3d_last_error().decode()))
+
+
+def check_polyline_sets(n_sets, row_off, pl_ids, n_views):
+    """eg3d_check_polyline_sets: the device-free checks of a polyline-sets CSR (row_off ascending, ids strictly ascending
+    within every row). Raises Eg3dError if the sets are refused."""
+    row_off = np.ascontiguousarray(row_off, np.uint32)
+    pl_ids = np.ascontiguousarray(pl_ids if len(pl_ids) else [0], np.uint32)
+    ps = D.PolylineSets(n_sets, D.np_ptr(row_off, C.c_uint32), D.np_ptr(pl_ids, C.c_uint32))
+    _check(lib().eg3d_check_polyline_sets(C.byref(ps), n_views), "eg3d_check_polyline_sets")
 
 
 def device_count():

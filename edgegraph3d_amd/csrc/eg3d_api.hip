@@ -2204,10 +2204,44 @@ extern "C" int eg3d_match_refpoints(eg3d_ctx* c, const eg3d_seeds* seeds, uint32
   return eg3d_match_resident(c, b, e, device_only, out, times);
 }
 
+extern "C" int eg3d_check_polyline_sets(const eg3d_polyline_sets* ps, int32_t n_views) {
+  if (!ps || !ps->row_off || n_views < 1) {
+    g_err = "eg3d_check_polyline_sets: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  const uint64_t n_rows = (uint64_t)ps->n_sets * (uint64_t)n_views;
+  if (n_rows > 0xffffffffull) {
+    g_err = "eg3d_match_polyline_sets: too many rows";
+    return EG3D_ERR_ARG;
+  }
+  if (ps->row_off[n_rows] && !ps->pl_ids) {
+    g_err = "eg3d_match_polyline_sets: pl_ids is null";
+    return EG3D_ERR_ARG;
+  }
+  for (uint64_t r = 0; r < n_rows; r++) {
+    if (ps->row_off[r + 1] < ps->row_off[r]) {
+      g_err = "eg3d_match_polyline_sets: row_off is not ascending";
+      return EG3D_ERR_ARG;
+    }
+    // a row is the reference's set<ulong>: strictly ascending, no repeats (a repeated id would be sampled and scanned
+    // twice — an input the reference cannot produce)
+    for (uint32_t k = ps->row_off[r] + 1; k < ps->row_off[r + 1]; k++)
+      if (ps->pl_ids[k] <= ps->pl_ids[k - 1]) {
+        g_err = "eg3d_match_polyline_sets: polyline ids of a row are not strictly ascending";
+        return EG3D_ERR_ARG;
+      }
+  }
+  return EG3D_OK;
+}
+
 extern "C" int eg3d_match_polyline_sets(eg3d_ctx* c, const eg3d_polyline_sets* ps, uint32_t set_b, uint32_t set_e,
                                         int device_only, eg3d_edgepoints* out, eg3d_stage_times* times) {
   if (!c || !ps || !out || !ps->row_off || set_b > set_e || set_e > ps->n_sets) {
     g_err = "eg3d_match_polyline_sets: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  if ((uint64_t)ps->n_sets * (uint64_t)c->V > 0xffffffffull) {
+    g_err = "eg3d_match_polyline_sets: too many rows";
     return EG3D_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
@@ -2230,6 +2264,10 @@ extern "C" int eg3d_match_polyline_sets(eg3d_ctx* c, const eg3d_polyline_sets* p
           return EG3D_ERR_ARG;
         }
     }
+  }
+  {
+    const int rc = eg3d_check_polyline_sets(ps, c->V);  // (the checks that need no scene: rows are sets)
+    if (rc != EG3D_OK) return rc;
   }
   BUF_TRY(upload(c->b_sets_off, ps->row_off, (size_t)n_rows + 1, c->stream));
   BUF_TRY(upload(c->b_sets_ids, ps->pl_ids, n_ids, c->stream));

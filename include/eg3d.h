@@ -195,10 +195,15 @@ int eg3d_match_refpoints(eg3d_ctx* ctx, const eg3d_seeds* seeds, uint32_t seed_b
 typedef struct eg3d_polyline_sets {
   uint32_t n_sets;
   const uint32_t* row_off; /* [n_sets * n_views + 1] CSR over rows (set * n_views + view) */
-  const uint32_t* pl_ids;  /* view-local polyline ids, ascending within a row */
+  const uint32_t* pl_ids;  /* view-local polyline ids, strictly ascending within a row (a set: no repeats;
+                              EG3D_ERR_ARG otherwise) */
 } eg3d_polyline_sets;
 int eg3d_match_polyline_sets(eg3d_ctx* ctx, const eg3d_polyline_sets* sets, uint32_t set_begin, uint32_t set_end,
                              int device_only, eg3d_edgepoints* out, eg3d_stage_times* times);
+/* The checks of `sets` that need no device and no scene (eg3d_match_polyline_sets runs them too, after its id-range
+ * check): row_off ascending, ids strictly ascending within every row. EG3D_OK or EG3D_ERR_ARG (eg3d_last_error says
+ * which). Usable without a GPU. */
+int eg3d_check_polyline_sets(const eg3d_polyline_sets* sets, int32_t n_views);
 
 void eg3d_free_edgepoints(eg3d_edgepoints* e);
 

@@ -393,7 +393,13 @@ class PLGEdgeManager : public EdgeManager {
     if (!ctx_) return res;
     std::vector<uint32_t> row_off(1, 0), ids;
     for (const auto& per_view : compat) {
-      for (unsigned long id : per_view) ids.push_back((uint32_t)id);
+      for (unsigned long id : per_view) {
+        if (id > 0xfffffffful) {  // (narrowed, it would alias a smaller id and break the row's order)
+          status_ = EG3D_ERR_ARG;
+          return res;
+        }
+        ids.push_back((uint32_t)id);
+      }
       row_off.push_back((uint32_t)ids.size());
     }
     if (ids.empty()) ids.push_back(0);

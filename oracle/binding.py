@@ -37,6 +37,8 @@ def lib():
         L.orc_match_polyline_sets.argtypes = [C.c_void_p, C.c_uint32, D.u32p, D.u32p, C.c_uint32, C.c_uint32, C.c_int,
                                               C.POINTER(D.EdgePoints), C.POINTER(Stats)]
         L.orc_free_edgepoints.argtypes = [C.POINTER(D.EdgePoints)]
+        L.orc_count_set_samples.argtypes = [C.c_void_p, C.c_uint32, D.u32p, D.u32p, D.u32p]
+        L.orc_polyline_samples.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, D.f32p, D.u32p]
         L.orc_candidates.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32, C.POINTER(D.Candidates)]
         L.orc_free_candidates.argtypes = [C.POINTER(D.Candidates)]
         L.orc_gn_filter.argtypes = [C.c_void_p, D.f32p, D.u32p, D.i32p, D.f32p, C.c_uint64, C.c_float, C.c_int,
@@ -161,6 +163,27 @@ class Oracle:
         lib().orc_free_edgepoints(C.byref(e))
         d["stats"] = {f[0]: getattr(st, f[0]) for f in Stats._fields_}
         return d
+
+    def count_set_samples(self, n_sets, row_off, pl_ids):
+        """The extractor's count_set_samples of every set (oracle_plg.hpp): uint32[n_sets]."""
+        row_off = np.ascontiguousarray(row_off, np.uint32)
+        pl_ids = np.ascontiguousarray(pl_ids if len(pl_ids) else [0], np.uint32)
+        out = np.zeros(max(1, n_sets), np.uint32)
+        rc = lib().orc_count_set_samples(self._h, n_sets, D.np_ptr(row_off, C.c_uint32), D.np_ptr(pl_ids, C.c_uint32),
+                                         D.np_ptr(out, C.c_uint32))
+        if rc != 0:
+            raise RuntimeError("orc_count_set_samples failed")
+        return out[:n_sets]
+
+    def polyline_samples(self, view, pl_id):
+        """The samples the extractor walks on one polyline: (xy float32[n, 2], seg uint32[n])."""
+        n = lib().orc_polyline_samples(self._h, view, pl_id, 0, None, None)
+        if n < 0:
+            raise RuntimeError("orc_polyline_samples failed")
+        xy = np.zeros((max(1, n), 2), np.float32)
+        seg = np.zeros(max(1, n), np.uint32)
+        lib().orc_polyline_samples(self._h, view, pl_id, n, D.np_ptr(xy, C.c_float), D.np_ptr(seg, C.c_uint32))
+        return xy[:n], seg[:n]
 
     def replay_matches(self, cloud):
         """Row a17 (plg_matches_manager.cpp:99-180) over the chains of `cloud` (an edge-point dict)."""

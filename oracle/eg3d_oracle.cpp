@@ -241,6 +241,36 @@ extern "C" int orc_match_polyline_sets(orc_ctx* c, uint32_t n_sets, const uint32
   return pack_edgepoints(c, per_set, tstats, t0, out, stats);
 }
 
+extern "C" int orc_count_set_samples(orc_ctx* c, uint32_t n_sets, const uint32_t* row_off, const uint32_t* pl_ids,
+                                     uint32_t* out) {
+  if (!c || !row_off || !out) return -1;
+  const int V = (int)c->sc.plgs.size();
+  for (uint32_t i = 0; i < n_sets; i++) {
+    std::vector<std::vector<ulong_t>> set(V);
+    for (int v = 0; v < V; v++) {
+      const uint32_t row = i * (uint32_t)V + (uint32_t)v;
+      for (uint32_t k = row_off[row]; k < row_off[row + 1]; k++) {
+        if (pl_ids[k] >= c->sc.plgs[v].polylines.size()) return -1;
+        set[v].push_back(pl_ids[k]);
+      }
+    }
+    out[i] = count_set_samples(c->sc, set);
+  }
+  return 0;
+}
+
+extern "C" int orc_polyline_samples(orc_ctx* c, int view, uint32_t pl_id, uint32_t cap, float* xy, uint32_t* seg) {
+  if (!c || view < 0 || view >= (int)c->sc.plgs.size() || pl_id >= c->sc.plgs[view].polylines.size()) return -1;
+  std::vector<pl_point> smp;
+  polyline_samples(c->sc, view, pl_id, smp);
+  for (size_t i = 0; i < smp.size() && i < cap; i++) {
+    xy[2 * i] = smp[i].coords.x;
+    xy[2 * i + 1] = smp[i].coords.y;
+    seg[i] = (uint32_t)smp[i].segment_index;
+  }
+  return (int)smp.size();
+}
+
 extern "C" void orc_free_edgepoints(eg3d_edgepoints* e) {
   if (!e) return;
   free(e->X);

@@ -42,6 +42,11 @@ int orc_match_refpoints(orc_ctx*, const eg3d_seeds* seeds, uint32_t seed_begin, 
  * the call, start view, 0, index in chain). */
 int orc_match_polyline_sets(orc_ctx*, uint32_t n_sets, const uint32_t* row_off, const uint32_t* pl_ids,
                             uint32_t set_begin, uint32_t set_end, int nthreads, eg3d_edgepoints* out, orc_stats* stats);
+/* TEST HOOKS of the extractor's sampling: count_set_samples of each of sets [0, n_sets) into out[n_sets] (0 or -1 for
+ * an id out of range), and the samples of one polyline (every 20 px from its start towards its end, as the extractor
+ * walks it): returns their number, writes the first `cap` (xy[cap][2], seg[cap]); -1 for a bad view / id. */
+int orc_count_set_samples(orc_ctx*, uint32_t n_sets, const uint32_t* row_off, const uint32_t* pl_ids, uint32_t* out);
+int orc_polyline_samples(orc_ctx*, int view, uint32_t pl_id, uint32_t cap, float* xy, uint32_t* seg);
 void orc_free_edgepoints(eg3d_edgepoints* e);
 int orc_candidates(orc_ctx*, const eg3d_seeds* seeds, uint32_t seed_begin, uint32_t seed_end, eg3d_candidates* out);
 void orc_free_candidates(eg3d_candidates* c);

@@ -777,18 +777,26 @@ static inline void plg_matching_from_refpoint(const Scene& sc, const SeedView& s
 // Invalid / empty polylines (for which the reference's get_start_plp() would read out of bounds)
 // are skipped. `sample_base` numbers the samples of the call; key = (sample, view, polyline, i).
 static const float SPLIT_INTERVAL_DISTANCE = (float)20.0;
+// The samples of ONE polyline (the only copy of the walk: count_set_samples and match_polyline_set use it, and the
+// test hook orc_polyline_samples exposes it)
+static inline void polyline_samples(const Scene& sc, int view, ulong_t pl_id, std::vector<pl_point>& out) {
+  out.clear();
+  const polyline& pl = sc.plgs[view].polylines[pl_id];
+  if (!pl.valid || pl.polyline_coords.size() < 2) return;
+  bool reached_end;
+  pl_point plp = pl.next_pl_point_by_distance(pl.get_start_plp(), pl.end, SPLIT_INTERVAL_DISTANCE, reached_end);
+  while (!reached_end) {
+    out.push_back(plp);
+    plp = pl.next_pl_point_by_distance(plp, pl.end, SPLIT_INTERVAL_DISTANCE, reached_end);
+  }
+}
 static inline uint32_t count_set_samples(const Scene& sc, const std::vector<std::vector<ulong_t>>& compat) {
   uint32_t n = 0;
+  std::vector<pl_point> smp;
   for (size_t v = 0; v < compat.size(); v++)
     for (ulong_t pl_id : compat[v]) {
-      const polyline& pl = sc.plgs[v].polylines[pl_id];
-      if (!pl.valid || pl.polyline_coords.size() < 2) continue;
-      bool reached;
-      pl_point plp = pl.next_pl_point_by_distance(pl.get_start_plp(), pl.end, SPLIT_INTERVAL_DISTANCE, reached);
-      while (!reached) {
-        n++;
-        plp = pl.next_pl_point_by_distance(plp, pl.end, SPLIT_INTERVAL_DISTANCE, reached);
-      }
+      polyline_samples(sc, (int)v, pl_id, smp);
+      n += (uint32_t)smp.size();
     }
   return n;
 }
@@ -798,11 +806,9 @@ static inline void match_polyline_set(const Scene& sc, const std::vector<std::ve
   uint32_t sample = sample_base;
   for (int starting_plg_id = 0; starting_plg_id < V; starting_plg_id++)
     for (ulong_t starting_polyline_id : compat[starting_plg_id]) {
-      const polyline& pl = sc.plgs[starting_plg_id].polylines[starting_polyline_id];
-      if (!pl.valid || pl.polyline_coords.size() < 2) continue;
-      bool reached_end;
-      pl_point plp = pl.next_pl_point_by_distance(pl.get_start_plp(), pl.end, SPLIT_INTERVAL_DISTANCE, reached_end);
-      while (!reached_end) {
+      std::vector<pl_point> smp;
+      polyline_samples(sc, starting_plg_id, starting_polyline_id, smp);
+      for (const pl_point& plp : smp) {
         const plg_point starting_plgp(starting_polyline_id, plp);
         if (st) {
           st->n_tasks++;
@@ -839,7 +845,6 @@ static inline void match_polyline_set(const Scene& sc, const std::vector<std::ve
           res.push_back(e);
         }
         sample++;
-        plp = pl.next_pl_point_by_distance(plp, pl.end, SPLIT_INTERVAL_DISTANCE, reached_end);
       }
     }
 }
