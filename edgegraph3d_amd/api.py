@@ -56,6 +56,13 @@ def lib():
         L.eg3d_set_pipelining.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.eg3d_gn_filter.argtypes = [C.c_void_p, D.f32p, D.u32p, D.i32p, D.f32p, C.c_uint64, C.c_float, C.c_int,
                                      D.f32p, D.u8p, D.f32p]
+        L.eg3d_context_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.eg3d_gn_filter_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.c_void_p, C.c_float, C.c_int,
+                                            C.c_void_p, C.c_void_p, D.u64p, D.u64p, D.f32p]
+        L.eg3d_compact_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.POINTER(D.DeviceEdgePoints)]
+        L.eg3d_filter_resident.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, D.u64p, C.c_int,
+                                           C.POINTER(D.EdgePoints), C.POINTER(D.DeviceEdgePoints), C.POINTER(D.FilterStats)]
         _LIB = L
     return _LIB
 
@@ -65,6 +72,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_last_error", "eg3d_device_count", "eg3d_dlt_rows", "eg3d_create", "eg3d_clone", "eg3d_destroy", "eg3d_get_grid", "eg3d_candidates_run",
     "eg3d_free_candidates", "eg3d_match_refpoints", "eg3d_free_edgepoints", "eg3d_upload_seeds",
     "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
+    "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
 ]
 
 
@@ -86,6 +94,76 @@ def device_count():
     return int(lib().eg3d_device_count())
 
 
+_HIP = None
+
+
+def _hip():
+    """The HIP runtime libeg3d.so itself is linked against (loaded once): the copy already in the process by its SONAME,
+    the ROCm installation's otherwise."""
+    global _HIP
+    if _HIP is None:
+        lib()   # (libeg3d.so first: its runtime is then the one the SONAME finds)
+        try:
+            hip = C.CDLL("libamdhip64.so.7")
+        except OSError:
+            hip = C.CDLL("/opt/rocm/lib/libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipFree.argtypes = [C.c_void_p]
+        hip.hipSetDevice.argtypes = [C.c_int]
+        _HIP = hip
+    return _HIP
+
+
+class DeviceArray:
+    """A block of HBM owned by Python (hipMalloc / hipFree): where callers place masks and receive the per-point results of
+    the device-resident filter. `ptr` is the device address; numpy() copies it back. The memory is freed when the object
+    is collected: keep the object, not just its `ptr`, for as long as a device view refers to it."""
+
+    def __init__(self, nbytes, device=0):
+        self.nbytes, self.device, self.ptr = int(nbytes), int(device), None
+        p = C.c_void_p()
+        if _hip().hipSetDevice(self.device) != 0 or _hip().hipMalloc(C.byref(p), max(self.nbytes, 256)) != 0:
+            raise Eg3dError("hipMalloc(%d) failed" % self.nbytes)
+        self.ptr = p.value
+
+    def numpy(self, dtype, shape=None):
+        a = np.empty(self.nbytes // np.dtype(dtype).itemsize, dtype)
+        if a.nbytes and _hip().hipMemcpy(a.ctypes.data, C.c_void_p(self.ptr), a.nbytes, 2) != 0:
+            raise Eg3dError("hipMemcpy from the device failed")
+        return a.reshape(shape) if shape is not None else a
+
+    def free(self):
+        if self.ptr:
+            _hip().hipFree(C.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def device_alloc(nbytes, device=0):
+    return DeviceArray(nbytes, device)
+
+
+def upload(array, device=0):
+    """A numpy array copied into a fresh DeviceArray on `device`."""
+    a = np.ascontiguousarray(array)
+    d = DeviceArray(a.nbytes, device)
+    if a.nbytes and _hip().hipMemcpy(C.c_void_p(d.ptr), a.ctypes.data, a.nbytes, 1) != 0:
+        raise Eg3dError("hipMemcpy to the device failed")
+    return d
+
+
+def _dev_ptr(x):
+    if x is None:
+        return None
+    return C.c_void_p(x.ptr if isinstance(x, DeviceArray) else int(x))
+
+
 class Context:
     def __init__(self, scene_ptr, device=0, _handle=None):
         self._h = C.c_void_p()
@@ -93,6 +171,9 @@ class Context:
             self._h = _handle
         else:
             _check(lib().eg3d_create(scene_ptr, device, C.byref(self._h)), "eg3d_create")
+        nv, dv = C.c_int32(), C.c_int32()
+        _check(lib().eg3d_context_info(self._h, C.byref(nv), C.byref(dv)), "eg3d_context_info")
+        self.n_views, self.device = nv.value, dv.value
 
     def clone(self):
         """A context sharing this one's scene and resident seeds (own stream and work buffers)."""
@@ -273,3 +354,52 @@ class Context:
                                     1 if legacy_abs else 0, D.np_ptr(Xo, C.c_float), D.np_ptr(inl, C.c_uint8),
                                     C.byref(ms)), "eg3d_gn_filter")
         return Xo, inl, ms.value
+
+    # ---- the filter stage on a device-resident cloud (include/eg3d.h) ----
+    def device_alloc(self, nbytes):
+        """A DeviceArray of nbytes on this context's device."""
+        return DeviceArray(nbytes, self.device)
+
+    def upload(self, array):
+        """A numpy array copied into a fresh DeviceArray on this context's device."""
+        return upload(array, self.device)
+
+    def gn_filter_device(self, cloud, keep=None, gn_max_mse=2.25, legacy_abs=False, X_out=None, inlier=None):
+        """eg3d_gn_filter_device on `cloud` (a DeviceEdgePoints). keep / X_out / inlier: DeviceArray or device address;
+        X_out and inlier are allocated when not given. Returns (X_out, inlier, hist[n_views + 1] int64, n_inliers, ms);
+        n_inliers counts the inliers of no bin (more observations than views) too."""
+        n = int(cloud.n_points)
+        X_out = X_out if X_out is not None else DeviceArray(12 * n, self.device)
+        inlier = inlier if inlier is not None else DeviceArray(n, self.device)
+        hist = np.zeros(self.n_views + 1, np.uint64)
+        ms, n_inl = C.c_float(0), C.c_uint64(0)
+        _check(lib().eg3d_gn_filter_device(self._h, C.byref(cloud), _dev_ptr(keep), gn_max_mse, 1 if legacy_abs else 0,
+                                           _dev_ptr(X_out), _dev_ptr(inlier), D.np_ptr(hist, C.c_uint64), C.byref(n_inl),
+                                           C.byref(ms)), "eg3d_gn_filter_device")
+        return X_out, inlier, hist.astype(np.int64), int(n_inl.value), ms.value
+
+    def compact_device(self, cloud, keep=None, X_new=None, min_obs=-1):
+        """eg3d_compact_device: the DeviceEdgePoints of the survivors (buffers of this context, valid until its next
+        compaction)."""
+        out = D.DeviceEdgePoints()
+        _check(lib().eg3d_compact_device(self._h, C.byref(cloud), _dev_ptr(keep), _dev_ptr(X_new), int(min_obs),
+                                         C.byref(out)), "eg3d_compact_device")
+        return out
+
+    def filter_resident(self, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, to_host=True):
+        """eg3d_filter_resident on the last device output. Returns (cloud dict or None, DeviceEdgePoints, stats dict)."""
+        e, dv, st = D.EdgePoints(), D.DeviceEdgePoints(), D.FilterStats()
+        st.struct_size = C.sizeof(D.FilterStats)
+        bh = None
+        if base_hist is not None:
+            bh = np.ascontiguousarray(base_hist, np.uint64)
+            if len(bh) != self.n_views + 1:
+                raise ValueError("base_hist needs n_views + 1 entries")
+        _check(lib().eg3d_filter_resident(self._h, gn_max_mse, 1 if legacy_abs else 0, int(forced_min_filter),
+                                          D.np_ptr(bh, C.c_uint64) if bh is not None else None, 1 if to_host else 0,
+                                          C.byref(e) if to_host else None, C.byref(dv), C.byref(st)), "eg3d_filter_resident")
+        d = None
+        if to_host:
+            d = D.edgepoints_to_dict(e)
+            lib().eg3d_free_edgepoints(C.byref(e))
+        return d, dv, {f[0]: getattr(st, f[0]) for f in D.FilterStats._fields_}

@@ -192,7 +192,13 @@ RESOURCE_BOUNDS = {
     "k3b_expand_t<4, 1, 2>": {"vgpr_spill_count": 140, "private_segment_fixed_size": 256, "group_segment_fixed_size": 10240},
     "k3a_orient": {"vgpr_spill_count": 0, "group_segment_fixed_size": 12800},
     "k3a_follow_spec": {"vgpr_spill_count": 0, "group_segment_fixed_size": 12800},
-    "k5_gn_filter": {"vgpr_spill_count": 0},
+    "k5_gn_filter": {"vgpr_spill_count": 0},  # (a substring: every instantiation)
+    # host clouds (eg3d_gn_filter): the figures of the kernel before it became a template — 57 VGPRs, 47 124 B of LDS
+    "k5_gn_filter<unsigned int, true>": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "vgpr_count": 57,
+                                         "group_segment_fixed_size": 47124},
+    # device clouds (eg3d_gn_filter_device): + the 258 histogram bins (measured: 62 VGPRs, 48 164 B)
+    "k5_gn_filter<unsigned long, false>": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 48164},
+    "k6_compact_scatter": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 3104},
     "k2_epipolar_hits": {"vgpr_spill_count": 0},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }

@@ -228,6 +228,10 @@ struct eg3d_ctx {
       b_cscratch, b_couts, b_cpts, b_cobs, b_cpoff, b_cooff, b_scan_tmp, b_scanchk, b_cost, b_cidx, b_cost2, b_order, b_redo[2];
   DevBuf o_X, o_off, o_view, o_pl, o_seg, o_xy, o_key;
   DevBuf f_X, f_off, f_view, f_xy, f_Xo, f_inl;
+  // eg3d_gn_filter_device / eg3d_compact_device / eg3d_filter_resident: histogram + flag word, block totals of the
+  // compaction, the compacted cloud (valid until the next compaction), X_out / inlier of eg3d_filter_resident
+  DevBuf r_hist, r_blk, r_Xo, r_inl, c_X, c_off, c_view, c_pl, c_seg, c_xy, c_key;
+  bool compact_nt = false;  // EG3D_COMPACT_NT=1 (read by eg3d_create): non-temporal loads of the compaction's source
   DevBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
@@ -555,6 +559,7 @@ extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
   eg3d_ctx* c = new eg3d_ctx();
   c->device = device;
   c->tune = Tunables::from_env();
+  if (const char* e = getenv("EG3D_COMPACT_NT")) c->compact_nt = e[0] == '1';
   if (c->tune.hyp_cap) c->hyp_cap = c->tune.hyp_cap;
   c->hg = std::make_shared<HostGrids>();
   if (c->tune.lane_priorities) {
@@ -863,6 +868,7 @@ extern "C" int eg3d_clone(eg3d_ctx* parent, eg3d_ctx** out) {
   eg3d_ctx* c = new eg3d_ctx();
   c->device = parent->device;
   c->tune = parent->tune;
+  c->compact_nt = parent->compact_nt;
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (int i = 0; i < 8; i++) {
     HIP_TRY(hipEventCreate(&c->ea[i]));
@@ -923,7 +929,7 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
                    &c->b_nhyp, &c->b_hyp_off, &c->b_res, &c->b_arena, &c->b_ctr, &c->b_cs_task,
                    &c->b_valid, &c->b_chain_off, &c->b_chains, &c->b_cscratch, &c->b_couts, &c->b_cpts, &c->b_cobs,
                    &c->b_cpoff, &c->b_cooff, &c->b_scan_tmp, &c->b_scanchk, &c->b_cost, &c->b_cidx, &c->b_cost2, &c->b_order, &c->b_redo[0], &c->b_redo[1], &c->o_X, &c->o_off, &c->o_view, &c->o_pl, &c->o_seg,
-                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
+                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->r_hist, &c->r_blk, &c->r_Xo, &c->r_inl, &c->c_X, &c->c_off, &c->c_view, &c->c_pl, &c->c_seg, &c->c_xy, &c->c_key, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
                    &c->b_pools, &c->b_stage_pts, &c->b_stage_obs, &c->b_stage_used};
   for (DevBuf* b : all) b->release();
   if (c->pinned) (void)hipHostFree(c->pinned);
@@ -2471,6 +2477,258 @@ extern "C" int eg3d_gn_filter(eg3d_ctx* c, const float* X, const uint32_t* obs_o
   }
   HIP_TRY(hipStreamSynchronize(st));
   if (ms_kernel) HIP_TRY(hipEventElapsedTime(ms_kernel, c->ea[0], c->eb[0]));
+  return EG3D_OK;
+}
+
+// ---- the filter and the compaction on a device-resident cloud ----------------------------------------------------------
+extern "C" int eg3d_context_info(eg3d_ctx* c, int32_t* n_views, int32_t* device) {
+  if (!c) {
+    g_err = "eg3d_context_info: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  if (n_views) *n_views = c->V;
+  if (device) *device = c->device;
+  return EG3D_OK;
+}
+static CloudView cloud_view(const eg3d_device_edgepoints* d) {
+  return CloudView{d->n_points, d->n_obs, d->X, d->obs_off, d->obs_view, d->obs_pl, d->obs_seg, d->obs_xy, d->key};
+}
+static int check_cloud(const eg3d_device_edgepoints* d, const char* who, bool all_arrays) {
+  const bool pts = !d->n_points || (d->X && d->obs_off && (!all_arrays || d->key));
+  const bool obs = !d->n_obs || (d->obs_view && d->obs_xy && (!all_arrays || (d->obs_pl && d->obs_seg)));
+  if (!pts || !obs || (d->n_obs && !d->n_points)) {
+    g_err = std::string(who) + ": the device view has null arrays";
+    return EG3D_ERR_ARG;
+  }
+  if (!d->complete) {
+    g_err = std::string(who) + ": the device view does not hold a whole cloud (complete == 0)";
+    return EG3D_ERR_ARG;
+  }
+  return EG3D_OK;
+}
+static int device_flags_error(const char* who, uint32_t flags) {
+  if (flags & K5_FLAG_BAD_VIEW)
+    g_err = std::string(who) + ": view id out of range";
+  else
+    g_err = std::string(who) + ": obs_off is not ascending within [0, n_obs], or a list holds more than 2^24 observations";
+  return EG3D_ERR_ARG;
+}
+// hist_all: [V + 2] (bin k for k <= V, bin V + 1 for longer lists)
+static int gn_filter_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, const uint8_t* keep_dev, float gn_max_mse,
+                                 int legacy_abs, float* X_out_dev, uint8_t* inlier_dev, std::vector<uint64_t>& hist_all,
+                                 float* ms_kernel) {
+  const size_t bins = (size_t)c->V + 2;
+  hist_all.assign(bins, 0);
+  hipStream_t st = c->stream;
+  BUF_TRY(c->r_hist.ensure(8 * bins + 8));
+  HIP_TRY(hipMemsetAsync(c->r_hist.p, 0, 8 * bins + 8, st));
+  K5Dev ext{keep_dev, d->n_obs, c->r_hist.as<unsigned long long>(), (uint32_t*)(c->r_hist.as<unsigned long long>() + bins)};
+  HIP_TRY(hipEventRecord(c->ea[0], st));
+  launch_k5_device(st, c->ds.cam_P, c->V, d->X, d->obs_off, d->obs_view, d->obs_xy, d->n_points, gn_max_mse, legacy_abs, X_out_dev,
+                   inlier_dev, ext);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->eb[0], st));
+  std::vector<uint64_t> back(bins + 1);
+  HIP_TRY(hipMemcpyAsync(back.data(), c->r_hist.p, 8 * bins + 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ms_kernel) HIP_TRY(hipEventElapsedTime(ms_kernel, c->ea[0], c->eb[0]));
+  const uint32_t flags = (uint32_t)back[bins];
+  if (flags) return device_flags_error("eg3d_gn_filter_device", flags);
+  std::copy(back.begin(), back.begin() + bins, hist_all.begin());
+  return EG3D_OK;
+}
+
+extern "C" int eg3d_gn_filter_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, const uint8_t* keep_dev, float gn_max_mse,
+                                     int legacy_abs, float* X_out_dev, uint8_t* inlier_dev, uint64_t* obs_hist_host,
+                                     uint64_t* n_inliers_host, float* ms_kernel) {
+  if (!c || !cloud || (cloud->n_points && (!X_out_dev || !inlier_dev))) {
+    g_err = "eg3d_gn_filter_device: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  BUF_TRY(check_cloud(cloud, "eg3d_gn_filter_device", false));
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<uint64_t> hist;
+  if (ms_kernel) *ms_kernel = 0;
+  BUF_TRY(gn_filter_device_impl(c, cloud, keep_dev, gn_max_mse, legacy_abs, X_out_dev, inlier_dev, hist, ms_kernel));
+  if (obs_hist_host) std::copy(hist.begin(), hist.begin() + c->V + 1, obs_hist_host);
+  if (n_inliers_host) {
+    *n_inliers_host = 0;
+    for (uint64_t h : hist) *n_inliers_host += h;  // (the last bin: lists longer than the rig has views)
+  }
+  return EG3D_OK;
+}
+
+static int compact_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, const uint8_t* keep_dev, const float* X_new_dev,
+                               int32_t min_obs, eg3d_device_edgepoints* out, float* ms) {
+  const void* mine[] = {c->c_X.p, c->c_off.p, c->c_view.p, c->c_pl.p, c->c_seg.p, c->c_xy.p, c->c_key.p};
+  const void* theirs[] = {d->X, d->obs_off, d->obs_view, d->obs_pl, d->obs_seg, d->obs_xy, d->key, X_new_dev};
+  for (const void* a : mine)
+    for (const void* b : theirs)
+      if (a && a == b) {
+        g_err = "eg3d_compact_device: the input views this context's compaction buffers, which the call overwrites";
+        return EG3D_ERR_ARG;
+      }
+  hipStream_t st = c->stream;
+  const CloudView in = cloud_view(d);
+  const uint64_t nb = (d->n_points + K6_BLOCK - 1) / K6_BLOCK;
+  BUF_TRY(c->r_blk.ensure(16 * (nb + 1) + 8));
+  unsigned long long* blk = c->r_blk.as<unsigned long long>();
+  uint32_t* flags = (uint32_t*)(blk + 2 * (nb + 1));
+  HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
+  HIP_TRY(hipEventRecord(c->ea[0], st));
+  launch_compact_count(st, in, keep_dev, min_obs, blk, flags);
+  launch_compact_scan(st, nb, blk);
+  HIP_TRY(hipGetLastError());
+  uint64_t back[3];  // surviving points, surviving observations, flags
+  HIP_TRY(hipMemcpyAsync(back, blk + 2 * nb, sizeof(back), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if ((uint32_t)back[2]) return device_flags_error("eg3d_compact_device", (uint32_t)back[2]);
+  const uint64_t np = back[0], no = back[1];
+  BUF_TRY(c->c_X.ensure(12 * np));
+  BUF_TRY(c->c_off.ensure(8 * np));
+  BUF_TRY(c->c_key.ensure(16 * np));
+  BUF_TRY(c->c_view.ensure(4 * no));
+  BUF_TRY(c->c_pl.ensure(4 * no));
+  BUF_TRY(c->c_seg.ensure(4 * no));
+  BUF_TRY(c->c_xy.ensure(8 * no));
+  CloudOut o{c->c_X.as<float>(), c->c_off.as<eg3d_off_t>(), c->c_view.as<int32_t>(), c->c_pl.as<uint32_t>(),
+             c->c_seg.as<uint32_t>(), c->c_xy.as<float>(), c->c_key.as<uint32_t>()};
+  launch_compact_scatter(st, in, keep_dev, X_new_dev, min_obs, blk, o, c->compact_nt);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->eb[0], st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ea[0], c->eb[0]));
+  out->n_points = np;
+  out->n_obs = no;
+  out->X = o.X;
+  out->obs_off = o.obs_off;
+  out->obs_view = o.obs_view;
+  out->obs_pl = o.obs_pl;
+  out->obs_seg = o.obs_seg;
+  out->obs_xy = o.obs_xy;
+  out->key = o.key;
+  out->complete = 1;
+  return EG3D_OK;
+}
+
+extern "C" int eg3d_compact_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, const uint8_t* keep_dev,
+                                   const float* X_new_dev, int32_t min_obs, eg3d_device_edgepoints* out) {
+  if (!c || !cloud || !out) {
+    g_err = "eg3d_compact_device: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  if ((const void*)out == (const void*)cloud) {
+    g_err = "eg3d_compact_device: out must not alias cloud";
+    return EG3D_ERR_ARG;
+  }
+  BUF_TRY(check_cloud(cloud, "eg3d_compact_device", true));
+  HIP_TRY(hipSetDevice(c->device));
+  return compact_device_impl(c, cloud, keep_dev, X_new_dev, min_obs, out, nullptr);
+}
+
+// The rule of eg3d_host_observation_filter (host/post_steps.cpp) on a histogram by list length: hist[k], k = 0 .. V, and
+// `count` points in all (lists longer than V are counted but sit in no bin, as there).
+static int observation_threshold(const uint64_t* hist, int V, uint64_t count, int forced_min_filter) {
+  uint64_t acc = 0;
+  int median = 0;
+  for (median = 0; median < V; median++) {
+    acc += hist[median + 1];
+    if (acc >= count / 2) break;
+  }
+  int threshold = median / 2 - 1;
+  if (threshold < 3) threshold = 3;
+  if (forced_min_filter > -1) threshold = forced_min_filter;
+  return threshold;
+}
+
+extern "C" int eg3d_filter_resident(eg3d_ctx* c, float gn_max_mse, int legacy_abs, int forced_min_filter,
+                                    const uint64_t* base_hist, int to_host, eg3d_edgepoints* out_host,
+                                    eg3d_device_edgepoints* out_dev, eg3d_filter_stats* stats) {
+  if (!c || (to_host && !out_host)) {
+    g_err = "eg3d_filter_resident: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  if (stats && stats->struct_size < sizeof(eg3d_filter_stats)) {
+    g_err = "eg3d_filter_resident: stats->struct_size is smaller than this library's eg3d_filter_stats (" +
+            std::to_string(sizeof(eg3d_filter_stats)) + " bytes): set it to sizeof(eg3d_filter_stats)";
+    return EG3D_ERR_ARG;
+  }
+  eg3d_device_edgepoints d;
+  BUF_TRY(eg3d_last_device_output(c, &d));
+  BUF_TRY(check_cloud(&d, "eg3d_filter_resident", true));
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t n = d.n_points;
+  BUF_TRY(c->r_Xo.ensure(12 * n));
+  BUF_TRY(c->r_inl.ensure(n));
+  std::vector<uint64_t> hist;
+  float ms_filter = 0, ms_compact = 0;
+  BUF_TRY(gn_filter_device_impl(c, &d, nullptr, gn_max_mse, legacy_abs, c->r_Xo.as<float>(), c->r_inl.as<uint8_t>(), hist,
+                                &ms_filter));
+  uint64_t inliers = 0, count = 0;
+  for (uint64_t h : hist) inliers += h;
+  count = inliers;
+  if (base_hist)
+    for (int k = 0; k <= c->V; k++) {
+      hist[k] += base_hist[k];
+      count += base_hist[k];
+    }
+  const int threshold = observation_threshold(hist.data(), c->V, count, forced_min_filter);
+  eg3d_device_edgepoints o;
+  BUF_TRY(compact_device_impl(c, &d, c->r_inl.as<uint8_t>(), c->r_Xo.as<float>(), threshold, &o, &ms_compact));
+  float ms_copy = 0;
+  if (to_host) {
+    const auto t0 = std::chrono::steady_clock::now();
+    memset(out_host, 0, sizeof(*out_host));
+    const uint64_t np = o.n_points, no = o.n_obs;
+    out_host->X = (float*)malloc(12 * std::max<uint64_t>(np, 1));
+    out_host->obs_off = (uint64_t*)malloc(8 * (np + 1));
+    out_host->key = (uint32_t*)malloc(16 * std::max<uint64_t>(np, 1));
+    out_host->obs_view = (int32_t*)malloc(4 * std::max<uint64_t>(no, 1));
+    out_host->obs_pl = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
+    out_host->obs_seg = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
+    out_host->obs_xy = (float*)malloc(8 * std::max<uint64_t>(no, 1));
+    if (!out_host->X || !out_host->obs_off || !out_host->key || !out_host->obs_view || !out_host->obs_pl ||
+        !out_host->obs_seg || !out_host->obs_xy) {
+      eg3d_free_edgepoints(out_host);
+      g_err = "eg3d_filter_resident: out of host memory";
+      return EG3D_ERR_HIP;
+    }
+    struct { void* dst; const void* src; size_t bytes; } cp[] = {
+        {out_host->X, o.X, 12 * np},          {out_host->obs_off, o.obs_off, 8 * np}, {out_host->key, o.key, 16 * np},
+        {out_host->obs_view, o.obs_view, 4 * no}, {out_host->obs_pl, o.obs_pl, 4 * no},   {out_host->obs_seg, o.obs_seg, 4 * no},
+        {out_host->obs_xy, o.obs_xy, 8 * no}};
+    for (auto& q : cp)
+      if (q.bytes) {
+        const hipError_t e = hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) {
+          eg3d_free_edgepoints(out_host);
+          g_err = std::string("eg3d_filter_resident: copy to the host: ") + hipGetErrorString(e);
+          return EG3D_ERR_HIP;
+        }
+      }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) {
+      eg3d_free_edgepoints(out_host);
+      g_err = "eg3d_filter_resident: copy to the host failed";
+      return EG3D_ERR_HIP;
+    }
+    out_host->obs_off[np] = no;
+    out_host->n_points = np;
+    out_host->n_obs = no;
+    ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  if (out_dev) *out_dev = o;
+  if (stats) {
+    stats->struct_size = (uint32_t)sizeof(eg3d_filter_stats);
+    stats->threshold = threshold;
+    stats->n_points_in = n;
+    stats->n_masked_in = n;
+    stats->n_gn_inliers = inliers;
+    stats->n_kept = o.n_points;
+    stats->n_obs_kept = o.n_obs;
+    stats->ms_filter = ms_filter;
+    stats->ms_compact = ms_compact;
+    stats->ms_copy = ms_copy;
+  }
   return EG3D_OK;
 }
 

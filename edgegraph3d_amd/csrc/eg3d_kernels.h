@@ -127,4 +127,57 @@ void launch_k5(hipStream_t st, const float* cam_P, int n_views, const float* X, 
                const int32_t* obs_view, const float* obs_xy, uint64_t n, float gn_max_mse, int legacy_abs, float* X_out,
                uint8_t* inlier);
 
+// ---- the filter and the compaction on device-resident clouds (eg3d_gn_filter_device / eg3d_compact_device) ----
+// Second instantiation of the K5 body: 64-bit offsets without a sentinel, optional keep mask, histogram of the inliers'
+// list lengths, device-side checks of what the host form validates on the host (see k5_gn_filter).
+enum : uint32_t { K5_FLAG_BAD_VIEW = 1u /* a view id outside [0, n_views) */,
+                  K5_FLAG_BAD_OFFSETS = 2u /* a list that is not an ascending range inside [0, n_obs], or longer than K5_MAX_LIST */ };
+#define K5_MAX_LIST (1u << 24) /* observations of ONE point on the device-cloud entry points: 64 such lists sum to at most 2^30, inside the int of wave_incl_scan */
+struct K5Host {};  // eg3d_gn_filter: nothing beyond the legacy arguments
+struct K5Dev {
+  const uint8_t* keep;       // may be null: all points
+  uint64_t n_obs;            // end of the last point's list
+  unsigned long long* hist;  // [n_views + 2], zeroed by the caller
+  uint32_t* flags;           // K5_FLAG_*, zeroed by the caller
+};
+template <bool SENTINEL>
+struct K5ExtOf { typedef K5Dev type; };
+template <>
+struct K5ExtOf<true> { typedef K5Host type; };
+template <bool SENTINEL>
+using K5Ext = typename K5ExtOf<SENTINEL>::type;
+void launch_k5_device(hipStream_t st, const float* cam_P, int n_views, const float* X, const eg3d_off_t* obs_off,
+                      const int32_t* obs_view, const float* obs_xy, uint64_t n, float gn_max_mse, int legacy_abs, float* X_out,
+                      uint8_t* inlier, K5Dev ext);
+// Order-preserving stream compaction of a device cloud, three launches. A point survives when keep[i] != 0 (keep may be
+// null) and its list is longer than min_obs (min_obs < 0: no count test).
+struct CloudView {  // = eg3d_device_edgepoints without `complete`
+  uint64_t n_points, n_obs;
+  const float* X;
+  const eg3d_off_t* obs_off;
+  const int32_t* obs_view;
+  const uint32_t* obs_pl;
+  const uint32_t* obs_seg;
+  const float* obs_xy;
+  const uint32_t* key;
+};
+struct CloudOut {
+  float* X;
+  eg3d_off_t* obs_off;
+  int32_t* obs_view;
+  uint32_t* obs_pl;
+  uint32_t* obs_seg;
+  float* obs_xy;
+  uint32_t* key;
+};
+#define K6_BLOCK 256
+// (1) per K6_BLOCK source points: surviving points and observations -> blk[2 b], blk[2 b + 1]
+void launch_compact_count(hipStream_t st, CloudView in, const uint8_t* keep, int32_t min_obs, unsigned long long* blk,
+                          uint32_t* flags);
+// (2) exclusive scan of both columns in place, totals -> blk[2 n_blocks], blk[2 n_blocks + 1]
+void launch_compact_scan(hipStream_t st, uint64_t n_blocks, unsigned long long* blk);
+// (3) scatter; nt: non-temporal loads of the source
+void launch_compact_scatter(hipStream_t st, CloudView in, const uint8_t* keep, const float* X_new, int32_t min_obs,
+                            const unsigned long long* blk, CloudOut out, bool nt);
+
 }  // namespace eg3d

@@ -1796,10 +1796,22 @@ __global__ void __launch_bounds__(64) k4_emit(const TaskDesc* tasks, const Chain
 #define K5_OBS_CAP 2816
 #define K5_VIEW_CAP 256
 #define K5_KBUCKETS 65 /* list lengths 0..63 and "64 or more" */
+// The body has two instantiations. <uint32_t, true>: host clouds as eg3d_gn_filter uploads them (32-bit offsets with a
+// sentinel, validated on the host; ext is empty). <uint64_t, false>: device-resident clouds as the match path leaves them
+// (eg3d_device_edgepoints: 64-bit offsets, the last point ends at ext.n_obs), which nothing has validated: a list that
+// does not lie inside [0, n_obs] in ascending order, or a view id outside the rig, raises a bit of *ext.flags and the
+// point is skipped (no operand is read through a bad index). This form also takes the optional keep mask (a masked
+// point takes bucket 0 of the counting sort and costs no arithmetic) and accumulates the histogram of the inliers' list
+// lengths where the verdict and k are in registers: LDS bins per block and one 64-bit atomic per non-empty bin for rigs
+// of <= K5_VIEW_CAP views, global atomics otherwise (block-uniform). ext.hist has n_views + 2 bins: [k] for k <= n_views,
+// [n_views + 1] for longer lists.
+#define K5_SKIP 0x8000u /* s_perm: the point is masked out or malformed */
+template <typename OffT, bool SENTINEL>
 __global__ void __launch_bounds__(K5_BLOCK) k5_gn_filter(const float* cam_P, int n_views, const float* X,
-                                                        const uint32_t* obs_off, const int32_t* obs_view,
+                                                        const OffT* obs_off, const int32_t* obs_view,
                                                         const float* obs_xy, uint64_t n, float gn_max_mse,
-                                                        int legacy_abs, float* X_out, uint8_t* inlier) {
+                                                        int legacy_abs, float* X_out, uint8_t* inlier,
+                                                        K5Ext<SENTINEL> ext) {
   typedef const __attribute__((address_space(3))) float* lds_fp;
   typedef const __attribute__((address_space(3))) int32_t* lds_ip;
   __shared__ float sP[K5_VIEW_CAP * 12];
@@ -1807,26 +1819,72 @@ __global__ void __launch_bounds__(K5_BLOCK) k5_gn_filter(const float* cam_P, int
   __shared__ float sXY[2 * K5_OBS_CAP];
   __shared__ uint32_t s_cnt[K5_KBUCKETS], s_base[K5_KBUCKETS];
   __shared__ uint16_t s_perm[K5_BLOCK];
+  __shared__ uint32_t s_hist[SENTINEL ? 1 : K5_VIEW_CAP + 2];  // (never referenced by the host-cloud form: no LDS there)
   const uint64_t p0 = (uint64_t)blockIdx.x * K5_BLOCK;
   const uint64_t p1 = p0 + K5_BLOCK < n ? p0 + K5_BLOCK : n;
   const uint32_t np = (uint32_t)(p1 - p0);
-  const uint32_t o0 = obs_off[p0], o1 = obs_off[p1];
-  const uint32_t m = o1 - o0;
+  // end of point i's list
+  auto off_end = [&](uint64_t i) -> OffT {
+    if constexpr (SENTINEL)
+      return obs_off[i + 1];
+    else
+      return i + 1 < n ? obs_off[i + 1] : (OffT)ext.n_obs;
+  };
+  const OffT o0 = obs_off[p0], o1 = off_end(p1 - 1);
+  // the block's slice: a 64-bit difference on device clouds, held in 32 bits once it is known to fit the staging area
+  bool fits;
+  if constexpr (SENTINEL)
+    fits = (uint32_t)(o1 - o0) <= K5_OBS_CAP;
+  else
+    fits = o0 <= o1 && o1 <= ext.n_obs && o1 - o0 <= (OffT)K5_OBS_CAP;
+  const uint32_t m = (uint32_t)(o1 - o0);
   const uint32_t t = threadIdx.x;
-  const bool staged = n_views <= K5_VIEW_CAP && m <= K5_OBS_CAP;  // block-uniform
+  const bool staged = n_views <= K5_VIEW_CAP && fits;  // block-uniform
   if (staged) {
     for (uint32_t q = t; q < (uint32_t)n_views * 12u; q += K5_BLOCK) sP[q] = cam_P[(q / 12u) * 16u + q % 12u];
-    for (uint32_t q = t; q < m; q += K5_BLOCK) sV[q] = obs_view[o0 + q];
+    if constexpr (SENTINEL) {
+      for (uint32_t q = t; q < m; q += K5_BLOCK) sV[q] = obs_view[o0 + q];
+    } else {
+      bool bad_view = false;
+      for (uint32_t q = t; q < m; q += K5_BLOCK) {
+        const int32_t v = obs_view[o0 + q];
+        const bool bad = (uint32_t)v >= (uint32_t)n_views;
+        bad_view |= bad;
+        sV[q] = bad ? 0 : v;
+      }
+      if (bad_view) atomicOr(ext.flags, K5_FLAG_BAD_VIEW);
+    }
     for (uint32_t q = t; q < 2u * m; q += K5_BLOCK) sXY[q] = obs_xy[2 * (size_t)o0 + q];
   }
   if (t < K5_KBUCKETS) s_cnt[t] = 0;
+  if constexpr (!SENTINEL) {
+    if (n_views <= K5_VIEW_CAP)
+      for (uint32_t q = t; q < (uint32_t)n_views + 2u; q += K5_BLOCK) s_hist[q] = 0;
+  }
   __syncthreads();
   // ---- (1) counting sort of the block's points by list length (the order inside a bucket is whatever the LDS atomics
   // give: it decides which lane runs a point, not what the point computes)
   uint32_t kb = 0, rank = 0;
+  bool skip = false;
   if (t < np) {
-    const uint32_t k = obs_off[p0 + t + 1] - obs_off[p0 + t];
-    kb = k < K5_KBUCKETS - 1 ? k : K5_KBUCKETS - 1;
+    if constexpr (SENTINEL) {
+      const uint32_t k = obs_off[p0 + t + 1] - obs_off[p0 + t];
+      kb = k < K5_KBUCKETS - 1 ? k : K5_KBUCKETS - 1;
+    } else {
+      const OffT a = obs_off[p0 + t], b = off_end(p0 + t);
+      bool bad = !(a <= b && b <= ext.n_obs && b - a <= (OffT)K5_MAX_LIST) || (staged && !(a >= o0 && b <= o1));
+      if (!bad && !staged) {  // operands come straight from HBM: no view id may index past the rig's cameras
+        bool bad_view = false;
+        for (OffT q = a; q < b; q++) bad_view |= (uint32_t)obs_view[q] >= (uint32_t)n_views;
+        if (bad_view) atomicOr(ext.flags, K5_FLAG_BAD_VIEW);
+        bad = bad_view;
+      } else if (bad) {
+        atomicOr(ext.flags, K5_FLAG_BAD_OFFSETS);
+      }
+      skip = bad || (ext.keep && !ext.keep[p0 + t]);
+      const OffT k = skip ? 0 : b - a;
+      kb = k < K5_KBUCKETS - 1 ? (uint32_t)k : K5_KBUCKETS - 1;
+    }
     rank = atomicAdd(&s_cnt[kb], 1u);
   }
   __syncthreads();
@@ -1836,18 +1894,22 @@ __global__ void __launch_bounds__(K5_BLOCK) k5_gn_filter(const float* cam_P, int
     s_base[t] = base;
   }
   __syncthreads();
-  if (t < np) s_perm[s_base[kb] + rank] = (uint16_t)t;
+  if constexpr (SENTINEL) {
+    if (t < np) s_perm[s_base[kb] + rank] = (uint16_t)t;
+  } else {
+    if (t < np) s_perm[s_base[kb] + rank] = (uint16_t)(t | (skip ? K5_SKIP : 0u));
+  }
   __syncthreads();
   // ---- lane t takes the t-th point of the sorted order
   auto run_span = [&](uint32_t j, GnF32State& st, int it0, int it1) -> int {
     const uint64_t i = p0 + j;
-    const uint32_t a = obs_off[i], b = obs_off[i + 1];
+    const OffT a = obs_off[i], b = off_end(i);
     if (staged)
       return gauss_newton_f32_span((lds_fp)&sP[0], 12, (lds_ip)&sV[0] + (a - o0), (lds_fp)&sXY[0] + 2 * (a - o0), (int)(b - a),
                                    st, legacy_abs != 0, it0, it1);
     return gauss_newton_f32_span(cam_P, 16, obs_view + a, obs_xy + 2 * (size_t)a, (int)(b - a), st, legacy_abs != 0, it0, it1);
   };
-  auto finish = [&](uint32_t j, const GnF32State& st, int r) {  // gauss_newton.cpp:130-133: accepted on the last mse, converged or not
+  auto finish = [&](uint32_t j, const GnF32State& st, int r) -> bool {  // gauss_newton.cpp:130-133: accepted on the last mse, converged or not
     const uint64_t i = p0 + j;
     const bool ok = r != GN_F32_FAILED && st.last_mse < gn_max_mse;
     const float x0 = X[3 * i], x1 = X[3 * i + 1], x2 = X[3 * i + 2];
@@ -1855,16 +1917,211 @@ __global__ void __launch_bounds__(K5_BLOCK) k5_gn_filter(const float* cam_P, int
     X_out[3 * i] = ok ? st.X[0] : x0;
     X_out[3 * i + 1] = ok ? st.X[1] : x1;
     X_out[3 * i + 2] = ok ? st.X[2] : x2;
+    return ok;
   };
-  if (t < np) {
-    const uint32_t j = s_perm[t];
-    const uint64_t i = p0 + j;
-    GnF32State st;
-    st.X[0] = X[3 * i];
-    st.X[1] = X[3 * i + 1];
-    st.X[2] = X[3 * i + 2];
-    st.last_mse = 0;
-    finish(j, st, run_span(j, st, 0, 30));
+  if constexpr (SENTINEL) {
+    if (t < np) {
+      const uint32_t j = s_perm[t];
+      const uint64_t i = p0 + j;
+      GnF32State st;
+      st.X[0] = X[3 * i];
+      st.X[1] = X[3 * i + 1];
+      st.X[2] = X[3 * i + 2];
+      st.last_mse = 0;
+      finish(j, st, run_span(j, st, 0, 30));
+    }
+  } else {
+    const bool lds_bins = n_views <= K5_VIEW_CAP;  // block-uniform
+    if (t < np) {
+      const uint32_t pj = s_perm[t];
+      const uint32_t j = pj & (K5_SKIP - 1u);
+      const uint64_t i = p0 + j;
+      GnF32State st;
+      st.X[0] = X[3 * i];
+      st.X[1] = X[3 * i + 1];
+      st.X[2] = X[3 * i + 2];
+      st.last_mse = 0;
+      if (pj & K5_SKIP) {
+        inlier[i] = 0;
+        X_out[3 * i] = st.X[0];
+        X_out[3 * i + 1] = st.X[1];
+        X_out[3 * i + 2] = st.X[2];
+      } else if (finish(j, st, run_span(j, st, 0, 30))) {
+        const OffT k = off_end(i) - obs_off[i];
+        const uint32_t bin = k <= (OffT)n_views ? (uint32_t)k : (uint32_t)n_views + 1u;
+        if (lds_bins)
+          atomicAdd(&s_hist[bin], 1u);
+        else
+          atomicAdd(ext.hist + bin, 1ull);
+      }
+    }
+    if (lds_bins) {
+      __syncthreads();
+      for (uint32_t q = t; q < (uint32_t)n_views + 2u; q += K5_BLOCK) {
+        const uint32_t c = s_hist[q];
+        if (c) atomicAdd(ext.hist + q, (unsigned long long)c);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ K6 ---------
+// Order-preserving stream compaction of a device-resident cloud (all seven arrays), three launches:
+//   k6_compact_count    1 lane / point, K6_BLOCK points per block: surviving points and observations of the block
+//   k6_compact_scan     one workgroup: exclusive scan of the block totals, both columns 64-bit, totals appended
+//   k6_compact_scatter  1 WAVE / 64 source points (shaped like k4_emit): __ballot + popcount rank the surviving points,
+//                       wave_incl_scan gives their observation offsets; then the lanes stride over the wave's contiguous
+//                       DESTINATION observation range and each finds its source point by a binary search over the <= 64
+//                       offsets the wave holds in LDS — the stores of the five observation arrays are coalesced rows, the
+//                       loads are coalesced within every surviving list.
+// A list that is not an ascending range inside [0, n_obs], or longer than K5_MAX_LIST, drops its point and raises
+// K5_FLAG_BAD_OFFSETS in the count pass (the host then fails the call before anything is scattered).
+struct K6Pt {
+  bool surv;
+  uint32_t k;
+  uint64_t a;
+};
+__device__ __forceinline__ K6Pt k6_point(const CloudView& in, const uint8_t* keep, int32_t min_obs, uint64_t i, bool* bad) {
+  K6Pt p{false, 0, 0};
+  if (i >= in.n_points) return p;
+  const uint64_t a = in.obs_off[i], b = i + 1 < in.n_points ? in.obs_off[i + 1] : in.n_obs;
+  if (!(a <= b && b <= in.n_obs && b - a <= (uint64_t)K5_MAX_LIST)) {
+    *bad = true;
+    return p;
+  }
+  p.a = a;
+  p.k = (uint32_t)(b - a);
+  p.surv = (!keep || keep[i]) && (min_obs < 0 || p.k > (uint32_t)min_obs);
+  return p;
+}
+__global__ void __launch_bounds__(K6_BLOCK) k6_compact_count(CloudView in, const uint8_t* keep, int32_t min_obs,
+                                                            unsigned long long* blk, uint32_t* flags) {
+  __shared__ uint32_t s_p[K6_BLOCK / 64], s_o[K6_BLOCK / 64];
+  const uint32_t t = threadIdx.x, w = t >> 6;
+  bool bad = false;
+  const K6Pt p = k6_point(in, keep, min_obs, (uint64_t)blockIdx.x * K6_BLOCK + t, &bad);
+  if (bad) atomicOr(flags, K5_FLAG_BAD_OFFSETS);
+  const uint32_t np = (uint32_t)__popcll(__ballot(p.surv));
+  const uint32_t no = lane_bcast((uint32_t)wave_incl_scan((int)(p.surv ? p.k : 0u)), 63);  // <= 64 x 2^24
+  if ((t & 63u) == 0) {
+    s_p[w] = np;
+    s_o[w] = no;
+  }
+  __syncthreads();
+  if (t == 0) {
+    unsigned long long sp = 0, so = 0;
+    for (uint32_t q = 0; q < K6_BLOCK / 64; q++) {
+      sp += s_p[q];
+      so += s_o[q];
+    }
+    blk[2 * (uint64_t)blockIdx.x] = sp;
+    blk[2 * (uint64_t)blockIdx.x + 1] = so;
+  }
+}
+__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long v) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long u = __shfl_up(v, d, 64);
+    if (lane >= (uint32_t)d) v += u;
+  }
+  return v;
+}
+__global__ void __launch_bounds__(1024) k6_compact_scan(uint64_t n_blocks, unsigned long long* blk) {
+  __shared__ unsigned long long s_p[16], s_o[16];
+  const uint32_t t = threadIdx.x, w = t >> 6;
+  unsigned long long base_p = 0, base_o = 0;
+  for (uint64_t c0 = 0; c0 < n_blocks; c0 += 1024) {
+    const uint64_t i = c0 + t;
+    const unsigned long long vp = i < n_blocks ? blk[2 * i] : 0, vo = i < n_blocks ? blk[2 * i + 1] : 0;
+    const unsigned long long ip = wave_incl_scan_u64(vp), io = wave_incl_scan_u64(vo);
+    if ((t & 63u) == 63u) {
+      s_p[w] = ip;
+      s_o[w] = io;
+    }
+    __syncthreads();
+    unsigned long long pre_p = 0, pre_o = 0, tot_p = 0, tot_o = 0;
+    for (uint32_t q = 0; q < 16; q++) {
+      if (q < w) {
+        pre_p += s_p[q];
+        pre_o += s_o[q];
+      }
+      tot_p += s_p[q];
+      tot_o += s_o[q];
+    }
+    if (i < n_blocks) {
+      blk[2 * i] = base_p + pre_p + ip - vp;
+      blk[2 * i + 1] = base_o + pre_o + io - vo;
+    }
+    base_p += tot_p;
+    base_o += tot_o;
+    __syncthreads();
+  }
+  if (t == 0) {
+    blk[2 * n_blocks] = base_p;
+    blk[2 * n_blocks + 1] = base_o;
+  }
+}
+template <bool NT, typename T>
+__device__ __forceinline__ T k6_load(const T* p) {
+  if constexpr (NT)
+    return __builtin_nontemporal_load(p);
+  else
+    return *p;
+}
+template <bool NT>
+__global__ void __launch_bounds__(K6_BLOCK) k6_compact_scatter(CloudView in, const uint8_t* keep, const float* X_new,
+                                                              int32_t min_obs, const unsigned long long* blk, CloudOut out) {
+  __shared__ uint32_t s_p[K6_BLOCK / 64], s_o[K6_BLOCK / 64];
+  __shared__ uint32_t s_incl[K6_BLOCK / 64][64];  // inclusive sums of the surviving lists of the wave's points
+  __shared__ uint64_t s_src[K6_BLOCK / 64][64];   // first source observation of the point minus its exclusive sum
+  const uint32_t t = threadIdx.x, w = t >> 6, lane = t & 63u;
+  const uint64_t i = (uint64_t)blockIdx.x * K6_BLOCK + t;
+  bool bad = false;
+  const K6Pt p = k6_point(in, keep, min_obs, i, &bad);
+  const unsigned long long mask = __ballot(p.surv);
+  const uint32_t prank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+  const uint32_t ks = p.surv ? p.k : 0u;
+  const uint32_t incl = (uint32_t)wave_incl_scan((int)ks);
+  const uint32_t wave_obs = lane_bcast(incl, 63);
+  s_incl[w][lane] = incl;
+  s_src[w][lane] = p.a - (uint64_t)(incl - ks);
+  if (lane == 0) {
+    s_p[w] = (uint32_t)__popcll(mask);
+    s_o[w] = wave_obs;
+  }
+  __syncthreads();
+  uint64_t pbase = blk[2 * (uint64_t)blockIdx.x], obase = blk[2 * (uint64_t)blockIdx.x + 1];
+  for (uint32_t q = 0; q < w; q++) {
+    pbase += s_p[q];
+    obase += s_o[q];
+  }
+  if (p.surv) {
+    const uint64_t d = pbase + prank;
+    const float* xs = X_new ? X_new : in.X;
+    out.X[3 * d] = k6_load<NT>(xs + 3 * i);
+    out.X[3 * d + 1] = k6_load<NT>(xs + 3 * i + 1);
+    out.X[3 * d + 2] = k6_load<NT>(xs + 3 * i + 2);
+    out.obs_off[d] = obase + (incl - ks);
+    out.key[4 * d] = k6_load<NT>(in.key + 4 * i);
+    out.key[4 * d + 1] = k6_load<NT>(in.key + 4 * i + 1);
+    out.key[4 * d + 2] = k6_load<NT>(in.key + 4 * i + 2);
+    out.key[4 * d + 3] = k6_load<NT>(in.key + 4 * i + 3);
+  }
+  for (uint32_t f = lane; f < wave_obs; f += 64) {
+    uint32_t lo = 0, hi = 63;  // the first lane whose inclusive sum exceeds f (it exists: f < s_incl[w][63])
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (s_incl[w][mid] > f)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    const uint64_t so = s_src[w][lo] + f, o = obase + f;
+    out.obs_view[o] = k6_load<NT>(in.obs_view + so);
+    out.obs_pl[o] = k6_load<NT>(in.obs_pl + so);
+    out.obs_seg[o] = k6_load<NT>(in.obs_seg + so);
+    *(unsigned long long*)(out.obs_xy + 2 * o) = k6_load<NT>((const unsigned long long*)(in.obs_xy + 2 * so));  // (x, y) as one 8-byte word
   }
 }
 
@@ -2126,8 +2383,33 @@ void launch_k5(hipStream_t st, const float* cam_P, int n_views, const float* X, 
                const int32_t* obs_view, const float* obs_xy, uint64_t n, float gn_max_mse, int legacy_abs, float* X_out,
                uint8_t* inlier) {
   if (!n) return;
-  hipLaunchKernelGGL(k5_gn_filter, blocks_for(n, K5_BLOCK), dim3(K5_BLOCK), 0, st, cam_P, n_views, X, obs_off, obs_view,
-                     obs_xy, n, gn_max_mse, legacy_abs, X_out, inlier);
+  hipLaunchKernelGGL((k5_gn_filter<uint32_t, true>), blocks_for(n, K5_BLOCK), dim3(K5_BLOCK), 0, st, cam_P, n_views, X, obs_off,
+                     obs_view, obs_xy, n, gn_max_mse, legacy_abs, X_out, inlier, K5Host{});
+}
+void launch_k5_device(hipStream_t st, const float* cam_P, int n_views, const float* X, const eg3d_off_t* obs_off,
+                      const int32_t* obs_view, const float* obs_xy, uint64_t n, float gn_max_mse, int legacy_abs, float* X_out,
+                      uint8_t* inlier, K5Dev ext) {
+  if (!n) return;
+  hipLaunchKernelGGL((k5_gn_filter<eg3d_off_t, false>), blocks_for(n, K5_BLOCK), dim3(K5_BLOCK), 0, st, cam_P, n_views, X,
+                     obs_off, obs_view, obs_xy, n, gn_max_mse, legacy_abs, X_out, inlier, ext);
+}
+void launch_compact_count(hipStream_t st, CloudView in, const uint8_t* keep, int32_t min_obs, unsigned long long* blk,
+                          uint32_t* flags) {
+  if (!in.n_points) return;
+  hipLaunchKernelGGL(k6_compact_count, blocks_for(in.n_points, K6_BLOCK), dim3(K6_BLOCK), 0, st, in, keep, min_obs, blk, flags);
+}
+void launch_compact_scan(hipStream_t st, uint64_t n_blocks, unsigned long long* blk) {
+  hipLaunchKernelGGL(k6_compact_scan, dim3(1), dim3(1024), 0, st, n_blocks, blk);
+}
+void launch_compact_scatter(hipStream_t st, CloudView in, const uint8_t* keep, const float* X_new, int32_t min_obs,
+                            const unsigned long long* blk, CloudOut out, bool nt) {
+  if (!in.n_points) return;
+  if (nt)
+    hipLaunchKernelGGL(k6_compact_scatter<true>, blocks_for(in.n_points, K6_BLOCK), dim3(K6_BLOCK), 0, st, in, keep, X_new,
+                       min_obs, blk, out);
+  else
+    hipLaunchKernelGGL(k6_compact_scatter<false>, blocks_for(in.n_points, K6_BLOCK), dim3(K6_BLOCK), 0, st, in, keep, X_new,
+                       min_obs, blk, out);
 }
 
 }  // namespace eg3d

@@ -336,3 +336,64 @@ class HostCloudGather:
         out["obs_xy"] = out["obs_xy"].reshape(-1, 2)
         out["n_points"], out["n_obs"] = tp, to
         return out, 0
+
+
+# ---- the filter stage over ranks: each rank filters the shard it already holds in HBM, only the survivors travel ----
+def observation_threshold(hist, n_views, forced_min_filter=-1, count=None):
+    """The rule of eg3d_host_observation_filter (host/post_steps.cpp) on a histogram by list length: hist[k] = points with
+    k observations, k = 0 .. n_views; `count` = all points, those with longer lists included (default: the histogram's
+    sum). The median bin, then max(3, median // 2 - 1); forced_min_filter > -1 overrides. A point is kept with MORE
+    observations than the result."""
+    hist = [int(h) for h in hist]
+    if len(hist) != n_views + 1:
+        raise ValueError("the histogram needs n_views + 1 entries")
+    count = sum(hist) if count is None else int(count)
+    acc, median = 0, n_views
+    for m in range(n_views):
+        acc += hist[m + 1]
+        if acc >= count // 2:
+            median = m
+            break
+    threshold = max(3, median // 2 - 1)
+    return int(forced_min_filter) if forced_min_filter > -1 else threshold
+
+
+def global_observation_threshold(dist, local_hist, n_views, forced_min_filter=-1, base_hist=None, local_count=None):
+    """Sum-all-reduce of the ranks' int64 histograms (Context.gn_filter_device returns one per shard), then the threshold
+    of the whole cloud, the same on every rank. base_hist: the caller's SfM points ([n_views + 1], the same on every
+    rank: added once). local_count: this rank's inliers when some have more than n_views observations (default: the
+    histogram's sum). dist = torch.distributed, or None for a single process."""
+    v = [int(h) for h in local_hist]
+    if len(v) != n_views + 1:
+        raise ValueError("the histogram needs n_views + 1 entries")
+    t = torch.tensor(v + [sum(v) if local_count is None else int(local_count)], dtype=torch.int64)
+    if dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+        if dist.get_backend() == "nccl":
+            t = t.cuda()
+        dist.all_reduce(t)
+        t = t.cpu()
+    hist, count = t[:-1].tolist(), int(t[-1])
+    if base_hist is not None:
+        if len(base_hist) != n_views + 1:
+            raise ValueError("base_hist needs n_views + 1 entries")
+        hist = [h + int(b) for h, b in zip(hist, base_hist)]
+        count += sum(int(b) for b in base_hist)
+    return observation_threshold(hist, n_views, forced_min_filter, count)
+
+
+def filter_then_gather(ctx, gather, dist, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, keep=None):
+    """The end of a multi-GPU run without a gathered intermediate: (1) Context.gn_filter_device on this rank's
+    device-only cloud (keep: optional device mask of the shard, e.g. its dedup mask), (2) the global threshold,
+    (3) Context.compact_device of the inliers above it, new X in place, (4) gather.allgather of the compacted shard.
+    Returns (DeviceEdgePoints of all ranks' survivors, rc of the gather, threshold). Every rank must call it."""
+    cloud = ctx.last_device_output()
+    if not cloud.complete:
+        raise RuntimeError("the device view does not hold the whole cloud of the last call")
+    # (inliers with more observations than views sit in no bin: n_inl counts them too)
+    X_out, inlier, hist, n_inl, _ = ctx.gn_filter_device(cloud, keep, gn_max_mse, legacy_abs)
+    thr = global_observation_threshold(dist, hist, ctx.n_views, forced_min_filter, base_hist, local_count=n_inl)
+    shard = ctx.compact_device(cloud, inlier, X_out, thr)
+    out, rc = gather.allgather(shard)
+    X_out.free()
+    inlier.free()
+    return out, rc, thr

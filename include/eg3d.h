@@ -256,6 +256,66 @@ int eg3d_gn_filter(eg3d_ctx* ctx, const float* X, const uint32_t* obs_off, const
                    const float* obs_xy, uint64_t n_points, float gn_max_mse, int legacy_abs,
                    float* X_out, uint8_t* inlier, float* ms_kernel /* may be NULL */);
 
+/* The view count of the context's scene and the HIP device it lives on (either pointer may be NULL); clones answer too. */
+int eg3d_context_info(eg3d_ctx* ctx, int32_t* n_views, int32_t* device);
+
+/* ---- the filter stage on a device-resident cloud ------------------------------------------------------------------
+ * gaussNewtonFiltering, the observation-count filter and the copy of the survivors (gauss_newton.cpp:136-178,
+ * outliers_filtering.cpp:14-114) on a cloud that is already in HBM: this context's last output after a device_only call,
+ * the result of the multi-GPU gather or concatenation (include/eg3d_rccl.h), or caller-built device arrays. Offsets are
+ * 64-bit without a sentinel (the last point ends at n_obs), so clouds of 2^32 observations and more pass. Nothing is
+ * validated on the host: the kernels check what they index, and a view id outside the context's rig, offsets that do not
+ * ascend within [0, n_obs] or a single list of more than 2^24 observations fail the call with EG3D_ERR_ARG (the outputs
+ * are then unspecified). One caller thread at a time per context, as everywhere. Caller-built arrays must be aligned as
+ * hipMalloc aligns them, at least to their element: 4 bytes for X, key, obs_view, obs_pl and obs_seg, 8 bytes for obs_off and
+ * for obs_xy (an (x, y) pair moves as one 8-byte word).
+ *
+ * Order of the reference: it removes points whose observations fall within 3 px of an earlier point's
+ * (filter_3d_points_close_2d_array; sequential, host: the host library's filter_close_2d step) BEFORE it filters. The
+ * Gauss-Newton verdict of a point depends on that point alone, so the reference-exact sequence is
+ *   1. host dedup mask -> upload as keep_dev -> the Gauss-Newton filter below;
+ *   2. the compaction with keep = dedup AND inlier, min_obs = the observation threshold.
+ *
+ * Gauss-Newton filter. keep_dev: optional device byte mask, NULL = all points; a masked-out point costs no arithmetic, gets
+ * inlier 0 and X_out = X. Per point the arithmetic is that of the host-array entry point above, bit for bit (both abs
+ * behaviours of Q9). X_out_dev ([n_points][3]) may alias cloud->X; inlier_dev is [n_points]. obs_hist_host, optional,
+ * [n_views + 1]: entry k = number of inliers with k observations; lists longer than n_views go to no bin, as in the host
+ * library's observation filter. n_inliers_host, optional: the number of ALL inliers, those of no bin included — the count
+ * the threshold rule needs beside the histogram, without a copy of inlier_dev. */
+int eg3d_gn_filter_device(eg3d_ctx* ctx, const eg3d_device_edgepoints* cloud, const uint8_t* keep_dev, float gn_max_mse,
+                          int legacy_abs, float* X_out_dev, uint8_t* inlier_dev, uint64_t* obs_hist_host /* may be NULL */,
+                          uint64_t* n_inliers_host /* may be NULL */, float* ms_kernel /* may be NULL */);
+/* Order-preserving stream compaction of all seven arrays: keeps the points with keep_dev[i] != 0 (NULL = all) AND more than
+ * min_obs observations (min_obs < 0: no count test); X_new_dev, if given, replaces X. The result lives in buffers of the
+ * context that are separate from the match output, and is valid until the next compaction on this context or its
+ * destruction; complete = 1 and obs_off has no sentinel, so it feeds the multi-GPU gather unchanged. `out` must not alias
+ * `cloud`, and `cloud` must not view the result of an earlier compaction on this context (EG3D_ERR_ARG). */
+int eg3d_compact_device(eg3d_ctx* ctx, const eg3d_device_edgepoints* cloud, const uint8_t* keep_dev,
+                        const float* X_new_dev /* may be NULL */, int32_t min_obs, eg3d_device_edgepoints* out);
+/* Filled by the composition below. struct_size: the CALLER sets it to sizeof(eg3d_filter_stats) before the call; a value
+ * smaller than the library's struct is refused with EG3D_ERR_ARG before anything is written (new members are appended). */
+typedef struct eg3d_filter_stats {
+  uint32_t struct_size;
+  int32_t threshold;       /* a point is kept with MORE observations than this */
+  uint64_t n_points_in;    /* points of the cloud */
+  uint64_t n_masked_in;    /* ... that the keep mask let through (no mask here: all) */
+  uint64_t n_gn_inliers;   /* ... accepted by the Gauss-Newton filter */
+  uint64_t n_kept;         /* ... that also passed the observation threshold */
+  uint64_t n_obs_kept;     /* observations of the kept points */
+  float ms_filter;         /* the filter kernel (HIP events) */
+  float ms_compact;        /* the three compaction launches and the read-back of their totals (HIP events) */
+  float ms_copy;           /* the copy of the survivors to the host (wall; 0 without to_host) */
+} eg3d_filter_stats;
+/* Convenience composition on the context's last device output (which must be `complete`): Gauss-Newton filter WITHOUT a
+ * mask, threshold by the rule of the host library's observation filter over the histogram of the inliers plus base_hist
+ * (optional, [n_views + 1], entry k = the caller's SfM points with k observations, which the reference counts in the same
+ * histogram): the median bin, max(3, median / 2 - 1), overridden by forced_min_filter > -1; compaction; with to_host a copy
+ * of the survivors into a library-owned cloud (obs_off with its sentinel; release with eg3d_free_edgepoints). out_host is
+ * required with to_host; out_dev and stats may be NULL. This filters the cloud as matched, NOT deduplicated: it is not the
+ * reference's filter step (see the order above). */
+int eg3d_filter_resident(eg3d_ctx* ctx, float gn_max_mse, int legacy_abs, int forced_min_filter, const uint64_t* base_hist,
+                         int to_host, eg3d_edgepoints* out_host, eg3d_device_edgepoints* out_dev, eg3d_filter_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
