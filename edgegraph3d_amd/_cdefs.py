@@ -59,6 +59,14 @@ class FilterStats(C.Structure):
                 ("n_obs_kept", C.c_uint64), ("ms_filter", C.c_float), ("ms_compact", C.c_float), ("ms_copy", C.c_float)]
 
 
+class DedupStats(C.Structure):
+    """eg3d_dedup_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_int32), ("n_points_in", C.c_uint64),
+                ("n_dedup_kept", C.c_uint64), ("n_gn_inliers", C.c_uint64), ("n_kept", C.c_uint64),
+                ("n_obs_kept", C.c_uint64), ("ms_dedup", C.c_float), ("ms_filter", C.c_float), ("ms_compact", C.c_float),
+                ("ms_copy", C.c_float)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("n_seeds", C.c_uint32), ("n_curves", C.c_int32),
                 ("rng_seed", C.c_uint64), ("max_track", C.c_int32), ("obs_noise_px", C.c_float),

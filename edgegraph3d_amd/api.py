@@ -63,6 +63,10 @@ def lib():
                                           C.POINTER(D.DeviceEdgePoints)]
         L.eg3d_filter_resident.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, D.u64p, C.c_int,
                                            C.POINTER(D.EdgePoints), C.POINTER(D.DeviceEdgePoints), C.POINTER(D.FilterStats)]
+        L.eg3d_dedup_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.c_uint64, C.c_int, C.c_void_p, D.u64p]
+        L.eg3d_dedup_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, D.u64p,
+                                          C.c_int, C.POINTER(D.EdgePoints), C.POINTER(D.DeviceEdgePoints),
+                                          C.POINTER(D.DedupStats)]
         _LIB = L
     return _LIB
 
@@ -73,6 +77,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_free_candidates", "eg3d_match_refpoints", "eg3d_free_edgepoints", "eg3d_upload_seeds",
     "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
+    "eg3d_dedup_device", "eg3d_dedup_resident",
 ]
 
 
@@ -403,3 +408,38 @@ class Context:
             d = D.edgepoints_to_dict(e)
             lib().eg3d_free_edgepoints(C.byref(e))
         return d, dv, {f[0]: getattr(st, f[0]) for f in D.FilterStats._fields_}
+
+    # ---- the 3 px dedup on a device-resident cloud (include/eg3d.h) ----
+    def dedup_device(self, cloud, index_base=0, reset=True, keep=None):
+        """eg3d_dedup_device on `cloud` (a DeviceEdgePoints): the mask by the first-claim rule (cloudnp.np_dedup) against
+        this context's claim map. reset: clear the map first; otherwise the claims of the earlier calls stand and this
+        cloud's points count from index_base. keep: DeviceArray or device address of n_points bytes, allocated when not
+        given. Returns (keep, n_kept)."""
+        n = int(cloud.n_points)
+        keep = keep if keep is not None else DeviceArray(n, self.device)
+        n_kept = C.c_uint64(0)
+        _check(lib().eg3d_dedup_device(self._h, C.byref(cloud), int(index_base), 1 if reset else 0, _dev_ptr(keep),
+                                       C.byref(n_kept)), "eg3d_dedup_device")
+        return keep, int(n_kept.value)
+
+    def dedup_resident(self, index_base=0, reset=True, with_filter=False, gn_max_mse=2.25, legacy_abs=False,
+                       forced_min_filter=-1, base_hist=None, to_host=True):
+        """eg3d_dedup_resident on the last device output: dedup, optionally the Gauss-Newton filter and the observation
+        threshold, compaction, optionally the copy of the survivors. Returns (cloud dict or None, DeviceEdgePoints, stats
+        dict)."""
+        e, dv, st = D.EdgePoints(), D.DeviceEdgePoints(), D.DedupStats()
+        st.struct_size = C.sizeof(D.DedupStats)
+        bh = None
+        if base_hist is not None:
+            bh = np.ascontiguousarray(base_hist, np.uint64)
+            if len(bh) != self.n_views + 1:
+                raise ValueError("base_hist needs n_views + 1 entries")
+        _check(lib().eg3d_dedup_resident(self._h, int(index_base), 1 if reset else 0, 1 if with_filter else 0, gn_max_mse,
+                                         1 if legacy_abs else 0, int(forced_min_filter),
+                                         D.np_ptr(bh, C.c_uint64) if bh is not None else None, 1 if to_host else 0,
+                                         C.byref(e) if to_host else None, C.byref(dv), C.byref(st)), "eg3d_dedup_resident")
+        d = None
+        if to_host:
+            d = D.edgepoints_to_dict(e)
+            lib().eg3d_free_edgepoints(C.byref(e))
+        return d, dv, {f[0]: getattr(st, f[0]) for f in D.DedupStats._fields_}

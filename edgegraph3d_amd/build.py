@@ -199,6 +199,9 @@ RESOURCE_BOUNDS = {
     # device clouds (eg3d_gn_filter_device): + the 258 histogram bins (measured: 62 VGPRs, 48 164 B)
     "k5_gn_filter<unsigned long, false>": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 48164},
     "k6_compact_scatter": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 3104},
+    # the 3 px dedup (eg3d_dedup_device): 64 staged 64-bit offsets per wave / one count per wave; no spills, no scratch
+    "k7_dedup_claim": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},
+    "k7_dedup_keep": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 16},
     "k2_epipolar_hits": {"vgpr_spill_count": 0},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }

@@ -1,5 +1,6 @@
-"""Host-side helpers on cloud dicts (numpy): order-preserving compaction and bit-exact comparison — what the tests and
-tools/bench_filter_resident.py compare the device-resident filter stage with."""
+"""Host-side helpers on cloud dicts (numpy): order-preserving compaction, the 3 px dedup as the first-claim rule and
+bit-exact comparison — what the tests, tools/bench_filter_resident.py and tools/bench_dedup_resident.py compare the
+device-resident filter and dedup stages with."""
 import numpy as np
 
 ARRAYS = ("X", "obs_off", "key", "obs_view", "obs_pl", "obs_seg", "obs_xy")
@@ -19,6 +20,47 @@ def np_compact(c, keep, X_new=None, min_obs=-1):
             "obs_off": np.concatenate([[0], np.cumsum(k[sel])]).astype(np.uint64), "key": c["key"][sel],
             "obs_view": c["obs_view"][osel], "obs_pl": c["obs_pl"][osel], "obs_seg": c["obs_seg"][osel],
             "obs_xy": c["obs_xy"][osel]}
+
+
+DEDUP_CELL = 3
+UNCLAIMED = 0xFFFFFFFF
+
+
+def dedup_claims(n_views, width, height):
+    """An empty claim map for np_dedup: one entry per 3 px cell of every view (0xFFFFFFFF = no point has touched it)."""
+    w, h = int(np.ceil(np.float32(width) / np.float32(DEDUP_CELL))), int(np.ceil(np.float32(height) / np.float32(DEDUP_CELL)))
+    return np.full((int(n_views), h, w), UNCLAIMED, np.uint32)
+
+
+def np_dedup(c, n_views, width, height, claims=None, index_base=0):
+    """The 3 px dedup (eg3d_host_filter_close_2d, eg3d_dedup_device) of a host cloud dict as the first-claim rule: the first
+    point that touches a cell is always kept, so keep[i] = some observation of i lies in a valid cell whose smallest
+    touching point index is i. Two order-independent passes: a minimum per cell, one test per point. claims: a map from
+    dedup_claims that is updated in place (None: a fresh one); with the map of cloud A and index_base = |A| the mask of
+    cloud B is the second half of the mask of A || B. Returns the uint8 mask."""
+    off = np.asarray(c["obs_off"]).astype(np.int64)
+    n = len(off) - 1
+    if claims is None:
+        claims = dedup_claims(n_views, width, height)
+    V, h, w = claims.shape
+    if index_base + n >= UNCLAIMED:
+        raise ValueError("index_base + n_points must stay below 2^32 - 1")
+    a, b = int(off[0]), int(off[-1])
+    view = np.asarray(c["obs_view"], np.int32)[a:b].astype(np.int64)
+    xy = np.asarray(c["obs_xy"], np.float32).reshape(-1, 2)[a:b]
+    with np.errstate(invalid="ignore", over="ignore"):
+        fx, fy = xy[:, 0] / np.float32(DEDUP_CELL), xy[:, 1] / np.float32(DEDUP_CELL)   # float32, a true division
+        ok = (view >= 0) & (view < V) & (fx > -1) & (fy > -1) & (fx < np.float32(w)) & (fy < np.float32(h))  # NaN fails
+        cx, cy = np.trunc(np.where(ok, fx, 0)).astype(np.int64), np.trunc(np.where(ok, fy, 0)).astype(np.int64)
+    ok &= (cx >= 0) & (cy >= 0) & (cx < w) & (cy < h)     # (-1, 0) truncates to cell 0
+    owner = np.repeat(np.arange(n, dtype=np.int64), np.diff(off)) + int(index_base)
+    cell = ((view * h + cy) * w + cx)[ok]
+    flat = claims.reshape(-1)
+    np.minimum.at(flat, cell, owner[ok].astype(np.uint32))
+    keep = np.zeros(n, np.uint8)
+    mine = flat[cell] == owner[ok]
+    keep[owner[ok][mine] - int(index_base)] = 1
+    return keep
 
 
 def same_cloud(a, b):

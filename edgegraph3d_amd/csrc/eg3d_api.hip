@@ -60,6 +60,22 @@ struct DevBuf {
     cap = want;
     return EG3D_OK;
   }
+  // exactly `bytes` (no growth reserve): for a buffer whose size is fixed by the scene and may be hundreds of MB
+  int ensure_exact(size_t bytes) {
+    bytes = std::max<size_t>(bytes, 256);
+    if (p && cap == bytes) return EG3D_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+      p = nullptr;
+      g_err = std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
+      return EG3D_ERR_HIP;
+    }
+    cap = bytes;
+    return EG3D_OK;
+  }
   // grow, keeping the first `keep` bytes (device-to-device copy on `st`, old block freed once it is done)
   int ensure_keep(size_t bytes, size_t keep, hipStream_t st) {
     if (bytes <= cap && p) return EG3D_OK;
@@ -232,6 +248,10 @@ struct eg3d_ctx {
   // compaction, the compacted cloud (valid until the next compaction), X_out / inlier of eg3d_filter_resident
   DevBuf r_hist, r_blk, r_Xo, r_inl, c_X, c_off, c_view, c_pl, c_seg, c_xy, c_key;
   bool compact_nt = false;  // EG3D_COMPACT_NT=1 (read by eg3d_create): non-temporal loads of the compaction's source
+  // eg3d_dedup_device / eg3d_dedup_resident: the claim map (this context's own; created on first use), the kept count +
+  // flag word, the mask of eg3d_dedup_resident
+  DevBuf d_first, d_cnt, d_keep;
+  bool dedup_valid = false;   // the claim map holds the claims of the earlier calls (false: it is filled before use)
   DevBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
@@ -929,7 +949,7 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
                    &c->b_nhyp, &c->b_hyp_off, &c->b_res, &c->b_arena, &c->b_ctr, &c->b_cs_task,
                    &c->b_valid, &c->b_chain_off, &c->b_chains, &c->b_cscratch, &c->b_couts, &c->b_cpts, &c->b_cobs,
                    &c->b_cpoff, &c->b_cooff, &c->b_scan_tmp, &c->b_scanchk, &c->b_cost, &c->b_cidx, &c->b_cost2, &c->b_order, &c->b_redo[0], &c->b_redo[1], &c->o_X, &c->o_off, &c->o_view, &c->o_pl, &c->o_seg,
-                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->r_hist, &c->r_blk, &c->r_Xo, &c->r_inl, &c->c_X, &c->c_off, &c->c_view, &c->c_pl, &c->c_seg, &c->c_xy, &c->c_key, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
+                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->r_hist, &c->r_blk, &c->r_Xo, &c->r_inl, &c->c_X, &c->c_off, &c->c_view, &c->c_pl, &c->c_seg, &c->c_xy, &c->c_key, &c->d_first, &c->d_cnt, &c->d_keep, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
                    &c->b_pools, &c->b_stage_pts, &c->b_stage_obs, &c->b_stage_used};
   for (DevBuf* b : all) b->release();
   if (c->pinned) (void)hipHostFree(c->pinned);
@@ -2641,6 +2661,50 @@ static int observation_threshold(const uint64_t* hist, int V, uint64_t count, in
   return threshold;
 }
 
+// The copy of a compacted cloud into a library-owned host cloud (obs_off with its sentinel); *ms_copy: wall time.
+static int copy_survivors_to_host(eg3d_ctx* c, const eg3d_device_edgepoints& o, eg3d_edgepoints* out_host, const char* who,
+                                  float* ms_copy) {
+  const auto t0 = std::chrono::steady_clock::now();
+  memset(out_host, 0, sizeof(*out_host));
+  const uint64_t np = o.n_points, no = o.n_obs;
+  out_host->X = (float*)malloc(12 * std::max<uint64_t>(np, 1));
+  out_host->obs_off = (uint64_t*)malloc(8 * (np + 1));
+  out_host->key = (uint32_t*)malloc(16 * std::max<uint64_t>(np, 1));
+  out_host->obs_view = (int32_t*)malloc(4 * std::max<uint64_t>(no, 1));
+  out_host->obs_pl = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
+  out_host->obs_seg = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
+  out_host->obs_xy = (float*)malloc(8 * std::max<uint64_t>(no, 1));
+  if (!out_host->X || !out_host->obs_off || !out_host->key || !out_host->obs_view || !out_host->obs_pl ||
+      !out_host->obs_seg || !out_host->obs_xy) {
+    eg3d_free_edgepoints(out_host);
+    g_err = std::string(who) + ": out of host memory";
+    return EG3D_ERR_HIP;
+  }
+  struct { void* dst; const void* src; size_t bytes; } cp[] = {
+      {out_host->X, o.X, 12 * np},          {out_host->obs_off, o.obs_off, 8 * np}, {out_host->key, o.key, 16 * np},
+      {out_host->obs_view, o.obs_view, 4 * no}, {out_host->obs_pl, o.obs_pl, 4 * no},   {out_host->obs_seg, o.obs_seg, 4 * no},
+      {out_host->obs_xy, o.obs_xy, 8 * no}};
+  for (auto& q : cp)
+    if (q.bytes) {
+      const hipError_t e = hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream);
+      if (e != hipSuccess) {
+        eg3d_free_edgepoints(out_host);
+        g_err = std::string(who) + ": copy to the host: " + hipGetErrorString(e);
+        return EG3D_ERR_HIP;
+      }
+    }
+  if (hipStreamSynchronize(c->stream) != hipSuccess) {
+    eg3d_free_edgepoints(out_host);
+    g_err = std::string(who) + ": copy to the host failed";
+    return EG3D_ERR_HIP;
+  }
+  out_host->obs_off[np] = no;
+  out_host->n_points = np;
+  out_host->n_obs = no;
+  *ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return EG3D_OK;
+}
+
 extern "C" int eg3d_filter_resident(eg3d_ctx* c, float gn_max_mse, int legacy_abs, int forced_min_filter,
                                     const uint64_t* base_hist, int to_host, eg3d_edgepoints* out_host,
                                     eg3d_device_edgepoints* out_dev, eg3d_filter_stats* stats) {
@@ -2676,46 +2740,7 @@ extern "C" int eg3d_filter_resident(eg3d_ctx* c, float gn_max_mse, int legacy_ab
   eg3d_device_edgepoints o;
   BUF_TRY(compact_device_impl(c, &d, c->r_inl.as<uint8_t>(), c->r_Xo.as<float>(), threshold, &o, &ms_compact));
   float ms_copy = 0;
-  if (to_host) {
-    const auto t0 = std::chrono::steady_clock::now();
-    memset(out_host, 0, sizeof(*out_host));
-    const uint64_t np = o.n_points, no = o.n_obs;
-    out_host->X = (float*)malloc(12 * std::max<uint64_t>(np, 1));
-    out_host->obs_off = (uint64_t*)malloc(8 * (np + 1));
-    out_host->key = (uint32_t*)malloc(16 * std::max<uint64_t>(np, 1));
-    out_host->obs_view = (int32_t*)malloc(4 * std::max<uint64_t>(no, 1));
-    out_host->obs_pl = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
-    out_host->obs_seg = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
-    out_host->obs_xy = (float*)malloc(8 * std::max<uint64_t>(no, 1));
-    if (!out_host->X || !out_host->obs_off || !out_host->key || !out_host->obs_view || !out_host->obs_pl ||
-        !out_host->obs_seg || !out_host->obs_xy) {
-      eg3d_free_edgepoints(out_host);
-      g_err = "eg3d_filter_resident: out of host memory";
-      return EG3D_ERR_HIP;
-    }
-    struct { void* dst; const void* src; size_t bytes; } cp[] = {
-        {out_host->X, o.X, 12 * np},          {out_host->obs_off, o.obs_off, 8 * np}, {out_host->key, o.key, 16 * np},
-        {out_host->obs_view, o.obs_view, 4 * no}, {out_host->obs_pl, o.obs_pl, 4 * no},   {out_host->obs_seg, o.obs_seg, 4 * no},
-        {out_host->obs_xy, o.obs_xy, 8 * no}};
-    for (auto& q : cp)
-      if (q.bytes) {
-        const hipError_t e = hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) {
-          eg3d_free_edgepoints(out_host);
-          g_err = std::string("eg3d_filter_resident: copy to the host: ") + hipGetErrorString(e);
-          return EG3D_ERR_HIP;
-        }
-      }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) {
-      eg3d_free_edgepoints(out_host);
-      g_err = "eg3d_filter_resident: copy to the host failed";
-      return EG3D_ERR_HIP;
-    }
-    out_host->obs_off[np] = no;
-    out_host->n_points = np;
-    out_host->n_obs = no;
-    ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
+  if (to_host) BUF_TRY(copy_survivors_to_host(c, o, out_host, "eg3d_filter_resident", &ms_copy));
   if (out_dev) *out_dev = o;
   if (stats) {
     stats->struct_size = (uint32_t)sizeof(eg3d_filter_stats);
@@ -2725,6 +2750,126 @@ extern "C" int eg3d_filter_resident(eg3d_ctx* c, float gn_max_mse, int legacy_ab
     stats->n_gn_inliers = inliers;
     stats->n_kept = o.n_points;
     stats->n_obs_kept = o.n_obs;
+    stats->ms_filter = ms_filter;
+    stats->ms_compact = ms_compact;
+    stats->ms_copy = ms_copy;
+  }
+  return EG3D_OK;
+}
+
+// ---- the 3 px de-duplication on a device-resident cloud ------------------------------------------------------------------
+#define EG3D_DEDUP_MAX_INDEX 0xFFFFFFFFull /* K7_UNCLAIMED: index_base + n_points stays below it */
+static int dedup_index_check(const char* who, uint64_t index_base, uint64_t n_points) {
+  if (index_base >= EG3D_DEDUP_MAX_INDEX || n_points >= EG3D_DEDUP_MAX_INDEX - index_base) {
+    g_err = std::string(who) + ": index_base + n_points must stay below 2^32 - 1 (the claim map holds 32-bit point indices)";
+    return EG3D_ERR_ARG;
+  }
+  return EG3D_OK;
+}
+static int dedup_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, uint64_t index_base, int reset, uint8_t* keep_dev,
+                             uint64_t* n_kept, float* ms) {
+  hipStream_t st = c->stream;
+  const int w = (int)std::ceil((float)c->W / 3), h = (int)std::ceil((float)c->H / 3);  // as host/post_steps.cpp
+  const size_t map_bytes = 4 * (size_t)c->V * (size_t)w * (size_t)h;
+  if (!c->d_first.p) c->dedup_valid = false;
+  BUF_TRY(c->d_first.ensure_exact(map_bytes));  // (it never grows, and a many-view rig's map is hundreds of MB)
+  const bool fill = reset || !c->dedup_valid;
+  c->dedup_valid = false;  // until this call is known to have completed: a failure below leaves the map to be refilled
+  if (fill) HIP_TRY(hipMemsetAsync(c->d_first.p, 0xFF, map_bytes, st));
+  BUF_TRY(c->d_cnt.ensure(16));
+  HIP_TRY(hipMemsetAsync(c->d_cnt.p, 0, 16, st));
+  unsigned long long* cnt = c->d_cnt.as<unsigned long long>();
+  const K7Map m{c->d_first.as<uint32_t>(), c->V, w, h};
+  const CloudView in = cloud_view(d);
+  HIP_TRY(hipEventRecord(c->ea[0], st));
+  launch_dedup_claim(st, in, m, (uint32_t)index_base);
+  launch_dedup_keep(st, in, m, (uint32_t)index_base, keep_dev, cnt, (uint32_t*)(cnt + 1));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->eb[0], st));
+  uint64_t back[2];  // kept points, flags
+  HIP_TRY(hipMemcpyAsync(back, cnt, sizeof(back), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ea[0], c->eb[0]));
+  // (claims made through bad offsets are discarded: dedup_valid stays false, the next call starts from an empty map)
+  if ((uint32_t)back[1]) return device_flags_error("eg3d_dedup_device", (uint32_t)back[1]);
+  c->dedup_valid = true;
+  if (n_kept) *n_kept = back[0];
+  return EG3D_OK;
+}
+
+extern "C" int eg3d_dedup_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, uint64_t index_base, int reset,
+                                 uint8_t* keep_dev, uint64_t* n_kept_host) {
+  if (cloud) BUF_TRY(dedup_index_check("eg3d_dedup_device", index_base, cloud->n_points));
+  if (!c || !cloud || (cloud->n_points && !keep_dev)) {
+    g_err = "eg3d_dedup_device: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  BUF_TRY(check_cloud(cloud, "eg3d_dedup_device", false));
+  HIP_TRY(hipSetDevice(c->device));
+  return dedup_device_impl(c, cloud, index_base, reset, keep_dev, n_kept_host, nullptr);
+}
+
+extern "C" int eg3d_dedup_resident(eg3d_ctx* c, uint64_t index_base, int reset, int with_filter, float gn_max_mse,
+                                   int legacy_abs, int forced_min_filter, const uint64_t* base_hist, int to_host,
+                                   eg3d_edgepoints* out_host, eg3d_device_edgepoints* out_dev, eg3d_dedup_stats* stats) {
+  if (stats && stats->struct_size < sizeof(eg3d_dedup_stats)) {
+    g_err = "eg3d_dedup_resident: stats->struct_size is smaller than this library's eg3d_dedup_stats (" +
+            std::to_string(sizeof(eg3d_dedup_stats)) + " bytes): set it to sizeof(eg3d_dedup_stats)";
+    return EG3D_ERR_ARG;
+  }
+  if (!c || (to_host && !out_host)) {
+    g_err = "eg3d_dedup_resident: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  eg3d_device_edgepoints d;
+  BUF_TRY(eg3d_last_device_output(c, &d));
+  BUF_TRY(dedup_index_check("eg3d_dedup_resident", index_base, d.n_points));
+  BUF_TRY(check_cloud(&d, "eg3d_dedup_resident", true));
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t n = d.n_points;
+  BUF_TRY(c->d_keep.ensure(n));
+  uint64_t dedup_kept = 0, inliers = 0;
+  float ms_dedup = 0, ms_filter = 0, ms_compact = 0, ms_copy = 0;
+  BUF_TRY(dedup_device_impl(c, &d, index_base, reset, c->d_keep.as<uint8_t>(), &dedup_kept, &ms_dedup));
+  // a step that fails from here on leaves no cloud for the claims just made: they are discarded with the earlier ones
+  struct ClaimGuard {
+    eg3d_ctx* c;
+    bool ok = false;
+    ~ClaimGuard() { if (!ok) c->dedup_valid = false; }
+  } guard{c};
+  int threshold = -1;
+  eg3d_device_edgepoints o;
+  if (with_filter) {
+    // a masked-out point gets inlier 0, so r_inl is dedup AND inlier, and the histogram counts the deduplicated inliers
+    BUF_TRY(c->r_Xo.ensure(12 * n));
+    BUF_TRY(c->r_inl.ensure(n));
+    std::vector<uint64_t> hist;
+    BUF_TRY(gn_filter_device_impl(c, &d, c->d_keep.as<uint8_t>(), gn_max_mse, legacy_abs, c->r_Xo.as<float>(),
+                                  c->r_inl.as<uint8_t>(), hist, &ms_filter));
+    for (uint64_t hh : hist) inliers += hh;
+    uint64_t count = inliers;
+    if (base_hist)
+      for (int k = 0; k <= c->V; k++) {
+        hist[k] += base_hist[k];
+        count += base_hist[k];
+      }
+    threshold = observation_threshold(hist.data(), c->V, count, forced_min_filter);
+    BUF_TRY(compact_device_impl(c, &d, c->r_inl.as<uint8_t>(), c->r_Xo.as<float>(), threshold, &o, &ms_compact));
+  } else {
+    BUF_TRY(compact_device_impl(c, &d, c->d_keep.as<uint8_t>(), nullptr, -1, &o, &ms_compact));
+  }
+  if (to_host) BUF_TRY(copy_survivors_to_host(c, o, out_host, "eg3d_dedup_resident", &ms_copy));
+  guard.ok = true;
+  if (out_dev) *out_dev = o;
+  if (stats) {
+    stats->struct_size = (uint32_t)sizeof(eg3d_dedup_stats);
+    stats->threshold = threshold;
+    stats->n_points_in = n;
+    stats->n_dedup_kept = dedup_kept;
+    stats->n_gn_inliers = inliers;
+    stats->n_kept = o.n_points;
+    stats->n_obs_kept = o.n_obs;
+    stats->ms_dedup = ms_dedup;
     stats->ms_filter = ms_filter;
     stats->ms_compact = ms_compact;
     stats->ms_copy = ms_copy;

@@ -180,4 +180,20 @@ void launch_compact_scan(hipStream_t st, uint64_t n_blocks, unsigned long long* 
 void launch_compact_scatter(hipStream_t st, CloudView in, const uint8_t* keep, const float* X_new, int32_t min_obs,
                             const unsigned long long* blk, CloudOut out, bool nt);
 
+// ---- the 3 px de-duplication of a device-resident cloud (eg3d_dedup_device) ----
+// The claim map: per view a w x h grid of 3 px cells, w = ceil((float)width / 3), h = ceil((float)height / 3) as the host
+// step computes them; an entry is the smallest point index that has an observation in the cell, 0xFFFFFFFF = none yet.
+struct K7Map {
+  uint32_t* first;  // [n_views][h][w]
+  int32_t n_views, w, h;
+};
+#define K7_BLOCK 256
+#define K7_UNCLAIMED 0xFFFFFFFFu
+// (1) one lane per observation: atomicMin(first[cell], index_base + owning point)
+void launch_dedup_claim(hipStream_t st, CloudView in, K7Map m, uint32_t index_base);
+// (2) 8 lanes per point: keep[i] = an observation of i lies in a cell that holds index_base + i; *n_kept += kept points;
+//     K5_FLAG_BAD_OFFSETS into *flags for offsets that do not ascend within [0, n_obs]
+void launch_dedup_keep(hipStream_t st, CloudView in, K7Map m, uint32_t index_base, uint8_t* keep, unsigned long long* n_kept,
+                       uint32_t* flags);
+
 }  // namespace eg3d

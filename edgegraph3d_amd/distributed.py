@@ -383,7 +383,9 @@ def global_observation_threshold(dist, local_hist, n_views, forced_min_filter=-1
 
 def filter_then_gather(ctx, gather, dist, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, keep=None):
     """The end of a multi-GPU run without a gathered intermediate: (1) Context.gn_filter_device on this rank's
-    device-only cloud (keep: optional device mask of the shard, e.g. its dedup mask), (2) the global threshold,
+    device-only cloud (keep: optional device mask of the shard, e.g. its dedup mask — Context.dedup_device now produces
+    it on the device, for a shard on its own or for a gathered / concatenated cloud; the dedup of a SHARDED cloud against
+    the other ranks' shards before the gather would need the claim maps exchanged and is not built), (2) the global threshold,
     (3) Context.compact_device of the inliers above it, new X in place, (4) gather.allgather of the compacted shard.
     Returns (DeviceEdgePoints of all ranks' survivors, rc of the gather, threshold). Every rank must call it."""
     cloud = ctx.last_device_output()

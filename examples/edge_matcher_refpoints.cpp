@@ -200,15 +200,19 @@ int main(int argc, char** argv) {
   if (argc >= 4 && std::strcmp(argv[1], "--make-synthetic") == 0) return make_synthetic(std::atoi(argv[2]), argv[3]);
   if (argc >= 4 && std::strcmp(argv[1], "--make-plgs") == 0) return make_plgs(argv[2], argc - 3, argv + 3);
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F] [--all-pairs]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F] [--all-pairs] [--resident-dedup]\n", argv[0]);
     return 2;
   }
   bool do_filter = false, estimate_F = false, all_pairs = false;
+  // --resident-dedup: every stage is matched device_only and deduplicated on the device against the claims of the stages
+  // before it (eg3d_dedup_resident); only the survivors cross to the host. The output is the default path's, byte for byte.
+  bool resident_dedup = false;
   const char* sets_path[2] = {nullptr, nullptr};
   for (int a = 4; a < argc; a++) {
     do_filter |= std::strcmp(argv[a], "--filter") == 0;
     estimate_F |= std::strcmp(argv[a], "--estimate-F") == 0;
     all_pairs |= std::strcmp(argv[a], "--all-pairs") == 0;  // analytic F for every pair, ignoring the 10-point rule
+    resident_dedup |= std::strcmp(argv[a], "--resident-dedup") == 0;
     if (std::strcmp(argv[a], "--sets1") == 0 && a + 1 < argc) sets_path[0] = argv[++a];
     else if (std::strcmp(argv[a], "--sets2") == 0 && a + 1 < argc) sets_path[1] = argv[++a];
   }
@@ -263,6 +267,24 @@ int main(int argc, char** argv) {
   lap("eg3d_create (incl. HIP runtime start-up)");
   Cloud all_stages;
   eg3d_stage_times tm;
+  // --resident-dedup: the cloud the last match left in HBM -> dedup against the earlier stages' claims (the first stage
+  // resets them; index_base = points matched so far) -> compaction -> copy of the survivors -> append
+  uint64_t n_matched = 0;
+  bool first_stage = true;
+  auto append_resident = [&](const eg3d_edgepoints& matched) -> bool {
+    eg3d_edgepoints surv;
+    eg3d_dedup_stats st;
+    st.struct_size = (uint32_t)sizeof(st);
+    if (eg3d_dedup_resident(ctx, n_matched, first_stage ? 1 : 0, 0, 0.f, 0, -1, nullptr, 1, &surv, nullptr, &st) != EG3D_OK)
+      return false;
+    std::printf("  dedup on the device: %llu of %llu points kept (kernels %.3f ms, compaction %.3f ms, copy %.3f ms)\n",
+                (unsigned long long)st.n_kept, (unsigned long long)st.n_points_in, st.ms_dedup, st.ms_compact, st.ms_copy);
+    all_stages.append(surv);
+    eg3d_free_edgepoints(&surv);
+    n_matched += matched.n_points;
+    first_stage = false;
+    return true;
+  };
   // ---- pipelines 1 and 2 (pipelines.cpp:219-223): the extractor over the polyline matches of each stage, in
   // match order (one call takes all matches of a stage: eg3d_match_polyline_sets emits them set by set)
   for (int stage = 0; stage < 2; stage++) {
@@ -274,10 +296,15 @@ int main(int argc, char** argv) {
     ps.row_off = ms.row_off.data();
     ps.pl_ids = ms.ids.data();
     eg3d_edgepoints e;
-    if (eg3d_match_polyline_sets(ctx, &ps, 0, ms.n_sets, 0, &e, &tm) != EG3D_OK) return fail("eg3d_match_polyline_sets");
+    if (eg3d_match_polyline_sets(ctx, &ps, 0, ms.n_sets, resident_dedup ? 1 : 0, &e, &tm) != EG3D_OK)
+      return fail("eg3d_match_polyline_sets");
     std::printf("pipeline %d: %u polyline matches -> %llu edge-points (%llu observations) in %.2f ms on the GPU\n", stage + 1,
                 ms.n_sets, (unsigned long long)e.n_points, (unsigned long long)e.n_obs, tm.ms_total);
-    all_stages.append(e);
+    if (resident_dedup) {
+      if (!append_resident(e)) return fail("eg3d_dedup_resident");
+    } else {
+      all_stages.append(e);
+    }
     eg3d_free_edgepoints(&e);
   }
   // ---- pipeline 3 on the GPU (pipelines.cpp:160-176, :227)
@@ -285,11 +312,16 @@ int main(int argc, char** argv) {
   eg3d_sfm_seeds(sfm, &seeds);
   {
     eg3d_edgepoints e;
-    if (eg3d_match_refpoints(ctx, &seeds, 0, seeds.n_seeds, 0, &e, &tm) != EG3D_OK) return fail("eg3d_match_refpoints");
+    if (eg3d_match_refpoints(ctx, &seeds, 0, seeds.n_seeds, resident_dedup ? 1 : 0, &e, &tm) != EG3D_OK)
+      return fail("eg3d_match_refpoints");
     std::printf("matched %u reference points -> %llu edge-points (%llu observations) in %.2f ms on the GPU\n", seeds.n_seeds,
                 (unsigned long long)e.n_points, (unsigned long long)e.n_obs, tm.ms_total);
-    lap("eg3d_match_refpoints (first call, with the copy)");
-    all_stages.append(e);
+    lap(resident_dedup ? "eg3d_match_refpoints (first call, device only)" : "eg3d_match_refpoints (first call, with the copy)");
+    if (resident_dedup) {
+      if (!append_resident(e)) return fail("eg3d_dedup_resident");
+    } else {
+      all_stages.append(e);
+    }
     eg3d_free_edgepoints(&e);
     lap("append to the run's cloud");
   }
@@ -297,7 +329,10 @@ int main(int argc, char** argv) {
 
   // ---- filter_3d_points_close_2d_array + add_3dpoints_to_sfmd (pipelines.cpp:236-239; edge_matcher.cpp:150-158)
   std::vector<uint8_t> keep(pts.n_points ? pts.n_points : 1);
-  if (eg3d_host_filter_close_2d(V, sc.width, sc.height, &pts, keep.data()) != 0) return fail("dedup");
+  if (resident_dedup)
+    std::fill(keep.begin(), keep.end(), (uint8_t)1);  // the cloud holds survivors only
+  else if (eg3d_host_filter_close_2d(V, sc.width, sc.height, &pts, keep.data()) != 0)
+    return fail("dedup");
   lap("3 px de-duplication (filter_3d_points_close_2d_array)");
   uint64_t kept = 0;
   for (uint64_t i = 0; i < pts.n_points; i++) kept += keep[i];

@@ -271,10 +271,12 @@ int eg3d_context_info(eg3d_ctx* ctx, int32_t* n_views, int32_t* device);
  * for obs_xy (an (x, y) pair moves as one 8-byte word).
  *
  * Order of the reference: it removes points whose observations fall within 3 px of an earlier point's
- * (filter_3d_points_close_2d_array; sequential, host: the host library's filter_close_2d step) BEFORE it filters. The
- * Gauss-Newton verdict of a point depends on that point alone, so the reference-exact sequence is
- *   1. host dedup mask -> upload as keep_dev -> the Gauss-Newton filter below;
- *   2. the compaction with keep = dedup AND inlier, min_obs = the observation threshold.
+ * (filter_3d_points_close_2d_array) BEFORE it filters. The Gauss-Newton verdict of a point depends on that point alone, so
+ * the reference-exact sequence, all of it on the device, is
+ *   1. eg3d_dedup_device -> its mask as keep_dev -> the Gauss-Newton filter below;
+ *   2. the compaction with keep = dedup AND inlier (what the masked filter writes), min_obs = the observation threshold;
+ * eg3d_dedup_resident (at the end of this header) runs exactly this on the context's last device output. The host
+ * library's filter_close_2d step gives the same mask from a host copy of the cloud.
  *
  * Gauss-Newton filter. keep_dev: optional device byte mask, NULL = all points; a masked-out point costs no arithmetic, gets
  * inlier 0 and X_out = X. Per point the arithmetic is that of the host-array entry point above, bit for bit (both abs
@@ -311,10 +313,58 @@ typedef struct eg3d_filter_stats {
  * (optional, [n_views + 1], entry k = the caller's SfM points with k observations, which the reference counts in the same
  * histogram): the median bin, max(3, median / 2 - 1), overridden by forced_min_filter > -1; compaction; with to_host a copy
  * of the survivors into a library-owned cloud (obs_off with its sentinel; release with eg3d_free_edgepoints). out_host is
- * required with to_host; out_dev and stats may be NULL. This filters the cloud as matched, NOT deduplicated: it is not the
- * reference's filter step (see the order above). */
+ * required with to_host; out_dev and stats may be NULL. This filters the cloud as matched, NOT deduplicated: the reference's
+ * filter step, which dedups first, is eg3d_dedup_resident below (see the order above). */
 int eg3d_filter_resident(eg3d_ctx* ctx, float gn_max_mse, int legacy_abs, int forced_min_filter, const uint64_t* base_hist,
                          int to_host, eg3d_edgepoints* out_host, eg3d_device_edgepoints* out_dev, eg3d_filter_stats* stats);
+
+/* ---- the 3 px de-duplication on a device-resident cloud ------------------------------------------------------------
+ * filter_3d_points_close_2d_array (filtering_close_plgps.cpp:75-124): every view carries an occupancy grid of 3 px cells,
+ * w = ceil((float)width / 3) by h = ceil((float)height / 3); in cloud order a point is kept when one of its observations
+ * falls into a cell no earlier kept point occupies, and a kept point occupies the cells of all its observations. The first
+ * point that touches a cell is always kept, so the rule is order-independent: keep[i] = some observation of i lies in a
+ * cell whose smallest touching point index is i. The context owns a claim map of those minima (one uint32 per cell of
+ * every view, created on first use: 4 * n_views * w * h bytes; a clone has its own, empty at first).
+ *
+ * Writes the byte mask keep_dev[n_points] (device memory) and, if given, the number of kept points to *n_kept_host.
+ * reset != 0 clears the claim map first; otherwise the claims of the earlier calls on this context stand, and the points
+ * of this cloud are numbered from index_base. Contract: the dedup of cloud A (reset, index_base 0) and then of cloud B
+ * (no reset, index_base = |A|) gives the two halves of the mask of the concatenation A || B - the reference dedups the
+ * concatenation of its three pipeline stages this way (pipelines.cpp:219-239). index_base + n_points must stay below
+ * 2^32 - 1: EG3D_ERR_ARG otherwise, before anything is launched. An observation with a view id outside the rig, or with
+ * coordinates outside the grid (x / 3 or y / 3 not inside (-1, w) x (-1, h), NaN included), is NOT an error here, unlike in
+ * the filter: it claims nothing and keeps nothing, the rule of the host step and of the CPU oracle; a point with an empty
+ * list is dropped. Offsets that do not ascend within [0, n_obs] fail the call with EG3D_ERR_ARG (device-side check). A
+ * call that fails after its arguments were accepted, for this or any other reason, discards its claims with all earlier
+ * ones: the next call on the context starts from an empty map whatever its `reset`. cloud->obs_pl,
+ * obs_seg and key are not read. */
+int eg3d_dedup_device(eg3d_ctx* ctx, const eg3d_device_edgepoints* cloud, uint64_t index_base, int reset,
+                      uint8_t* keep_dev, uint64_t* n_kept_host /* may be NULL */);
+/* Filled by eg3d_dedup_resident. struct_size as in eg3d_filter_stats: set by the caller, a smaller value is refused. */
+typedef struct eg3d_dedup_stats {
+  uint32_t struct_size;
+  int32_t threshold;       /* the observation threshold (kept: MORE observations than this); -1 without the filter */
+  uint64_t n_points_in;    /* points of the cloud */
+  uint64_t n_dedup_kept;   /* ... kept by the dedup */
+  uint64_t n_gn_inliers;   /* ... of those accepted by the Gauss-Newton filter (0 without the filter) */
+  uint64_t n_kept;         /* points of the result */
+  uint64_t n_obs_kept;     /* observations of the result */
+  float ms_dedup;          /* the two dedup kernels (HIP events; the fill of a reset map precedes them) */
+  float ms_filter;         /* the filter kernel (HIP events; 0 without the filter) */
+  float ms_compact;        /* the compaction, as in eg3d_filter_stats */
+  float ms_copy;           /* the copy of the survivors to the host (wall; 0 without to_host) */
+} eg3d_dedup_stats;
+/* The reference's dedup + filter on the context's last device output (which must be `complete`), without the host in it:
+ * eg3d_dedup_device with the caller's reset and index_base; with with_filter != 0 the Gauss-Newton filter with the dedup
+ * mask as keep_dev and the observation threshold by the rule of eg3d_filter_resident (base_hist, forced_min_filter as
+ * there); eg3d_compact_device with the resulting mask (and the filter's new X); with to_host a copy of the survivors
+ * into a library-owned cloud (release with eg3d_free_edgepoints). out_host is required with to_host; out_dev and stats may
+ * be NULL. The result lives in the compaction's buffers: valid until the next compaction on this context. If a step after
+ * the dedup fails (the filter refuses a view id outside the rig, which the dedup tolerates), the claims are discarded as
+ * after a failed eg3d_dedup_device. */
+int eg3d_dedup_resident(eg3d_ctx* ctx, uint64_t index_base, int reset, int with_filter, float gn_max_mse, int legacy_abs,
+                        int forced_min_filter, const uint64_t* base_hist, int to_host, eg3d_edgepoints* out_host,
+                        eg3d_device_edgepoints* out_dev, eg3d_dedup_stats* stats);
 
 #ifdef __cplusplus
 }
