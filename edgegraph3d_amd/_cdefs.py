@@ -67,6 +67,22 @@ class DedupStats(C.Structure):
                 ("ms_copy", C.c_float)]
 
 
+class DeviceGraph3D(C.Structure):
+    """eg3d_device_graph3d: the members of eg3d_graph3d, the pointers into HBM."""
+    _fields_ = [("n_nodes", C.c_uint64), ("n_real_nodes", C.c_uint64), ("node_X", C.c_void_p), ("node_point", C.c_void_p),
+                ("n_polylines", C.c_uint64), ("pl_start", C.c_void_p), ("pl_end", C.c_void_p), ("conn_off", C.c_void_p),
+                ("conn_pl", C.c_void_p), ("n_scene_polylines", C.c_uint64), ("iv_off", C.c_void_p),
+                ("iv_start_seg", C.c_void_p), ("iv_start_xy", C.c_void_p), ("iv_end_seg", C.c_void_p),
+                ("iv_end_xy", C.c_void_p)]
+
+
+class ReplayStats(C.Structure):
+    """eg3d_replay_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs", C.c_uint64), ("n_nodes", C.c_uint64), ("n_polylines", C.c_uint64),
+                ("n_intervals", C.c_uint64), ("table_slots", C.c_uint64), ("ms_graph", C.c_float),
+                ("ms_intervals", C.c_float), ("ms_copy", C.c_float)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("n_seeds", C.c_uint32), ("n_curves", C.c_int32),
                 ("rng_seed", C.c_uint64), ("max_track", C.c_int32), ("obs_noise_px", C.c_float),

@@ -67,6 +67,10 @@ def lib():
         L.eg3d_dedup_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, D.u64p,
                                           C.c_int, C.POINTER(D.EdgePoints), C.POINTER(D.DeviceEdgePoints),
                                           C.POINTER(D.DedupStats)]
+        L.eg3d_replay_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.POINTER(D.DeviceGraph3D),
+                                         C.POINTER(D.Graph3D), C.POINTER(D.ReplayStats)]
+        L.eg3d_free_graph3d.argtypes = [C.POINTER(D.Graph3D)]
+        L.eg3d_free_graph3d.restype = None
         _LIB = L
     return _LIB
 
@@ -77,7 +81,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_free_candidates", "eg3d_match_refpoints", "eg3d_free_edgepoints", "eg3d_upload_seeds",
     "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
-    "eg3d_dedup_device", "eg3d_dedup_resident",
+    "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
 ]
 
 
@@ -443,3 +447,39 @@ class Context:
             d = D.edgepoints_to_dict(e)
             lib().eg3d_free_edgepoints(C.byref(e))
         return d, dv, {f[0]: getattr(st, f[0]) for f in D.DedupStats._fields_}
+
+    # ---- the PLGMatchesManager replay on a device-resident cloud (include/eg3d.h) ----
+    def replay_device(self, cloud=None, to_host=True):
+        """eg3d_replay_device on `cloud` (a DeviceEdgePoints; None = the last device output): the 3-D polyline graph and
+        the matched 2-D intervals of row a17. Returns (graph or None, DeviceGraph3D, stats dict); the graph is a dict of
+        numpy arrays under the field names of eg3d_graph3d, as host.replay_matches returns it; the DeviceGraph3D views
+        buffers of this context that stay valid until its next replay."""
+        g, dv, st = D.Graph3D(), D.DeviceGraph3D(), D.ReplayStats()
+        st.struct_size = C.sizeof(D.ReplayStats)
+        _check(lib().eg3d_replay_device(self._h, C.byref(cloud) if cloud is not None else None, C.byref(dv),
+                                        C.byref(g) if to_host else None, C.byref(st)), "eg3d_replay_device")
+        d = None
+        if to_host:
+            d = D.graph3d_to_dict(g)
+            lib().eg3d_free_graph3d(C.byref(g))
+        return d, dv, {f[0]: getattr(st, f[0]) for f in D.ReplayStats._fields_}
+
+    def fetch_device_graph(self, dv):
+        """Test/bench plumbing: the graph a DeviceGraph3D views (HBM), copied into the dict graph3d_to_dict gives."""
+        def fetch(ptr, n, dtype):
+            a = np.empty(int(n), dtype)
+            if a.nbytes and _hip().hipMemcpy(a.ctypes.data, C.c_void_p(ptr), a.nbytes, 2) != 0:
+                raise Eg3dError("hipMemcpy of the device graph failed")
+            return a
+        nn, npl, nsp = int(dv.n_nodes), int(dv.n_polylines), int(dv.n_scene_polylines)
+        conn_off = fetch(dv.conn_off, nn + 1, np.uint64)
+        iv_off = fetch(dv.iv_off, nsp + 1, np.uint64)
+        nc, ni = int(conn_off[-1]), int(iv_off[-1])
+        return {"n_nodes": nn, "n_real_nodes": int(dv.n_real_nodes), "n_polylines": npl,
+                "node_X": fetch(dv.node_X, 3 * nn, np.float32).reshape(nn, 3), "node_point": fetch(dv.node_point, nn, np.uint64),
+                "pl_start": fetch(dv.pl_start, npl, np.uint32), "pl_end": fetch(dv.pl_end, npl, np.uint32),
+                "conn_off": conn_off, "conn_pl": fetch(dv.conn_pl, nc, np.uint32), "iv_off": iv_off,
+                "iv_start_seg": fetch(dv.iv_start_seg, ni, np.uint32),
+                "iv_start_xy": fetch(dv.iv_start_xy, 2 * ni, np.float32).reshape(ni, 2),
+                "iv_end_seg": fetch(dv.iv_end_seg, ni, np.uint32),
+                "iv_end_xy": fetch(dv.iv_end_xy, 2 * ni, np.float32).reshape(ni, 2)}

@@ -202,6 +202,8 @@ RESOURCE_BOUNDS = {
     # the 3 px dedup (eg3d_dedup_device): 64 staged 64-bit offsets per wave / one count per wave; no spills, no scratch
     "k7_dedup_claim": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},
     "k7_dedup_keep": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 16},
+    # the replay (eg3d_replay_device): small kernels, no LDS; no spills, no scratch (a substring: all of them)
+    "k8_": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     "k2_epipolar_hits": {"vgpr_spill_count": 0},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }

@@ -28,6 +28,7 @@
 #include "../../include/eg3d_host.h"
 #include "eg3d_host_copy.h"
 #include "eg3d_kernels.h"
+#include "eg3d_k8_replay.h"
 
 using namespace eg3d;
 
@@ -252,6 +253,15 @@ struct eg3d_ctx {
   // flag word, the mask of eg3d_dedup_resident
   DevBuf d_first, d_cnt, d_keep;
   bool dedup_valid = false;   // the claim map holds the claims of the earlier calls (false: it is filled before use)
+  // eg3d_replay_device (K8). Work: counters + flag word, the node table (slot / last), per point the first point of its
+  // node, flags, their scans, the last point of a node, the sort buffers, rocPRIM's scratch, the interval claim map over
+  // the scene's segments with its flags and scan. Result (valid until the next replay): the arrays of eg3d_graph3d.
+  DevBuf k8_cnt, k8_slot, k8_last, k8_firstof, k8_flag, k8_rank, k8_lastof, k8_plid, k8_key[2], k8_val[2], k8_tmp, k8_map,
+      k8_sflag, k8_pos;
+  DevBuf g_nodeX, g_nodept, g_pls, g_ple, g_conoff, g_conpl, g_ivoff, g_ivss, g_ivsxy, g_ives, g_ivexy;
+  int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (read by eg3d_create; tests): a node table of 2^bits slots, raised to the
+                              // smallest power of two above the number of lookups; 0 = the default, about twice that
+  uint32_t n_pl = 0, n_vtx = 0;  // polylines and vertices of the scene as uploaded
   DevBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
@@ -580,6 +590,7 @@ extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
   c->device = device;
   c->tune = Tunables::from_env();
   if (const char* e = getenv("EG3D_COMPACT_NT")) c->compact_nt = e[0] == '1';
+  if (const char* e = getenv("EG3D_REPLAY_TABLE_BITS")) c->replay_table_bits = std::min(40, std::max(0, atoi(e)));
   if (c->tune.hyp_cap) c->hyp_cap = c->tune.hyp_cap;
   c->hg = std::make_shared<HostGrids>();
   if (c->tune.lane_priorities) {
@@ -622,6 +633,8 @@ extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
     }
   }
   const uint32_t NV = pvo_up[NP];
+  c->n_pl = NP;
+  c->n_vtx = NV;
   int rc;
 #define UP(buf, ptr, n)                                        \
   if ((rc = upload(c->buf, ptr, (size_t)(n), c->stream)) != EG3D_OK) { \
@@ -889,6 +902,9 @@ extern "C" int eg3d_clone(eg3d_ctx* parent, eg3d_ctx** out) {
   c->device = parent->device;
   c->tune = parent->tune;
   c->compact_nt = parent->compact_nt;
+  c->replay_table_bits = parent->replay_table_bits;
+  c->n_pl = parent->n_pl;
+  c->n_vtx = parent->n_vtx;
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (int i = 0; i < 8; i++) {
     HIP_TRY(hipEventCreate(&c->ea[i]));
@@ -949,7 +965,11 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
                    &c->b_nhyp, &c->b_hyp_off, &c->b_res, &c->b_arena, &c->b_ctr, &c->b_cs_task,
                    &c->b_valid, &c->b_chain_off, &c->b_chains, &c->b_cscratch, &c->b_couts, &c->b_cpts, &c->b_cobs,
                    &c->b_cpoff, &c->b_cooff, &c->b_scan_tmp, &c->b_scanchk, &c->b_cost, &c->b_cidx, &c->b_cost2, &c->b_order, &c->b_redo[0], &c->b_redo[1], &c->o_X, &c->o_off, &c->o_view, &c->o_pl, &c->o_seg,
-                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->r_hist, &c->r_blk, &c->r_Xo, &c->r_inl, &c->c_X, &c->c_off, &c->c_view, &c->c_pl, &c->c_seg, &c->c_xy, &c->c_key, &c->d_first, &c->d_cnt, &c->d_keep, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
+                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->r_hist, &c->r_blk, &c->r_Xo, &c->r_inl, &c->c_X, &c->c_off, &c->c_view, &c->c_pl, &c->c_seg, &c->c_xy, &c->c_key, &c->d_first, &c->d_cnt, &c->d_keep,
+                   &c->k8_cnt, &c->k8_slot, &c->k8_last, &c->k8_firstof, &c->k8_flag, &c->k8_rank, &c->k8_lastof, &c->k8_plid,
+                   &c->k8_key[0], &c->k8_key[1], &c->k8_val[0], &c->k8_val[1], &c->k8_tmp, &c->k8_map, &c->k8_sflag, &c->k8_pos,
+                   &c->g_nodeX, &c->g_nodept, &c->g_pls, &c->g_ple, &c->g_conoff, &c->g_conpl, &c->g_ivoff, &c->g_ivss,
+                   &c->g_ivsxy, &c->g_ives, &c->g_ivexy, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
                    &c->b_pools, &c->b_stage_pts, &c->b_stage_obs, &c->b_stage_used};
   for (DevBuf* b : all) b->release();
   if (c->pinned) (void)hipHostFree(c->pinned);
@@ -2872,6 +2892,261 @@ extern "C" int eg3d_dedup_resident(eg3d_ctx* c, uint64_t index_base, int reset, 
     stats->ms_dedup = ms_dedup;
     stats->ms_filter = ms_filter;
     stats->ms_compact = ms_compact;
+    stats->ms_copy = ms_copy;
+  }
+  return EG3D_OK;
+}
+
+// ---- the PLGMatchesManager replay on a device-resident cloud (K8, eg3d_k8_replay.hip) ---------------------------------------
+static int k8_scan(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n) {
+  size_t bytes = 0;
+  HIP_TRY(k8_scan_u32(c->stream, nullptr, bytes, in, out, n));
+  BUF_TRY(c->k8_tmp.ensure(bytes));
+  HIP_TRY(k8_scan_u32(c->stream, c->k8_tmp.p, bytes, in, out, n));
+  return EG3D_OK;
+}
+static int k8_read_u32(eg3d_ctx* c, const uint32_t* dev, uint64_t* v) {
+  uint32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, dev, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *v = h;
+  return EG3D_OK;
+}
+static uint64_t pow2_above(uint64_t n) {  // the smallest power of two > n
+  uint64_t p = 1;
+  while (p <= n) p <<= 1;
+  return p;
+}
+
+extern "C" void eg3d_free_graph3d(eg3d_graph3d* g) {
+  if (!g) return;
+  void* all[] = {g->node_X, g->node_point, g->pl_start, g->pl_end, g->conn_off, g->conn_pl, g->iv_off, g->iv_start_seg,
+                 g->iv_start_xy, g->iv_end_seg, g->iv_end_xy};
+  for (void* p : all) free(p);
+  memset(g, 0, sizeof(*g));
+}
+
+extern "C" int eg3d_replay_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, eg3d_device_graph3d* out_dev,
+                                  eg3d_graph3d* out_host, eg3d_replay_stats* stats) {
+  if (stats && stats->struct_size < sizeof(eg3d_replay_stats)) {
+    g_err = "eg3d_replay_device: stats->struct_size is smaller than this library's eg3d_replay_stats (" +
+            std::to_string(sizeof(eg3d_replay_stats)) + " bytes): set it to sizeof(eg3d_replay_stats)";
+    return EG3D_ERR_ARG;
+  }
+  if (!c) {
+    g_err = "eg3d_replay_device: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  eg3d_device_edgepoints d;
+  if (cloud)
+    d = *cloud;
+  else
+    BUF_TRY(eg3d_last_device_output(c, &d));
+  if (d.n_points >= 0xfffffff0ull) {
+    g_err = "eg3d_replay_device: n_points must stay below 0xfffffff0 (node and polyline ids are 32-bit)";
+    return EG3D_ERR_CAPACITY;
+  }
+  BUF_TRY(check_cloud(&d, "eg3d_replay_device", true));
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const CloudView in = cloud_view(&d);
+  const uint64_t N = d.n_points, NP = c->n_pl, NV = c->n_vtx;
+
+  // ---- the checks, before anything is indexed or written
+  BUF_TRY(c->k8_cnt.ensure(16));
+  HIP_TRY(hipMemsetAsync(c->k8_cnt.p, 0, 16, st));
+  unsigned long long* cnt = c->k8_cnt.as<unsigned long long>();
+  launch_k8_pairs(st, in, c->ds, cnt, (uint32_t*)(cnt + 1));
+  HIP_TRY(hipGetLastError());
+  uint64_t back[2];  // pairs, flags
+  HIP_TRY(hipMemcpyAsync(back, cnt, sizeof(back), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t flags = (uint32_t)back[1];
+  if (flags & ~K8_FLAG_HOSTONLY) {
+    g_err = std::string("eg3d_replay_device: ") +
+            (flags & K8_FLAG_BAD_OFFSETS ? "obs_off is not ascending within [0, n_obs]"
+             : flags & K8_FLAG_BAD_VIEW  ? "view id out of range"
+             : flags & K8_FLAG_BAD_PL    ? "polyline id outside its view"
+                                         : "segment index outside its polyline (or a polyline without segments)");
+    return EG3D_ERR_ARG;
+  }
+  if (flags & K8_FLAG_HOSTONLY) {
+    g_err = "eg3d_replay_device: a point of a chain pair has a NaN coordinate or x or y == -1 (the reference's invalid-node "
+            "rule): replay this cloud with eg3d_host_replay_matches";
+    return EG3D_ERR_HOSTONLY;
+  }
+  const uint64_t n_pairs = back[0];
+
+  uint64_t n_nodes = 0, n_pl = 0, n_conn = 0, n_iv = 0, slots = 0;
+  float ms_graph = 0, ms_iv = 0, ms_copy = 0;
+  K8Graph g{};
+  BUF_TRY(c->g_ivoff.ensure(8 * (NP + 1)));
+  g.iv_off = c->g_ivoff.as<unsigned long long>();
+  if (!n_pairs) {  // an empty cloud, or one-point chains only: the all-zero graph
+    BUF_TRY(c->g_conoff.ensure(8));
+    g.conn_off = c->g_conoff.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(g.conn_off, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(g.iv_off, 0, 8 * (NP + 1), st));
+  } else {
+    // ---- nodes
+    slots = c->replay_table_bits ? std::max<uint64_t>(1ull << c->replay_table_bits, pow2_above(2 * n_pairs))
+                                 : pow2_above(std::max<uint64_t>(4 * n_pairs, 63));
+    BUF_TRY(c->k8_slot.ensure(4 * slots));
+    BUF_TRY(c->k8_last.ensure(4 * slots));
+    BUF_TRY(c->k8_firstof.ensure(4 * N));
+    BUF_TRY(c->k8_lastof.ensure(4 * N));
+    BUF_TRY(c->k8_flag.ensure(4 * (N + 1)));
+    BUF_TRY(c->k8_rank.ensure(4 * (N + 1)));
+    BUF_TRY(c->k8_plid.ensure(4 * (N + 1)));
+    const size_t sort_n = std::max<uint64_t>(N, 2 * n_pairs);  // the pairs' keys by point, then two incidences per polyline
+    for (int k = 0; k < 2; k++) {
+      BUF_TRY(c->k8_key[k].ensure(8 * sort_n));
+      BUF_TRY(c->k8_val[k].ensure(4 * N));
+    }
+    const K8Table tab{c->k8_slot.as<uint32_t>(), c->k8_last.as<uint32_t>(), slots - 1};
+    uint32_t* first_of = c->k8_firstof.as<uint32_t>();
+    uint32_t* last_of = c->k8_lastof.as<uint32_t>();
+    uint32_t* flag = c->k8_flag.as<uint32_t>();
+    uint32_t* rank = c->k8_rank.as<uint32_t>();
+    uint32_t* pl_id = c->k8_plid.as<uint32_t>();
+    unsigned long long* key[2] = {c->k8_key[0].as<unsigned long long>(), c->k8_key[1].as<unsigned long long>()};
+    uint32_t* val[2] = {c->k8_val[0].as<uint32_t>(), c->k8_val[1].as<uint32_t>()};
+    HIP_TRY(hipEventRecord(c->ea[0], st));
+    HIP_TRY(hipMemsetAsync(tab.slot, 0xFF, 4 * slots, st));
+    HIP_TRY(hipMemsetAsync(tab.last, 0, 4 * slots, st));
+    HIP_TRY(hipMemsetAsync(flag, 0, 4 * (N + 1), st));
+    launch_k8_node_claim(st, in, tab);
+    launch_k8_node_resolve(st, in, tab, first_of, flag, last_of);
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(k8_scan(c, flag, rank, N + 1));
+    BUF_TRY(k8_read_u32(c, rank + N, &n_nodes));
+    BUF_TRY(c->g_nodeX.ensure(12 * n_nodes));
+    BUF_TRY(c->g_nodept.ensure(8 * n_nodes));
+    BUF_TRY(c->g_conoff.ensure(8 * (n_nodes + 1)));
+    g.node_X = c->g_nodeX.as<float>();
+    g.node_point = c->g_nodept.as<unsigned long long>();
+    g.conn_off = c->g_conoff.as<unsigned long long>();
+    launch_k8_node_write(st, in, first_of, flag, rank, last_of, g, key[0], val[0]);
+    HIP_TRY(hipGetLastError());
+    // ---- polylines: a stable sort keeps the pairs of one connection in cloud order, the first of a run creates it
+    size_t bytes = 0;
+    HIP_TRY(k8_sort_pairs(st, nullptr, bytes, key[0], key[1], val[0], val[1], N));
+    BUF_TRY(c->k8_tmp.ensure(bytes));
+    HIP_TRY(k8_sort_pairs(st, c->k8_tmp.p, bytes, key[0], key[1], val[0], val[1], N));
+    HIP_TRY(hipMemsetAsync(flag, 0, 4 * (N + 1), st));
+    launch_k8_pl_heads(st, key[1], val[1], n_pairs, flag);
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(k8_scan(c, flag, pl_id, N + 1));
+    BUF_TRY(k8_read_u32(c, pl_id + N, &n_pl));
+    BUF_TRY(c->g_pls.ensure(4 * n_pl));
+    BUF_TRY(c->g_ple.ensure(4 * n_pl));
+    BUF_TRY(c->g_conpl.ensure(8 * n_pl));
+    g.pl_start = c->g_pls.as<uint32_t>();
+    g.pl_end = c->g_ple.as<uint32_t>();
+    g.conn_pl = c->g_conpl.as<uint32_t>();
+    launch_k8_pl_write(st, in, first_of, rank, flag, pl_id, g, key[0]);
+    HIP_TRY(hipGetLastError());
+    // ---- connections: the (node, polyline) incidences sorted = every node's polylines in ascending id
+    HIP_TRY(k8_sort_keys(st, nullptr, bytes, key[0], key[1], 2 * n_pl));
+    BUF_TRY(c->k8_tmp.ensure(bytes));
+    HIP_TRY(k8_sort_keys(st, c->k8_tmp.p, bytes, key[0], key[1], 2 * n_pl));
+    launch_k8_conn(st, key[1], 2 * n_pl, n_nodes, g);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->eb[0], st));
+    HIP_TRY(hipMemcpyAsync(&n_conn, g.conn_off + n_nodes, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&ms_graph, c->ea[0], c->eb[0]));
+    // ---- matched intervals: the claim map is indexed by the scene's global segment index
+    BUF_TRY(c->k8_map.ensure(8 * std::max<uint64_t>(NV, 1)));
+    BUF_TRY(c->k8_sflag.ensure(4 * (NV + 1)));
+    BUF_TRY(c->k8_pos.ensure(4 * (NV + 1)));
+    unsigned long long* map = c->k8_map.as<unsigned long long>();
+    uint32_t* pos = c->k8_pos.as<uint32_t>();
+    HIP_TRY(hipEventRecord(c->ea[0], st));
+    HIP_TRY(hipMemsetAsync(map, 0xFF, 8 * std::max<uint64_t>(NV, 1), st));
+    launch_k8_iv(st, false, in, c->ds, map, pos, g);
+    launch_k8_seg_flags(st, map, NV, c->k8_sflag.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(k8_scan(c, c->k8_sflag.as<uint32_t>(), pos, NV + 1));
+    BUF_TRY(k8_read_u32(c, pos + NV, &n_iv));
+    BUF_TRY(c->g_ivss.ensure(4 * n_iv));
+    BUF_TRY(c->g_ives.ensure(4 * n_iv));
+    BUF_TRY(c->g_ivsxy.ensure(8 * n_iv));
+    BUF_TRY(c->g_ivexy.ensure(8 * n_iv));
+    g.iv_start_seg = c->g_ivss.as<uint32_t>();
+    g.iv_end_seg = c->g_ives.as<uint32_t>();
+    g.iv_start_xy = c->g_ivsxy.as<float>();
+    g.iv_end_xy = c->g_ivexy.as<float>();
+    launch_k8_iv(st, true, in, c->ds, map, pos, g);
+    launch_k8_iv_off(st, c->ds, (uint32_t)NP, pos, g);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->eb[0], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&ms_iv, c->ea[0], c->eb[0]));
+  }
+
+  if (out_host) {
+    const auto t0 = std::chrono::steady_clock::now();
+    eg3d_graph3d h;
+    memset(&h, 0, sizeof(h));
+    struct { void** dst; const void* src; size_t bytes; } cp[] = {
+        {(void**)&h.node_X, g.node_X, 12 * n_nodes},      {(void**)&h.node_point, g.node_point, 8 * n_nodes},
+        {(void**)&h.pl_start, g.pl_start, 4 * n_pl},      {(void**)&h.pl_end, g.pl_end, 4 * n_pl},
+        {(void**)&h.conn_off, g.conn_off, 8 * (n_nodes + 1)}, {(void**)&h.conn_pl, g.conn_pl, 4 * n_conn},
+        {(void**)&h.iv_off, g.iv_off, 8 * (NP + 1)},      {(void**)&h.iv_start_seg, g.iv_start_seg, 4 * n_iv},
+        {(void**)&h.iv_start_xy, g.iv_start_xy, 8 * n_iv}, {(void**)&h.iv_end_seg, g.iv_end_seg, 4 * n_iv},
+        {(void**)&h.iv_end_xy, g.iv_end_xy, 8 * n_iv}};
+    hipError_t e = hipSuccess;
+    bool oom = false;
+    for (auto& q : cp) {
+      *q.dst = malloc(std::max<size_t>(q.bytes, 1));
+      if (!*q.dst) {
+        oom = true;
+        break;
+      }
+      if (q.bytes && (e = hipMemcpyAsync(*q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+    }
+    const hipError_t es = hipStreamSynchronize(st);  // (also after a failure: no copy may still be writing what is freed)
+    if (e == hipSuccess) e = es;
+    if (oom || e != hipSuccess) {
+      eg3d_free_graph3d(&h);
+      g_err = oom ? std::string("eg3d_replay_device: out of host memory")
+                  : std::string("eg3d_replay_device: copy to the host: ") + hipGetErrorString(e);
+      return EG3D_ERR_HIP;
+    }
+    h.n_nodes = h.n_real_nodes = n_nodes;
+    h.n_polylines = n_pl;
+    h.n_scene_polylines = NP;
+    *out_host = h;
+    ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  } else {
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (out_dev) {
+    out_dev->n_nodes = out_dev->n_real_nodes = n_nodes;
+    out_dev->n_polylines = n_pl;
+    out_dev->n_scene_polylines = NP;
+    out_dev->node_X = g.node_X;
+    out_dev->node_point = (const uint64_t*)g.node_point;
+    out_dev->pl_start = g.pl_start;
+    out_dev->pl_end = g.pl_end;
+    out_dev->conn_off = (const uint64_t*)g.conn_off;
+    out_dev->conn_pl = g.conn_pl;
+    out_dev->iv_off = (const uint64_t*)g.iv_off;
+    out_dev->iv_start_seg = g.iv_start_seg;
+    out_dev->iv_start_xy = g.iv_start_xy;
+    out_dev->iv_end_seg = g.iv_end_seg;
+    out_dev->iv_end_xy = g.iv_end_xy;
+  }
+  if (stats) {
+    stats->struct_size = (uint32_t)sizeof(eg3d_replay_stats);
+    stats->n_pairs = n_pairs;
+    stats->n_nodes = n_nodes;
+    stats->n_polylines = n_pl;
+    stats->n_intervals = n_iv;
+    stats->table_slots = slots;
+    stats->ms_graph = ms_graph;
+    stats->ms_intervals = ms_iv;
     stats->ms_copy = ms_copy;
   }
   return EG3D_OK;

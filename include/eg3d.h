@@ -47,6 +47,7 @@ extern "C" {
 #define EG3D_ERR_HIP -2
 #define EG3D_ERR_CAPACITY -3 /* a device-side fixed capacity was exceeded; flags say which */
 #define EG3D_ERR_NODEVICE -4
+#define EG3D_ERR_HOSTONLY -5 /* the input needs the host form of the entry point (eg3d_replay_device) */
 
 /* ---------------------------------------------------------------- scene ---- */
 /* Flat, read-only description of everything the path reads besides the seeds.
@@ -365,6 +366,73 @@ typedef struct eg3d_dedup_stats {
 int eg3d_dedup_resident(eg3d_ctx* ctx, uint64_t index_base, int reset, int with_filter, float gn_max_mse, int legacy_abs,
                         int forced_min_filter, const uint64_t* base_hist, int to_host, eg3d_edgepoints* out_host,
                         eg3d_device_edgepoints* out_dev, eg3d_dedup_stats* stats);
+
+/* ---- the PLGMatchesManager replay (row a17) on a device-resident cloud ---------------------------------------------
+ * What plgmm.add_matched_3dpolyline leaves behind when the reference runs the path (plg_matches_manager.cpp:99-180): the
+ * 3-D polyline graph the reference serialises as outgraph.3dg, and the matched 2-D intervals per (view, polyline). The
+ * result is the eg3d_graph3d of include/eg3d_host.h, field for field and byte for byte what the host library's
+ * eg3d_host_replay_matches builds from a host copy of the same cloud; it needs the WHOLE cloud as matched, not the
+ * survivors of the dedup or the filter, and on the device only the graph has to travel. `cloud`: NULL = this context's last
+ * device output (which must be `complete`), or the result of eg3d_compact_device, of the multi-GPU gather or concatenation
+ * (include/eg3d_rccl.h), or caller-built device arrays under the alignment contract of the filter stage; offsets are 64-bit
+ * without a sentinel. A graph that accumulates over several calls is not offered: concatenate the clouds first.
+ *
+ * The rules, in the order-independent form the kernels use (host/replay.cpp is the sequential statement): a pair is
+ * (i - 1, i) with equal key[0..2] and key[3] counting up by one. Two points are one node when the bit patterns of their
+ * (x, y, z) are equal, -0 counting as +0; node ids count the nodes by their first point in cloud order, node_X holds that
+ * point's coordinates as stored, node_point the LAST point of the node. A polyline is a distinct unordered pair of nodes
+ * (a loop on one node is allowed and linked once), numbered by its first pair and oriented as that pair; conn lists a
+ * node's polylines in ascending id. Of the intervals that start on one segment of one scene polyline the first in the
+ * order (pair, view ascending) is kept (the reference's std::set compares the start segment only); where a point lists a
+ * view twice, the last observation counts.
+ *
+ * Refused, by device-side checks that run before anything is indexed or written (out_dev, out_host and stats are left
+ * untouched and the result of an earlier replay stays valid):
+ *   EG3D_ERR_HOSTONLY  a NaN coordinate, or an x or y equal to -1.0f (the reference's INVALID_POINT_COORDS), in the X of a
+ *                      point that belongs to a pair: the reference then makes a new node on every lookup and wipes the
+ *                      earlier ones, which the rules above do not cover. Copy such a cloud to the host and give it to
+ *                      eg3d_host_replay_matches. The same values in a point of no pair are never looked up and pass.
+ *   EG3D_ERR_ARG       a view id outside the rig, a polyline id outside its view, a segment index outside its polyline or
+ *                      on a polyline with fewer than two vertices (an invalid polyline of the scene has none here), offsets
+ *                      that do not ascend within [0, n_obs]; it takes precedence over EG3D_ERR_HOSTONLY (the host form
+ *                      refuses such a cloud too);
+ *   EG3D_ERR_CAPACITY  n_points >= 0xfffffff0: node and polyline ids are 32-bit (the host form answers -3).
+ * out_dev: the graph in buffers of the context that are separate from the match output and the compaction output, valid
+ * until the next replay on this context. out_host: a library-owned copy, released with eg3d_free_graph3d (NOT with the
+ * host library's function: libeg3d.so does not depend on libeg3d_host.so). Any of out_dev, out_host, stats may be NULL.
+ * EG3D_REPLAY_TABLE_BITS=b (read when the context is created; tests) asks for a node table of 2^b slots; it is raised to
+ * the smallest power of two above the number of lookups (two per pair), so small values make the probe sequences long. */
+struct eg3d_graph3d;
+typedef struct eg3d_device_graph3d { /* the members of eg3d_graph3d, the pointers into HBM */
+  uint64_t n_nodes;
+  uint64_t n_real_nodes;       /* = n_nodes: no node is ever invalidated on this path (see EG3D_ERR_HOSTONLY) */
+  const float* node_X;         /* [n_nodes][3] */
+  const uint64_t* node_point;  /* [n_nodes] */
+  uint64_t n_polylines;
+  const uint32_t* pl_start;    /* [n_polylines] */
+  const uint32_t* pl_end;
+  const uint64_t* conn_off;    /* [n_nodes + 1] */
+  const uint32_t* conn_pl;     /* [conn_off[n_nodes]] */
+  uint64_t n_scene_polylines;
+  const uint64_t* iv_off;      /* [n_scene_polylines + 1] */
+  const uint32_t* iv_start_seg;/* [iv_off[n_scene_polylines]] */
+  const float* iv_start_xy;    /* [..][2] */
+  const uint32_t* iv_end_seg;
+  const float* iv_end_xy;
+} eg3d_device_graph3d;
+/* struct_size as in eg3d_filter_stats: set by the caller, a smaller value is refused before anything is written. */
+typedef struct eg3d_replay_stats {
+  uint32_t struct_size;
+  uint64_t n_pairs;        /* consecutive chain-point pairs replayed */
+  uint64_t n_nodes, n_polylines, n_intervals;
+  uint64_t table_slots;    /* node table capacity actually used (0 for a cloud without pairs) */
+  float ms_graph;          /* nodes, polylines and connections (HIP events; the small read-backs between the passes included) */
+  float ms_intervals;      /* the interval claims, their scan and the records (HIP events) */
+  float ms_copy;           /* the copy of the graph to the host (wall; 0 without out_host) */
+} eg3d_replay_stats;
+int eg3d_replay_device(eg3d_ctx* ctx, const eg3d_device_edgepoints* cloud, eg3d_device_graph3d* out_dev,
+                       struct eg3d_graph3d* out_host, eg3d_replay_stats* stats);
+void eg3d_free_graph3d(struct eg3d_graph3d* g);
 
 #ifdef __cplusplus
 }
