@@ -83,6 +83,18 @@ class ReplayStats(C.Structure):
                 ("ms_intervals", C.c_float), ("ms_copy", C.c_float)]
 
 
+class PolylineMatches(C.Structure):
+    """eg3d_polyline_matches (library-owned; eg3d_free_polyline_matches)."""
+    _fields_ = [("n_refpoints", C.c_uint32), ("refpoints", u32p), ("n_sets", C.c_uint32), ("row_off", u32p), ("pl_ids", u32p)]
+
+
+class PolymatchStats(C.Structure):
+    """eg3d_polymatch_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_entries", C.c_uint64), ("n_accepted", C.c_uint64), ("n_nodes", C.c_uint64),
+                ("n_sets", C.c_uint64), ("ms_grid", C.c_float), ("ms_search", C.c_float), ("ms_components", C.c_float),
+                ("ms_copy", C.c_float)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("n_seeds", C.c_uint32), ("n_curves", C.c_int32),
                 ("rng_seed", C.c_uint64), ("max_track", C.c_int32), ("obs_noise_px", C.c_float),

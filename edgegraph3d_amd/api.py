@@ -71,6 +71,10 @@ def lib():
                                          C.POINTER(D.Graph3D), C.POINTER(D.ReplayStats)]
         L.eg3d_free_graph3d.argtypes = [C.POINTER(D.Graph3D)]
         L.eg3d_free_graph3d.restype = None
+        L.eg3d_match_polylines_closeness.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32,
+                                                     C.POINTER(D.PolylineMatches), C.POINTER(D.PolymatchStats)]
+        L.eg3d_free_polyline_matches.argtypes = [C.POINTER(D.PolylineMatches)]
+        L.eg3d_free_polyline_matches.restype = None
         _LIB = L
     return _LIB
 
@@ -82,6 +86,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
     "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
+    "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches",
 ]
 
 
@@ -282,6 +287,26 @@ class Context:
             d = D.edgepoints_to_dict(e)
         lib().eg3d_free_edgepoints(C.byref(e))
         d["times"] = {f[0]: getattr(tm, f[0]) for f in D.StageTimes._fields_}
+        return d
+
+    def match_polylines_closeness(self, seeds_ptr=None, begin=0, end=None):
+        """Pipeline 2's polyline matcher (eg3d_match_polylines_closeness) on seeds [begin, end) of `seeds_ptr`, or of the
+        uploaded seeds when it is None (`end` is then required). Returns the accepted reference points, the sets as the
+        CSR match_polyline_sets takes (n_sets, row_off, pl_ids), and the call's stats."""
+        if end is None:
+            if seeds_ptr is None:
+                raise Eg3dError("match_polylines_closeness: `end` is required with the uploaded seeds")
+            end = int(seeds_ptr.contents.n_seeds) if hasattr(seeds_ptr, "contents") else int(seeds_ptr.n_seeds)
+        m, st = D.PolylineMatches(), D.PolymatchStats()
+        st.struct_size = C.sizeof(D.PolymatchStats)
+        _check(lib().eg3d_match_polylines_closeness(self._h, seeds_ptr, begin, end, C.byref(m), C.byref(st)),
+               "eg3d_match_polylines_closeness")
+        n_rows = int(m.n_sets) * self.n_views
+        row_off = D.as_np(m.row_off, n_rows + 1, np.uint32).copy()
+        d = {"refpoints": D.as_np(m.refpoints, int(m.n_refpoints), np.uint32).copy(), "n_sets": int(m.n_sets),
+             "row_off": row_off, "pl_ids": D.as_np(m.pl_ids, int(row_off[-1]), np.uint32).copy(),
+             "stats": {f[0]: getattr(st, f[0]) for f in D.PolymatchStats._fields_}}
+        lib().eg3d_free_polyline_matches(C.byref(m))
         return d
 
     def last_device_output(self):

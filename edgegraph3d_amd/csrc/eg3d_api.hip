@@ -29,6 +29,7 @@
 #include "eg3d_host_copy.h"
 #include "eg3d_kernels.h"
 #include "eg3d_k8_replay.h"
+#include "eg3d_k9_polymatch.h"
 
 using namespace eg3d;
 
@@ -130,15 +131,27 @@ struct DevOwner {
 };
 // Host copies of the grids for eg3d_get_grid (per view CSR with view-local offsets). The grids live on the device (K0 builds
 // them there); the copies are made by the first eg3d_get_grid call that asks for a cell size — tests do, the hot path never.
+// Index 2 is the 10 px map of the polyline matcher (eg3d_match_polylines_closeness): no context has it until the first such
+// call on the context or on one of its clones builds it (ensure_grid10, under `mu`); it then belongs to this object, which
+// the context and its clones share, and goes away with the last of them.
 struct HostGrids {
   std::mutex mu;
-  bool have[2] = {false, false};
-  std::vector<std::vector<uint32_t>> h_off[2], h_ids[2];
+  bool have[3] = {false, false, false};
+  std::vector<std::vector<uint32_t>> h_off[3], h_ids[3];
   // where to fetch them from (device arrays of the shared, immutable scene)
   int device = 0, n_views = 0;
-  const uint32_t* d_off[2] = {nullptr, nullptr};
-  const uint32_t* d_ids[2] = {nullptr, nullptr};
-  uint32_t cells_per_view[2] = {0, 0};
+  const uint32_t* d_off[3] = {nullptr, nullptr, nullptr};
+  const uint32_t* d_ids[3] = {nullptr, nullptr, nullptr};
+  uint32_t cells_per_view[3] = {0, 0, 0};
+  bool built10 = false;
+  uint32_t w10 = 0, h10 = 0;
+  DevBuf g10o, g10i;  // the 10 px map's device arrays (d_off[2] / d_ids[2] point into them)
+  ~HostGrids() {
+    if (!g10o.p && !g10i.p) return;
+    (void)hipSetDevice(device);
+    g10o.release();
+    g10i.release();
+  }
 };
 
 // Test / tuning knobs, read from the environment ONCE when a context is created (eg3d_create; clones
@@ -259,6 +272,11 @@ struct eg3d_ctx {
   DevBuf k8_cnt, k8_slot, k8_last, k8_firstof, k8_flag, k8_rank, k8_lastof, k8_plid, k8_key[2], k8_val[2], k8_tmp, k8_map,
       k8_sflag, k8_pos;
   DevBuf g_nodeX, g_nodept, g_pls, g_ple, g_conoff, g_conpl, g_ivoff, g_ivss, g_ivsxy, g_ives, g_ivexy;
+  // eg3d_match_polylines_closeness (K9). Work: entry -> seed, the per-entry search results, the accept flags and their scan,
+  // the match graph over the scene's polylines, the sort buffers, counters + flag word. Result on the device: the accepted
+  // ids, row_off, pl_ids (copied to the caller's library-owned arrays at the end of the call).
+  DevBuf k9_svseed, k9_cnt, k9_pl, k9_dist, k9_acc, k9_accoff, k9_first, k9_parent, k9_root, k9_ckey, k9_rank, k9_key[2], k9_ctr,
+      k9_ref, k9_rowoff, k9_plids;
   int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (read by eg3d_create; tests): a node table of 2^bits slots, raised to the
                               // smallest power of two above the number of lookups; 0 = the default, about twice that
   uint32_t n_pl = 0, n_vtx = 0;  // polylines and vertices of the scene as uploaded
@@ -430,75 +448,120 @@ static int scan_total_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t
   return EG3D_OK;
 }
 
-// K0: both uniform grids of the scene on the device (the scene's polylines are already resident: c->ds). Per cell size:
-// count the (cell, polyline) pairs of every polyline, exclusive scan, write them as 64-bit keys, radix sort, unique, CSR.
-// Temporaries (24 B per pair) are freed before the function returns.
-static int build_grids_device(eg3d_ctx* c, uint32_t NP) {
+// K0: one uniform grid of the scene on the device (the scene's polylines are already resident: c->ds): count the (cell,
+// polyline) pairs of every polyline, exclusive scan, write them as 64-bit keys, radix sort, unique, CSR. The temporaries (24 B
+// per pair) belong to the caller, which frees them once the stream has drained.
+struct GridTemps {
+  DevBuf cnt, off, keys, keys2, n;  // n: [0] unique keys, [1] samples outside the image (summed over the builds)
+  ~GridTemps() {
+    for (DevBuf* x : {&cnt, &off, &keys, &keys2, &n}) x->release();
+  }
+};
+static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t, DevBuf& g_off, DevBuf& g_ids, uint32_t* out_w,
+                             uint32_t* out_h, uint32_t* dropped) {
   hipStream_t st = c->stream;
   const int V = c->V;
-  DevBuf t_cnt, t_off, t_keys, t_keys2, t_n;
-  struct Release {
-    DevBuf* b[5];
-    ~Release() {
-      for (DevBuf* x : b) x->release();
-    }
-  } rel{{&t_cnt, &t_off, &t_keys, &t_keys2, &t_n}};
-  BUF_TRY(t_n.ensure(2 * sizeof(uint32_t)));  // [0] unique keys, [1] samples outside the image
-  HIP_TRY(hipMemsetAsync(t_n.p, 0, 2 * sizeof(uint32_t), st));
-  for (int which = 0; which < 2; which++) {
-    const float cell = which == 0 ? 30.0f : 4.0f;
-    const int map_w = (int)std::ceil(c->W / cell), map_h = (int)std::ceil(c->H / cell);  // (as host/grid_build.cpp: float division)
-    c->gw[which] = (uint32_t)map_w;
-    c->gh[which] = (uint32_t)map_h;
-    const unsigned long long total_cells = (unsigned long long)V * (unsigned long long)map_w * (unsigned long long)map_h;
-    if (total_cells >= 0xffffffffull) {
-      g_err = "eg3d_create: the scene's grids have more than 2^32-2 cells";
-      return EG3D_ERR_CAPACITY;
-    }
-    DevBuf& g_off = which == 0 ? c->b_g30o : c->b_g4o;
-    DevBuf& g_ids = which == 0 ? c->b_g30i : c->b_g4i;
-    BUF_TRY(t_cnt.ensure(sizeof(uint32_t) * ((size_t)NP + 1)));
-    BUF_TRY(t_off.ensure(sizeof(uint32_t) * ((size_t)NP + 1)));
-    HIP_TRY(hipMemsetAsync(t_cnt.as<uint32_t>() + NP, 0, sizeof(uint32_t), st));
-    launch_k0_pairs(st, false, c->ds, NP, cell, map_w, map_h, t_cnt.as<uint32_t>(), nullptr, nullptr, t_n.as<uint32_t>() + 1);
-    uint32_t n_pairs = 0;
-    BUF_TRY(scan_total_u32(c, t_cnt.as<uint32_t>(), t_off.as<uint32_t>(), (size_t)NP + 1, n_pairs, "(cell, polyline) entries of the grids"));
-    BUF_TRY(g_off.ensure(sizeof(uint32_t) * ((size_t)total_cells + 1)));
-    uint32_t n_unique = 0;
+  if (!t.n.p) {
+    BUF_TRY(t.n.ensure(2 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(t.n.p, 0, 2 * sizeof(uint32_t), st));
+  }
+  const int map_w = (int)std::ceil(c->W / cell), map_h = (int)std::ceil(c->H / cell);  // (as host/grid_build.cpp: float division)
+  *out_w = (uint32_t)map_w;
+  *out_h = (uint32_t)map_h;
+  const unsigned long long total_cells = (unsigned long long)V * (unsigned long long)map_w * (unsigned long long)map_h;
+  if (total_cells >= 0xffffffffull) {
+    g_err = "eg3d: the scene's grids have more than 2^32-2 cells";
+    return EG3D_ERR_CAPACITY;
+  }
+  BUF_TRY(t.cnt.ensure(sizeof(uint32_t) * ((size_t)NP + 1)));
+  BUF_TRY(t.off.ensure(sizeof(uint32_t) * ((size_t)NP + 1)));
+  HIP_TRY(hipMemsetAsync(t.cnt.as<uint32_t>() + NP, 0, sizeof(uint32_t), st));
+  launch_k0_pairs(st, false, c->ds, NP, cell, map_w, map_h, t.cnt.as<uint32_t>(), nullptr, nullptr, t.n.as<uint32_t>() + 1);
+  uint32_t n_pairs = 0;
+  BUF_TRY(scan_total_u32(c, t.cnt.as<uint32_t>(), t.off.as<uint32_t>(), (size_t)NP + 1, n_pairs, "(cell, polyline) entries of the grids"));
+  BUF_TRY(g_off.ensure(sizeof(uint32_t) * ((size_t)total_cells + 1)));
+  uint32_t n_unique = 0;
+  {
     if (n_pairs) {
-      BUF_TRY(t_keys.ensure(sizeof(unsigned long long) * (size_t)n_pairs));
-      BUF_TRY(t_keys2.ensure(sizeof(unsigned long long) * (size_t)n_pairs));
-      launch_k0_pairs(st, true, c->ds, NP, cell, map_w, map_h, nullptr, t_off.as<uint32_t>(), t_keys.as<unsigned long long>(), nullptr);
+      BUF_TRY(t.keys.ensure(sizeof(unsigned long long) * (size_t)n_pairs));
+      BUF_TRY(t.keys2.ensure(sizeof(unsigned long long) * (size_t)n_pairs));
+      launch_k0_pairs(st, true, c->ds, NP, cell, map_w, map_h, nullptr, t.off.as<uint32_t>(), t.keys.as<unsigned long long>(), nullptr);
       int end_bit = EG3D_K0_PL_BITS_HOST;
       while (end_bit < 64 && (total_cells >> (end_bit - EG3D_K0_PL_BITS_HOST)) != 0) end_bit++;
       size_t tmp = 0;
-      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, t_keys.as<unsigned long long>(), t_keys2.as<unsigned long long>(),
+      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, t.keys.as<unsigned long long>(), t.keys2.as<unsigned long long>(),
                                                 (int)n_pairs, 0, end_bit, st));
       BUF_TRY(c->b_scan_tmp.ensure(tmp));
-      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->b_scan_tmp.p, tmp, t_keys.as<unsigned long long>(), t_keys2.as<unsigned long long>(),
+      HIP_TRY(hipcub::DeviceRadixSort::SortKeys(c->b_scan_tmp.p, tmp, t.keys.as<unsigned long long>(), t.keys2.as<unsigned long long>(),
                                                 (int)n_pairs, 0, end_bit, st));
       tmp = 0;
-      HIP_TRY(hipcub::DeviceSelect::Unique(nullptr, tmp, t_keys2.as<unsigned long long>(), t_keys.as<unsigned long long>(),
-                                           t_n.as<uint32_t>(), (int)n_pairs, st));
+      HIP_TRY(hipcub::DeviceSelect::Unique(nullptr, tmp, t.keys2.as<unsigned long long>(), t.keys.as<unsigned long long>(),
+                                           t.n.as<uint32_t>(), (int)n_pairs, st));
       BUF_TRY(c->b_scan_tmp.ensure(tmp));
-      HIP_TRY(hipcub::DeviceSelect::Unique(c->b_scan_tmp.p, tmp, t_keys2.as<unsigned long long>(), t_keys.as<unsigned long long>(),
-                                           t_n.as<uint32_t>(), (int)n_pairs, st));
+      HIP_TRY(hipcub::DeviceSelect::Unique(c->b_scan_tmp.p, tmp, t.keys2.as<unsigned long long>(), t.keys.as<unsigned long long>(),
+                                           t.n.as<uint32_t>(), (int)n_pairs, st));
       Readback rb(c);
-      const int in = rb.add(t_n.p, 2);
+      const int in = rb.add(t.n.p, 2);
       BUF_TRY(rb.run());
       n_unique = rb.item(in)[0];
-      if (which == 1) c->grid_dropped = rb.item(in)[1];  // (both cell sizes have been counted by now)
+      *dropped = rb.item(in)[1];  // (every cell size built with `t` so far has been counted by now)
     }
     BUF_TRY(g_ids.ensure(sizeof(uint32_t) * std::max<size_t>(n_unique, 1)));
     if (n_unique)
-      launch_k0_csr(st, t_keys.as<unsigned long long>(), n_unique, (uint32_t)total_cells, g_off.as<uint32_t>(), g_ids.as<uint32_t>());
+      launch_k0_csr(st, t.keys.as<unsigned long long>(), n_unique, (uint32_t)total_cells, g_off.as<uint32_t>(), g_ids.as<uint32_t>());
     else
       HIP_TRY(hipMemsetAsync(g_off.p, 0, sizeof(uint32_t) * ((size_t)total_cells + 1), st));
+  }
+  return EG3D_OK;
+}
+// The 30 px and 4 px grids of eg3d_create.
+static int build_grids_device(eg3d_ctx* c, uint32_t NP) {
+  GridTemps t;
+  for (int which = 0; which < 2; which++) {
+    DevBuf& g_off = which == 0 ? c->b_g30o : c->b_g4o;
+    DevBuf& g_ids = which == 0 ? c->b_g30i : c->b_g4i;
+    BUF_TRY(build_grid_device(c, NP, which == 0 ? 30.0f : 4.0f, t, g_off, g_ids, &c->gw[which], &c->gh[which], &c->grid_dropped));
     c->hg->d_off[which] = g_off.as<uint32_t>();
     c->hg->d_ids[which] = g_ids.as<uint32_t>();
-    c->hg->cells_per_view[which] = (uint32_t)(map_w * map_h);
+    c->hg->cells_per_view[which] = c->gw[which] * c->gh[which];
   }
-  HIP_TRY(hipStreamSynchronize(st));  // the temporaries go away
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the temporaries go away
+  return EG3D_OK;
+}
+// The 10 px map of the polyline matcher, built by the first call that needs it on this context or a clone of it and shared
+// by all of them from then on (HostGrids). eg3d_create neither builds nor allocates it.
+static int ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms) {
+  HostGrids& hg = *c->hg;
+  std::lock_guard<std::mutex> lk(hg.mu);
+  if (!hg.built10) {
+    const auto t0 = std::chrono::steady_clock::now();
+    // (the build runs on the calling context's stream and scratch; `mu` only keeps a second context of the family from
+    // building the same map at the same time)
+    GridTemps t;
+    DevBuf& g_off = hg.g10o;
+    DevBuf& g_ids = hg.g10i;
+    uint32_t dropped = 0;
+    int rc = build_grid_device(c, c->n_pl, 10.0f, t, g_off, g_ids, &hg.w10, &hg.h10, &dropped);
+    if (rc == EG3D_OK && hipStreamSynchronize(c->stream) != hipSuccess) {
+      g_err = "eg3d_match_polylines_closeness: building the 10 px map failed";
+      rc = EG3D_ERR_HIP;
+    }
+    if (rc != EG3D_OK) {
+      (void)hipStreamSynchronize(c->stream);
+      g_off.release();
+      g_ids.release();
+      return rc;
+    }
+    hg.d_off[2] = g_off.as<uint32_t>();
+    hg.d_ids[2] = g_ids.as<uint32_t>();
+    hg.cells_per_view[2] = hg.w10 * hg.h10;
+    hg.built10 = true;
+    if (ms) *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  out->w = (int32_t)hg.w10;
+  out->h = (int32_t)hg.h10;
+  out->off = hg.d_off[2];
+  out->ids = hg.d_ids[2];
   return EG3D_OK;
 }
 
@@ -969,7 +1032,9 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
                    &c->k8_cnt, &c->k8_slot, &c->k8_last, &c->k8_firstof, &c->k8_flag, &c->k8_rank, &c->k8_lastof, &c->k8_plid,
                    &c->k8_key[0], &c->k8_key[1], &c->k8_val[0], &c->k8_val[1], &c->k8_tmp, &c->k8_map, &c->k8_sflag, &c->k8_pos,
                    &c->g_nodeX, &c->g_nodept, &c->g_pls, &c->g_ple, &c->g_conoff, &c->g_conpl, &c->g_ivoff, &c->g_ivss,
-                   &c->g_ivsxy, &c->g_ives, &c->g_ivexy, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
+                   &c->g_ivsxy, &c->g_ives, &c->g_ivexy, &c->k9_svseed, &c->k9_cnt, &c->k9_pl, &c->k9_dist, &c->k9_acc, &c->k9_accoff,
+                   &c->k9_first, &c->k9_parent, &c->k9_root, &c->k9_ckey, &c->k9_rank, &c->k9_key[0], &c->k9_key[1], &c->k9_ctr,
+                   &c->k9_ref, &c->k9_rowoff, &c->k9_plids, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
                    &c->b_pools, &c->b_stage_pts, &c->b_stage_obs, &c->b_stage_used};
   for (DevBuf* b : all) b->release();
   if (c->pinned) (void)hipHostFree(c->pinned);
@@ -986,13 +1051,17 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
 
 extern "C" int eg3d_get_grid(eg3d_ctx* c, int view, int which, uint32_t* ncols, uint32_t* nrows,
                              const uint32_t** cell_off, const uint32_t** ids) {
-  if (!c || view < 0 || view >= c->V || which < 0 || which > 1) {
+  if (!c || view < 0 || view >= c->V || which < 0 || which > 2) {
     g_err = "eg3d_get_grid: bad arguments";
     return EG3D_ERR_ARG;
   }
   HostGrids& hg = *c->hg;
   {
     std::lock_guard<std::mutex> lk(hg.mu);
+    if (which == 2 && !hg.built10) {
+      g_err = "eg3d_get_grid: the 10 px map does not exist before the first eg3d_match_polylines_closeness call";
+      return EG3D_ERR_ARG;
+    }
     if (!hg.have[which]) {  // first request for this cell size: fetch the device CSR and cut it into per-view CSRs
       HIP_TRY(hipSetDevice(hg.device));
       const size_t cpv = hg.cells_per_view[which], V = (size_t)hg.n_views;
@@ -1011,8 +1080,8 @@ extern "C" int eg3d_get_grid(eg3d_ctx* c, int view, int which, uint32_t* ncols, 
       hg.have[which] = true;
     }
   }
-  *ncols = c->gw[which];
-  *nrows = c->gh[which];
+  *ncols = which == 2 ? hg.w10 : c->gw[which];
+  *nrows = which == 2 ? hg.h10 : c->gh[which];
   *cell_off = hg.h_off[which][(size_t)view].data();
   *ids = hg.h_ids[which][(size_t)view].data();
   return EG3D_OK;
@@ -3150,6 +3219,217 @@ extern "C" int eg3d_replay_device(eg3d_ctx* c, const eg3d_device_edgepoints* clo
     stats->ms_copy = ms_copy;
   }
   return EG3D_OK;
+}
+
+// ---- polyline matching by closeness to the reference points (K9, eg3d_k9_polymatch.hip) ---------------------------------------
+static int k9_sort(eg3d_ctx* c, const unsigned long long* in, unsigned long long* out, size_t n) {
+  size_t bytes = 0;
+  HIP_TRY(k8_sort_keys(c->stream, nullptr, bytes, in, out, n));
+  BUF_TRY(c->k8_tmp.ensure(bytes));
+  HIP_TRY(k8_sort_keys(c->stream, c->k8_tmp.p, bytes, in, out, n));
+  return EG3D_OK;
+}
+
+extern "C" void eg3d_free_polyline_matches(eg3d_polyline_matches* m) {
+  if (!m) return;
+  free(m->refpoints);
+  free(m->row_off);
+  free(m->pl_ids);
+  memset(m, 0, sizeof(*m));
+}
+
+// `forced` (tests): per-entry results that take the place of the search's, host arrays of n_sv entries each
+struct K9Forced {
+  const uint32_t* cnt;
+  const uint32_t* pl;
+  const float* dist;
+};
+static int polymatch_impl(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint32_t e, const K9Forced* forced,
+                          eg3d_polyline_matches* out, eg3d_polymatch_stats* stats) {
+  if (stats && stats->struct_size < sizeof(eg3d_polymatch_stats)) {
+    g_err = "eg3d_match_polylines_closeness: stats->struct_size is smaller than this library's eg3d_polymatch_stats (" +
+            std::to_string(sizeof(eg3d_polymatch_stats)) + " bytes): set it to sizeof(eg3d_polymatch_stats)";
+    return EG3D_ERR_ARG;
+  }
+  if (!c || !out) {
+    g_err = "eg3d_match_polylines_closeness: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  if (seeds) BUF_TRY(eg3d_upload_seeds(c, seeds));
+  if (b > e || e > c->n_seeds) {
+    g_err = "eg3d_match_polylines_closeness: bad seed range (seeds uploaded?)";
+    return EG3D_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_seeds = e - b;
+  const uint32_t sv_base = n_seeds ? (*c->h_trk)[b] : 0, n_sv = n_seeds ? (*c->h_trk)[e] - sv_base : 0;
+  uint32_t n_acc = 0, n_nodes = 0, n_sets = 0;
+  float ms_grid = 0, ms_search = 0, ms_comp = 0, ms_copy = 0;
+  if (n_sv && NP) {
+    K9Grid g10;
+    BUF_TRY(ensure_grid10(c, &g10, &ms_grid));
+    SeedsDev sd;
+    sd.trk_off = c->b_toff.as<uint32_t>();
+    sd.trk_view = c->b_tview.as<int32_t>();
+    sd.trk_xy = c->b_txy.as<float>();
+    // ---- the view ids, before anything indexes with them
+    BUF_TRY(c->k9_ctr.ensure(4 * sizeof(uint32_t)));  // [0] flags, [1] nodes, [2] sets
+    BUF_TRY(c->k9_svseed.ensure(sizeof(uint32_t) * n_sv));
+    uint32_t* ctr = c->k9_ctr.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(uint32_t), st));
+    launch_k9_prep(st, sd, c->V, b, n_seeds, sv_base, c->k9_svseed.as<uint32_t>(), ctr);
+    HIP_TRY(hipGetLastError());
+    {
+      BUF_TRY(ensure_mailbox(c));
+      Readback rb(c);
+      const int it = rb.add(ctr, 1);
+      BUF_TRY(rb.run());
+      if (*rb.item(it) & K9_FLAG_BAD_VIEW) {
+        g_err = "eg3d_match_polylines_closeness: view id out of range";
+        return EG3D_ERR_ARG;
+      }
+    }
+    // ---- the search
+    BUF_TRY(c->k9_cnt.ensure(sizeof(uint32_t) * n_sv));
+    BUF_TRY(c->k9_pl.ensure(sizeof(uint32_t) * n_sv));
+    BUF_TRY(c->k9_dist.ensure(sizeof(float) * n_sv));
+    const K9Entries ent{c->k9_cnt.as<uint32_t>(), c->k9_pl.as<uint32_t>(), c->k9_dist.as<float>()};
+    HIP_TRY(hipEventRecord(c->ea[0], st));  // ms_search: the search kernel alone
+    if (!forced) {
+      launch_k9_close_polylines(st, c->ds, g10, sd, sv_base, n_sv, c->k9_svseed.as<uint32_t>(), ent);
+      HIP_TRY(hipGetLastError());
+    } else {
+      HIP_TRY(hipMemcpyAsync(ent.cnt, forced->cnt, sizeof(uint32_t) * n_sv, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(ent.pl, forced->pl, sizeof(uint32_t) * n_sv, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(ent.dist, forced->dist, sizeof(float) * n_sv, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));  // (pageable host arrays of the caller)
+    }
+    HIP_TRY(hipEventRecord(c->eb[0], st));
+    // ---- the rule, the match graph, its components and their order
+    BUF_TRY(c->k9_acc.ensure(sizeof(uint32_t) * ((size_t)n_seeds + 1)));
+    BUF_TRY(c->k9_accoff.ensure(sizeof(uint32_t) * ((size_t)n_seeds + 1)));
+    BUF_TRY(c->k9_first.ensure(8 * (size_t)NP));
+    BUF_TRY(c->k9_ckey.ensure(8 * (size_t)NP));
+    BUF_TRY(c->k9_parent.ensure(4 * (size_t)NP));
+    BUF_TRY(c->k9_root.ensure(4 * (size_t)NP));
+    BUF_TRY(c->k9_rank.ensure(4 * (size_t)NP));
+    for (int k = 0; k < 2; k++) BUF_TRY(c->k9_key[k].ensure(8 * (size_t)NP));
+    const K9Graph g{c->k9_first.as<unsigned long long>(), c->k9_parent.as<uint32_t>(), c->k9_root.as<uint32_t>(),
+                    c->k9_ckey.as<unsigned long long>(), c->k9_rank.as<uint32_t>()};
+    unsigned long long* key[2] = {c->k9_key[0].as<unsigned long long>(), c->k9_key[1].as<unsigned long long>()};
+    HIP_TRY(hipEventRecord(c->ea[1], st));
+    launch_k9_init(st, NP, g);
+    launch_k9_refpoint_rule(st, c->ds, sd, b, n_seeds, sv_base, ent, c->k9_acc.as<uint32_t>(), g);
+    launch_k9_flatten(st, NP, g, ctr + 1);
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(k9_sort(c, g.ckey, key[0], NP));
+    launch_k9_rank(st, key[0], NP, g, ctr + 2);
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(scan_queue_u32(c, c->k9_acc.as<uint32_t>(), c->k9_accoff.as<uint32_t>(), (size_t)n_seeds + 1, 0));
+    {
+      Readback rb(c);
+      const int ic = rb.add(ctr + 1, 2);
+      const int ia = rb.add(c->k9_accoff.as<uint32_t>() + n_seeds, 1);
+      const int iw = rb.add(c->b_scanchk.as<uint32_t>(), 1);
+      rb.clear_after(c->b_scanchk.as<uint32_t>());
+      BUF_TRY(rb.run());
+      if (*rb.item(iw)) return wrapped_error("accepted reference points");
+      n_nodes = rb.item(ic)[0];
+      n_sets = rb.item(ic)[1];
+      n_acc = *rb.item(ia);
+    }
+    if ((uint64_t)n_sets * V >= 0xffffffffull) {
+      g_err = "eg3d_match_polylines_closeness: the result has more than 2^32-2 rows (sets x views)";
+      return EG3D_ERR_CAPACITY;
+    }
+    BUF_TRY(c->k9_ref.ensure(sizeof(uint32_t) * std::max<size_t>(n_acc, 1)));
+    BUF_TRY(c->k9_rowoff.ensure(sizeof(uint32_t) * ((size_t)n_sets * V + 1)));
+    BUF_TRY(c->k9_plids.ensure(sizeof(uint32_t) * std::max<size_t>(n_nodes, 1)));
+    launch_k9_compact(st, c->k9_acc.as<uint32_t>(), c->k9_accoff.as<uint32_t>(), b, n_seeds, c->k9_ref.as<uint32_t>());
+    if (n_nodes) {
+      launch_k9_node_keys(st, c->ds, NP, g, key[0]);
+      HIP_TRY(hipGetLastError());
+      BUF_TRY(k9_sort(c, key[0], key[1], NP));
+      launch_k0_csr(st, key[1], n_nodes, n_sets * V, c->k9_rowoff.as<uint32_t>(), c->k9_plids.as<uint32_t>());
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->eb[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&ms_search, c->ea[0], c->eb[0]));
+    HIP_TRY(hipEventElapsedTime(&ms_comp, c->ea[1], c->eb[1]));
+  }
+  // ---- the result, library-owned
+  const auto t0 = std::chrono::steady_clock::now();
+  eg3d_polyline_matches m;
+  memset(&m, 0, sizeof(m));
+  const size_t n_rows1 = (size_t)n_sets * V + 1;
+  m.refpoints = (uint32_t*)malloc(sizeof(uint32_t) * std::max<size_t>(n_acc, 1));
+  m.row_off = (uint32_t*)malloc(sizeof(uint32_t) * n_rows1);
+  m.pl_ids = (uint32_t*)malloc(sizeof(uint32_t) * std::max<size_t>(n_nodes, 1));
+  hipError_t he = hipSuccess;
+  if (m.refpoints && m.row_off && m.pl_ids) {
+    m.row_off[0] = 0;
+    if (n_acc) he = hipMemcpyAsync(m.refpoints, c->k9_ref.p, sizeof(uint32_t) * n_acc, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && n_sets) he = hipMemcpyAsync(m.row_off, c->k9_rowoff.p, sizeof(uint32_t) * n_rows1, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && n_nodes) he = hipMemcpyAsync(m.pl_ids, c->k9_plids.p, sizeof(uint32_t) * n_nodes, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = es;
+  }
+  if (!(m.refpoints && m.row_off && m.pl_ids) || he != hipSuccess) {
+    g_err = he != hipSuccess ? std::string("eg3d_match_polylines_closeness: copy to the host: ") + hipGetErrorString(he)
+                             : std::string("eg3d_match_polylines_closeness: out of host memory");
+    eg3d_free_polyline_matches(&m);
+    return EG3D_ERR_HIP;
+  }
+  m.n_refpoints = n_acc;
+  m.n_sets = n_sets;
+  ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  *out = m;
+  if (stats) {
+    stats->struct_size = (uint32_t)sizeof(eg3d_polymatch_stats);
+    stats->n_entries = n_sv;
+    stats->n_accepted = n_acc;
+    stats->n_nodes = n_nodes;
+    stats->n_sets = n_sets;
+    stats->ms_grid = ms_grid;
+    stats->ms_search = ms_search;
+    stats->ms_components = ms_comp;
+    stats->ms_copy = ms_copy;
+  }
+  return EG3D_OK;
+}
+extern "C" int eg3d_match_polylines_closeness(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint32_t e,
+                                              eg3d_polyline_matches* out, eg3d_polymatch_stats* stats) {
+  return polymatch_impl(c, seeds, b, e, nullptr, out, stats);
+}
+/* Tests only, not declared in include/eg3d.h (tests/test_gpu_polymatch.py).
+ * eg3d_polymatch_test_entries: the per-entry results the last eg3d_match_polylines_closeness call on this context left on the
+ * device (n = its stats.n_entries): polylines within 10 px, the first one's id and its distance.
+ * eg3d_polymatch_test_rule: the matcher on the uploaded seeds [b, e) with the CALLER's per-entry results (one per track entry
+ * of the range; a polyline id must lie inside its view) in place of the search: the rule, the graph and the order alone. */
+extern "C" int eg3d_polymatch_test_entries(eg3d_ctx* c, uint32_t n, uint32_t* cnt, uint32_t* pl, float* dist) {
+  if (!c || (size_t)n * 4 > c->k9_cnt.cap || (size_t)n * 4 > c->k9_pl.cap || (size_t)n * 4 > c->k9_dist.cap) {
+    g_err = "eg3d_polymatch_test_entries: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n) {
+    HIP_TRY(hipMemcpy(cnt, c->k9_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pl, c->k9_pl.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dist, c->k9_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
+  return EG3D_OK;
+}
+extern "C" int eg3d_polymatch_test_rule(eg3d_ctx* c, uint32_t b, uint32_t e, const uint32_t* cnt, const uint32_t* pl,
+                                        const float* dist, eg3d_polyline_matches* out) {
+  if (!cnt || !pl || !dist) {
+    g_err = "eg3d_polymatch_test_rule: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  const K9Forced f{cnt, pl, dist};
+  return polymatch_impl(c, nullptr, b, e, &f, out, nullptr);
 }
 
 #ifdef EG3D_SECTION_TIMING

@@ -316,6 +316,18 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31
   return v;
 }
+// Wave minimum through DPP (row_shr 1/2/4/8, row_bcast 15/31: lane 63 ends up with the minimum of all lanes) and one
+// v_readlane — seven short instructions instead of six dependent trips through the LDS crossbar. All lanes active.
+__device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
+  auto mn = [](uint32_t x, int y) { return (uint32_t)y < x ? (uint32_t)y : x; };
+  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));
+  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));
+  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));
+  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));
+  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));
+  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));
+  return (uint32_t)lane_bcast((int)v, 63);
+}
 struct GnRow {
   double j00, j01, j02, j10, j11, j12, r0, r1;
 };

@@ -13,6 +13,18 @@ struct SeedsDev {
   const float* trk_xy;
 };
 
+// Observation of `seed` in view `view`: the LAST track entry with that view id (Q2).
+__device__ __forceinline__ void seed_obs_in_view(const SeedsDev& sd, uint32_t t0, uint32_t k, int32_t view, float& x,
+                                                 float& y) {
+  x = 0.f;
+  y = 0.f;
+  for (uint32_t i = 0; i < k; i++)
+    if (sd.trk_view[t0 + i] == view) {
+      x = sd.trk_xy[2 * (t0 + i)];
+      y = sd.trk_xy[2 * (t0 + i) + 1];
+    }
+}
+
 enum : uint32_t { CTR_ARENA_OVERFLOW = 0x100u, CTR_SLOT_STARVED = 0x200u /* k3b_expand found no free working slice (internal) */,
                   CTR_LONG_REFUSED = 0x400u /* the few-views build of k3b_expand met a solve of more than 32 rows (internal) */ };
 typedef uint64_t eg3d_off_t;  // element type of obs_off in the output cloud (include/eg3d.h)

@@ -45,19 +45,6 @@ __device__ __forceinline__ float wave_min_f32(float v) {
   return v;
 }
 
-// Wave minimum through DPP (row_shr 1/2/4/8, row_bcast 15/31: lane 63 ends up with the minimum of all lanes) and one
-// v_readlane — seven short instructions instead of six dependent trips through the LDS crossbar. All lanes active.
-__device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
-  auto mn = [](uint32_t x, int y) { return (uint32_t)y < x ? (uint32_t)y : x; };
-  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));
-  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));
-  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));
-  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));
-  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));
-  v = mn(v, __builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));
-  return (uint32_t)lane_bcast((int)v, 63);
-}
-
 // ------------------------------------------------------------------ prep -------
 __global__ void k_seed_prep(SeedsDev sd, uint32_t seed_begin, uint32_t n_seeds, uint32_t sv_base, uint32_t* sv_seed,
                             int32_t* map_view, uint32_t* map_entry, uint32_t* map_n) {
@@ -67,18 +54,6 @@ __global__ void k_seed_prep(SeedsDev sd, uint32_t seed_begin, uint32_t n_seeds, 
   uint32_t t0 = sd.trk_off[seed], t1 = sd.trk_off[seed + 1];
   for (uint32_t e = t0; e < t1; e++) sv_seed[e - sv_base] = seed;
   map_n[i] = build_seed_view_map(sd.trk_view + t0, t1 - t0, map_view + (t0 - sv_base), map_entry + (t0 - sv_base));
-}
-
-// Observation of `seed` in view `view`: the LAST track entry with that view id (Q2).
-__device__ __forceinline__ void seed_obs_in_view(const SeedsDev& sd, uint32_t t0, uint32_t k, int32_t view, float& x,
-                                                 float& y) {
-  x = 0.f;
-  y = 0.f;
-  for (uint32_t i = 0; i < k; i++)
-    if (sd.trk_view[t0 + i] == view) {
-      x = sd.trk_xy[2 * (t0 + i)];
-      y = sd.trk_xy[2 * (t0 + i) + 1];
-    }
 }
 
 __global__ void k1_count_raw(DevScene s, SeedsDev sd, uint32_t sv_base, uint32_t n_sv, const uint32_t* sv_seed,

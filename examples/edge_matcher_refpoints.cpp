@@ -30,7 +30,7 @@
 //        builds the polyline graph of every binary edge image (view i = i-th image; SURVEY N2,
 //        edge_matcher.cpp:84-94 convert_edge_images_to_optimized_polyline_graphs) and writes the container
 //   edge_matcher_refpoints <dir>/input.json <dir>/plgs.bin <out.json> [--filter] [--estimate-F] [--all-pairs]
-//                          [--sets1 <polyline matches of pipeline 1>] [--sets2 <... of pipeline 2>]
+//                          [--sets1 <polyline matches of pipeline 1>] [--sets2 <... of pipeline 2> | --match2]
 //        a match file is text: "eg3d-polyline-sets 1", then "<n_sets> <n_views>", then one line per (set, view):
 //        "<count> <polyline id> ..." with view-local ids (the reference's vector<set<ulong>> per match)
 //        (--make-synthetic also writes <dir>/sets1.txt and <dir>/sets2.txt: the polylines of 3-D curves 0-2 / 3-5)
@@ -216,6 +216,13 @@ int main(int argc, char** argv) {
     if (std::strcmp(argv[a], "--sets1") == 0 && a + 1 < argc) sets_path[0] = argv[++a];
     else if (std::strcmp(argv[a], "--sets2") == 0 && a + 1 < argc) sets_path[1] = argv[++a];
   }
+  // --match2: pipeline 2's polyline matches are computed on the device (eg3d_match_polylines_closeness) where --sets2 reads them
+  bool match2 = false;
+  for (int a = 4; a < argc; a++) match2 |= std::strcmp(argv[a], "--match2") == 0;
+  if (match2 && sets_path[1]) {
+    std::fprintf(stderr, "--match2 and --sets2 exclude each other\n");
+    return 2;
+  }
 
   // wall time of every stage of the run, host stages included (--times prints them; stderr)
   bool print_times = false;
@@ -288,9 +295,21 @@ int main(int argc, char** argv) {
   // ---- pipelines 1 and 2 (pipelines.cpp:219-223): the extractor over the polyline matches of each stage, in
   // match order (one call takes all matches of a stage: eg3d_match_polyline_sets emits them set by set)
   for (int stage = 0; stage < 2; stage++) {
-    if (!sets_path[stage]) continue;
+    if (!sets_path[stage] && !(stage == 1 && match2)) continue;
     MatchSets ms;
-    if (!read_match_sets(sets_path[stage], V, ms)) return fail("reading a polyline match file");
+    if (stage == 1 && match2) {  // pipelines.cpp:118
+      eg3d_seeds rp;
+      eg3d_sfm_seeds(sfm, &rp);
+      eg3d_polyline_matches pm;
+      if (eg3d_match_polylines_closeness(ctx, &rp, 0, rp.n_seeds, &pm, nullptr) != EG3D_OK)
+        return fail("eg3d_match_polylines_closeness");
+      ms.n_sets = pm.n_sets;
+      ms.row_off.assign(pm.row_off, pm.row_off + (size_t)pm.n_sets * V + 1);
+      ms.ids.assign(pm.pl_ids, pm.pl_ids + ms.row_off.back());
+      if (ms.ids.empty()) ms.ids.push_back(0);
+      std::printf("pipeline 2: %u reference points accepted by the polyline matcher\n", pm.n_refpoints);
+      eg3d_free_polyline_matches(&pm);
+    } else if (!read_match_sets(sets_path[stage], V, ms)) return fail("reading a polyline match file");
     eg3d_polyline_sets ps;
     ps.n_sets = ms.n_sets;
     ps.row_off = ms.row_off.data();

@@ -165,7 +165,8 @@ void eg3d_destroy(eg3d_ctx* ctx);
  * does not affect the others. */
 int eg3d_clone(eg3d_ctx* parent, eg3d_ctx** out);
 
-/* which: 0 = 30 px candidate grid, 1 = 4 px expand-all-views grid. Pointers stay
+/* which: 0 = 30 px candidate grid, 1 = 4 px expand-all-views grid, 2 = 10 px map of eg3d_match_polylines_closeness (exists
+ * after the first such call; EG3D_ERR_ARG before). Pointers stay
  * valid until eg3d_destroy. cell index = row*ncols + col. (The grids are built and kept on the device; the first call for a
  * cell size copies that grid to the host.) */
 int eg3d_get_grid(eg3d_ctx* ctx, int view, int which, uint32_t* ncols, uint32_t* nrows,
@@ -433,6 +434,35 @@ typedef struct eg3d_replay_stats {
 int eg3d_replay_device(eg3d_ctx* ctx, const eg3d_device_edgepoints* cloud, eg3d_device_graph3d* out_dev,
                        struct eg3d_graph3d* out_host, eg3d_replay_stats* stats);
 void eg3d_free_graph3d(struct eg3d_graph3d* g);
+
+/* ---- pipeline 2: polyline matching by closeness to the reference points ---------------------------------------------
+ * polyline_matching_closeness_to_refpoints (src/edgegraph3d/matching/polyline_matching/polyline_matcher.cpp:75-168, called
+ * from pipelines.cpp:113-158), on the device. For every seed of [seed_begin, seed_end), ascending, and every entry of its
+ * track, the polylines within 10 px of the point's observation in that view are looked up on a 10 px map
+ * (PolyLine2DMapSearch with FIND_WITHIN_DIST, polyLine_2d_map_search.cpp:46-77,122-137; the observation of a view is the
+ * one eg3d_match_refpoints uses). With n = the track's length, the point is accepted when no entry finds more than one
+ * polyline, the distinct (view, polyline) pairs found are at least 0.7 n and at least two, and neither min < max / 3 nor
+ * max > 3 min holds for the distances (float, max starting at FLT_MIN: a point whose distances are all 0 is rejected, as in
+ * the reference). The pairs of an accepted point are a clique of the match graph; the result lists the graph's connected
+ * components in the reference's order (by the first accepted point that names one of their polylines, then by (view,
+ * polyline)), each as one ascending id set per view: exactly the rows of an eg3d_polyline_sets, so
+ *     eg3d_polyline_sets s = {m.n_sets, m.row_off, m.pl_ids};  eg3d_match_polyline_sets(ctx, &s, 0, s.n_sets, ...);
+ * runs the reference's pipeline 2 end to end. The 10 px map is built by the first call on the context or on one of its
+ * clones, which then share it (stats->ms_grid: that call only); eg3d_get_grid(which = 2) reads it back from then on and
+ * answers EG3D_ERR_ARG before. An empty range, or no accepted point: n_sets = 0, row_off = {0}, EG3D_OK. A track view id
+ * outside the rig: EG3D_ERR_ARG, by a device-side check that runs before anything else reads the ids (`out` and `stats`
+ * are left untouched; the seeds uploaded before stay in place, as after any refused eg3d_upload_seeds). stats->ms_search is the
+ * search kernel alone, ms_components everything between it and the copy. seeds == NULL: the seeds uploaded last (eg3d_upload_seeds). One caller thread per context. */
+typedef struct eg3d_polyline_matches {   /* library-owned; eg3d_free_polyline_matches */
+  uint32_t n_refpoints;  uint32_t* refpoints;       /* accepted reference points, ascending */
+  uint32_t n_sets;       uint32_t* row_off;         /* [n_sets * n_views + 1] */
+  uint32_t* pl_ids;                                 /* as eg3d_polyline_sets */
+} eg3d_polyline_matches;
+typedef struct eg3d_polymatch_stats { uint32_t struct_size; /* caller sets it; smaller is refused */
+  uint64_t n_entries, n_accepted, n_nodes, n_sets; float ms_grid, ms_search, ms_components, ms_copy; } eg3d_polymatch_stats;
+int eg3d_match_polylines_closeness(eg3d_ctx*, const eg3d_seeds* seeds /* NULL = the uploaded seeds */,
+                                   uint32_t seed_begin, uint32_t seed_end, eg3d_polyline_matches* out, eg3d_polymatch_stats* stats);
+void eg3d_free_polyline_matches(eg3d_polyline_matches*);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,10 @@ struct EdgeMatchingOptions {
   // extractor, eg3d_match_polyline_sets, is built; examples/edge_matcher_refpoints.cpp feeds it from a file). The output can
   // therefore hold fewer edge-points than the reference's. quiet = false prints one line to stderr saying so per call;
   // after a call skipped_pipelines says which were left out.
+  // run_pipeline2 = true: pipeline 2 runs too (pipelines.cpp:113-158) — its polyline matcher on the device
+  // (polyline_matching_closeness_to_refpoints), every match through the extractor, its cloud in front of pipeline 3's as in
+  // the reference; skipped_pipelines is then 1. Off by default: the call behaves as before.
+  bool run_pipeline2 = false;
   bool quiet = false;
   int skipped_pipelines = 0;  // bit 0: pipeline 1 (similarity graph), bit 1: pipeline 2 (closeness to refpoints) [out]
 };
@@ -312,12 +316,27 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
 
   // edge_reconstruction_pipeline (pipelines.cpp:201-246): pipelines 1-2 have no polyline matches here (their matchers are
   // out of scope); pipeline 3
-  edge_matching_options().skipped_pipelines = 3;
-  if (!edge_matching_options().quiet)
+  const bool pipeline2 = edge_matching_options().run_pipeline2;
+  edge_matching_options().skipped_pipelines = pipeline2 ? 1 : 3;
+  std::vector<new_3dpoint_plgp_matches> p3ds;
+  if (pipeline2) {
+    if (!edge_matching_options().quiet)
+      std::fprintf(stderr, "eg3d edge_matching: pipeline 1 (polyline matches of the similarity-graph / Louvain matcher) is not "
+                           "part of this build; running pipelines 2 and 3: the output may hold fewer edge-points than the "
+                           "reference's (INTEGRATION.md)\n");
+    const auto pmctr_res = polyline_matching_closeness_to_refpoints(sfm_data, em.get());
+    for (const auto& potentially_compatible_polylines : pmctr_res.second) {
+      const auto cur = find_new_3d_points_from_compatible_polylines_expandallviews_parallel(sfm_data, em.get(),
+                                                                                            potentially_compatible_polylines);
+      detail::throw_if_failed(em.get(), "find_new_3d_points_from_compatible_polylines_expandallviews_parallel");
+      p3ds.insert(p3ds.end(), cur.begin(), cur.end());
+    }
+  } else if (!edge_matching_options().quiet)
     std::fprintf(stderr, "eg3d edge_matching: pipelines 1-2 (polyline matches of the similarity-graph / Louvain matchers) are not "
                          "part of this build; running pipeline 3 (reference points) only: the output may hold fewer edge-points "
                          "than the reference's (INTEGRATION.md)\n");
-  std::vector<new_3dpoint_plgp_matches> p3ds = plg_matching_from_refpoints_parallel(sfm_data, em.get(), cm.get(), plgmm);
+  const std::vector<new_3dpoint_plgp_matches> p3ds_r = plg_matching_from_refpoints_parallel(sfm_data, em.get(), cm.get(), plgmm);
+  p3ds.insert(p3ds.end(), p3ds_r.begin(), p3ds_r.end());
   const std::vector<new_3dpoint_plgp_matches> filtered_p3ds =
       filter_3d_points_close_2d_array(sfm_data.numCameras_, sfm_data.imageWidth_, sfm_data.imageHeight_, p3ds);
   add_3dpoints_to_sfmd(sfm_data, filtered_p3ds);

@@ -425,6 +425,25 @@ class PLGEdgeManager : public EdgeManager {
     return res;
   }
 
+  // polyline_matching_closeness_to_refpoints (polyline_matcher.cpp:75-168) over all reference points: ONE call of the C ABI
+  // (eg3d_match_polylines_closeness). first: the accepted reference points; second: per polyline match, per view, the set
+  // of polyline ids. Empty result + last_status() on failure.
+  std::pair<std::vector<unsigned long>, std::vector<std::vector<std::set<unsigned long>>>> match_polylines_closeness() {
+    std::pair<std::vector<unsigned long>, std::vector<std::vector<std::set<unsigned long>>>> res;
+    if (!ctx_) return res;
+    eg3d_seeds s = seeds_struct();
+    eg3d_polyline_matches m;
+    status_ = eg3d_match_polylines_closeness(ctx_, &s, 0, (uint32_t)sfmd_.numPoints_, &m, nullptr);
+    if (status_ != EG3D_OK) return res;
+    res.first.assign(m.refpoints, m.refpoints + m.n_refpoints);
+    const size_t V = (size_t)sfmd_.numCameras_;
+    res.second.resize(m.n_sets, std::vector<std::set<unsigned long>>(V));
+    for (size_t r = 0; r < (size_t)m.n_sets * V; r++)
+      res.second[r / V][r % V].insert(m.pl_ids + m.row_off[r], m.pl_ids + m.row_off[r + 1]);
+    eg3d_free_polyline_matches(&m);
+    return res;
+  }
+
   // All chains of ONE reference point, grouped the way the reference's loop produces them
   // (plg_matching_from_refpoints.cpp:69-78): [track entry][starting intersection] -> chain (possibly empty).
   // n_start[entry] = starting intersections of that entry (a chain-less intersection still has its — empty — slot).
@@ -648,6 +667,15 @@ inline std::vector<new_3dpoint_plgp_matches> plg_matching_from_refpoints(const S
 inline std::vector<new_3dpoint_plgp_matches> find_new_3d_points_from_compatible_polylines_expandallviews_parallel(
     const SfMData&, PLGEdgeManager* em, const std::vector<std::set<unsigned long>>& potentially_compatible_polylines) {
   return em->match_polyline_set(potentially_compatible_polylines);
+}
+
+// polyline_matching_closeness_to_refpoints (include/edgegraph3d/matching/polyline_matching/polyline_matcher.hpp): plgs and
+// the image size of the reference signature live in the edge manager. Throws Eg3dError on failure.
+inline std::pair<std::vector<unsigned long>, std::vector<std::vector<std::set<unsigned long>>>>
+polyline_matching_closeness_to_refpoints(const SfMData&, PLGEdgeManager* em) {
+  auto res = em->match_polylines_closeness();
+  detail::throw_if_failed(em, "polyline_matching_closeness_to_refpoints");
+  return res;
 }
 
 namespace detail {
