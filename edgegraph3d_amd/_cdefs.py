@@ -95,6 +95,53 @@ class PolymatchStats(C.Structure):
                 ("ms_copy", C.c_float)]
 
 
+class Simgraph(C.Structure):
+    """eg3d_simgraph (library-owned; eg3d_free_simgraph)."""
+    _fields_ = [("n_nodes", C.c_uint32), ("node_view", u32p), ("node_pl", u32p), ("adj_off", u32p), ("adj_node", u32p),
+                ("adj_w", f32p), ("seed_begin", C.c_uint32), ("n_points", C.c_uint32), ("point_weight", f32p),
+                ("cp_off", u32p), ("cp_view", u32p), ("cp_pl", u32p), ("n_polylines", C.c_uint32), ("cr_off", u32p),
+                ("cr_point", u32p)]
+
+
+class SimgraphStats(C.Structure):
+    """eg3d_simgraph_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_entries", C.c_uint64), ("n_nodes", C.c_uint64), ("n_edges", C.c_uint64),
+                ("n_pair_instances", C.c_uint64), ("n_chunks", C.c_uint64), ("ms_grid", C.c_float), ("ms_search", C.c_float),
+                ("ms_graph", C.c_float), ("ms_weights", C.c_float), ("ms_copy", C.c_float)]
+
+
+def simgraph_to_dict(g):
+    """Numpy copies of every array of an eg3d_simgraph."""
+    nn, npt, npl = int(g.n_nodes), int(g.n_points), int(g.n_polylines)
+    adj_off = as_np(g.adj_off, nn + 1, np.uint32)
+    cp_off = as_np(g.cp_off, npt + 1, np.uint32)
+    cr_off = as_np(g.cr_off, npl + 1, np.uint32)
+    na, ncp, ncr = int(adj_off[-1]), int(cp_off[-1]), int(cr_off[-1])
+    return {"n_nodes": nn, "node_view": as_np(g.node_view, nn, np.uint32), "node_pl": as_np(g.node_pl, nn, np.uint32),
+            "adj_off": adj_off, "adj_node": as_np(g.adj_node, na, np.uint32), "adj_w": as_np(g.adj_w, na, np.float32),
+            "seed_begin": int(g.seed_begin), "n_points": npt, "point_weight": as_np(g.point_weight, npt, np.float32),
+            "cp_off": cp_off, "cp_view": as_np(g.cp_view, ncp, np.uint32), "cp_pl": as_np(g.cp_pl, ncp, np.uint32),
+            "n_polylines": npl, "cr_off": cr_off, "cr_point": as_np(g.cr_point, ncr, np.uint32)}
+
+
+class SimgraphArrays:
+    """Owns numpy copies of a compatibility graph (a dict as returned by simgraph_to_dict / Context.similarity_graph) and
+    exposes a Simgraph struct over them, for the host steps that consume one."""
+
+    def __init__(self, d):
+        u = lambda k: np.ascontiguousarray(d[k] if len(d[k]) else [0], np.uint32)
+        f = lambda k: np.ascontiguousarray(d[k] if len(d[k]) else [0], np.float32)
+        self.a = {k: u(k) for k in ("node_view", "node_pl", "adj_off", "adj_node", "cp_off", "cp_view", "cp_pl", "cr_off",
+                                    "cr_point")}
+        self.a.update({k: f(k) for k in ("adj_w", "point_weight")})
+        a, p = self.a, np_ptr
+        self.c = Simgraph(int(d["n_nodes"]), p(a["node_view"], C.c_uint32), p(a["node_pl"], C.c_uint32),
+                          p(a["adj_off"], C.c_uint32), p(a["adj_node"], C.c_uint32), p(a["adj_w"], C.c_float),
+                          int(d.get("seed_begin", 0)), int(d["n_points"]), p(a["point_weight"], C.c_float),
+                          p(a["cp_off"], C.c_uint32), p(a["cp_view"], C.c_uint32), p(a["cp_pl"], C.c_uint32),
+                          int(d["n_polylines"]), p(a["cr_off"], C.c_uint32), p(a["cr_point"], C.c_uint32))
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("n_seeds", C.c_uint32), ("n_curves", C.c_int32),
                 ("rng_seed", C.c_uint64), ("max_track", C.c_int32), ("obs_noise_px", C.c_float),

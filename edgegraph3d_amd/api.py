@@ -75,6 +75,10 @@ def lib():
                                                      C.POINTER(D.PolylineMatches), C.POINTER(D.PolymatchStats)]
         L.eg3d_free_polyline_matches.argtypes = [C.POINTER(D.PolylineMatches)]
         L.eg3d_free_polyline_matches.restype = None
+        L.eg3d_similarity_graph.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32, C.POINTER(D.Simgraph),
+                                            C.POINTER(D.SimgraphStats)]
+        L.eg3d_free_simgraph.argtypes = [C.POINTER(D.Simgraph)]
+        L.eg3d_free_simgraph.restype = None
         _LIB = L
     return _LIB
 
@@ -86,7 +90,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
     "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
-    "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches",
+    "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches", "eg3d_similarity_graph", "eg3d_free_simgraph",
 ]
 
 
@@ -307,6 +311,23 @@ class Context:
              "row_off": row_off, "pl_ids": D.as_np(m.pl_ids, int(row_off[-1]), np.uint32).copy(),
              "stats": {f[0]: getattr(st, f[0]) for f in D.PolymatchStats._fields_}}
         lib().eg3d_free_polyline_matches(C.byref(m))
+        return d
+
+    def similarity_graph(self, seeds_ptr=None, begin=0, end=None):
+        """The graph half of pipeline 1's polyline matcher (eg3d_similarity_graph) on seeds [begin, end) of `seeds_ptr`, or
+        of the uploaded seeds when it is None (`end` is then required). Returns every array of eg3d_simgraph as numpy
+        copies (the weighted adjacency CSR over node ids, the nodes, the point weights, close_polylines and
+        close_refpoints) and the call's stats. host.write_compat_graph / host.sets_from_communities take the dict."""
+        if end is None:
+            if seeds_ptr is None:
+                raise Eg3dError("similarity_graph: `end` is required with the uploaded seeds")
+            end = int(seeds_ptr.contents.n_seeds) if hasattr(seeds_ptr, "contents") else int(seeds_ptr.n_seeds)
+        g, st = D.Simgraph(), D.SimgraphStats()
+        st.struct_size = C.sizeof(D.SimgraphStats)
+        _check(lib().eg3d_similarity_graph(self._h, seeds_ptr, begin, end, C.byref(g), C.byref(st)), "eg3d_similarity_graph")
+        d = D.simgraph_to_dict(g)
+        d["stats"] = {f[0]: getattr(st, f[0]) for f in D.SimgraphStats._fields_}
+        lib().eg3d_free_simgraph(C.byref(g))
         return d
 
     def last_device_output(self):

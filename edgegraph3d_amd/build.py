@@ -207,6 +207,9 @@ RESOURCE_BOUNDS = {
     # the polyline matcher (eg3d_match_polylines_closeness): no spills, no scratch (a substring: all of them); LDS only in the
     # search, one 64-bit slot per lane as in k1_seed_candidates
     "k9_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},
+    # the compatibility graph (eg3d_similarity_graph): as K9 — no spills, no scratch; LDS only in the list-form search, the
+    # same one 64-bit slot per lane
+    "k10_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},
     "k2_epipolar_hits": {"vgpr_spill_count": 0},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }

@@ -30,6 +30,7 @@
 #include "eg3d_kernels.h"
 #include "eg3d_k8_replay.h"
 #include "eg3d_k9_polymatch.h"
+#include "eg3d_k10_simgraph.h"
 
 using namespace eg3d;
 
@@ -277,6 +278,15 @@ struct eg3d_ctx {
   // ids, row_off, pl_ids (copied to the caller's library-owned arrays at the end of the call).
   DevBuf k9_svseed, k9_cnt, k9_pl, k9_dist, k9_acc, k9_accoff, k9_first, k9_parent, k9_root, k9_ckey, k9_rank, k9_key[2], k9_ctr,
       k9_ref, k9_rowoff, k9_plids;
+  // eg3d_similarity_graph (K10). Work: entry -> seed, the per-entry counts and their scan, the (point, polyline) pairs and
+  // their swapped form (two sort buffers each way), the CSRs and columns of close_polylines / close_refpoints, the weights,
+  // the visibility rows, the pair counts and their 64-bit scan, the node tables, the edge keys (k10_edge: the unique list
+  // with the current chunk behind it, and the sort's output), the directed keys and weights, counters + flag word.
+  DevBuf k10_svseed, k10_cnt, k10_off, k10_pair[2], k10_crkey, k10_cpoff, k10_cpview, k10_cppl, k10_croff, k10_crpoint, k10_weight, k10_vis,
+      k10_npairs, k10_pairoff, k10_nkey[2], k10_nodeof, k10_nodeg, k10_nodeview, k10_nodepl, k10_edge[2], k10_dkey[2], k10_dval[2],
+      k10_adjoff, k10_adjnode, k10_ctr;
+  uint64_t simgraph_pair_budget = 0;  // EG3D_SIMGRAPH_PAIR_BUDGET (read by eg3d_create; tests): edge keys one chunk of the clique
+                                      // expansion may write; 0 = EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
   int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (read by eg3d_create; tests): a node table of 2^bits slots, raised to the
                               // smallest power of two above the number of lookups; 0 = the default, about twice that
   uint32_t n_pl = 0, n_vtx = 0;  // polylines and vertices of the scene as uploaded
@@ -654,6 +664,7 @@ extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
   c->tune = Tunables::from_env();
   if (const char* e = getenv("EG3D_COMPACT_NT")) c->compact_nt = e[0] == '1';
   if (const char* e = getenv("EG3D_REPLAY_TABLE_BITS")) c->replay_table_bits = std::min(40, std::max(0, atoi(e)));
+  if (const char* e = getenv("EG3D_SIMGRAPH_PAIR_BUDGET")) c->simgraph_pair_budget = std::min(1ull << 31, strtoull(e, nullptr, 10));
   if (c->tune.hyp_cap) c->hyp_cap = c->tune.hyp_cap;
   c->hg = std::make_shared<HostGrids>();
   if (c->tune.lane_priorities) {
@@ -966,6 +977,7 @@ extern "C" int eg3d_clone(eg3d_ctx* parent, eg3d_ctx** out) {
   c->tune = parent->tune;
   c->compact_nt = parent->compact_nt;
   c->replay_table_bits = parent->replay_table_bits;
+  c->simgraph_pair_budget = parent->simgraph_pair_budget;
   c->n_pl = parent->n_pl;
   c->n_vtx = parent->n_vtx;
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -1034,7 +1046,12 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
                    &c->g_nodeX, &c->g_nodept, &c->g_pls, &c->g_ple, &c->g_conoff, &c->g_conpl, &c->g_ivoff, &c->g_ivss,
                    &c->g_ivsxy, &c->g_ives, &c->g_ivexy, &c->k9_svseed, &c->k9_cnt, &c->k9_pl, &c->k9_dist, &c->k9_acc, &c->k9_accoff,
                    &c->k9_first, &c->k9_parent, &c->k9_root, &c->k9_ckey, &c->k9_rank, &c->k9_key[0], &c->k9_key[1], &c->k9_ctr,
-                   &c->k9_ref, &c->k9_rowoff, &c->k9_plids, &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
+                   &c->k9_ref, &c->k9_rowoff, &c->k9_plids,
+                   &c->k10_svseed, &c->k10_cnt, &c->k10_off, &c->k10_pair[0], &c->k10_pair[1], &c->k10_crkey, &c->k10_cpoff, &c->k10_cpview, &c->k10_cppl,
+                   &c->k10_croff, &c->k10_crpoint, &c->k10_weight, &c->k10_vis, &c->k10_npairs, &c->k10_pairoff, &c->k10_nkey[0],
+                   &c->k10_nkey[1], &c->k10_nodeof, &c->k10_nodeg, &c->k10_nodeview, &c->k10_nodepl, &c->k10_edge[0], &c->k10_edge[1],
+                   &c->k10_dkey[0], &c->k10_dkey[1], &c->k10_dval[0], &c->k10_dval[1], &c->k10_adjoff, &c->k10_adjnode, &c->k10_ctr,
+                   &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
                    &c->b_pools, &c->b_stage_pts, &c->b_stage_obs, &c->b_stage_used};
   for (DevBuf* b : all) b->release();
   if (c->pinned) (void)hipHostFree(c->pinned);
@@ -3430,6 +3447,303 @@ extern "C" int eg3d_polymatch_test_rule(eg3d_ctx* c, uint32_t b, uint32_t e, con
   }
   const K9Forced f{cnt, pl, dist};
   return polymatch_impl(c, nullptr, b, e, &f, out, nullptr);
+}
+
+// ---- pipeline 1's polyline compatibility graph (K10, eg3d_k10_simgraph.hip) ---------------------------------------------------
+// Edge keys one chunk of the clique expansion writes when EG3D_SIMGRAPH_PAIR_BUDGET does not say.
+#ifndef EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
+#define EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT (1ull << 22)
+#endif
+
+extern "C" void eg3d_free_simgraph(eg3d_simgraph* g) {
+  if (!g) return;
+  free(g->node_view);
+  free(g->node_pl);
+  free(g->adj_off);
+  free(g->adj_node);
+  free(g->adj_w);
+  free(g->point_weight);
+  free(g->cp_off);
+  free(g->cp_view);
+  free(g->cp_pl);
+  free(g->cr_off);
+  free(g->cr_point);
+  memset(g, 0, sizeof(*g));
+}
+
+static int k10_sort_pairs(eg3d_ctx* c, const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin, uint32_t* vout,
+                          size_t n) {
+  size_t bytes = 0;
+  HIP_TRY(k8_sort_pairs(c->stream, nullptr, bytes, kin, kout, vin, vout, n));
+  BUF_TRY(c->k8_tmp.ensure(bytes));
+  HIP_TRY(k8_sort_pairs(c->stream, c->k8_tmp.p, bytes, kin, kout, vin, vout, n));
+  return EG3D_OK;
+}
+
+extern "C" int eg3d_similarity_graph(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint32_t e, eg3d_simgraph* out,
+                                     eg3d_simgraph_stats* stats) {
+  if (stats && stats->struct_size < sizeof(eg3d_simgraph_stats)) {
+    g_err = "eg3d_similarity_graph: stats->struct_size is smaller than this library's eg3d_simgraph_stats (" +
+            std::to_string(sizeof(eg3d_simgraph_stats)) + " bytes): set it to sizeof(eg3d_simgraph_stats)";
+    return EG3D_ERR_ARG;
+  }
+  if (!c || !out) {
+    g_err = "eg3d_similarity_graph: bad arguments";
+    return EG3D_ERR_ARG;
+  }
+  if (seeds) BUF_TRY(eg3d_upload_seeds(c, seeds));
+  if (b > e || e > c->n_seeds) {
+    g_err = "eg3d_similarity_graph: bad seed range (seeds uploaded?)";
+    return EG3D_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_pts = e - b;
+  const uint32_t sv_base = n_pts ? (*c->h_trk)[b] : 0, n_sv = n_pts ? (*c->h_trk)[e] - sv_base : 0;
+  const uint64_t budget = c->simgraph_pair_budget ? c->simgraph_pair_budget : EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT;
+  uint32_t n_pair = 0, n_nodes = 0, n_uniq = 0, n_kept = 0, n_chunks = 0;
+  uint64_t n_inst = 0;
+  float ms_grid = 0, ms_search = 0, ms_graph = 0, ms_weights = 0, ms_copy = 0;
+  if (n_sv && NP) {
+    K9Grid g10;
+    BUF_TRY(ensure_grid10(c, &g10, &ms_grid));
+    SeedsDev sd;
+    sd.trk_off = c->b_toff.as<uint32_t>();
+    sd.trk_view = c->b_tview.as<int32_t>();
+    sd.trk_xy = c->b_txy.as<float>();
+    // ---- the view ids, before anything indexes with them (K9's check)
+    BUF_TRY(c->k10_ctr.ensure(4 * sizeof(uint32_t)));  // [0] flags, [1] nodes, [2] distinct edges, [3] kept edges
+    BUF_TRY(c->k10_svseed.ensure(sizeof(uint32_t) * n_sv));
+    uint32_t* ctr = c->k10_ctr.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(uint32_t), st));
+    launch_k9_prep(st, sd, c->V, b, n_pts, sv_base, c->k10_svseed.as<uint32_t>(), ctr);
+    HIP_TRY(hipGetLastError());
+    {
+      BUF_TRY(ensure_mailbox(c));
+      Readback rb(c);
+      const int it = rb.add(ctr, 1);
+      BUF_TRY(rb.run());
+      if (*rb.item(it) & K9_FLAG_BAD_VIEW) {
+        g_err = "eg3d_similarity_graph: view id out of range";
+        return EG3D_ERR_ARG;
+      }
+    }
+    // ---- the search, list form: count, scan, fill
+    BUF_TRY(c->k10_cnt.ensure(sizeof(uint32_t) * ((size_t)n_sv + 1)));
+    BUF_TRY(c->k10_off.ensure(sizeof(uint32_t) * ((size_t)n_sv + 1)));
+    uint32_t* cnt = c->k10_cnt.as<uint32_t>();
+    uint32_t* off = c->k10_off.as<uint32_t>();
+    HIP_TRY(hipEventRecord(c->ea[0], st));
+    HIP_TRY(hipMemsetAsync(cnt + n_sv, 0, sizeof(uint32_t), st));
+    launch_k10_close_list(st, false, c->ds, g10, sd, sv_base, n_sv, c->k10_svseed.as<uint32_t>(), cnt, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(scan_queue_u32(c, cnt, off, (size_t)n_sv + 1, 0));
+    {
+      Readback rb(c);
+      const int it = rb.add(off + n_sv, 1);
+      const int iw = rb.add(c->b_scanchk.as<uint32_t>(), 1);
+      rb.clear_after(c->b_scanchk.as<uint32_t>());
+      BUF_TRY(rb.run());
+      if (*rb.item(iw)) return wrapped_error("close polylines");
+      n_pair = *rb.item(it);
+    }
+    for (int k = 0; k < 2; k++) BUF_TRY(c->k10_pair[k].ensure(8 * std::max<size_t>(n_pair, 1)));
+    unsigned long long* pair[2] = {c->k10_pair[0].as<unsigned long long>(), c->k10_pair[1].as<unsigned long long>()};
+    launch_k10_close_list(st, true, c->ds, g10, sd, sv_base, n_sv, c->k10_svseed.as<uint32_t>(), nullptr, off, pair[0]);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->eb[0], st));
+    HIP_TRY(hipEventRecord(c->ea[1], st));
+    HIP_TRY(hipEventRecord(c->eb[1], st));  // (re-recorded below: both pairs are always defined)
+    HIP_TRY(hipEventRecord(c->ea[2], st));
+    HIP_TRY(hipEventRecord(c->eb[2], st));
+  }
+  if (n_pair) {
+    // ---- close_polylines, close_refpoints, the weights, the nodes
+    HIP_TRY(hipEventRecord(c->ea[1], st));
+    const uint32_t vis_words = (V + 31u) / 32u;
+    BUF_TRY(c->k10_crkey.ensure(8 * (size_t)n_pair));
+    BUF_TRY(c->k10_cpoff.ensure(4 * ((size_t)n_pts + 1)));
+    BUF_TRY(c->k10_cpview.ensure(4 * (size_t)n_pair));
+    BUF_TRY(c->k10_cppl.ensure(4 * (size_t)n_pair));
+    BUF_TRY(c->k10_croff.ensure(4 * ((size_t)NP + 1)));
+    BUF_TRY(c->k10_crpoint.ensure(4 * (size_t)n_pair));
+    BUF_TRY(c->k10_weight.ensure(4 * (size_t)n_pts));
+    BUF_TRY(c->k10_vis.ensure(4 * (size_t)n_pts * vis_words));
+    BUF_TRY(c->k10_npairs.ensure(8 * ((size_t)n_pts + 1)));
+    BUF_TRY(c->k10_pairoff.ensure(8 * ((size_t)n_pts + 1)));
+    for (int k = 0; k < 2; k++) BUF_TRY(c->k10_nkey[k].ensure(8 * (size_t)NP));
+    BUF_TRY(c->k10_nodeof.ensure(4 * (size_t)NP));
+    BUF_TRY(c->k10_nodeg.ensure(4 * (size_t)NP));
+    BUF_TRY(c->k10_nodeview.ensure(4 * (size_t)NP));
+    BUF_TRY(c->k10_nodepl.ensure(4 * (size_t)NP));
+    SeedsDev sd;
+    sd.trk_off = c->b_toff.as<uint32_t>();
+    sd.trk_view = c->b_tview.as<int32_t>();
+    sd.trk_xy = c->b_txy.as<float>();
+    uint32_t* ctr = c->k10_ctr.as<uint32_t>();
+    unsigned long long* const raw = c->k10_pair[0].as<unsigned long long>();
+    unsigned long long* const pair = c->k10_pair[1].as<unsigned long long>();    // point << 32 | g, ascending
+    unsigned long long* const crkey = c->k10_crkey.as<unsigned long long>();     // g << 32 | point, ascending
+    unsigned long long* const pair_off = c->k10_pairoff.as<unsigned long long>();
+    BUF_TRY(k9_sort(c, raw, pair, n_pair));
+    launch_k10_pairs(st, c->ds, pair, n_pair, c->k10_cpview.as<uint32_t>(), c->k10_cppl.as<uint32_t>(), raw);
+    launch_k10_row_off(st, pair, n_pair, b, n_pts, c->k10_cpoff.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(k9_sort(c, raw, crkey, n_pair));
+    launch_k10_low_words(st, crkey, n_pair, c->k10_crpoint.as<uint32_t>());
+    launch_k10_row_off(st, crkey, n_pair, 0, NP, c->k10_croff.as<uint32_t>());
+    launch_k10_points(st, sd, b, n_pts, c->k10_cpoff.as<uint32_t>(), c->k10_cpview.as<uint32_t>(), vis_words,
+                      c->k10_weight.as<float>(), c->k10_vis.as<uint32_t>(), c->k10_npairs.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    {
+      size_t bytes = 0;
+      HIP_TRY(k10_scan_u64(st, nullptr, bytes, c->k10_npairs.as<unsigned long long>(), pair_off, (size_t)n_pts + 1));
+      BUF_TRY(c->k8_tmp.ensure(bytes));
+      HIP_TRY(k10_scan_u64(st, c->k8_tmp.p, bytes, c->k10_npairs.as<unsigned long long>(), pair_off, (size_t)n_pts + 1));
+    }
+    launch_k10_node_keys(st, NP, c->k10_croff.as<uint32_t>(), c->k10_crpoint.as<uint32_t>(), c->k10_nkey[0].as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    BUF_TRY(k9_sort(c, c->k10_nkey[0].as<unsigned long long>(), c->k10_nkey[1].as<unsigned long long>(), NP));
+    launch_k10_nodes(st, c->ds, c->k10_nkey[1].as<unsigned long long>(), NP, c->k10_nodeof.as<uint32_t>(), c->k10_nodeg.as<uint32_t>(),
+                     c->k10_nodeview.as<uint32_t>(), c->k10_nodepl.as<uint32_t>(), ctr + 1);
+    HIP_TRY(hipGetLastError());
+    {
+      Readback rb(c);
+      const int in = rb.add(ctr + 1, 1);
+      const int ip = rb.add(pair_off + n_pts, 2);
+      BUF_TRY(rb.run());
+      n_nodes = *rb.item(in);
+      n_inst = (uint64_t)rb.item(ip)[0] | ((uint64_t)rb.item(ip)[1] << 32);
+    }
+    K10Graph g;
+    g.seed_begin = b;
+    g.n_pts = n_pts;
+    g.n_pl = NP;
+    g.vis_words = vis_words;
+    g.pair = pair;
+    g.cp_off = c->k10_cpoff.as<uint32_t>();
+    g.cr_off = c->k10_croff.as<uint32_t>();
+    g.cr_point = c->k10_crpoint.as<uint32_t>();
+    g.weight = c->k10_weight.as<float>();
+    g.vis = c->k10_vis.as<uint32_t>();
+    g.node_g = c->k10_nodeg.as<uint32_t>();
+    g.node_view = c->k10_nodeview.as<uint32_t>();
+    // ---- the distinct edges: the cliques a chunk of pair instances at a time, each chunk written behind the distinct keys
+    // so far (k10_edge[0]), the whole sorted (k10_edge[1]) and made distinct again (k10_edge[0])
+    for (uint64_t t0 = 0; t0 < n_inst; t0 += budget) {
+      const uint32_t n = (uint32_t)std::min<uint64_t>(budget, n_inst - t0);
+      const size_t total = (size_t)n_uniq + n;
+      BUF_TRY(c->k10_edge[0].ensure_keep(8 * total, 8 * (size_t)n_uniq, st));
+      BUF_TRY(c->k10_edge[1].ensure(8 * total));
+      unsigned long long* const ek0 = c->k10_edge[0].as<unsigned long long>();
+      unsigned long long* const ek1 = c->k10_edge[1].as<unsigned long long>();
+      launch_k10_expand(st, g, pair_off, c->k10_nodeof.as<uint32_t>(), t0, n, ek0 + n_uniq);
+      HIP_TRY(hipGetLastError());
+      BUF_TRY(k9_sort(c, ek0, ek1, total));
+      size_t bytes = 0;
+      HIP_TRY(k10_unique(st, nullptr, bytes, ek1, ek0, ctr + 2, total));
+      BUF_TRY(c->k8_tmp.ensure(bytes));
+      HIP_TRY(k10_unique(st, c->k8_tmp.p, bytes, ek1, ek0, ctr + 2, total));
+      Readback rb(c);
+      const int iu = rb.add(ctr + 2, 1);
+      BUF_TRY(rb.run());
+      n_uniq = *rb.item(iu);
+      n_chunks++;
+      if (n_uniq >= 0x80000000u) {
+        g_err = "eg3d_similarity_graph: the graph has 2^31 or more distinct edges (adjacency offsets are 32-bit)";
+        return EG3D_ERR_CAPACITY;
+      }
+    }
+    HIP_TRY(hipEventRecord(c->eb[1], st));
+    // ---- the edge weights and the adjacency
+    HIP_TRY(hipEventRecord(c->ea[2], st));
+    BUF_TRY(c->k10_adjoff.ensure(4 * ((size_t)n_nodes + 1)));
+    if (n_uniq) {
+      for (int k = 0; k < 2; k++) {
+        BUF_TRY(c->k10_dkey[k].ensure(16 * (size_t)n_uniq));
+        BUF_TRY(c->k10_dval[k].ensure(8 * (size_t)n_uniq));
+      }
+      launch_k10_edge_weights(st, g, c->k10_edge[0].as<unsigned long long>(), n_uniq, c->k10_dkey[0].as<unsigned long long>(),
+                              c->k10_dval[0].as<uint32_t>(), ctr + 3);
+      HIP_TRY(hipGetLastError());
+      BUF_TRY(k10_sort_pairs(c, c->k10_dkey[0].as<unsigned long long>(), c->k10_dkey[1].as<unsigned long long>(),
+                             c->k10_dval[0].as<uint32_t>(), c->k10_dval[1].as<uint32_t>(), 2 * (size_t)n_uniq));
+      Readback rb(c);
+      const int ik = rb.add(ctr + 3, 1);
+      BUF_TRY(rb.run());
+      n_kept = *rb.item(ik);
+      BUF_TRY(c->k10_adjnode.ensure(8 * std::max<size_t>(n_kept, 1)));
+      launch_k10_low_words(st, c->k10_dkey[1].as<unsigned long long>(), 2 * n_kept, c->k10_adjnode.as<uint32_t>());
+    }
+    // (directed keys that are not kept sort behind every node's: the offsets look at the kept ones only)
+    launch_k10_row_off(st, c->k10_dkey[1].as<unsigned long long>(), 2 * n_kept, 0, n_nodes, c->k10_adjoff.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->eb[2], st));
+  }
+  if (n_sv && NP) {
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&ms_search, c->ea[0], c->eb[0]));
+    HIP_TRY(hipEventElapsedTime(&ms_graph, c->ea[1], c->eb[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_weights, c->ea[2], c->eb[2]));
+  }
+  // ---- the result, library-owned
+  const auto t0 = std::chrono::steady_clock::now();
+  eg3d_simgraph m;
+  memset(&m, 0, sizeof(m));
+  const size_t n_adj = 2 * (size_t)n_kept;
+  auto u32s = [](size_t n) { return (uint32_t*)calloc(std::max<size_t>(n, 1), sizeof(uint32_t)); };
+  m.node_view = u32s(n_nodes);
+  m.node_pl = u32s(n_nodes);
+  m.adj_off = u32s((size_t)n_nodes + 1);
+  m.adj_node = u32s(n_adj);
+  m.adj_w = (float*)u32s(n_adj);
+  m.point_weight = (float*)u32s(n_pts);
+  m.cp_off = u32s((size_t)n_pts + 1);
+  m.cp_view = u32s(n_pair);
+  m.cp_pl = u32s(n_pair);
+  m.cr_off = u32s((size_t)NP + 1);
+  m.cr_point = u32s(n_pair);
+  const bool have = m.node_view && m.node_pl && m.adj_off && m.adj_node && m.adj_w && m.point_weight && m.cp_off && m.cp_view &&
+                    m.cp_pl && m.cr_off && m.cr_point;
+  hipError_t he = hipSuccess;
+  if (have && n_pair) {
+    const struct { void* dst; const void* src; size_t n; } copies[] = {
+        {m.node_view, c->k10_nodeview.p, n_nodes}, {m.node_pl, c->k10_nodepl.p, n_nodes},
+        {m.adj_off, c->k10_adjoff.p, (size_t)n_nodes + 1}, {m.adj_node, c->k10_adjnode.p, n_adj},
+        {m.adj_w, c->k10_dval[1].p, n_adj}, {m.point_weight, c->k10_weight.p, n_pts},
+        {m.cp_off, c->k10_cpoff.p, (size_t)n_pts + 1}, {m.cp_view, c->k10_cpview.p, n_pair}, {m.cp_pl, c->k10_cppl.p, n_pair},
+        {m.cr_off, c->k10_croff.p, (size_t)NP + 1}, {m.cr_point, c->k10_crpoint.p, n_pair}};
+    for (const auto& cp : copies)
+      if (he == hipSuccess && cp.n) he = hipMemcpyAsync(cp.dst, cp.src, sizeof(uint32_t) * cp.n, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = es;
+  }
+  if (!have || he != hipSuccess) {
+    g_err = he != hipSuccess ? std::string("eg3d_similarity_graph: copy to the host: ") + hipGetErrorString(he)
+                             : std::string("eg3d_similarity_graph: out of host memory");
+    eg3d_free_simgraph(&m);
+    return EG3D_ERR_HIP;
+  }
+  m.n_nodes = n_nodes;
+  m.seed_begin = b;
+  m.n_points = n_pts;
+  m.n_polylines = NP;
+  ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  *out = m;
+  if (stats) {
+    stats->struct_size = (uint32_t)sizeof(eg3d_simgraph_stats);
+    stats->n_entries = n_sv;
+    stats->n_nodes = n_nodes;
+    stats->n_edges = n_kept;
+    stats->n_pair_instances = n_inst;
+    stats->n_chunks = n_chunks;
+    stats->ms_grid = ms_grid;
+    stats->ms_search = ms_search;
+    stats->ms_graph = ms_graph;
+    stats->ms_weights = ms_weights;
+    stats->ms_copy = ms_copy;
+  }
+  return EG3D_OK;
 }
 
 #ifdef EG3D_SECTION_TIMING

@@ -49,6 +49,12 @@ def lib():
         L.eg3d_plg_scene.restype = C.POINTER(D.Scene)
         L.eg3d_plg_scene.argtypes = [C.c_void_p]
         L.eg3d_plg_destroy.argtypes = [C.c_void_p]
+        L.eg3d_host_write_compat_graph.argtypes = [C.c_char_p, C.POINTER(D.Simgraph)]
+        L.eg3d_host_read_communities.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_uint64)]
+        L.eg3d_host_sets_from_communities.argtypes = [C.POINTER(D.Simgraph), C.POINTER(C.c_int64), C.c_uint64, C.c_int32,
+                                                      C.POINTER(D.PolylineSets)]
+        L.eg3d_host_free_polyline_sets.argtypes = [C.POINTER(D.PolylineSets)]
+        L.eg3d_host_free_polyline_sets.restype = None
         _LIB = L
     return _LIB
 
@@ -172,6 +178,43 @@ def replay_matches(scene_ptr, cloud):
     d = D.graph3d_to_dict(g)
     lib().eg3d_host_free_graph3d(C.byref(g))
     return d
+
+
+def write_compat_graph(path, graph):
+    """Pipeline 1's compatibility graph (a dict as returned by Context.similarity_graph) as the text file the reference
+    hands to its community detection (eg3d_host_write_compat_graph)."""
+    g = D.SimgraphArrays(graph)
+    rc = lib().eg3d_host_write_compat_graph(os.fsencode(path), C.byref(g.c))
+    if rc != 0:
+        raise RuntimeError("eg3d_host_write_compat_graph(%s) failed (%d)" % (path, rc))
+
+
+def read_communities(path):
+    """One community id per node, as the reference reads its community detection's output (int64 array)."""
+    ids, n = C.POINTER(C.c_int64)(), C.c_uint64()
+    rc = lib().eg3d_host_read_communities(os.fsencode(path), C.byref(ids), C.byref(n))
+    if rc != 0:
+        raise RuntimeError("eg3d_host_read_communities(%s) failed (%d)" % (path, rc))
+    out = D.as_np(ids, n.value, np.int64)
+    lib().eg3d_host_free(ids)
+    return out
+
+
+def sets_from_communities(graph, ids, n_views):
+    """The polyline sets of pipeline 1 from the graph's nodes and one community id per node: (n_sets, row_off, pl_ids), the
+    CSR Context.match_polyline_sets takes. A negative id leaves its node out; a wrong number of ids is refused."""
+    g = D.SimgraphArrays(graph)
+    ids = np.ascontiguousarray(ids, np.int64)
+    buf = ids if len(ids) else np.zeros(1, np.int64)
+    ps = D.PolylineSets()
+    rc = lib().eg3d_host_sets_from_communities(C.byref(g.c), D.np_ptr(buf, C.c_int64), len(ids), n_views, C.byref(ps))
+    if rc != 0:
+        raise RuntimeError("eg3d_host_sets_from_communities failed (%d)" % rc)
+    n_sets = int(ps.n_sets)
+    row_off = D.as_np(ps.row_off, n_sets * n_views + 1, np.uint32)
+    pl_ids = D.as_np(ps.pl_ids, int(row_off[-1]), np.uint32)
+    lib().eg3d_host_free_polyline_sets(C.byref(ps))
+    return n_sets, row_off, pl_ids
 
 
 def plg_from_mask(mask):

@@ -223,6 +223,20 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--match2 and --sets2 exclude each other\n");
     return 2;
   }
+  // --match1-graph <file>: the compatibility graph of pipeline 1's polyline matcher is built on the device
+  // (eg3d_similarity_graph) and written as the reference writes it for its community detection (Grappolo: third-party, not
+  // part of this example). --communities <file>: one community id per node of that graph, from whatever clustered the file;
+  // the sets they make go through pipeline 1's extractor where --sets1 reads them.
+  const char* graph_path = nullptr;
+  const char* communities_path = nullptr;
+  for (int a = 4; a < argc; a++) {
+    if (std::strcmp(argv[a], "--match1-graph") == 0 && a + 1 < argc) graph_path = argv[++a];
+    else if (std::strcmp(argv[a], "--communities") == 0 && a + 1 < argc) communities_path = argv[++a];
+  }
+  if (communities_path && sets_path[0]) {
+    std::fprintf(stderr, "--communities and --sets1 exclude each other\n");
+    return 2;
+  }
 
   // wall time of every stage of the run, host stages included (--times prints them; stderr)
   bool print_times = false;
@@ -295,9 +309,38 @@ int main(int argc, char** argv) {
   // ---- pipelines 1 and 2 (pipelines.cpp:219-223): the extractor over the polyline matches of each stage, in
   // match order (one call takes all matches of a stage: eg3d_match_polyline_sets emits them set by set)
   for (int stage = 0; stage < 2; stage++) {
-    if (!sets_path[stage] && !(stage == 1 && match2)) continue;
+    const bool match1 = stage == 0 && (graph_path || communities_path);
+    if (!sets_path[stage] && !(stage == 1 && match2) && !match1) continue;
     MatchSets ms;
-    if (stage == 1 && match2) {  // pipelines.cpp:118
+    if (match1) {  // pipelines.cpp:219 -> polyline_matcher.cpp:222-336, the community detection left to the caller
+      eg3d_seeds rp;
+      eg3d_sfm_seeds(sfm, &rp);
+      eg3d_simgraph sg;
+      eg3d_simgraph_stats st;
+      st.struct_size = (uint32_t)sizeof(st);
+      if (eg3d_similarity_graph(ctx, &rp, 0, rp.n_seeds, &sg, &st) != EG3D_OK) return fail("eg3d_similarity_graph");
+      std::printf("pipeline 1: compatibility graph of %llu polylines, %llu edges\n", (unsigned long long)st.n_nodes,
+                  (unsigned long long)st.n_edges);
+      if (graph_path && eg3d_host_write_compat_graph(graph_path, &sg) != EG3D_OK) return fail("writing the compatibility graph");
+      if (!communities_path) {
+        std::fprintf(stderr, "pipeline 1: wrote %s; clustering it is the caller's (--communities <file> continues)\n", graph_path);
+        eg3d_free_simgraph(&sg);
+        continue;
+      }
+      int64_t* ids = nullptr;
+      uint64_t n_ids = 0;
+      if (eg3d_host_read_communities(communities_path, &ids, &n_ids) != EG3D_OK) return fail("reading the communities");
+      eg3d_polyline_sets cs;
+      const int rc = eg3d_host_sets_from_communities(&sg, ids, n_ids, V, &cs);
+      eg3d_host_free(ids);
+      eg3d_free_simgraph(&sg);
+      if (rc != EG3D_OK) return fail("the communities do not fit the graph (one id per node)");
+      ms.n_sets = cs.n_sets;
+      ms.row_off.assign(cs.row_off, cs.row_off + (size_t)cs.n_sets * V + 1);
+      ms.ids.assign(cs.pl_ids, cs.pl_ids + ms.row_off.back());
+      if (ms.ids.empty()) ms.ids.push_back(0);
+      eg3d_host_free_polyline_sets(&cs);
+    } else if (stage == 1 && match2) {  // pipelines.cpp:118
       eg3d_seeds rp;
       eg3d_sfm_seeds(sfm, &rp);
       eg3d_polyline_matches pm;

@@ -464,6 +464,41 @@ int eg3d_match_polylines_closeness(eg3d_ctx*, const eg3d_seeds* seeds /* NULL = 
                                    uint32_t seed_begin, uint32_t seed_end, eg3d_polyline_matches* out, eg3d_polymatch_stats* stats);
 void eg3d_free_polyline_matches(eg3d_polyline_matches*);
 
+/* ---- pipeline 1: the polyline compatibility graph ------------------------------------------------------------------
+ * The graph half of polyline_matching_similarity_graph (polyline_matcher.cpp:222-327), on the device; the community
+ * detection the reference runs on the graph (Grappolo, third-party) is the caller's, and include/eg3d_host.h has both sides
+ * of its file seam. For every seed of [seed_begin, seed_end), ascending, the search of eg3d_match_polylines_closeness runs
+ * at every entry of its track; ALL polylines within 10 px count (there is no acceptance rule). The distinct (view,
+ * polyline) pairs of a point are a clique; nodes are numbered by first appearance, as the reference numbers them. A point
+ * weighs (views with a close polyline) / (float)(pairs), 0 without any; the edge between (v1, p1) and (v2, p2) weighs
+ * sum(weight over A and B) / sum(weight over A or B) with A = the points close to p1 on v1 whose track lists v2 and B = the
+ * points close to p2 on v2 whose track lists v1, each sum a float that starts at 0 and adds in ascending point order; an
+ * edge is kept where that is > 0. The cliques are expanded a fixed budget of edge keys at a time and merged into the
+ * sorted list of distinct edges, so no input is refused for its size short of 2^31 distinct edges (EG3D_ERR_CAPACITY);
+ * EG3D_SIMGRAPH_PAIR_BUDGET=n (read when the context is created; tests) sets the budget in keys.
+ * An empty range, or no close polyline: n_nodes = 0, adj_off = {0}, EG3D_OK (the per-point and per-polyline arrays are
+ * still there, all zero). A view id outside the rig, struct_size, seeds == NULL, the 10 px map and the threading rule: as
+ * eg3d_match_polylines_closeness; the map is built by the first call of either and shared. */
+typedef struct eg3d_simgraph {            /* library-owned; eg3d_free_simgraph */
+  uint32_t n_nodes;      uint32_t* node_view;  uint32_t* node_pl;   /* polyline_matches_vector, in node-id order */
+  uint32_t* adj_off;     /* [n_nodes + 1] adjacency_lists: both directions of every kept edge, neighbours ascending */
+  uint32_t* adj_node;    float* adj_w;         /* [adj_off[n_nodes]] */
+  uint32_t seed_begin;   uint32_t n_points;    /* = seed_end - seed_begin; point i is seed seed_begin + i */
+  float* point_weight;   /* [n_points] */
+  uint32_t* cp_off;      /* [n_points + 1] close_polylines, sparse: per point its (view, polyline) pairs, ascending */
+  uint32_t* cp_view;     uint32_t* cp_pl;      /* [cp_off[n_points]] */
+  uint32_t n_polylines;  /* = view_pl_off[n_views] */
+  uint32_t* cr_off;      /* [n_polylines + 1] close_refpoints over the global polyline index view_pl_off[view] + pl */
+  uint32_t* cr_point;    /* [cr_off[n_polylines]] absolute seed ids, ascending per row */
+} eg3d_simgraph;
+typedef struct eg3d_simgraph_stats { uint32_t struct_size; /* caller sets it; smaller is refused */
+  uint64_t n_entries, n_nodes, n_edges /* undirected, kept */, n_pair_instances /* sum of m (m - 1) / 2 */, n_chunks;
+  float ms_grid, ms_search /* count, scan, fill */, ms_graph /* lists, nodes, distinct edges */,
+        ms_weights /* edge weights and the adjacency */, ms_copy; } eg3d_simgraph_stats;
+int eg3d_similarity_graph(eg3d_ctx*, const eg3d_seeds* seeds /* NULL = the uploaded seeds */, uint32_t seed_begin,
+                          uint32_t seed_end, eg3d_simgraph* out, eg3d_simgraph_stats* stats);
+void eg3d_free_simgraph(eg3d_simgraph*);
+
 #ifdef __cplusplus
 }
 #endif

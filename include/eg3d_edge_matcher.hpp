@@ -67,6 +67,14 @@ struct EdgeMatchingOptions {
   // (polyline_matching_closeness_to_refpoints), every match through the extractor, its cloud in front of pipeline 3's as in
   // the reference; skipped_pipelines is then 1. Off by default: the call behaves as before.
   bool run_pipeline2 = false;
+  // run_pipeline1 = true: the graph half of pipeline 1's matcher runs on the device (polyline_matching_similarity_graph up
+  // to its community detection) and the compatibility graph is written to pipeline1_graph_file (if not empty) in the
+  // reference's format. The community detection itself (Grappolo in the reference) is the caller's: with
+  // pipeline1_communities_file empty the stage stops there, says so on stderr and stays skipped; with a file of one
+  // community id per node (from a clustering of the graph file of an earlier call) the matches go through the extractor,
+  // their cloud in front of pipeline 2's and 3's as in the reference, and bit 0 of skipped_pipelines is cleared.
+  bool run_pipeline1 = false;
+  std::string pipeline1_graph_file, pipeline1_communities_file;
   bool quiet = false;
   int skipped_pipelines = 0;  // bit 0: pipeline 1 (similarity graph), bit 1: pipeline 2 (closeness to refpoints) [out]
 };
@@ -319,8 +327,40 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
   const bool pipeline2 = edge_matching_options().run_pipeline2;
   edge_matching_options().skipped_pipelines = pipeline2 ? 1 : 3;
   std::vector<new_3dpoint_plgp_matches> p3ds;
+  bool pipeline1_ran = false;
+  if (edge_matching_options().run_pipeline1) {
+    const EdgeMatchingOptions& o = edge_matching_options();
+    const auto graph = polyline_matching_similarity_graph_before_communities(sfm_data, em.get());
+    if (!o.pipeline1_graph_file.empty() && graph.write_to_file(o.pipeline1_graph_file.c_str()) != EG3D_OK)
+      throw Eg3dError(EG3D_ERR_ARG, "edge_matching: cannot write the compatibility graph file");
+    if (o.pipeline1_communities_file.empty()) {
+      std::fprintf(stderr, "eg3d edge_matching: pipeline 1: the compatibility graph (%zu polylines) %s%s; its community detection "
+                           "is the caller's: cluster the file and call again with pipeline1_communities_file (INTEGRATION.md). "
+                           "The stage is skipped\n", graph.polyline_matches_vector.size(),
+                   o.pipeline1_graph_file.empty() ? "was built but not written (pipeline1_graph_file is empty)" : "was written to ",
+                   o.pipeline1_graph_file.c_str());
+    } else {
+      int64_t* ids = nullptr;
+      uint64_t n_ids = 0;
+      if (eg3d_host_read_communities(o.pipeline1_communities_file.c_str(), &ids, &n_ids) != EG3D_OK)
+        throw Eg3dError(EG3D_ERR_ARG, "edge_matching: cannot read the communities file");
+      const std::vector<long> component_ids(ids, ids + n_ids);
+      eg3d_host_free(ids);
+      if (component_ids.size() != graph.polyline_matches_vector.size())
+        throw Eg3dError(EG3D_ERR_ARG, "edge_matching: the communities file does not hold one id per node of the graph");
+      for (const auto& potentially_compatible_polylines :
+           compute_polyline_matches_from_nodes_component_ids(graph.polyline_matches_vector, sfm_data.numCameras_, component_ids)) {
+        const auto cur = find_new_3d_points_from_compatible_polylines_expandallviews_parallel(sfm_data, em.get(),
+                                                                                              potentially_compatible_polylines);
+        detail::throw_if_failed(em.get(), "find_new_3d_points_from_compatible_polylines_expandallviews_parallel");
+        p3ds.insert(p3ds.end(), cur.begin(), cur.end());
+      }
+      pipeline1_ran = true;
+      edge_matching_options().skipped_pipelines &= ~1;
+    }
+  }
   if (pipeline2) {
-    if (!edge_matching_options().quiet)
+    if (!edge_matching_options().quiet && !pipeline1_ran)
       std::fprintf(stderr, "eg3d edge_matching: pipeline 1 (polyline matches of the similarity-graph / Louvain matcher) is not "
                            "part of this build; running pipelines 2 and 3: the output may hold fewer edge-points than the "
                            "reference's (INTEGRATION.md)\n");
@@ -331,7 +371,7 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
       detail::throw_if_failed(em.get(), "find_new_3d_points_from_compatible_polylines_expandallviews_parallel");
       p3ds.insert(p3ds.end(), cur.begin(), cur.end());
     }
-  } else if (!edge_matching_options().quiet)
+  } else if (!edge_matching_options().quiet && !pipeline1_ran)
     std::fprintf(stderr, "eg3d edge_matching: pipelines 1-2 (polyline matches of the similarity-graph / Louvain matchers) are not "
                          "part of this build; running pipeline 3 (reference points) only: the output may hold fewer edge-points "
                          "than the reference's (INTEGRATION.md)\n");

@@ -444,6 +444,67 @@ class PLGEdgeManager : public EdgeManager {
     return res;
   }
 
+  // The graph half of polyline_matching_similarity_graph (polyline_matcher.cpp:222-327) over all reference points: ONE call
+  // of the C ABI (eg3d_similarity_graph). close_polylines[point][view], close_refpoints[view][polyline], the nodes
+  // (polyline_matches_vector) and the weighted adjacency (adjacency_lists and weights of the reference's
+  // GraphAdjacencySetUndirectedNoTypeWeighted); `raw` keeps the arrays for eg3d_host_write_compat_graph. Empty + last_status()
+  // on failure.
+  struct SimilarityGraph {
+    std::vector<std::vector<std::set<unsigned long>>> close_polylines;
+    std::vector<std::vector<std::vector<unsigned long>>> close_refpoints;
+    std::vector<std::pair<int, unsigned long>> polyline_matches_vector;
+    std::vector<std::set<unsigned long>> adjacency_lists;
+    std::vector<std::vector<float>> weights;  // weights[n][k]: the edge to the k-th (ascending) neighbour of n
+    eg3d_simgraph raw{};
+    SimilarityGraph() = default;
+    SimilarityGraph(const SimilarityGraph&) = delete;
+    SimilarityGraph& operator=(const SimilarityGraph&) = delete;
+    SimilarityGraph(SimilarityGraph&& o) noexcept { *this = std::move(o); }
+    SimilarityGraph& operator=(SimilarityGraph&& o) noexcept {
+      if (this != &o) {
+        eg3d_free_simgraph(&raw);
+        close_polylines = std::move(o.close_polylines);
+        close_refpoints = std::move(o.close_refpoints);
+        polyline_matches_vector = std::move(o.polyline_matches_vector);
+        adjacency_lists = std::move(o.adjacency_lists);
+        weights = std::move(o.weights);
+        raw = o.raw;
+        std::memset(&o.raw, 0, sizeof(o.raw));
+      }
+      return *this;
+    }
+    ~SimilarityGraph() { eg3d_free_simgraph(&raw); }
+    // write_to_file of the reference's weighted graph: the input of its community detection
+    int write_to_file(const char* path) const { return eg3d_host_write_compat_graph(path, &raw); }
+  };
+  SimilarityGraph similarity_graph() {
+    SimilarityGraph res;
+    if (!ctx_) return res;
+    eg3d_seeds s = seeds_struct();
+    status_ = eg3d_similarity_graph(ctx_, &s, 0, (uint32_t)sfmd_.numPoints_, &res.raw, nullptr);
+    if (status_ != EG3D_OK) return res;
+    const eg3d_simgraph& g = res.raw;
+    const size_t V = (size_t)sfmd_.numCameras_;
+    res.close_polylines.assign(g.n_points, std::vector<std::set<unsigned long>>(V));
+    for (uint32_t i = 0; i < g.n_points; i++)
+      for (uint32_t k = g.cp_off[i]; k < g.cp_off[i + 1]; k++) res.close_polylines[i][g.cp_view[k]].insert(g.cp_pl[k]);
+    res.close_refpoints.resize(V);
+    for (size_t v = 0; v < V; v++) {
+      const uint32_t g0 = scene_.view_pl_off[v], g1 = scene_.view_pl_off[v + 1];
+      res.close_refpoints[v].resize(g1 - g0);
+      for (uint32_t gp = g0; gp < g1; gp++)
+        res.close_refpoints[v][gp - g0].assign(g.cr_point + g.cr_off[gp], g.cr_point + g.cr_off[gp + 1]);
+    }
+    res.adjacency_lists.resize(g.n_nodes);
+    res.weights.resize(g.n_nodes);
+    for (uint32_t n = 0; n < g.n_nodes; n++) {
+      res.polyline_matches_vector.emplace_back((int)g.node_view[n], (unsigned long)g.node_pl[n]);
+      res.adjacency_lists[n].insert(g.adj_node + g.adj_off[n], g.adj_node + g.adj_off[n + 1]);
+      res.weights[n].assign(g.adj_w + g.adj_off[n], g.adj_w + g.adj_off[n + 1]);
+    }
+    return res;
+  }
+
   // All chains of ONE reference point, grouped the way the reference's loop produces them
   // (plg_matching_from_refpoints.cpp:69-78): [track entry][starting intersection] -> chain (possibly empty).
   // n_start[entry] = starting intersections of that entry (a chain-less intersection still has its — empty — slot).
@@ -675,6 +736,29 @@ inline std::pair<std::vector<unsigned long>, std::vector<std::vector<std::set<un
 polyline_matching_closeness_to_refpoints(const SfMData&, PLGEdgeManager* em) {
   auto res = em->match_polylines_closeness();
   detail::throw_if_failed(em, "polyline_matching_closeness_to_refpoints");
+  return res;
+}
+
+// The graph half of polyline_matching_similarity_graph (polyline_matcher.hpp; polyline_matcher.cpp:222-327): everything up to
+// the community detection, which the reference hands to Grappolo through a file and this library leaves to the caller
+// (SimilarityGraph::write_to_file writes that file; read the ids back with eg3d_host_read_communities). Throws on failure.
+inline PLGEdgeManager::SimilarityGraph polyline_matching_similarity_graph_before_communities(const SfMData&, PLGEdgeManager* em) {
+  auto res = em->similarity_graph();
+  detail::throw_if_failed(em, "polyline_matching_similarity_graph");
+  return res;
+}
+
+// compute_polyline_matches_from_nodes_component_ids (polyline_matcher.cpp:202-214), the reference's signature: one set per
+// community id up to the largest, a node with a negative id in none.
+inline std::vector<std::vector<std::set<unsigned long>>> compute_polyline_matches_from_nodes_component_ids(
+    const std::vector<std::pair<int, unsigned long>>& polyline_matches_vector, int amount_of_plgs,
+    const std::vector<long>& nodes_component_ids) {
+  long max_id = -1;
+  for (long id : nodes_component_ids) max_id = id > max_id ? id : max_id;
+  std::vector<std::vector<std::set<unsigned long>>> res((size_t)(max_id + 1), std::vector<std::set<unsigned long>>((size_t)amount_of_plgs));
+  for (size_t i = 0; i < polyline_matches_vector.size() && i < nodes_component_ids.size(); i++)
+    if (nodes_component_ids[i] >= 0)
+      res[(size_t)nodes_component_ids[i]][(size_t)polyline_matches_vector[i].first].insert(polyline_matches_vector[i].second);
   return res;
 }
 
