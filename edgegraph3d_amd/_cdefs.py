@@ -110,6 +110,25 @@ class SimgraphStats(C.Structure):
                 ("ms_graph", C.c_float), ("ms_weights", C.c_float), ("ms_copy", C.c_float)]
 
 
+class LouvainParams(C.Structure):
+    """eg3d_louvain_params: a field of 0 is its default."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_phases", C.c_uint32), ("max_sweeps", C.c_uint32),
+                ("sweep_threshold", C.c_double), ("phase_threshold", C.c_double)]
+
+
+class Communities(C.Structure):
+    """eg3d_communities (library-owned; eg3d_free_communities)."""
+    _fields_ = [("n_nodes", C.c_uint32), ("ids", C.POINTER(C.c_int64)), ("n_communities", C.c_uint32)]
+
+
+class LouvainStats(C.Structure):
+    """eg3d_louvain_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_phases", C.c_uint32), ("n_sweeps", C.c_uint32), ("n_communities", C.c_uint32),
+                ("n_isolated", C.c_uint32), ("n_overflow_rows", C.c_uint64), ("total_q", C.c_uint64), ("numer_hi", C.c_uint64),
+                ("numer_lo", C.c_uint64), ("modularity", C.c_double), ("ms_upload", C.c_float), ("ms_sweeps", C.c_float),
+                ("ms_coarsen", C.c_float), ("ms_copy", C.c_float)]
+
+
 def simgraph_to_dict(g):
     """Numpy copies of every array of an eg3d_simgraph."""
     nn, npt, npl = int(g.n_nodes), int(g.n_points), int(g.n_polylines)

@@ -79,6 +79,10 @@ def lib():
                                             C.POINTER(D.SimgraphStats)]
         L.eg3d_free_simgraph.argtypes = [C.POINTER(D.Simgraph)]
         L.eg3d_free_simgraph.restype = None
+        L.eg3d_detect_communities.argtypes = [C.c_void_p, C.POINTER(D.Simgraph), C.POINTER(D.LouvainParams),
+                                              C.POINTER(D.Communities), C.POINTER(D.LouvainStats)]
+        L.eg3d_free_communities.argtypes = [C.POINTER(D.Communities)]
+        L.eg3d_free_communities.restype = None
         _LIB = L
     return _LIB
 
@@ -91,6 +95,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
     "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
     "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches", "eg3d_similarity_graph", "eg3d_free_simgraph",
+    "eg3d_detect_communities", "eg3d_free_communities",
 ]
 
 
@@ -328,6 +333,32 @@ class Context:
         d = D.simgraph_to_dict(g)
         d["stats"] = {f[0]: getattr(st, f[0]) for f in D.SimgraphStats._fields_}
         lib().eg3d_free_simgraph(C.byref(g))
+        return d
+
+    def communities(self, g, **params):
+        """Pipeline 1's community detection (eg3d_detect_communities) on the weighted adjacency of `g`: a dict with n_nodes,
+        adj_off, adj_node and adj_w, such as similarity_graph returns. `params` are the fields of eg3d_louvain_params
+        (max_phases, max_sweeps, sweep_threshold, phase_threshold; 0 or absent = the default). Returns ids (int64, numbered by
+        ascending smallest member, -1 for a node without a neighbour), n_communities and the call's stats."""
+        n = int(g["n_nodes"])
+        off = np.ascontiguousarray(g["adj_off"] if n else [0], np.uint32)
+        node = np.ascontiguousarray(g["adj_node"] if len(g["adj_node"]) else [0], np.uint32)
+        w = np.ascontiguousarray(g["adj_w"] if len(g["adj_w"]) else [0], np.float32)
+        if len(off) != n + 1 or (n and (len(g["adj_node"]) != int(off[-1]) or len(g["adj_w"]) != int(off[-1]))):
+            raise Eg3dError("communities: adj_off must hold n_nodes + 1 offsets and adj_node / adj_w adj_off[n_nodes] entries")
+        sg = D.Simgraph()
+        sg.n_nodes = n
+        sg.adj_off, sg.adj_node, sg.adj_w = D.np_ptr(off, C.c_uint32), D.np_ptr(node, C.c_uint32), D.np_ptr(w, C.c_float)
+        unknown = set(params) - {f[0] for f in D.LouvainParams._fields_[1:]}
+        if unknown:
+            raise Eg3dError("communities: unknown parameter(s) %s" % sorted(unknown))
+        pr = D.LouvainParams(C.sizeof(D.LouvainParams), **params)
+        m, st = D.Communities(), D.LouvainStats()
+        st.struct_size = C.sizeof(D.LouvainStats)
+        _check(lib().eg3d_detect_communities(self._h, C.byref(sg), C.byref(pr), C.byref(m), C.byref(st)), "eg3d_detect_communities")
+        d = {"ids": D.as_np(m.ids, int(m.n_nodes), np.int64), "n_communities": int(m.n_communities),
+             "stats": {f[0]: getattr(st, f[0]) for f in D.LouvainStats._fields_}}
+        lib().eg3d_free_communities(C.byref(m))
         return d
 
     def last_device_output(self):

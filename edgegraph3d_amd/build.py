@@ -210,6 +210,9 @@ RESOURCE_BOUNDS = {
     # the compatibility graph (eg3d_similarity_graph): as K9 — no spills, no scratch; LDS only in the list-form search, the
     # same one 64-bit slot per lane
     "k10_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},
+    # the community detection (eg3d_detect_communities): no spills, no scratch (a substring: all of them). The sweep's hash
+    # table is dynamic LDS (sized per launch, not in this figure); the only static LDS is k11_inside's one partial sum per wave
+    "k11_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 32},
     "k2_epipolar_hits": {"vgpr_spill_count": 0},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }

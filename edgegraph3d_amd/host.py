@@ -51,6 +51,7 @@ def lib():
         L.eg3d_plg_destroy.argtypes = [C.c_void_p]
         L.eg3d_host_write_compat_graph.argtypes = [C.c_char_p, C.POINTER(D.Simgraph)]
         L.eg3d_host_read_communities.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_uint64)]
+        L.eg3d_host_write_communities.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_uint64]
         L.eg3d_host_sets_from_communities.argtypes = [C.POINTER(D.Simgraph), C.POINTER(C.c_int64), C.c_uint64, C.c_int32,
                                                       C.POINTER(D.PolylineSets)]
         L.eg3d_host_free_polyline_sets.argtypes = [C.POINTER(D.PolylineSets)]
@@ -198,6 +199,15 @@ def read_communities(path):
     out = D.as_np(ids, n.value, np.int64)
     lib().eg3d_host_free(ids)
     return out
+
+
+def write_communities(path, ids):
+    """One community id per line, as Grappolo writes the file the reference reads (eg3d_host_write_communities)."""
+    ids = np.ascontiguousarray(ids, np.int64)
+    buf = ids if len(ids) else np.zeros(1, np.int64)
+    rc = lib().eg3d_host_write_communities(os.fsencode(path), D.np_ptr(buf, C.c_int64), len(ids))
+    if rc != 0:
+        raise RuntimeError("eg3d_host_write_communities(%s) failed (%d)" % (path, rc))
 
 
 def sets_from_communities(graph, ids, n_views):

@@ -1,6 +1,7 @@
 // The file seam of pipeline 1 (eg3d_host.h): the reference hands its compatibility graph to the community detection as a
 // text file and reads one community id per node back (community_detection_interface.cpp:42-73). Both sides of that seam
 // and the step that follows it, on the arrays of eg3d_similarity_graph.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -47,6 +48,17 @@ extern "C" int eg3d_host_read_communities(const char* path, int64_t** ids, uint6
   *ids = out;
   *n = res.size();
   return EG3D_OK;
+}
+
+// The other direction of the same file: one id per line, printed with %ld as Grappolo prints the file the reference reads
+// (a node without a neighbour is -1 there too).
+extern "C" int eg3d_host_write_communities(const char* path, const int64_t* ids, uint64_t n) {
+  if (!path || (n && !ids)) return EG3D_ERR_ARG;
+  FILE* f = fopen(path, "w");
+  if (!f) return EG3D_ERR_ARG;
+  bool ok = true;
+  for (uint64_t i = 0; i < n && ok; i++) ok = fprintf(f, "%ld\n", (long)ids[i]) > 0;
+  return (fclose(f) == 0 && ok) ? EG3D_OK : EG3D_ERR_ARG;
 }
 
 extern "C" void eg3d_host_free_polyline_sets(eg3d_polyline_sets* s) {

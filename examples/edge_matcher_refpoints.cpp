@@ -226,15 +226,27 @@ int main(int argc, char** argv) {
   // --match1-graph <file>: the compatibility graph of pipeline 1's polyline matcher is built on the device
   // (eg3d_similarity_graph) and written as the reference writes it for its community detection (Grappolo: third-party, not
   // part of this example). --communities <file>: one community id per node of that graph, from whatever clustered the file;
-  // the sets they make go through pipeline 1's extractor where --sets1 reads them.
+  // the sets they make go through pipeline 1's extractor where --sets1 reads them. --louvain [communities-out]: the
+  // library's own community detection runs on the graph instead (eg3d_detect_communities, on the device; no --communities
+  // needed) and its ids are written to communities-out if one is named.
   const char* graph_path = nullptr;
   const char* communities_path = nullptr;
+  const char* louvain_out = nullptr;
+  bool louvain = false;
   for (int a = 4; a < argc; a++) {
     if (std::strcmp(argv[a], "--match1-graph") == 0 && a + 1 < argc) graph_path = argv[++a];
     else if (std::strcmp(argv[a], "--communities") == 0 && a + 1 < argc) communities_path = argv[++a];
+    else if (std::strcmp(argv[a], "--louvain") == 0) {
+      louvain = true;
+      if (a + 1 < argc && std::strncmp(argv[a + 1], "--", 2) != 0) louvain_out = argv[++a];
+    }
   }
-  if (communities_path && sets_path[0]) {
-    std::fprintf(stderr, "--communities and --sets1 exclude each other\n");
+  if ((communities_path || louvain) && sets_path[0]) {
+    std::fprintf(stderr, "--communities / --louvain and --sets1 exclude each other\n");
+    return 2;
+  }
+  if (communities_path && louvain) {
+    std::fprintf(stderr, "--communities and --louvain exclude each other\n");
     return 2;
   }
 
@@ -309,10 +321,10 @@ int main(int argc, char** argv) {
   // ---- pipelines 1 and 2 (pipelines.cpp:219-223): the extractor over the polyline matches of each stage, in
   // match order (one call takes all matches of a stage: eg3d_match_polyline_sets emits them set by set)
   for (int stage = 0; stage < 2; stage++) {
-    const bool match1 = stage == 0 && (graph_path || communities_path);
+    const bool match1 = stage == 0 && (graph_path || communities_path || louvain);
     if (!sets_path[stage] && !(stage == 1 && match2) && !match1) continue;
     MatchSets ms;
-    if (match1) {  // pipelines.cpp:219 -> polyline_matcher.cpp:222-336, the community detection left to the caller
+    if (match1) {  // pipelines.cpp:219 -> polyline_matcher.cpp:222-336; the community detection: --louvain, or the caller's
       eg3d_seeds rp;
       eg3d_sfm_seeds(sfm, &rp);
       eg3d_simgraph sg;
@@ -322,17 +334,31 @@ int main(int argc, char** argv) {
       std::printf("pipeline 1: compatibility graph of %llu polylines, %llu edges\n", (unsigned long long)st.n_nodes,
                   (unsigned long long)st.n_edges);
       if (graph_path && eg3d_host_write_compat_graph(graph_path, &sg) != EG3D_OK) return fail("writing the compatibility graph");
-      if (!communities_path) {
-        std::fprintf(stderr, "pipeline 1: wrote %s; clustering it is the caller's (--communities <file> continues)\n", graph_path);
+      if (!communities_path && !louvain) {
+        std::fprintf(stderr, "pipeline 1: wrote %s; --louvain clusters it on the device, or cluster it yourself (--communities <file> continues)\n", graph_path);
         eg3d_free_simgraph(&sg);
         continue;
       }
       int64_t* ids = nullptr;
       uint64_t n_ids = 0;
-      if (eg3d_host_read_communities(communities_path, &ids, &n_ids) != EG3D_OK) return fail("reading the communities");
+      eg3d_communities cm;
+      std::memset(&cm, 0, sizeof(cm));
+      if (louvain) {  // community_detection_interface.cpp:57-73, on the device
+        eg3d_louvain_stats ls;
+        ls.struct_size = (uint32_t)sizeof(ls);
+        if (eg3d_detect_communities(ctx, &sg, nullptr, &cm, &ls) != EG3D_OK) return fail("eg3d_detect_communities");
+        std::printf("pipeline 1: %u communities in %u phases and %u sweeps, modularity %.6f\n", ls.n_communities, ls.n_phases,
+                    ls.n_sweeps, ls.modularity);
+        if (louvain_out && eg3d_host_write_communities(louvain_out, cm.ids, cm.n_nodes) != EG3D_OK) return fail("writing the communities");
+        ids = cm.ids;
+        n_ids = cm.n_nodes;
+      } else if (eg3d_host_read_communities(communities_path, &ids, &n_ids) != EG3D_OK) {
+        return fail("reading the communities");
+      }
       eg3d_polyline_sets cs;
       const int rc = eg3d_host_sets_from_communities(&sg, ids, n_ids, V, &cs);
-      eg3d_host_free(ids);
+      if (louvain) eg3d_free_communities(&cm);
+      else eg3d_host_free(ids);
       eg3d_free_simgraph(&sg);
       if (rc != EG3D_OK) return fail("the communities do not fit the graph (one id per node)");
       ms.n_sets = cs.n_sets;

@@ -466,8 +466,8 @@ void eg3d_free_polyline_matches(eg3d_polyline_matches*);
 
 /* ---- pipeline 1: the polyline compatibility graph ------------------------------------------------------------------
  * The graph half of polyline_matching_similarity_graph (polyline_matcher.cpp:222-327), on the device; the community
- * detection the reference runs on the graph (Grappolo, third-party) is the caller's, and include/eg3d_host.h has both sides
- * of its file seam. For every seed of [seed_begin, seed_end), ascending, the search of eg3d_match_polylines_closeness runs
+ * detection the reference runs on the graph (Grappolo, third-party) is eg3d_detect_communities below, or a program of the
+ * caller's: include/eg3d_host.h has both sides of its file seam. For every seed of [seed_begin, seed_end), ascending, the search of eg3d_match_polylines_closeness runs
  * at every entry of its track; ALL polylines within 10 px count (there is no acceptance rule). The distinct (view,
  * polyline) pairs of a point are a clique; nodes are numbered by first appearance, as the reference numbers them. A point
  * weighs (views with a close polyline) / (float)(pairs), 0 without any; the edge between (v1, p1) and (v2, p2) weighs
@@ -498,6 +498,35 @@ typedef struct eg3d_simgraph_stats { uint32_t struct_size; /* caller sets it; sm
 int eg3d_similarity_graph(eg3d_ctx*, const eg3d_seeds* seeds /* NULL = the uploaded seeds */, uint32_t seed_begin,
                           uint32_t seed_end, eg3d_simgraph* out, eg3d_simgraph_stats* stats);
 void eg3d_free_simgraph(eg3d_simgraph*);
+
+/* ---- pipeline 1: community detection on the compatibility graph -----------------------------------------------------
+ * A deterministic Louvain on the device (K11), in the place where the reference calls Grappolo. It keeps Grappolo's rules
+ * (synchronous sweeps, equal gains go to the smaller label, two singletons do not swap, phases on the coarsened graph) and
+ * uses exact arithmetic: a weight w is the integer llrint((double)w * 2^32), every sum is an integer sum, gains and the
+ * modularity numerator N = (weight inside communities) * M - sum of a_c^2 (M = the sum of all directed weights, a_c = a
+ * community's total degree) are exact 128-bit integers, and doubles appear only in the two threshold tests
+ * (double)(N_new - N_old) < threshold * ((double)M * (double)M). The result does not depend on the device, the table size or
+ * the order in which lanes arrive; tests/louvain_ref.py restates the algorithm and is its definition.
+ * `g` is read for n_nodes, adj_off, adj_node and adj_w only (host memory): both directions of every edge, neighbours
+ * strictly ascending, no self-loop, weights finite and in (0, 1], the two directions of an edge with the same weight bits,
+ * fewer than 2^31 entries (EG3D_ERR_CAPACITY). A violation is EG3D_ERR_ARG (device-side check before anything else;
+ * eg3d_last_error names the rule; `out` and `stats` stay untouched). ids[i] is the community of node i, numbered by
+ * ascending smallest member; a node without a neighbour gets -1, which eg3d_host_sets_from_communities drops.
+ * n_nodes == 0: an empty result, EG3D_OK. EG3D_LOUVAIN_TABLE_SLOTS=n (read when the context is created; tests) sets the
+ * slots of the sweep's per-wavefront table (a power of two in 16 .. 1024, default 512); rows with more distinct
+ * neighbouring communities than slots take the sort-and-reduce path (stats.n_overflow_rows). struct_size and the threading
+ * rule: as eg3d_similarity_graph. */
+typedef struct eg3d_louvain_params { uint32_t struct_size; /* caller sets it; smaller is refused */
+  uint32_t max_phases /* 200 */, max_sweeps /* per phase: 1000 */;
+  double sweep_threshold, phase_threshold /* 1e-6 each; negative or NaN is refused */; } eg3d_louvain_params; /* NULL = defaults; 0 in a field = its default */
+typedef struct eg3d_communities { uint32_t n_nodes; int64_t* ids; uint32_t n_communities; } eg3d_communities; /* library-owned; eg3d_free_communities */
+typedef struct eg3d_louvain_stats { uint32_t struct_size; /* caller sets it; smaller is refused */
+  uint32_t n_phases, n_sweeps, n_communities, n_isolated; uint64_t n_overflow_rows /* summed over sweeps */,
+  total_q /* M */, numer_hi, numer_lo /* the final N, two's complement */; double modularity /* (double)N / ((double)M * (double)M); 0 for M == 0 */;
+  float ms_upload /* and the checks */, ms_sweeps, ms_coarsen /* renumbering and the coarse graphs */, ms_copy; } eg3d_louvain_stats;
+int eg3d_detect_communities(eg3d_ctx*, const eg3d_simgraph* g, const eg3d_louvain_params* params, eg3d_communities* out,
+                            eg3d_louvain_stats* stats);
+void eg3d_free_communities(eg3d_communities*);
 
 #ifdef __cplusplus
 }

@@ -21,9 +21,11 @@
 //                                            edge_matching_options().estimate_F is set (cv::findFundamentalMat(FM_LMEDS)
 //                                            is randomised OpenCV code: not reproducible)
 //   new PLGEdgeManager / PLGPCM3ViewsPLGFollowing / PLGMatchesManager / 4 px maps   the shim's managers (GPU context)
-//   edge_reconstruction_pipeline             pipelines 1-2 start from polyline matches of the Louvain matchers (third
-//                                            party, out of scope: no matches -> no points, as with an empty match
-//                                            list); pipeline 3 = plg_matching_from_refpoints_parallel on the GPU; then
+//   edge_reconstruction_pipeline             pipelines 1-2 run on request (EdgeMatchingOptions: run_pipeline2;
+//                                            run_pipeline1 with pipeline1_detect_communities, the library's own
+//                                            community detection in Grappolo's place, or with a communities file); left
+//                                            out, they add no points, as with an empty match list; pipeline 3 =
+//                                            plg_matching_from_refpoints_parallel on the GPU; then
 //                                            filter_3d_points_close_2d_array + add_3dpoints_to_sfmd
 //   output_sfm_data(before_filtering.json)   eg3d_sfm_write_json with the input file passed through
 //   filter(sfm_data, first_edgepoint)        eg3d_ref::filter (GPU Gauss-Newton filter + observation filter)
@@ -58,10 +60,9 @@ struct EdgeMatchingOptions {
   bool estimate_F = false;  // fundamental matrices estimated from the tracks (own LMedS) instead of analytic from the cameras
   bool require_images = true;  // the photographs named by the SfM data must exist in images_folder (as parse_images fails without them)
   int device = 0;
-  // edge_reconstruction_pipeline (pipelines.cpp:201-246) runs three pipelines; this build runs pipeline 3 (reference points)
-  // only: pipelines 1-2 consume polyline matches of the similarity-graph / Louvain matchers, which are out of scope (their
-  // extractor, eg3d_match_polyline_sets, is built; examples/edge_matcher_refpoints.cpp feeds it from a file). The output can
-  // therefore hold fewer edge-points than the reference's. quiet = false prints one line to stderr saying so per call;
+  // edge_reconstruction_pipeline (pipelines.cpp:201-246) runs three pipelines; by default this build runs pipeline 3
+  // (reference points) only: pipelines 1-2 consume polyline matches of the similarity-graph / Louvain matchers and run on
+  // request (below). The output can therefore hold fewer edge-points than the reference's. quiet = false prints one line to stderr saying so per call;
   // after a call skipped_pipelines says which were left out.
   // run_pipeline2 = true: pipeline 2 runs too (pipelines.cpp:113-158) — its polyline matcher on the device
   // (polyline_matching_closeness_to_refpoints), every match through the extractor, its cloud in front of pipeline 3's as in
@@ -69,12 +70,18 @@ struct EdgeMatchingOptions {
   bool run_pipeline2 = false;
   // run_pipeline1 = true: the graph half of pipeline 1's matcher runs on the device (polyline_matching_similarity_graph up
   // to its community detection) and the compatibility graph is written to pipeline1_graph_file (if not empty) in the
-  // reference's format. The community detection itself (Grappolo in the reference) is the caller's: with
+  // reference's format. The community detection itself (Grappolo in the reference) is the caller's by default: with
   // pipeline1_communities_file empty the stage stops there, says so on stderr and stays skipped; with a file of one
   // community id per node (from a clustering of the graph file of an earlier call) the matches go through the extractor,
   // their cloud in front of pipeline 2's and 3's as in the reference, and bit 0 of skipped_pipelines is cleared.
+  // pipeline1_detect_communities = true (with run_pipeline1 and no pipeline1_communities_file; a given file still wins):
+  // the library's own community detection runs on the device where the reference runs Grappolo (eg3d_detect_communities,
+  // a deterministic Louvain: DESIGN.md 4, K11), its ids take the same path as a file's and are written to
+  // pipeline1_communities_out_file (if not empty), one per line. Off by default: the call behaves as before.
   bool run_pipeline1 = false;
   std::string pipeline1_graph_file, pipeline1_communities_file;
+  bool pipeline1_detect_communities = false;
+  std::string pipeline1_communities_out_file;
   bool quiet = false;
   int skipped_pipelines = 0;  // bit 0: pipeline 1 (similarity graph), bit 1: pipeline 2 (closeness to refpoints) [out]
 };
@@ -333,19 +340,24 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
     const auto graph = polyline_matching_similarity_graph_before_communities(sfm_data, em.get());
     if (!o.pipeline1_graph_file.empty() && graph.write_to_file(o.pipeline1_graph_file.c_str()) != EG3D_OK)
       throw Eg3dError(EG3D_ERR_ARG, "edge_matching: cannot write the compatibility graph file");
-    if (o.pipeline1_communities_file.empty()) {
+    if (o.pipeline1_communities_file.empty() && !o.pipeline1_detect_communities) {
       std::fprintf(stderr, "eg3d edge_matching: pipeline 1: the compatibility graph (%zu polylines) %s%s; its community detection "
                            "is the caller's: cluster the file and call again with pipeline1_communities_file (INTEGRATION.md). "
                            "The stage is skipped\n", graph.polyline_matches_vector.size(),
                    o.pipeline1_graph_file.empty() ? "was built but not written (pipeline1_graph_file is empty)" : "was written to ",
                    o.pipeline1_graph_file.c_str());
     } else {
-      int64_t* ids = nullptr;
-      uint64_t n_ids = 0;
-      if (eg3d_host_read_communities(o.pipeline1_communities_file.c_str(), &ids, &n_ids) != EG3D_OK)
-        throw Eg3dError(EG3D_ERR_ARG, "edge_matching: cannot read the communities file");
-      const std::vector<long> component_ids(ids, ids + n_ids);
-      eg3d_host_free(ids);
+      std::vector<long> component_ids;
+      if (!o.pipeline1_communities_file.empty()) {
+        int64_t* ids = nullptr;
+        uint64_t n_ids = 0;
+        if (eg3d_host_read_communities(o.pipeline1_communities_file.c_str(), &ids, &n_ids) != EG3D_OK)
+          throw Eg3dError(EG3D_ERR_ARG, "edge_matching: cannot read the communities file");
+        component_ids.assign(ids, ids + n_ids);
+        eg3d_host_free(ids);
+      } else {
+        component_ids = compute_communities(graph, nullptr, o.pipeline1_communities_out_file.c_str());
+      }
       if (component_ids.size() != graph.polyline_matches_vector.size())
         throw Eg3dError(EG3D_ERR_ARG, "edge_matching: the communities file does not hold one id per node of the graph");
       for (const auto& potentially_compatible_polylines :

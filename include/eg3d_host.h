@@ -157,17 +157,21 @@ void eg3d_host_free_graph3d(eg3d_graph3d* g);
 /* The reference writes the weighted compatibility graph of polyline_matching_similarity_graph to a text file, runs Grappolo
  * (third-party; not part of this library) on it and reads one community id per node back
  * (community_detection_interface.cpp:42-73). These are both sides of that seam and the step behind it, on the graph of
- * eg3d_similarity_graph; any Louvain implementation that reads the file format can stand between them.
+ * eg3d_similarity_graph. eg3d_detect_communities (eg3d.h) is the library's own community detection and needs no file; any
+ * Louvain implementation that reads the file format can stand between the two sides instead.
  * eg3d_host_write_compat_graph: byte for byte the file of GraphAdjacencySetUndirectedNoTypeWeighted::write_to_file
  *   (graph_adjacency_set_undirected_no_type_weighted.cpp:54-74): "p sp <nodes> <directed edges>", then "a <n1+1> <n2+1> <w>"
  *   per adjacency entry, the weight as an ofstream prints a float (6 significant digits).
  * eg3d_host_read_communities: read_cluster_info — one integer per line (stoul stored as long: "-1" is -1); *ids is
  *   malloc'd (eg3d_host_free). A line that is no number: EG3D_ERR_ARG.
+ * eg3d_host_write_communities: the same file written, one "%ld" per line as Grappolo prints it (the ids of
+ *   eg3d_detect_communities, -1 included); eg3d_host_read_communities reads it back unchanged.
  * eg3d_host_sets_from_communities: compute_polyline_matches_from_nodes_component_ids (polyline_matcher.cpp:202-214) as the
  *   rows of an eg3d_polyline_sets (eg3d_host_free_polyline_sets): max id + 1 sets; a node with a negative id is in none; a
  *   community no node names is an empty set (eg3d_check_polyline_sets accepts empty rows). n != g->n_nodes: EG3D_ERR_ARG. */
 int eg3d_host_write_compat_graph(const char* path, const eg3d_simgraph* g);
 int eg3d_host_read_communities(const char* path, int64_t** ids, uint64_t* n);
+int eg3d_host_write_communities(const char* path, const int64_t* ids, uint64_t n);
 int eg3d_host_sets_from_communities(const eg3d_simgraph* g, const int64_t* ids, uint64_t n, int32_t n_views,
                                     eg3d_polyline_sets* out);
 void eg3d_host_free_polyline_sets(eg3d_polyline_sets* s);

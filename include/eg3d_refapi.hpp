@@ -456,6 +456,7 @@ class PLGEdgeManager : public EdgeManager {
     std::vector<std::set<unsigned long>> adjacency_lists;
     std::vector<std::vector<float>> weights;  // weights[n][k]: the edge to the k-th (ascending) neighbour of n
     eg3d_simgraph raw{};
+    eg3d_ctx* ctx = nullptr;  // the manager's context (not owned): communities() runs on it
     SimilarityGraph() = default;
     SimilarityGraph(const SimilarityGraph&) = delete;
     SimilarityGraph& operator=(const SimilarityGraph&) = delete;
@@ -469,6 +470,7 @@ class PLGEdgeManager : public EdgeManager {
         adjacency_lists = std::move(o.adjacency_lists);
         weights = std::move(o.weights);
         raw = o.raw;
+        ctx = o.ctx;
         std::memset(&o.raw, 0, sizeof(o.raw));
       }
       return *this;
@@ -476,6 +478,17 @@ class PLGEdgeManager : public EdgeManager {
     ~SimilarityGraph() { eg3d_free_simgraph(&raw); }
     // write_to_file of the reference's weighted graph: the input of its community detection
     int write_to_file(const char* path) const { return eg3d_host_write_compat_graph(path, &raw); }
+    // The community detection the reference runs on the graph, on the device (eg3d_detect_communities): one id per node,
+    // numbered by ascending smallest member, -1 for a node without a neighbour. params == nullptr: the defaults. Throws on
+    // failure; the manager must still be alive.
+    std::vector<long> communities(const eg3d_louvain_params* params = nullptr, eg3d_louvain_stats* stats = nullptr) const {
+      eg3d_communities m{};
+      const int rc = eg3d_detect_communities(ctx, &raw, params, &m, stats);
+      if (rc != EG3D_OK) throw Eg3dError(rc, std::string("SimilarityGraph::communities: ") + eg3d_last_error());
+      std::vector<long> ids(m.ids, m.ids + m.n_nodes);
+      eg3d_free_communities(&m);
+      return ids;
+    }
   };
   SimilarityGraph similarity_graph() {
     SimilarityGraph res;
@@ -483,6 +496,7 @@ class PLGEdgeManager : public EdgeManager {
     eg3d_seeds s = seeds_struct();
     status_ = eg3d_similarity_graph(ctx_, &s, 0, (uint32_t)sfmd_.numPoints_, &res.raw, nullptr);
     if (status_ != EG3D_OK) return res;
+    res.ctx = ctx_;
     const eg3d_simgraph& g = res.raw;
     const size_t V = (size_t)sfmd_.numCameras_;
     res.close_polylines.assign(g.n_points, std::vector<std::set<unsigned long>>(V));
@@ -740,12 +754,29 @@ polyline_matching_closeness_to_refpoints(const SfMData&, PLGEdgeManager* em) {
 }
 
 // The graph half of polyline_matching_similarity_graph (polyline_matcher.hpp; polyline_matcher.cpp:222-327): everything up to
-// the community detection, which the reference hands to Grappolo through a file and this library leaves to the caller
-// (SimilarityGraph::write_to_file writes that file; read the ids back with eg3d_host_read_communities). Throws on failure.
+// the community detection, which the reference hands to Grappolo through a file: compute_communities below runs the
+// library's own on the device, or the caller clusters the file (SimilarityGraph::write_to_file writes it; read the ids back
+// with eg3d_host_read_communities). Throws on failure.
 inline PLGEdgeManager::SimilarityGraph polyline_matching_similarity_graph_before_communities(const SfMData&, PLGEdgeManager* em) {
   auto res = em->similarity_graph();
   detail::throw_if_failed(em, "polyline_matching_similarity_graph");
   return res;
+}
+
+// compute_communities (community_detection_interface.cpp:57-73), the reference's shape: writes the compatibility graph file,
+// detects the communities (on the device, SimilarityGraph::communities, where the reference runs Grappolo), writes one id
+// per line to out_polyline_communities and returns the ids. Either path may be null or empty: that file is not written.
+inline std::vector<long> compute_communities(const PLGEdgeManager::SimilarityGraph& pmgw, const char* out_compatibility_graph_file,
+                                             const char* out_polyline_communities) {
+  if (out_compatibility_graph_file && *out_compatibility_graph_file && pmgw.write_to_file(out_compatibility_graph_file) != EG3D_OK)
+    throw Eg3dError(EG3D_ERR_ARG, "compute_communities: cannot write the compatibility graph file");
+  const std::vector<long> ids = pmgw.communities();
+  if (out_polyline_communities && *out_polyline_communities) {
+    const std::vector<int64_t> ids64(ids.begin(), ids.end());
+    if (eg3d_host_write_communities(out_polyline_communities, ids64.data(), ids64.size()) != EG3D_OK)
+      throw Eg3dError(EG3D_ERR_ARG, "compute_communities: cannot write the communities file");
+  }
+  return ids;
 }
 
 // compute_polyline_matches_from_nodes_component_ids (polyline_matcher.cpp:202-214), the reference's signature: one set per
