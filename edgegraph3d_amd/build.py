@@ -278,9 +278,10 @@ def device_source_fingerprint(defines=()):
     """sha256 over the device CODE (sources with comments and blank lines removed) and the switches it is compiled with:
     what a PMC profile under profiles/ was measured ON. tools/profile_summary.py records it beside the traffic figures;
     bench.py reports `roofline.traffic` only while it still matches (a changed kernel makes the committed figure stale:
-    it is then reported as such, not as this run's traffic). Editing a comment does not change it. Of eg3d_api.hip (host
-    orchestration: no kernel lives there) only the preprocessor lines count — the macros that choose the kernel build,
-    its default form and the slot-pool sizing; EG3D_EXTRA_HIPFLAGS and the `defines` of the build are part of the switches."""
+    it is then reported as such, not as this run's traffic). Editing a comment does not change it. Of the eg3d_api* files
+    (eg3d_api.hip, the per-stage eg3d_api_*.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
+    the preprocessor lines count — the macros that choose the kernel build, its default form and the slot-pool sizing;
+    EG3D_EXTRA_HIPFLAGS and the `defines` of the build are part of the switches."""
     import hashlib
     import re
     h = hashlib.sha256()
@@ -289,7 +290,7 @@ def device_source_fingerprint(defines=()):
         text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)      # block comments
         text = re.sub(r"//[^\n]*", "", text)                     # line comments (no string of these sources holds "//")
         lines = [" ".join(l.split()) for l in text.splitlines() if l.strip()]
-        if os.path.basename(f) == "eg3d_api.hip":
+        if os.path.basename(f).startswith("eg3d_api"):
             lines = [l for l in lines if l.startswith("#") and not l.startswith("#include")]
         h.update(os.path.basename(f).encode())
         h.update("\n".join(lines).encode())
@@ -297,7 +298,7 @@ def device_source_fingerprint(defines=()):
     return h.hexdigest()[:16]
 
 
-# Environment switches of eg3d_api.hip's Tunables that change WHICH kernel build runs or how it is launched: with any of them
+# Environment switches of Tunables (csrc/eg3d_api_internal.h) that change WHICH kernel build runs or how it is launched: with any of them
 # set, a committed PMC profile does not describe the run (bench.py marks roofline.traffic stale).
 KERNEL_CHOICE_ENV = ("EG3D_K3B_ENGINE", "EG3D_K3B_FULL", "EG3D_K3B_ASSUME_SHORT", "EG3D_SLOTS_PER_XCD", "EG3D_MAX_SCRATCH_MB",
                      "EG3D_NO_LPT", "EG3D_K3C_WAVES", "EG3D_K3C_LANES", "EG3D_LIB")

@@ -4,6 +4,10 @@
 // two uniform grids), resident seeds, grow-only device work buffers, rocPRIM/hipCUB exclusive
 // scans between phases, HIP events for per-stage timing. No CPU fallback exists: every entry
 // point fails with EG3D_ERR_NODEVICE / EG3D_ERR_HIP when no gfx950 device is usable.
+//
+// This file: the context (create, clone, destroy), the grids, the seeds, the match pipeline, eg3d_gn_filter, the candidates,
+// the probes, and the definitions of what eg3d_api_internal.h declares — the only place that includes hipCUB. The post
+// stages' drivers are in eg3d_api_filter / _replay / _polymatch / _simgraph / _louvain.hip.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -24,318 +28,52 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/eg3d.h"
 #include "../../include/eg3d_host.h"
+#include "eg3d_api_internal.h"
 #include "eg3d_host_copy.h"
-#include "eg3d_kernels.h"
-#include "eg3d_k8_replay.h"
-#include "eg3d_k9_polymatch.h"
-#include "eg3d_k10_simgraph.h"
-#include "eg3d_k11_louvain.h"
 
-using namespace eg3d;
-
-static thread_local std::string g_err;
+thread_local std::string eg3d::api::g_err;
 extern "C" const char* eg3d_last_error(void) { return g_err.c_str(); }
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) {                                                                         \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(_e);                                    \
-      return EG3D_ERR_HIP;                                                                          \
-    }                                                                                               \
-  } while (0)
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap && p) return EG3D_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) {
-      cap = 0;
-      g_err = std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e);
-      return EG3D_ERR_HIP;
-    }
-    cap = want;
-    return EG3D_OK;
+// ---- the one place device memory is allocated and freed -------------------------------------------------------------------
+static std::atomic<int64_t> g_live_device_bytes{0};
+/* Tests only, not declared in include/eg3d.h (tests/test_gpu_buffer_ownership.py): bytes of device memory the library holds
+ * in this process, over all contexts. */
+extern "C" int64_t eg3d_test_live_device_bytes(void) { return g_live_device_bytes.load(); }
+EG3D_API_BEGIN
+int dev_alloc(void** p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    g_err = std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
+    return EG3D_ERR_HIP;
   }
-  // exactly `bytes` (no growth reserve): for a buffer whose size is fixed by the scene and may be hundreds of MB
-  int ensure_exact(size_t bytes) {
-    bytes = std::max<size_t>(bytes, 256);
-    if (p && cap == bytes) return EG3D_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      p = nullptr;
-      g_err = std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
-      return EG3D_ERR_HIP;
-    }
-    cap = bytes;
-    return EG3D_OK;
+  g_live_device_bytes += (int64_t)bytes;
+  return EG3D_OK;
+}
+void dev_free(void* p, size_t bytes) {
+  if (!p) return;
+  (void)hipFree(p);
+  g_live_device_bytes -= (int64_t)bytes;
+}
+int DevBuf::ensure_keep(size_t bytes, size_t keep, hipStream_t st) {
+  if (bytes <= cap && p) return EG3D_OK;
+  if (!p || !keep) return ensure(bytes);
+  DevBuf q;
+  q.cap = bytes + bytes / 2;
+  BUF_TRY(dev_alloc(&q.p, q.cap));
+  hipError_t e = hipMemcpyAsync(q.p, p, keep, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    q.release();
+    g_err = std::string("growing a device buffer: ") + hipGetErrorString(e);
+    return EG3D_ERR_HIP;
   }
-  // grow, keeping the first `keep` bytes (device-to-device copy on `st`, old block freed once it is done)
-  int ensure_keep(size_t bytes, size_t keep, hipStream_t st) {
-    if (bytes <= cap && p) return EG3D_OK;
-    if (!p || !keep) return ensure(bytes);
-    void* q = nullptr;
-    const size_t want = bytes + bytes / 2;
-    hipError_t e = hipMalloc(&q, want);
-    if (e != hipSuccess) {
-      g_err = std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e);
-      return EG3D_ERR_HIP;
-    }
-    e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      g_err = std::string("growing a device buffer: ") + hipGetErrorString(e);
-      return EG3D_ERR_HIP;
-    }
-    (void)hipFree(p);
-    p = q;
-    cap = want;
-    return EG3D_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-#define BUF_TRY(expr)          \
-  do {                         \
-    int _r = (expr);           \
-    if (_r != EG3D_OK) return _r; \
-  } while (0)
-
-// Device allocations shared by a context and its clones (immutable scene / resident seeds): freed
-// when the last context referring to them goes away.
-struct DevOwner {
-  int device = 0;
-  std::vector<void*> ptrs;
-  ~DevOwner() {
-    (void)hipSetDevice(device);
-    for (void* p : ptrs)
-      if (p) (void)hipFree(p);
-  }
-};
-// Host copies of the grids for eg3d_get_grid (per view CSR with view-local offsets). The grids live on the device (K0 builds
-// them there); the copies are made by the first eg3d_get_grid call that asks for a cell size — tests do, the hot path never.
-// Index 2 is the 10 px map of the polyline matcher (eg3d_match_polylines_closeness): no context has it until the first such
-// call on the context or on one of its clones builds it (ensure_grid10, under `mu`); it then belongs to this object, which
-// the context and its clones share, and goes away with the last of them.
-struct HostGrids {
-  std::mutex mu;
-  bool have[3] = {false, false, false};
-  std::vector<std::vector<uint32_t>> h_off[3], h_ids[3];
-  // where to fetch them from (device arrays of the shared, immutable scene)
-  int device = 0, n_views = 0;
-  const uint32_t* d_off[3] = {nullptr, nullptr, nullptr};
-  const uint32_t* d_ids[3] = {nullptr, nullptr, nullptr};
-  uint32_t cells_per_view[3] = {0, 0, 0};
-  bool built10 = false;
-  uint32_t w10 = 0, h10 = 0;
-  DevBuf g10o, g10i;  // the 10 px map's device arrays (d_off[2] / d_ids[2] point into them)
-  ~HostGrids() {
-    if (!g10o.p && !g10i.p) return;
-    (void)hipSetDevice(device);
-    g10o.release();
-    g10i.release();
-  }
-};
-
-// Test / tuning knobs, read from the environment ONCE when a context is created (eg3d_create; clones
-// inherit them) — the hot path never calls getenv:
-//   EG3D_K3A_ENGINE_WAVES=n  wavefronts per SIMD the K3a engine launches (default 2 = what its 256-VGPR build allows)
-//   EG3D_K3A_ENGINE_LANES=n  lanes of a K3a wavefront that take work (default: 64, fewer for small batches)
-#ifndef EG3D_K3B_ENGINE_DEFAULT
-#define EG3D_K3B_ENGINE_DEFAULT 0
-#endif
-//   EG3D_HYP_CAP=n         tests: points per following direction of the hypothesis stage (default 160; a list that would
-//                          outgrow it raises EG3D_FLAG_HYP_OVERFLOW and the call returns EG3D_ERR_CAPACITY)
-//   EG3D_SLOTS_PER_XCD=n   tests: working slices of the expand stage per XCD (default: what can be resident + margin)
-//   EG3D_TRACE_ARENA=1     print the hypothesis arena's use per batch to stderr
-//   EG3D_ARENA_CAP0=n      initial hypothesis arena capacity (tests: forces the overflow-and-retry path)
-//   EG3D_MAX_SCRATCH_MB=n  tests: cut the chains of a batch into several K3b launches of at most n MB / slice size
-//                          chains each (default: one launch takes all chains — their working slices are slots)
-//   EG3D_NO_LPT=1          launch chains in identity order instead of longest-first (diagnostic)
-//   EG3D_K3B_FULL=1        always run the general build of the expand kernel (default: the build for the scene's class —
-//                          polylines of <= 512 vertices and <= 28 views: small, >= 29 views: many views; general otherwise)
-//   EG3D_K3B_ENGINE=0|1    (builds with -DEG3D_WITH_K3C_ENGINE only: variants/libeg3d_engine.so) expand stage: 1 = the
-//                          lane-per-chain engine (k3c_engine, eg3d_k3c_engine.h), 0 = one wavefront per chain (k3b_expand).
-//                          EG3D_K3C_WAVES=n waves per SIMD of the engine's grid, EG3D_K3C_LANES=n lanes of a wave that own a
-//                          chain (default: as many waves as fit, then as few lanes as cover the chains). A library built
-//                          without the engine refuses EG3D_K3B_ENGINE=1 at eg3d_create.
-//   EG3D_PIPELINE_LANES=n  sub-batches of ONE eg3d_match_* call kept in flight on internal contexts (default 0 = by the kind of
-//                          call: 3 for a call that copies its cloud to the host, 1 for a device-only call; 1 = the call
-//                          runs as a single batch on the context's own stream). EG3D_PIPELINE_UNITS=n: sub-batches the call's
-//                          range is cut into (default: chosen from the range, see plan_seed_units). eg3d_set_pipelining
-//                          overrides both. Chosen by measurement (profiles/r06_experiments/pipelining_*.json):
-//   EG3D_UNIT_RAMP=r       unit i of a seed call gets a share ~ r^i of the range (default 0.6: the LAST unit, whose D2H copy
-//                          nothing can hide, is the smallest); EG3D_LANE_PRIORITIES=0|1: lane 0's stream high priority, lane
-//                          1 normal, the others low (default 1: the earlier units finish — and cross PCIe — first)
-//   EG3D_TEST_FAIL_UNIT=k  tests: the k-th unit (1-based) of every pipelined call fails when its turn to place comes
-struct Tunables {
-  bool grid_on_host = false;  // EG3D_GRID_ON_HOST=1 (diagnostic / A-B): build the uniform grids with the host builder on threads
-                              // (rounds 1-5, and round 6 before K0) instead of on the device
-  int lanes = 0, units = 0, test_fail_unit = 0;
-  int copy_threads = 0;  // EG3D_COPY_THREADS_PER_LANE: host threads that copy one piece of a cloud from the ring to the caller's
-                         // arrays (0 = EG3D_COPY_THREADS shared by the lanes of the call: 16 on one lane, 5 each on three)
-  double unit_ramp = 0.6;
-  int lane_priorities = 1;
-  static constexpr int kHostCallLanes = 3;  // lanes = 0: a host call's default
-  int k3a_engine_waves = 0, k3a_engine_lanes = 0;
-  int k3b_engine = EG3D_K3B_ENGINE_DEFAULT, k3c_waves = 0, k3c_lanes = 0;
-  bool assume_short = false;  // EG3D_K3B_ASSUME_SHORT=1 (tests): start with the few-views builds whatever the view count, so that
-                              // the CTR_LONG_REFUSED -> general build retry runs
-  bool trace_arena = false;
-  bool k3b_full = false;  // EG3D_K3B_FULL=1: always the full expand kernel (diagnostic)
-  uint32_t arena_cap0 = 0, hyp_cap = 0;
-  uint32_t chain_cap0 = 0, pool_cap0 = 0;  // EG3D_CHAIN_CAP0 / EG3D_POOL_CAP0 (tests): initial points / observation slots per chain,
-                                           // small enough to force the relaunch-what-overflowed path several times
-  size_t max_scratch = 0;  // 0 = no limit
-  uint32_t slots_per_xcd = 0;  // 0 = sized from the occupancy query
-  bool use_lpt = true;
-  static Tunables from_env() {
-    Tunables t;
-    if (const char* e = getenv("EG3D_K3A_ENGINE_WAVES")) t.k3a_engine_waves = atoi(e);
-    if (const char* e = getenv("EG3D_K3A_ENGINE_LANES")) t.k3a_engine_lanes = atoi(e);
-    if (const char* e = getenv("EG3D_K3B_ENGINE")) t.k3b_engine = atoi(e);
-    if (const char* e = getenv("EG3D_K3C_WAVES")) t.k3c_waves = atoi(e);
-    if (const char* e = getenv("EG3D_K3C_LANES")) t.k3c_lanes = atoi(e);
-    if (const char* e = getenv("EG3D_K3B_ASSUME_SHORT")) t.assume_short = e[0] == '1';
-    if (const char* e = getenv("EG3D_HYP_CAP")) t.hyp_cap = (uint32_t)std::max(1, atoi(e));
-    if (const char* e = getenv("EG3D_ARENA_CAP0")) t.arena_cap0 = (uint32_t)std::max(16, atoi(e));
-    if (const char* e = getenv("EG3D_CHAIN_CAP0")) t.chain_cap0 = (uint32_t)std::max(8, atoi(e));
-    if (const char* e = getenv("EG3D_POOL_CAP0")) t.pool_cap0 = (uint32_t)std::max(64, atoi(e));
-    if (const char* e = getenv("EG3D_MAX_SCRATCH_MB")) t.max_scratch = (size_t)std::max(1, atoi(e)) << 20;
-    if (const char* e = getenv("EG3D_NO_LPT")) t.use_lpt = !(e[0] == '1');
-    if (const char* e = getenv("EG3D_TRACE_ARENA")) t.trace_arena = e[0] == '1';
-    if (const char* e = getenv("EG3D_K3B_FULL")) t.k3b_full = e[0] == '1';
-    if (const char* e = getenv("EG3D_SLOTS_PER_XCD")) t.slots_per_xcd = (uint32_t)std::max(1, atoi(e));
-    if (const char* e = getenv("EG3D_PIPELINE_LANES")) t.lanes = std::min(16, std::max(0, atoi(e)));
-    if (const char* e = getenv("EG3D_TEST_FAIL_UNIT")) t.test_fail_unit = atoi(e);
-    if (const char* e = getenv("EG3D_GRID_ON_HOST")) t.grid_on_host = e[0] == '1';
-    if (const char* e = getenv("EG3D_COPY_THREADS_PER_LANE")) t.copy_threads = std::min(32, std::max(1, atoi(e)));
-    if (const char* e = getenv("EG3D_LANE_PRIORITIES")) t.lane_priorities = atoi(e);
-    if (const char* e = getenv("EG3D_UNIT_RAMP")) t.unit_ramp = std::min(16.0, std::max(1.0 / 16.0, atof(e)));
-    if (const char* e = getenv("EG3D_PIPELINE_UNITS")) t.units = std::min(4096, std::max(0, atoi(e)));
-    return t;
-  }
-};
-
-// the device buffers of eg3d_detect_communities (eg3d_ctx::k11)
-enum K11Buf { K11B_OFF0, K11B_OFF1, K11B_NBR0, K11B_NBR1, K11B_EROW0, K11B_EROW1, K11B_Q0, K11B_Q1, K11B_W, K11B_K, K11B_C, K11B_T,
-              K11B_A0, K11B_A1, K11B_SIZE0, K11B_SIZE1, K11B_MEMBER, K11B_MINM, K11B_FLAG, K11B_RANK, K11B_CN, K11B_OVF, K11B_OCNT,
-              K11B_OOFF, K11B_KEY0, K11B_KEY1, K11B_VAL0, K11B_VAL1, K11B_IDS, K11B_CTR, K11B_COUNT };
-
-struct eg3d_ctx {
-  int device = 0;
-  Tunables tune;
-  hipStream_t stream = nullptr;
-  int V = 0, W = 0, H = 0;
-  DevScene ds;
-  DevBuf b_camP, b_F, b_Fv, b_vpo, b_pvo, b_vtx, b_pls, b_ple, b_g30o, b_g30i, b_g4o, b_g4i, b_bbo, b_bb;
-  std::shared_ptr<DevOwner> scene_owner;  // owns b_camP .. b_g4i
-  // host copies of the grids for eg3d_get_grid (per view CSR with view-local offsets)
-  std::shared_ptr<HostGrids> hg;
-  uint32_t gw[2] = {0, 0}, gh[2] = {0, 0};
-  uint32_t grid_dropped = 0;
-  // resident seeds
-  uint32_t n_seeds = 0;
-  std::shared_ptr<std::vector<uint32_t>> h_trk;
-  DevBuf b_toff, b_tview, b_txy;
-  std::shared_ptr<DevOwner> seeds_owner;  // owns b_toff, b_tview, b_txy
-  // work buffers
-  DevBuf b_sv_seed, b_map_view, b_map_entry, b_map_n, b_raw_cnt, b_raw_off, b_cand_pl, b_start_hits, b_cand_cnt,
-      b_start_cnt, b_task_off, b_task_seed, b_task_entry, b_task_hit, b_task_k, b_task_list_off, b_list_cnt, b_list_ptr,
-      b_hits, b_tasks, b_nhyp, b_hyp_off, b_res, b_arena, b_ctr, b_cs_task, b_valid, b_chain_off, b_chains,
-      b_cscratch, b_couts, b_cpts, b_cobs, b_cpoff, b_cooff, b_scan_tmp, b_scanchk, b_cost, b_cidx, b_cost2, b_order, b_redo[2];
-  DevBuf o_X, o_off, o_view, o_pl, o_seg, o_xy, o_key;
-  DevBuf f_X, f_off, f_view, f_xy, f_Xo, f_inl;
-  // eg3d_gn_filter_device / eg3d_compact_device / eg3d_filter_resident: histogram + flag word, block totals of the
-  // compaction, the compacted cloud (valid until the next compaction), X_out / inlier of eg3d_filter_resident
-  DevBuf r_hist, r_blk, r_Xo, r_inl, c_X, c_off, c_view, c_pl, c_seg, c_xy, c_key;
-  bool compact_nt = false;  // EG3D_COMPACT_NT=1 (read by eg3d_create): non-temporal loads of the compaction's source
-  // eg3d_dedup_device / eg3d_dedup_resident: the claim map (this context's own; created on first use), the kept count +
-  // flag word, the mask of eg3d_dedup_resident
-  DevBuf d_first, d_cnt, d_keep;
-  bool dedup_valid = false;   // the claim map holds the claims of the earlier calls (false: it is filled before use)
-  // eg3d_replay_device (K8). Work: counters + flag word, the node table (slot / last), per point the first point of its
-  // node, flags, their scans, the last point of a node, the sort buffers, rocPRIM's scratch, the interval claim map over
-  // the scene's segments with its flags and scan. Result (valid until the next replay): the arrays of eg3d_graph3d.
-  DevBuf k8_cnt, k8_slot, k8_last, k8_firstof, k8_flag, k8_rank, k8_lastof, k8_plid, k8_key[2], k8_val[2], k8_tmp, k8_map,
-      k8_sflag, k8_pos;
-  DevBuf g_nodeX, g_nodept, g_pls, g_ple, g_conoff, g_conpl, g_ivoff, g_ivss, g_ivsxy, g_ives, g_ivexy;
-  // eg3d_match_polylines_closeness (K9). Work: entry -> seed, the per-entry search results, the accept flags and their scan,
-  // the match graph over the scene's polylines, the sort buffers, counters + flag word. Result on the device: the accepted
-  // ids, row_off, pl_ids (copied to the caller's library-owned arrays at the end of the call).
-  DevBuf k9_svseed, k9_cnt, k9_pl, k9_dist, k9_acc, k9_accoff, k9_first, k9_parent, k9_root, k9_ckey, k9_rank, k9_key[2], k9_ctr,
-      k9_ref, k9_rowoff, k9_plids;
-  // eg3d_similarity_graph (K10). Work: entry -> seed, the per-entry counts and their scan, the (point, polyline) pairs and
-  // their swapped form (two sort buffers each way), the CSRs and columns of close_polylines / close_refpoints, the weights,
-  // the visibility rows, the pair counts and their 64-bit scan, the node tables, the edge keys (k10_edge: the unique list
-  // with the current chunk behind it, and the sort's output), the directed keys and weights, counters + flag word.
-  DevBuf k10_svseed, k10_cnt, k10_off, k10_pair[2], k10_crkey, k10_cpoff, k10_cpview, k10_cppl, k10_croff, k10_crpoint, k10_weight, k10_vis,
-      k10_npairs, k10_pairoff, k10_nkey[2], k10_nodeof, k10_nodeg, k10_nodeview, k10_nodepl, k10_edge[2], k10_dkey[2], k10_dval[2],
-      k10_adjoff, k10_adjnode, k10_ctr;
-  // eg3d_detect_communities (K11): the graph of the current and of the next phase, the partition and its totals, the
-  // renumbering, the overflow rows, two (key, value) sort buffers, the ids, the counters (K11Buf names them).
-  DevBuf k11[K11B_COUNT];
-  uint32_t louvain_log2_slots = 0;  // EG3D_LOUVAIN_TABLE_SLOTS (read by eg3d_create; tests): slots of the sweep's per-wave LDS
-                                    // table, raised to a power of two in 16 .. 1024; 0 = K11_DEFAULT_SLOTS
-  uint64_t simgraph_pair_budget = 0;  // EG3D_SIMGRAPH_PAIR_BUDGET (read by eg3d_create; tests): edge keys one chunk of the clique
-                                      // expansion may write; 0 = EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
-  int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (read by eg3d_create; tests): a node table of 2^bits slots, raised to the
-                              // smallest power of two above the number of lookups; 0 = the default, about twice that
-  uint32_t n_pl = 0, n_vtx = 0;  // polylines and vertices of the scene as uploaded
-  DevBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
-  DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
-  // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
-  // and the staging area finished chains are packed into (sized from the previous launches; grow-only)
-  DevBuf b_pools, b_stage_pts, b_stage_obs, b_stage_used;
-  uint32_t slots_per_xcd = 0;
-  int k3c_per_cu = 0;            // resident blocks per CU of the lane-per-chain engine (occupancy query)
-  bool k3b_long_latched = false; // a launch of a few-views build met a solve of > 32 rows: the context runs the general builds from then on
-  uint32_t max_pl_vtx = 0;  // vertices of the scene's longest valid polyline
-  uint64_t stage_cap_pts = 0, stage_cap_obs = 0;
-  hipEvent_t ea[8], eb[8];  // begin/end events per stage: 1 K1, 2 K2, 3 K3a, 4 K3s, 5 K3b, 6 K4, 0 misc, 7 whole call
-  hipEvent_t ecopy[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // D2H of the cloud: one per ring buffer (EG3D_D2H_RING <= 7)
-  uint32_t chain_cap = 384, pool_cap = 0, hyp_cap = 160;
-  uint32_t n_simd = 0;  // SIMDs of the device (4 per CU): sizes the K3a engine's launch
-  int wall_clock_khz = 0;  // rate of wall_clock64() on the device (hipDeviceAttributeWallClockRate)
-  double arena_per_hyp = 16.0;  // hypothesis arena: points per hypothesis to reserve (learned from overflows)
-  void* pinned = nullptr;  // the ring of pinned host buffers the D2H copies of a cloud go through (ensure_d2h_ring)
-  size_t pinned_cap = 0, ring_chunk = 0;
-  // mailbox for the small read-backs of a step (scan totals, counters): pinned host memory mapped into the
-  // GPU's address space, written by k_publish, polled by the calling thread (no driver round trip)
-  uint32_t* mbox = nullptr;
-  uint32_t* mbox_dev = nullptr;
-  uint32_t mbox_seq = 0;
-  uint64_t last_np = 0, last_no = 0;
-  int last_chunks = 0;
-  bool last_accumulated = false;  // the output buffers hold the whole cloud of the last call (device-only calls)
-  uint32_t last_nc = 0;
-  uint32_t last_nhyp = 0;
-  // Internal pipelining of ONE call (run_pipelined): lane 0 is this context, lanes 1.. are clones created on first use
-  // (own stream / work buffers, shared scene and seeds). A lane is never handed to the caller.
-  std::vector<eg3d_ctx*> lanes;
-  bool is_lane = false;
-  uint32_t host_calls = 0;  // eg3d_match_* calls with device_only == 0 this context has completed (lanes_for)
-  uint64_t last_host_cloud_bytes = 0;  // ... and the size of the last one's cloud
-};
+  release();
+  *this = q;
+  return EG3D_OK;
+}
+EG3D_API_END
 
 // D2H ring of a context: EG3D_D2H_RING pinned buffers of `ring_chunk` bytes (run_stage_b) — 16 MB each for a cloud worth it,
 // 2 MB each for small ones (pinning memory costs ~0.2 ms per MB: the big ring is a fifth of a small scene's whole call).
@@ -362,14 +100,14 @@ static int ensure_d2h_ring(eg3d_ctx* c, size_t cloud_bytes) {
   return EG3D_OK;
 }
 
-template <typename T>
-static int upload(DevBuf& b, const T* src, size_t n, hipStream_t st) {
+template <typename Buf, typename T>
+static int upload(Buf& b, const T* src, size_t n, hipStream_t st) {
   BUF_TRY(b.ensure(sizeof(T) * std::max<size_t>(n, 1)));
   if (n) HIP_TRY(hipMemcpyAsync(b.p, src, sizeof(T) * n, hipMemcpyHostToDevice, st));
   return EG3D_OK;
 }
 
-static int scan_exclusive_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one) {
+int eg3d::api::scan_exclusive_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one) {
   // in[n] must be 0 (or ignored): out[n] = total
   size_t tmp_bytes = 0;
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, in, out, (int)n_plus_one, c->stream));
@@ -377,10 +115,11 @@ static int scan_exclusive_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, si
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->b_scan_tmp.p, tmp_bytes, in, out, (int)n_plus_one, c->stream));
   return EG3D_OK;
 }
+EG3D_API_BEGIN
 // ---- small read-backs through the mailbox ----------------------------------------------------------
 // b_scanchk: [0..3] "scan wrapped" flag words (ORed by k_scan_check, cleared by k_publish), [4..5] a saved
 // 64-bit counter.
-static int ensure_mailbox(eg3d_ctx* c) {
+int ensure_mailbox(eg3d_ctx* c) {
   if (!c->mbox) {
     void* h = nullptr;
     HIP_TRY(hipHostMalloc(&h, sizeof(uint32_t) * EG3D_MBOX_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
@@ -400,64 +139,44 @@ static int ensure_mailbox(eg3d_ctx* c) {
   }
   return EG3D_OK;
 }
-struct Readback {
-  eg3d_ctx* c;
-  PubArgs a{};
-  uint32_t off[6] = {0, 0, 0, 0, 0, 0};
-  uint32_t used = 2;
-  explicit Readback(eg3d_ctx* c_) : c(c_) {}
-  int add(const void* dev, uint32_t words) {  // returns the item's index
-    const int i = a.n++;
-    a.src[i] = (const uint32_t*)dev;
-    a.words[i] = words;
-    off[i] = used;
-    used += words;
-    return i;
+int Readback::run() {
+  if (a.n > 6 || a.n_clear > 3 || used > EG3D_MBOX_WORDS) {
+    g_err = "eg3d: internal: read-back too large";
+    return EG3D_ERR_ARG;
   }
-  void clear_after(uint32_t* dev) { a.clear[a.n_clear++] = dev; }
-  const uint32_t* item(int i) const { return c->mbox + off[i]; }
-  // Launch the publish kernel behind everything queued on the stream and wait for its data: a short poll of
-  // the mailbox (the common case: the GPU is a few microseconds behind), then a blocking wait for long kernels.
-  int run() {
-    if (a.n > 6 || a.n_clear > 3 || used > EG3D_MBOX_WORDS) {
-      g_err = "eg3d: internal: read-back too large";
-      return EG3D_ERR_ARG;
-    }
-    const uint32_t seq = ++c->mbox_seq;
-    launch_publish(c->stream, a, c->mbox_dev, seq);
-    HIP_TRY(hipGetLastError());
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spin = 0;; spin++) {
-      if (__atomic_load_n(c->mbox, __ATOMIC_ACQUIRE) == seq) return EG3D_OK;
-      __builtin_ia32_pause();
-      if ((spin & 255u) == 255u &&
-          std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1500))
-        break;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (__atomic_load_n(c->mbox, __ATOMIC_ACQUIRE) != seq) {
-      g_err = "eg3d: the read-back mailbox was not written";
-      return EG3D_ERR_HIP;
-    }
-    return EG3D_OK;
+  const uint32_t seq = ++c->mbox_seq;
+  launch_publish(c->stream, a, c->mbox_dev, seq);
+  HIP_TRY(hipGetLastError());
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t spin = 0;; spin++) {
+    if (__atomic_load_n(c->mbox, __ATOMIC_ACQUIRE) == seq) return EG3D_OK;
+    __builtin_ia32_pause();
+    if ((spin & 255u) == 255u &&
+        std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1500))
+      break;
   }
-};
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (__atomic_load_n(c->mbox, __ATOMIC_ACQUIRE) != seq) {
+    g_err = "eg3d: the read-back mailbox was not written";
+    return EG3D_ERR_HIP;
+  }
+  return EG3D_OK;
+}
 // Exclusive scan queued on the stream, its wrap check ORed into flag word `slot`; the total is out[n].
-static int scan_queue_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one, int slot) {
+int scan_queue_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one, int slot) {
   BUF_TRY(ensure_mailbox(c));
   BUF_TRY(scan_exclusive_u32(c, in, out, n_plus_one));
   launch_scan_check(c->stream, out, n_plus_one, c->b_scanchk.as<uint32_t>() + slot);
   return EG3D_OK;
 }
-static int wrapped_error(const char* what) {
+int wrapped_error(const char* what) {
   g_err = std::string("eg3d: the number of ") + what + " of this batch exceeds 2^32-1; use smaller seed / set ranges";
   return EG3D_ERR_CAPACITY;
 }
 // Exclusive scan + its total on the host, with overflow detection: phase totals (candidate slots,
 // tasks, lists, hits, hypotheses) are 32-bit; a batch whose total does not fit is refused with
 // EG3D_ERR_CAPACITY instead of sizing buffers from a wrapped number.
-static int scan_total_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one, uint32_t& total,
-                          const char* what) {
+int scan_total_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one, uint32_t& total, const char* what) {
   BUF_TRY(scan_queue_u32(c, in, out, n_plus_one, 0));
   Readback rb(c);
   const int it = rb.add(out + (n_plus_one - 1), 1);
@@ -468,17 +187,16 @@ static int scan_total_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t
   total = *rb.item(it);
   return EG3D_OK;
 }
+EG3D_API_END
 
 // K0: one uniform grid of the scene on the device (the scene's polylines are already resident: c->ds): count the (cell,
 // polyline) pairs of every polyline, exclusive scan, write them as 64-bit keys, radix sort, unique, CSR. The temporaries (24 B
 // per pair) belong to the caller, which frees them once the stream has drained.
 struct GridTemps {
-  DevBuf cnt, off, keys, keys2, n;  // n: [0] unique keys, [1] samples outside the image (summed over the builds)
-  ~GridTemps() {
-    for (DevBuf* x : {&cnt, &off, &keys, &keys2, &n}) x->release();
-  }
+  WorkBuf cnt, off, keys, keys2, n;  // n: [0] unique keys, [1] samples outside the image (summed over the builds)
 };
-static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t, DevBuf& g_off, DevBuf& g_ids, uint32_t* out_w,
+template <typename Buf>  // (the 30 px and 4 px grids are scene handles, the 10 px map belongs to HostGrids)
+static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t, Buf& g_off, Buf& g_ids, uint32_t* out_w,
                              uint32_t* out_h, uint32_t* dropped) {
   hipStream_t st = c->stream;
   const int V = c->V;
@@ -529,7 +247,7 @@ static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t,
     }
     BUF_TRY(g_ids.ensure(sizeof(uint32_t) * std::max<size_t>(n_unique, 1)));
     if (n_unique)
-      launch_k0_csr(st, t.keys.as<unsigned long long>(), n_unique, (uint32_t)total_cells, g_off.as<uint32_t>(), g_ids.as<uint32_t>());
+      launch_k0_csr(st, t.keys.as<unsigned long long>(), n_unique, (uint32_t)total_cells, (uint32_t*)g_off.p, (uint32_t*)g_ids.p);
     else
       HIP_TRY(hipMemsetAsync(g_off.p, 0, sizeof(uint32_t) * ((size_t)total_cells + 1), st));
   }
@@ -549,9 +267,7 @@ static int build_grids_device(eg3d_ctx* c, uint32_t NP) {
   HIP_TRY(hipStreamSynchronize(c->stream));  // the temporaries go away
   return EG3D_OK;
 }
-// The 10 px map of the polyline matcher, built by the first call that needs it on this context or a clone of it and shared
-// by all of them from then on (HostGrids). eg3d_create neither builds nor allocates it.
-static int ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms) {
+int eg3d::api::ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms) {
   HostGrids& hg = *c->hg;
   std::lock_guard<std::mutex> lk(hg.mu);
   if (!hg.built10) {
@@ -559,8 +275,8 @@ static int ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms) {
     // (the build runs on the calling context's stream and scratch; `mu` only keeps a second context of the family from
     // building the same map at the same time)
     GridTemps t;
-    DevBuf& g_off = hg.g10o;
-    DevBuf& g_ids = hg.g10i;
+    WorkBuf& g_off = hg.g10o;
+    WorkBuf& g_ids = hg.g10i;
     uint32_t dropped = 0;
     int rc = build_grid_device(c, c->n_pl, 10.0f, t, g_off, g_ids, &hg.w10, &hg.h10, &dropped);
     if (rc == EG3D_OK && hipStreamSynchronize(c->stream) != hipSuccess) {
@@ -973,7 +689,7 @@ extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
   // from here on the scene buffers belong to the (shareable) owner, not to this context
   c->scene_owner = std::make_shared<DevOwner>();
   c->scene_owner->device = device;
-  for (DevBuf* b : scene_bufs(c)) c->scene_owner->ptrs.push_back(b->p);
+  for (DevBuf* b : scene_bufs(c)) c->scene_owner->bufs.push_back(*b);
   *out = c;
   return EG3D_OK;
 }
@@ -1049,28 +765,6 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
     for (DevBuf* b : scene_bufs(c)) b->release();
   c->scene_owner.reset();
   c->seeds_owner.reset();
-  DevBuf* all[] = {&c->b_sv_seed, &c->b_map_view,
-                   &c->b_map_entry, &c->b_map_n, &c->b_raw_cnt, &c->b_raw_off, &c->b_cand_pl, &c->b_start_hits,
-                   &c->b_cand_cnt, &c->b_start_cnt, &c->b_task_off, &c->b_task_seed, &c->b_task_entry, &c->b_task_hit,
-                   &c->b_task_k, &c->b_task_list_off, &c->b_list_cnt, &c->b_list_ptr, &c->b_hits, &c->b_tasks,
-                   &c->b_nhyp, &c->b_hyp_off, &c->b_res, &c->b_arena, &c->b_ctr, &c->b_cs_task,
-                   &c->b_valid, &c->b_chain_off, &c->b_chains, &c->b_cscratch, &c->b_couts, &c->b_cpts, &c->b_cobs,
-                   &c->b_cpoff, &c->b_cooff, &c->b_scan_tmp, &c->b_scanchk, &c->b_cost, &c->b_cidx, &c->b_cost2, &c->b_order, &c->b_redo[0], &c->b_redo[1], &c->o_X, &c->o_off, &c->o_view, &c->o_pl, &c->o_seg,
-                   &c->o_xy, &c->o_key, &c->f_X, &c->f_off, &c->f_view, &c->f_xy, &c->f_Xo, &c->f_inl, &c->r_hist, &c->r_blk, &c->r_Xo, &c->r_inl, &c->c_X, &c->c_off, &c->c_view, &c->c_pl, &c->c_seg, &c->c_xy, &c->c_key, &c->d_first, &c->d_cnt, &c->d_keep,
-                   &c->k8_cnt, &c->k8_slot, &c->k8_last, &c->k8_firstof, &c->k8_flag, &c->k8_rank, &c->k8_lastof, &c->k8_plid,
-                   &c->k8_key[0], &c->k8_key[1], &c->k8_val[0], &c->k8_val[1], &c->k8_tmp, &c->k8_map, &c->k8_sflag, &c->k8_pos,
-                   &c->g_nodeX, &c->g_nodept, &c->g_pls, &c->g_ple, &c->g_conoff, &c->g_conpl, &c->g_ivoff, &c->g_ivss,
-                   &c->g_ivsxy, &c->g_ives, &c->g_ivexy, &c->k9_svseed, &c->k9_cnt, &c->k9_pl, &c->k9_dist, &c->k9_acc, &c->k9_accoff,
-                   &c->k9_first, &c->k9_parent, &c->k9_root, &c->k9_ckey, &c->k9_rank, &c->k9_key[0], &c->k9_key[1], &c->k9_ctr,
-                   &c->k9_ref, &c->k9_rowoff, &c->k9_plids,
-                   &c->k10_svseed, &c->k10_cnt, &c->k10_off, &c->k10_pair[0], &c->k10_pair[1], &c->k10_crkey, &c->k10_cpoff, &c->k10_cpview, &c->k10_cppl,
-                   &c->k10_croff, &c->k10_crpoint, &c->k10_weight, &c->k10_vis, &c->k10_npairs, &c->k10_pairoff, &c->k10_nkey[0],
-                   &c->k10_nkey[1], &c->k10_nodeof, &c->k10_nodeg, &c->k10_nodeview, &c->k10_nodepl, &c->k10_edge[0], &c->k10_edge[1],
-                   &c->k10_dkey[0], &c->k10_dkey[1], &c->k10_dval[0], &c->k10_dval[1], &c->k10_adjoff, &c->k10_adjnode, &c->k10_ctr,
-                   &c->b_sets_off, &c->b_sets_ids, &c->b_fscratch, &c->b_queue, &c->b_items,
-                   &c->b_pools, &c->b_stage_pts, &c->b_stage_obs, &c->b_stage_used};
-  for (DevBuf* b : all) b->release();
-  for (DevBuf& b : c->k11) b.release();
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->mbox) (void)hipHostFree(c->mbox);
   for (int i = 0; i < 8; i++) {
@@ -1080,7 +774,7 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
   for (int i = 0; i < 7; i++)
     if (c->ecopy[i]) (void)hipEventDestroy(c->ecopy[i]);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (the work buffers release themselves: nothing is queued on the stream any more)
 }
 
 extern "C" int eg3d_get_grid(eg3d_ctx* c, int view, int which, uint32_t* ncols, uint32_t* nrows,
@@ -1149,16 +843,14 @@ extern "C" int eg3d_upload_seeds(eg3d_ctx* c, const eg3d_seeds* s) {
     }
   // fresh buffers: the previous ones may still be in use by clones of this context
   c->seeds_owner.reset();
-  c->b_toff = DevBuf();
-  c->b_tview = DevBuf();
-  c->b_txy = DevBuf();
+  c->b_toff = c->b_tview = c->b_txy = DevBuf();
   c->n_seeds = 0;
   auto owner = std::make_shared<DevOwner>();
   owner->device = c->device;
   int rc = upload(c->b_toff, s->trk_off, n + 1, c->stream);
   if (rc == EG3D_OK) rc = upload(c->b_tview, s->trk_view, m, c->stream);
   if (rc == EG3D_OK) rc = upload(c->b_txy, s->trk_xy, (size_t)m * 2, c->stream);
-  owner->ptrs = {c->b_toff.p, c->b_tview.p, c->b_txy.p};
+  owner->bufs = {c->b_toff, c->b_tview, c->b_txy};
   if (rc != EG3D_OK) {
     c->b_toff = c->b_tview = c->b_txy = DevBuf();
     return rc;
@@ -1185,9 +877,7 @@ int run_stage_a(eg3d_ctx* c, BatchState& B, eg3d_stage_times* tm) {
   B.n_seeds = B.e - B.b;
   B.sv_base = (*c->h_trk)[B.b];
   B.n_sv = (*c->h_trk)[B.e] - B.sv_base;
-  B.sd.trk_off = c->b_toff.as<uint32_t>();
-  B.sd.trk_view = c->b_tview.as<int32_t>();
-  B.sd.trk_xy = c->b_txy.as<float>();
+  B.sd = seeds_dev(c);
   const uint32_t n_sv = B.n_sv;
   BUF_TRY(c->b_sv_seed.ensure(sizeof(uint32_t) * (n_sv + 1)));
   BUF_TRY(c->b_map_view.ensure(sizeof(int32_t) * (n_sv + 1)));
@@ -2633,10 +2323,10 @@ extern "C" int eg3d_context_info(eg3d_ctx* c, int32_t* n_views, int32_t* device)
   if (device) *device = c->device;
   return EG3D_OK;
 }
-static CloudView cloud_view(const eg3d_device_edgepoints* d) {
+CloudView eg3d::api::cloud_view(const eg3d_device_edgepoints* d) {
   return CloudView{d->n_points, d->n_obs, d->X, d->obs_off, d->obs_view, d->obs_pl, d->obs_seg, d->obs_xy, d->key};
 }
-static int check_cloud(const eg3d_device_edgepoints* d, const char* who, bool all_arrays) {
+int eg3d::api::check_cloud(const eg3d_device_edgepoints* d, const char* who, bool all_arrays) {
   const bool pts = !d->n_points || (d->X && d->obs_off && (!all_arrays || d->key));
   const bool obs = !d->n_obs || (d->obs_view && d->obs_xy && (!all_arrays || (d->obs_pl && d->obs_seg)));
   if (!pts || !obs || (d->n_obs && !d->n_points)) {
@@ -2649,1405 +2339,85 @@ static int check_cloud(const eg3d_device_edgepoints* d, const char* who, bool al
   }
   return EG3D_OK;
 }
-static int device_flags_error(const char* who, uint32_t flags) {
+int eg3d::api::device_flags_error(const char* who, uint32_t flags) {
   if (flags & K5_FLAG_BAD_VIEW)
     g_err = std::string(who) + ": view id out of range";
   else
     g_err = std::string(who) + ": obs_off is not ascending within [0, n_obs], or a list holds more than 2^24 observations";
   return EG3D_ERR_ARG;
 }
-// hist_all: [V + 2] (bin k for k <= V, bin V + 1 for longer lists)
-static int gn_filter_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, const uint8_t* keep_dev, float gn_max_mse,
-                                 int legacy_abs, float* X_out_dev, uint8_t* inlier_dev, std::vector<uint64_t>& hist_all,
-                                 float* ms_kernel) {
-  const size_t bins = (size_t)c->V + 2;
-  hist_all.assign(bins, 0);
-  hipStream_t st = c->stream;
-  BUF_TRY(c->r_hist.ensure(8 * bins + 8));
-  HIP_TRY(hipMemsetAsync(c->r_hist.p, 0, 8 * bins + 8, st));
-  K5Dev ext{keep_dev, d->n_obs, c->r_hist.as<unsigned long long>(), (uint32_t*)(c->r_hist.as<unsigned long long>() + bins)};
-  HIP_TRY(hipEventRecord(c->ea[0], st));
-  launch_k5_device(st, c->ds.cam_P, c->V, d->X, d->obs_off, d->obs_view, d->obs_xy, d->n_points, gn_max_mse, legacy_abs, X_out_dev,
-                   inlier_dev, ext);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->eb[0], st));
-  std::vector<uint64_t> back(bins + 1);
-  HIP_TRY(hipMemcpyAsync(back.data(), c->r_hist.p, 8 * bins + 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (ms_kernel) HIP_TRY(hipEventElapsedTime(ms_kernel, c->ea[0], c->eb[0]));
-  const uint32_t flags = (uint32_t)back[bins];
-  if (flags) return device_flags_error("eg3d_gn_filter_device", flags);
-  std::copy(back.begin(), back.begin() + bins, hist_all.begin());
-  return EG3D_OK;
+
+// ---- eg3d_api_internal.h: one copy of each idiom of the post stages -------------------------------------------------------
+EG3D_API_BEGIN
+int check_struct_size(const char* who, const char* type_name, size_t got, size_t want, const char* arg) {
+  if (got >= want) return EG3D_OK;
+  g_err = std::string(who) + ": " + arg + "->struct_size is smaller than this library's " + type_name + " (" + std::to_string(want) +
+          " bytes): set it to sizeof(" + type_name + ")";
+  return EG3D_ERR_ARG;
 }
 
-extern "C" int eg3d_gn_filter_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, const uint8_t* keep_dev, float gn_max_mse,
-                                     int legacy_abs, float* X_out_dev, uint8_t* inlier_dev, uint64_t* obs_hist_host,
-                                     uint64_t* n_inliers_host, float* ms_kernel) {
-  if (!c || !cloud || (cloud->n_points && (!X_out_dev || !inlier_dev))) {
-    g_err = "eg3d_gn_filter_device: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  BUF_TRY(check_cloud(cloud, "eg3d_gn_filter_device", false));
-  HIP_TRY(hipSetDevice(c->device));
-  std::vector<uint64_t> hist;
-  if (ms_kernel) *ms_kernel = 0;
-  BUF_TRY(gn_filter_device_impl(c, cloud, keep_dev, gn_max_mse, legacy_abs, X_out_dev, inlier_dev, hist, ms_kernel));
-  if (obs_hist_host) std::copy(hist.begin(), hist.begin() + c->V + 1, obs_hist_host);
-  if (n_inliers_host) {
-    *n_inliers_host = 0;
-    for (uint64_t h : hist) *n_inliers_host += h;  // (the last bin: lists longer than the rig has views)
-  }
-  return EG3D_OK;
-}
-
-static int compact_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, const uint8_t* keep_dev, const float* X_new_dev,
-                               int32_t min_obs, eg3d_device_edgepoints* out, float* ms) {
-  const void* mine[] = {c->c_X.p, c->c_off.p, c->c_view.p, c->c_pl.p, c->c_seg.p, c->c_xy.p, c->c_key.p};
-  const void* theirs[] = {d->X, d->obs_off, d->obs_view, d->obs_pl, d->obs_seg, d->obs_xy, d->key, X_new_dev};
-  for (const void* a : mine)
-    for (const void* b : theirs)
-      if (a && a == b) {
-        g_err = "eg3d_compact_device: the input views this context's compaction buffers, which the call overwrites";
-        return EG3D_ERR_ARG;
-      }
-  hipStream_t st = c->stream;
-  const CloudView in = cloud_view(d);
-  const uint64_t nb = (d->n_points + K6_BLOCK - 1) / K6_BLOCK;
-  BUF_TRY(c->r_blk.ensure(16 * (nb + 1) + 8));
-  unsigned long long* blk = c->r_blk.as<unsigned long long>();
-  uint32_t* flags = (uint32_t*)(blk + 2 * (nb + 1));
-  HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
-  HIP_TRY(hipEventRecord(c->ea[0], st));
-  launch_compact_count(st, in, keep_dev, min_obs, blk, flags);
-  launch_compact_scan(st, nb, blk);
-  HIP_TRY(hipGetLastError());
-  uint64_t back[3];  // surviving points, surviving observations, flags
-  HIP_TRY(hipMemcpyAsync(back, blk + 2 * nb, sizeof(back), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if ((uint32_t)back[2]) return device_flags_error("eg3d_compact_device", (uint32_t)back[2]);
-  const uint64_t np = back[0], no = back[1];
-  BUF_TRY(c->c_X.ensure(12 * np));
-  BUF_TRY(c->c_off.ensure(8 * np));
-  BUF_TRY(c->c_key.ensure(16 * np));
-  BUF_TRY(c->c_view.ensure(4 * no));
-  BUF_TRY(c->c_pl.ensure(4 * no));
-  BUF_TRY(c->c_seg.ensure(4 * no));
-  BUF_TRY(c->c_xy.ensure(8 * no));
-  CloudOut o{c->c_X.as<float>(), c->c_off.as<eg3d_off_t>(), c->c_view.as<int32_t>(), c->c_pl.as<uint32_t>(),
-             c->c_seg.as<uint32_t>(), c->c_xy.as<float>(), c->c_key.as<uint32_t>()};
-  launch_compact_scatter(st, in, keep_dev, X_new_dev, min_obs, blk, o, c->compact_nt);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->eb[0], st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ea[0], c->eb[0]));
-  out->n_points = np;
-  out->n_obs = no;
-  out->X = o.X;
-  out->obs_off = o.obs_off;
-  out->obs_view = o.obs_view;
-  out->obs_pl = o.obs_pl;
-  out->obs_seg = o.obs_seg;
-  out->obs_xy = o.obs_xy;
-  out->key = o.key;
-  out->complete = 1;
-  return EG3D_OK;
-}
-
-extern "C" int eg3d_compact_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, const uint8_t* keep_dev,
-                                   const float* X_new_dev, int32_t min_obs, eg3d_device_edgepoints* out) {
-  if (!c || !cloud || !out) {
-    g_err = "eg3d_compact_device: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  if ((const void*)out == (const void*)cloud) {
-    g_err = "eg3d_compact_device: out must not alias cloud";
-    return EG3D_ERR_ARG;
-  }
-  BUF_TRY(check_cloud(cloud, "eg3d_compact_device", true));
-  HIP_TRY(hipSetDevice(c->device));
-  return compact_device_impl(c, cloud, keep_dev, X_new_dev, min_obs, out, nullptr);
-}
-
-// The rule of eg3d_host_observation_filter (host/post_steps.cpp) on a histogram by list length: hist[k], k = 0 .. V, and
-// `count` points in all (lists longer than V are counted but sit in no bin, as there).
-static int observation_threshold(const uint64_t* hist, int V, uint64_t count, int forced_min_filter) {
-  uint64_t acc = 0;
-  int median = 0;
-  for (median = 0; median < V; median++) {
-    acc += hist[median + 1];
-    if (acc >= count / 2) break;
-  }
-  int threshold = median / 2 - 1;
-  if (threshold < 3) threshold = 3;
-  if (forced_min_filter > -1) threshold = forced_min_filter;
-  return threshold;
-}
-
-// The copy of a compacted cloud into a library-owned host cloud (obs_off with its sentinel); *ms_copy: wall time.
-static int copy_survivors_to_host(eg3d_ctx* c, const eg3d_device_edgepoints& o, eg3d_edgepoints* out_host, const char* who,
-                                  float* ms_copy) {
-  const auto t0 = std::chrono::steady_clock::now();
-  memset(out_host, 0, sizeof(*out_host));
-  const uint64_t np = o.n_points, no = o.n_obs;
-  out_host->X = (float*)malloc(12 * std::max<uint64_t>(np, 1));
-  out_host->obs_off = (uint64_t*)malloc(8 * (np + 1));
-  out_host->key = (uint32_t*)malloc(16 * std::max<uint64_t>(np, 1));
-  out_host->obs_view = (int32_t*)malloc(4 * std::max<uint64_t>(no, 1));
-  out_host->obs_pl = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
-  out_host->obs_seg = (uint32_t*)malloc(4 * std::max<uint64_t>(no, 1));
-  out_host->obs_xy = (float*)malloc(8 * std::max<uint64_t>(no, 1));
-  if (!out_host->X || !out_host->obs_off || !out_host->key || !out_host->obs_view || !out_host->obs_pl ||
-      !out_host->obs_seg || !out_host->obs_xy) {
-    eg3d_free_edgepoints(out_host);
-    g_err = std::string(who) + ": out of host memory";
-    return EG3D_ERR_HIP;
-  }
-  struct { void* dst; const void* src; size_t bytes; } cp[] = {
-      {out_host->X, o.X, 12 * np},          {out_host->obs_off, o.obs_off, 8 * np}, {out_host->key, o.key, 16 * np},
-      {out_host->obs_view, o.obs_view, 4 * no}, {out_host->obs_pl, o.obs_pl, 4 * no},   {out_host->obs_seg, o.obs_seg, 4 * no},
-      {out_host->obs_xy, o.obs_xy, 8 * no}};
-  for (auto& q : cp)
-    if (q.bytes) {
-      const hipError_t e = hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream);
-      if (e != hipSuccess) {
-        eg3d_free_edgepoints(out_host);
-        g_err = std::string(who) + ": copy to the host: " + hipGetErrorString(e);
-        return EG3D_ERR_HIP;
-      }
-    }
-  if (hipStreamSynchronize(c->stream) != hipSuccess) {
-    eg3d_free_edgepoints(out_host);
-    g_err = std::string(who) + ": copy to the host failed";
-    return EG3D_ERR_HIP;
-  }
-  out_host->obs_off[np] = no;
-  out_host->n_points = np;
-  out_host->n_obs = no;
-  *ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return EG3D_OK;
-}
-
-extern "C" int eg3d_filter_resident(eg3d_ctx* c, float gn_max_mse, int legacy_abs, int forced_min_filter,
-                                    const uint64_t* base_hist, int to_host, eg3d_edgepoints* out_host,
-                                    eg3d_device_edgepoints* out_dev, eg3d_filter_stats* stats) {
-  if (!c || (to_host && !out_host)) {
-    g_err = "eg3d_filter_resident: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  if (stats && stats->struct_size < sizeof(eg3d_filter_stats)) {
-    g_err = "eg3d_filter_resident: stats->struct_size is smaller than this library's eg3d_filter_stats (" +
-            std::to_string(sizeof(eg3d_filter_stats)) + " bytes): set it to sizeof(eg3d_filter_stats)";
-    return EG3D_ERR_ARG;
-  }
-  eg3d_device_edgepoints d;
-  BUF_TRY(eg3d_last_device_output(c, &d));
-  BUF_TRY(check_cloud(&d, "eg3d_filter_resident", true));
-  HIP_TRY(hipSetDevice(c->device));
-  const uint64_t n = d.n_points;
-  BUF_TRY(c->r_Xo.ensure(12 * n));
-  BUF_TRY(c->r_inl.ensure(n));
-  std::vector<uint64_t> hist;
-  float ms_filter = 0, ms_compact = 0;
-  BUF_TRY(gn_filter_device_impl(c, &d, nullptr, gn_max_mse, legacy_abs, c->r_Xo.as<float>(), c->r_inl.as<uint8_t>(), hist,
-                                &ms_filter));
-  uint64_t inliers = 0, count = 0;
-  for (uint64_t h : hist) inliers += h;
-  count = inliers;
-  if (base_hist)
-    for (int k = 0; k <= c->V; k++) {
-      hist[k] += base_hist[k];
-      count += base_hist[k];
-    }
-  const int threshold = observation_threshold(hist.data(), c->V, count, forced_min_filter);
-  eg3d_device_edgepoints o;
-  BUF_TRY(compact_device_impl(c, &d, c->r_inl.as<uint8_t>(), c->r_Xo.as<float>(), threshold, &o, &ms_compact));
-  float ms_copy = 0;
-  if (to_host) BUF_TRY(copy_survivors_to_host(c, o, out_host, "eg3d_filter_resident", &ms_copy));
-  if (out_dev) *out_dev = o;
-  if (stats) {
-    stats->struct_size = (uint32_t)sizeof(eg3d_filter_stats);
-    stats->threshold = threshold;
-    stats->n_points_in = n;
-    stats->n_masked_in = n;
-    stats->n_gn_inliers = inliers;
-    stats->n_kept = o.n_points;
-    stats->n_obs_kept = o.n_obs;
-    stats->ms_filter = ms_filter;
-    stats->ms_compact = ms_compact;
-    stats->ms_copy = ms_copy;
-  }
-  return EG3D_OK;
-}
-
-// ---- the 3 px de-duplication on a device-resident cloud ------------------------------------------------------------------
-#define EG3D_DEDUP_MAX_INDEX 0xFFFFFFFFull /* K7_UNCLAIMED: index_base + n_points stays below it */
-static int dedup_index_check(const char* who, uint64_t index_base, uint64_t n_points) {
-  if (index_base >= EG3D_DEDUP_MAX_INDEX || n_points >= EG3D_DEDUP_MAX_INDEX - index_base) {
-    g_err = std::string(who) + ": index_base + n_points must stay below 2^32 - 1 (the claim map holds 32-bit point indices)";
-    return EG3D_ERR_ARG;
-  }
-  return EG3D_OK;
-}
-static int dedup_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, uint64_t index_base, int reset, uint8_t* keep_dev,
-                             uint64_t* n_kept, float* ms) {
-  hipStream_t st = c->stream;
-  const int w = (int)std::ceil((float)c->W / 3), h = (int)std::ceil((float)c->H / 3);  // as host/post_steps.cpp
-  const size_t map_bytes = 4 * (size_t)c->V * (size_t)w * (size_t)h;
-  if (!c->d_first.p) c->dedup_valid = false;
-  BUF_TRY(c->d_first.ensure_exact(map_bytes));  // (it never grows, and a many-view rig's map is hundreds of MB)
-  const bool fill = reset || !c->dedup_valid;
-  c->dedup_valid = false;  // until this call is known to have completed: a failure below leaves the map to be refilled
-  if (fill) HIP_TRY(hipMemsetAsync(c->d_first.p, 0xFF, map_bytes, st));
-  BUF_TRY(c->d_cnt.ensure(16));
-  HIP_TRY(hipMemsetAsync(c->d_cnt.p, 0, 16, st));
-  unsigned long long* cnt = c->d_cnt.as<unsigned long long>();
-  const K7Map m{c->d_first.as<uint32_t>(), c->V, w, h};
-  const CloudView in = cloud_view(d);
-  HIP_TRY(hipEventRecord(c->ea[0], st));
-  launch_dedup_claim(st, in, m, (uint32_t)index_base);
-  launch_dedup_keep(st, in, m, (uint32_t)index_base, keep_dev, cnt, (uint32_t*)(cnt + 1));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->eb[0], st));
-  uint64_t back[2];  // kept points, flags
-  HIP_TRY(hipMemcpyAsync(back, cnt, sizeof(back), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ea[0], c->eb[0]));
-  // (claims made through bad offsets are discarded: dedup_valid stays false, the next call starts from an empty map)
-  if ((uint32_t)back[1]) return device_flags_error("eg3d_dedup_device", (uint32_t)back[1]);
-  c->dedup_valid = true;
-  if (n_kept) *n_kept = back[0];
-  return EG3D_OK;
-}
-
-extern "C" int eg3d_dedup_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, uint64_t index_base, int reset,
-                                 uint8_t* keep_dev, uint64_t* n_kept_host) {
-  if (cloud) BUF_TRY(dedup_index_check("eg3d_dedup_device", index_base, cloud->n_points));
-  if (!c || !cloud || (cloud->n_points && !keep_dev)) {
-    g_err = "eg3d_dedup_device: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  BUF_TRY(check_cloud(cloud, "eg3d_dedup_device", false));
-  HIP_TRY(hipSetDevice(c->device));
-  return dedup_device_impl(c, cloud, index_base, reset, keep_dev, n_kept_host, nullptr);
-}
-
-extern "C" int eg3d_dedup_resident(eg3d_ctx* c, uint64_t index_base, int reset, int with_filter, float gn_max_mse,
-                                   int legacy_abs, int forced_min_filter, const uint64_t* base_hist, int to_host,
-                                   eg3d_edgepoints* out_host, eg3d_device_edgepoints* out_dev, eg3d_dedup_stats* stats) {
-  if (stats && stats->struct_size < sizeof(eg3d_dedup_stats)) {
-    g_err = "eg3d_dedup_resident: stats->struct_size is smaller than this library's eg3d_dedup_stats (" +
-            std::to_string(sizeof(eg3d_dedup_stats)) + " bytes): set it to sizeof(eg3d_dedup_stats)";
-    return EG3D_ERR_ARG;
-  }
-  if (!c || (to_host && !out_host)) {
-    g_err = "eg3d_dedup_resident: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  eg3d_device_edgepoints d;
-  BUF_TRY(eg3d_last_device_output(c, &d));
-  BUF_TRY(dedup_index_check("eg3d_dedup_resident", index_base, d.n_points));
-  BUF_TRY(check_cloud(&d, "eg3d_dedup_resident", true));
-  HIP_TRY(hipSetDevice(c->device));
-  const uint64_t n = d.n_points;
-  BUF_TRY(c->d_keep.ensure(n));
-  uint64_t dedup_kept = 0, inliers = 0;
-  float ms_dedup = 0, ms_filter = 0, ms_compact = 0, ms_copy = 0;
-  BUF_TRY(dedup_device_impl(c, &d, index_base, reset, c->d_keep.as<uint8_t>(), &dedup_kept, &ms_dedup));
-  // a step that fails from here on leaves no cloud for the claims just made: they are discarded with the earlier ones
-  struct ClaimGuard {
-    eg3d_ctx* c;
-    bool ok = false;
-    ~ClaimGuard() { if (!ok) c->dedup_valid = false; }
-  } guard{c};
-  int threshold = -1;
-  eg3d_device_edgepoints o;
-  if (with_filter) {
-    // a masked-out point gets inlier 0, so r_inl is dedup AND inlier, and the histogram counts the deduplicated inliers
-    BUF_TRY(c->r_Xo.ensure(12 * n));
-    BUF_TRY(c->r_inl.ensure(n));
-    std::vector<uint64_t> hist;
-    BUF_TRY(gn_filter_device_impl(c, &d, c->d_keep.as<uint8_t>(), gn_max_mse, legacy_abs, c->r_Xo.as<float>(),
-                                  c->r_inl.as<uint8_t>(), hist, &ms_filter));
-    for (uint64_t hh : hist) inliers += hh;
-    uint64_t count = inliers;
-    if (base_hist)
-      for (int k = 0; k <= c->V; k++) {
-        hist[k] += base_hist[k];
-        count += base_hist[k];
-      }
-    threshold = observation_threshold(hist.data(), c->V, count, forced_min_filter);
-    BUF_TRY(compact_device_impl(c, &d, c->r_inl.as<uint8_t>(), c->r_Xo.as<float>(), threshold, &o, &ms_compact));
-  } else {
-    BUF_TRY(compact_device_impl(c, &d, c->d_keep.as<uint8_t>(), nullptr, -1, &o, &ms_compact));
-  }
-  if (to_host) BUF_TRY(copy_survivors_to_host(c, o, out_host, "eg3d_dedup_resident", &ms_copy));
-  guard.ok = true;
-  if (out_dev) *out_dev = o;
-  if (stats) {
-    stats->struct_size = (uint32_t)sizeof(eg3d_dedup_stats);
-    stats->threshold = threshold;
-    stats->n_points_in = n;
-    stats->n_dedup_kept = dedup_kept;
-    stats->n_gn_inliers = inliers;
-    stats->n_kept = o.n_points;
-    stats->n_obs_kept = o.n_obs;
-    stats->ms_dedup = ms_dedup;
-    stats->ms_filter = ms_filter;
-    stats->ms_compact = ms_compact;
-    stats->ms_copy = ms_copy;
-  }
-  return EG3D_OK;
-}
-
-// ---- the PLGMatchesManager replay on a device-resident cloud (K8, eg3d_k8_replay.hip) ---------------------------------------
-static int k8_scan(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n) {
-  size_t bytes = 0;
-  HIP_TRY(k8_scan_u32(c->stream, nullptr, bytes, in, out, n));
-  BUF_TRY(c->k8_tmp.ensure(bytes));
-  HIP_TRY(k8_scan_u32(c->stream, c->k8_tmp.p, bytes, in, out, n));
-  return EG3D_OK;
-}
-static int k8_read_u32(eg3d_ctx* c, const uint32_t* dev, uint64_t* v) {
-  uint32_t h = 0;
-  HIP_TRY(hipMemcpyAsync(&h, dev, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  *v = h;
-  return EG3D_OK;
-}
-static uint64_t pow2_above(uint64_t n) {  // the smallest power of two > n
-  uint64_t p = 1;
-  while (p <= n) p <<= 1;
-  return p;
-}
-
-extern "C" void eg3d_free_graph3d(eg3d_graph3d* g) {
-  if (!g) return;
-  void* all[] = {g->node_X, g->node_point, g->pl_start, g->pl_end, g->conn_off, g->conn_pl, g->iv_off, g->iv_start_seg,
-                 g->iv_start_xy, g->iv_end_seg, g->iv_end_xy};
-  for (void* p : all) free(p);
-  memset(g, 0, sizeof(*g));
-}
-
-extern "C" int eg3d_replay_device(eg3d_ctx* c, const eg3d_device_edgepoints* cloud, eg3d_device_graph3d* out_dev,
-                                  eg3d_graph3d* out_host, eg3d_replay_stats* stats) {
-  if (stats && stats->struct_size < sizeof(eg3d_replay_stats)) {
-    g_err = "eg3d_replay_device: stats->struct_size is smaller than this library's eg3d_replay_stats (" +
-            std::to_string(sizeof(eg3d_replay_stats)) + " bytes): set it to sizeof(eg3d_replay_stats)";
-    return EG3D_ERR_ARG;
-  }
-  if (!c) {
-    g_err = "eg3d_replay_device: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  eg3d_device_edgepoints d;
-  if (cloud)
-    d = *cloud;
-  else
-    BUF_TRY(eg3d_last_device_output(c, &d));
-  if (d.n_points >= 0xfffffff0ull) {
-    g_err = "eg3d_replay_device: n_points must stay below 0xfffffff0 (node and polyline ids are 32-bit)";
-    return EG3D_ERR_CAPACITY;
-  }
-  BUF_TRY(check_cloud(&d, "eg3d_replay_device", true));
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const CloudView in = cloud_view(&d);
-  const uint64_t N = d.n_points, NP = c->n_pl, NV = c->n_vtx;
-
-  // ---- the checks, before anything is indexed or written
-  BUF_TRY(c->k8_cnt.ensure(16));
-  HIP_TRY(hipMemsetAsync(c->k8_cnt.p, 0, 16, st));
-  unsigned long long* cnt = c->k8_cnt.as<unsigned long long>();
-  launch_k8_pairs(st, in, c->ds, cnt, (uint32_t*)(cnt + 1));
-  HIP_TRY(hipGetLastError());
-  uint64_t back[2];  // pairs, flags
-  HIP_TRY(hipMemcpyAsync(back, cnt, sizeof(back), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const uint32_t flags = (uint32_t)back[1];
-  if (flags & ~K8_FLAG_HOSTONLY) {
-    g_err = std::string("eg3d_replay_device: ") +
-            (flags & K8_FLAG_BAD_OFFSETS ? "obs_off is not ascending within [0, n_obs]"
-             : flags & K8_FLAG_BAD_VIEW  ? "view id out of range"
-             : flags & K8_FLAG_BAD_PL    ? "polyline id outside its view"
-                                         : "segment index outside its polyline (or a polyline without segments)");
-    return EG3D_ERR_ARG;
-  }
-  if (flags & K8_FLAG_HOSTONLY) {
-    g_err = "eg3d_replay_device: a point of a chain pair has a NaN coordinate or x or y == -1 (the reference's invalid-node "
-            "rule): replay this cloud with eg3d_host_replay_matches";
-    return EG3D_ERR_HOSTONLY;
-  }
-  const uint64_t n_pairs = back[0];
-
-  uint64_t n_nodes = 0, n_pl = 0, n_conn = 0, n_iv = 0, slots = 0;
-  float ms_graph = 0, ms_iv = 0, ms_copy = 0;
-  K8Graph g{};
-  BUF_TRY(c->g_ivoff.ensure(8 * (NP + 1)));
-  g.iv_off = c->g_ivoff.as<unsigned long long>();
-  if (!n_pairs) {  // an empty cloud, or one-point chains only: the all-zero graph
-    BUF_TRY(c->g_conoff.ensure(8));
-    g.conn_off = c->g_conoff.as<unsigned long long>();
-    HIP_TRY(hipMemsetAsync(g.conn_off, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(g.iv_off, 0, 8 * (NP + 1), st));
-  } else {
-    // ---- nodes
-    slots = c->replay_table_bits ? std::max<uint64_t>(1ull << c->replay_table_bits, pow2_above(2 * n_pairs))
-                                 : pow2_above(std::max<uint64_t>(4 * n_pairs, 63));
-    BUF_TRY(c->k8_slot.ensure(4 * slots));
-    BUF_TRY(c->k8_last.ensure(4 * slots));
-    BUF_TRY(c->k8_firstof.ensure(4 * N));
-    BUF_TRY(c->k8_lastof.ensure(4 * N));
-    BUF_TRY(c->k8_flag.ensure(4 * (N + 1)));
-    BUF_TRY(c->k8_rank.ensure(4 * (N + 1)));
-    BUF_TRY(c->k8_plid.ensure(4 * (N + 1)));
-    const size_t sort_n = std::max<uint64_t>(N, 2 * n_pairs);  // the pairs' keys by point, then two incidences per polyline
-    for (int k = 0; k < 2; k++) {
-      BUF_TRY(c->k8_key[k].ensure(8 * sort_n));
-      BUF_TRY(c->k8_val[k].ensure(4 * N));
-    }
-    const K8Table tab{c->k8_slot.as<uint32_t>(), c->k8_last.as<uint32_t>(), slots - 1};
-    uint32_t* first_of = c->k8_firstof.as<uint32_t>();
-    uint32_t* last_of = c->k8_lastof.as<uint32_t>();
-    uint32_t* flag = c->k8_flag.as<uint32_t>();
-    uint32_t* rank = c->k8_rank.as<uint32_t>();
-    uint32_t* pl_id = c->k8_plid.as<uint32_t>();
-    unsigned long long* key[2] = {c->k8_key[0].as<unsigned long long>(), c->k8_key[1].as<unsigned long long>()};
-    uint32_t* val[2] = {c->k8_val[0].as<uint32_t>(), c->k8_val[1].as<uint32_t>()};
-    HIP_TRY(hipEventRecord(c->ea[0], st));
-    HIP_TRY(hipMemsetAsync(tab.slot, 0xFF, 4 * slots, st));
-    HIP_TRY(hipMemsetAsync(tab.last, 0, 4 * slots, st));
-    HIP_TRY(hipMemsetAsync(flag, 0, 4 * (N + 1), st));
-    launch_k8_node_claim(st, in, tab);
-    launch_k8_node_resolve(st, in, tab, first_of, flag, last_of);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k8_scan(c, flag, rank, N + 1));
-    BUF_TRY(k8_read_u32(c, rank + N, &n_nodes));
-    BUF_TRY(c->g_nodeX.ensure(12 * n_nodes));
-    BUF_TRY(c->g_nodept.ensure(8 * n_nodes));
-    BUF_TRY(c->g_conoff.ensure(8 * (n_nodes + 1)));
-    g.node_X = c->g_nodeX.as<float>();
-    g.node_point = c->g_nodept.as<unsigned long long>();
-    g.conn_off = c->g_conoff.as<unsigned long long>();
-    launch_k8_node_write(st, in, first_of, flag, rank, last_of, g, key[0], val[0]);
-    HIP_TRY(hipGetLastError());
-    // ---- polylines: a stable sort keeps the pairs of one connection in cloud order, the first of a run creates it
-    size_t bytes = 0;
-    HIP_TRY(k8_sort_pairs(st, nullptr, bytes, key[0], key[1], val[0], val[1], N));
-    BUF_TRY(c->k8_tmp.ensure(bytes));
-    HIP_TRY(k8_sort_pairs(st, c->k8_tmp.p, bytes, key[0], key[1], val[0], val[1], N));
-    HIP_TRY(hipMemsetAsync(flag, 0, 4 * (N + 1), st));
-    launch_k8_pl_heads(st, key[1], val[1], n_pairs, flag);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k8_scan(c, flag, pl_id, N + 1));
-    BUF_TRY(k8_read_u32(c, pl_id + N, &n_pl));
-    BUF_TRY(c->g_pls.ensure(4 * n_pl));
-    BUF_TRY(c->g_ple.ensure(4 * n_pl));
-    BUF_TRY(c->g_conpl.ensure(8 * n_pl));
-    g.pl_start = c->g_pls.as<uint32_t>();
-    g.pl_end = c->g_ple.as<uint32_t>();
-    g.conn_pl = c->g_conpl.as<uint32_t>();
-    launch_k8_pl_write(st, in, first_of, rank, flag, pl_id, g, key[0]);
-    HIP_TRY(hipGetLastError());
-    // ---- connections: the (node, polyline) incidences sorted = every node's polylines in ascending id
-    HIP_TRY(k8_sort_keys(st, nullptr, bytes, key[0], key[1], 2 * n_pl));
-    BUF_TRY(c->k8_tmp.ensure(bytes));
-    HIP_TRY(k8_sort_keys(st, c->k8_tmp.p, bytes, key[0], key[1], 2 * n_pl));
-    launch_k8_conn(st, key[1], 2 * n_pl, n_nodes, g);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->eb[0], st));
-    HIP_TRY(hipMemcpyAsync(&n_conn, g.conn_off + n_nodes, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&ms_graph, c->ea[0], c->eb[0]));
-    // ---- matched intervals: the claim map is indexed by the scene's global segment index
-    BUF_TRY(c->k8_map.ensure(8 * std::max<uint64_t>(NV, 1)));
-    BUF_TRY(c->k8_sflag.ensure(4 * (NV + 1)));
-    BUF_TRY(c->k8_pos.ensure(4 * (NV + 1)));
-    unsigned long long* map = c->k8_map.as<unsigned long long>();
-    uint32_t* pos = c->k8_pos.as<uint32_t>();
-    HIP_TRY(hipEventRecord(c->ea[0], st));
-    HIP_TRY(hipMemsetAsync(map, 0xFF, 8 * std::max<uint64_t>(NV, 1), st));
-    launch_k8_iv(st, false, in, c->ds, map, pos, g);
-    launch_k8_seg_flags(st, map, NV, c->k8_sflag.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k8_scan(c, c->k8_sflag.as<uint32_t>(), pos, NV + 1));
-    BUF_TRY(k8_read_u32(c, pos + NV, &n_iv));
-    BUF_TRY(c->g_ivss.ensure(4 * n_iv));
-    BUF_TRY(c->g_ives.ensure(4 * n_iv));
-    BUF_TRY(c->g_ivsxy.ensure(8 * n_iv));
-    BUF_TRY(c->g_ivexy.ensure(8 * n_iv));
-    g.iv_start_seg = c->g_ivss.as<uint32_t>();
-    g.iv_end_seg = c->g_ives.as<uint32_t>();
-    g.iv_start_xy = c->g_ivsxy.as<float>();
-    g.iv_end_xy = c->g_ivexy.as<float>();
-    launch_k8_iv(st, true, in, c->ds, map, pos, g);
-    launch_k8_iv_off(st, c->ds, (uint32_t)NP, pos, g);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->eb[0], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&ms_iv, c->ea[0], c->eb[0]));
-  }
-
-  if (out_host) {
-    const auto t0 = std::chrono::steady_clock::now();
-    eg3d_graph3d h;
-    memset(&h, 0, sizeof(h));
-    struct { void** dst; const void* src; size_t bytes; } cp[] = {
-        {(void**)&h.node_X, g.node_X, 12 * n_nodes},      {(void**)&h.node_point, g.node_point, 8 * n_nodes},
-        {(void**)&h.pl_start, g.pl_start, 4 * n_pl},      {(void**)&h.pl_end, g.pl_end, 4 * n_pl},
-        {(void**)&h.conn_off, g.conn_off, 8 * (n_nodes + 1)}, {(void**)&h.conn_pl, g.conn_pl, 4 * n_conn},
-        {(void**)&h.iv_off, g.iv_off, 8 * (NP + 1)},      {(void**)&h.iv_start_seg, g.iv_start_seg, 4 * n_iv},
-        {(void**)&h.iv_start_xy, g.iv_start_xy, 8 * n_iv}, {(void**)&h.iv_end_seg, g.iv_end_seg, 4 * n_iv},
-        {(void**)&h.iv_end_xy, g.iv_end_xy, 8 * n_iv}};
-    hipError_t e = hipSuccess;
-    bool oom = false;
-    for (auto& q : cp) {
-      *q.dst = malloc(std::max<size_t>(q.bytes, 1));
-      if (!*q.dst) {
-        oom = true;
-        break;
-      }
-      if (q.bytes && (e = hipMemcpyAsync(*q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-    }
-    const hipError_t es = hipStreamSynchronize(st);  // (also after a failure: no copy may still be writing what is freed)
-    if (e == hipSuccess) e = es;
-    if (oom || e != hipSuccess) {
-      eg3d_free_graph3d(&h);
-      g_err = oom ? std::string("eg3d_replay_device: out of host memory")
-                  : std::string("eg3d_replay_device: copy to the host: ") + hipGetErrorString(e);
-      return EG3D_ERR_HIP;
-    }
-    h.n_nodes = h.n_real_nodes = n_nodes;
-    h.n_polylines = n_pl;
-    h.n_scene_polylines = NP;
-    *out_host = h;
-    ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  } else {
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  if (out_dev) {
-    out_dev->n_nodes = out_dev->n_real_nodes = n_nodes;
-    out_dev->n_polylines = n_pl;
-    out_dev->n_scene_polylines = NP;
-    out_dev->node_X = g.node_X;
-    out_dev->node_point = (const uint64_t*)g.node_point;
-    out_dev->pl_start = g.pl_start;
-    out_dev->pl_end = g.pl_end;
-    out_dev->conn_off = (const uint64_t*)g.conn_off;
-    out_dev->conn_pl = g.conn_pl;
-    out_dev->iv_off = (const uint64_t*)g.iv_off;
-    out_dev->iv_start_seg = g.iv_start_seg;
-    out_dev->iv_start_xy = g.iv_start_xy;
-    out_dev->iv_end_seg = g.iv_end_seg;
-    out_dev->iv_end_xy = g.iv_end_xy;
-  }
-  if (stats) {
-    stats->struct_size = (uint32_t)sizeof(eg3d_replay_stats);
-    stats->n_pairs = n_pairs;
-    stats->n_nodes = n_nodes;
-    stats->n_polylines = n_pl;
-    stats->n_intervals = n_iv;
-    stats->table_slots = slots;
-    stats->ms_graph = ms_graph;
-    stats->ms_intervals = ms_iv;
-    stats->ms_copy = ms_copy;
-  }
-  return EG3D_OK;
-}
-
-// ---- polyline matching by closeness to the reference points (K9, eg3d_k9_polymatch.hip) ---------------------------------------
-static int k9_sort(eg3d_ctx* c, const unsigned long long* in, unsigned long long* out, size_t n) {
-  size_t bytes = 0;
-  HIP_TRY(k8_sort_keys(c->stream, nullptr, bytes, in, out, n));
-  BUF_TRY(c->k8_tmp.ensure(bytes));
-  HIP_TRY(k8_sort_keys(c->stream, c->k8_tmp.p, bytes, in, out, n));
-  return EG3D_OK;
-}
-
-extern "C" void eg3d_free_polyline_matches(eg3d_polyline_matches* m) {
-  if (!m) return;
-  free(m->refpoints);
-  free(m->row_off);
-  free(m->pl_ids);
-  memset(m, 0, sizeof(*m));
-}
-
-// `forced` (tests): per-entry results that take the place of the search's, host arrays of n_sv entries each
-struct K9Forced {
-  const uint32_t* cnt;
-  const uint32_t* pl;
-  const float* dist;
-};
-static int polymatch_impl(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint32_t e, const K9Forced* forced,
-                          eg3d_polyline_matches* out, eg3d_polymatch_stats* stats) {
-  if (stats && stats->struct_size < sizeof(eg3d_polymatch_stats)) {
-    g_err = "eg3d_match_polylines_closeness: stats->struct_size is smaller than this library's eg3d_polymatch_stats (" +
-            std::to_string(sizeof(eg3d_polymatch_stats)) + " bytes): set it to sizeof(eg3d_polymatch_stats)";
-    return EG3D_ERR_ARG;
-  }
+int open_seed_range(eg3d_ctx* c, const char* who, const eg3d_seeds* seeds, uint32_t b, uint32_t e, const void* out,
+                    WorkBuf eg3d_ctx::*ctr_of, WorkBuf eg3d_ctx::*svseed_of, SeedRange* r) {
   if (!c || !out) {
-    g_err = "eg3d_match_polylines_closeness: bad arguments";
+    g_err = std::string(who) + ": bad arguments";
     return EG3D_ERR_ARG;
   }
   if (seeds) BUF_TRY(eg3d_upload_seeds(c, seeds));
   if (b > e || e > c->n_seeds) {
-    g_err = "eg3d_match_polylines_closeness: bad seed range (seeds uploaded?)";
+    g_err = std::string(who) + ": bad seed range (seeds uploaded?)";
     return EG3D_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_seeds = e - b;
-  const uint32_t sv_base = n_seeds ? (*c->h_trk)[b] : 0, n_sv = n_seeds ? (*c->h_trk)[e] - sv_base : 0;
-  uint32_t n_acc = 0, n_nodes = 0, n_sets = 0;
-  float ms_grid = 0, ms_search = 0, ms_comp = 0, ms_copy = 0;
-  if (n_sv && NP) {
-    K9Grid g10;
-    BUF_TRY(ensure_grid10(c, &g10, &ms_grid));
-    SeedsDev sd;
-    sd.trk_off = c->b_toff.as<uint32_t>();
-    sd.trk_view = c->b_tview.as<int32_t>();
-    sd.trk_xy = c->b_txy.as<float>();
-    // ---- the view ids, before anything indexes with them
-    BUF_TRY(c->k9_ctr.ensure(4 * sizeof(uint32_t)));  // [0] flags, [1] nodes, [2] sets
-    BUF_TRY(c->k9_svseed.ensure(sizeof(uint32_t) * n_sv));
-    uint32_t* ctr = c->k9_ctr.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(uint32_t), st));
-    launch_k9_prep(st, sd, c->V, b, n_seeds, sv_base, c->k9_svseed.as<uint32_t>(), ctr);
-    HIP_TRY(hipGetLastError());
-    {
-      BUF_TRY(ensure_mailbox(c));
-      Readback rb(c);
-      const int it = rb.add(ctr, 1);
-      BUF_TRY(rb.run());
-      if (*rb.item(it) & K9_FLAG_BAD_VIEW) {
-        g_err = "eg3d_match_polylines_closeness: view id out of range";
-        return EG3D_ERR_ARG;
-      }
-    }
-    // ---- the search
-    BUF_TRY(c->k9_cnt.ensure(sizeof(uint32_t) * n_sv));
-    BUF_TRY(c->k9_pl.ensure(sizeof(uint32_t) * n_sv));
-    BUF_TRY(c->k9_dist.ensure(sizeof(float) * n_sv));
-    const K9Entries ent{c->k9_cnt.as<uint32_t>(), c->k9_pl.as<uint32_t>(), c->k9_dist.as<float>()};
-    HIP_TRY(hipEventRecord(c->ea[0], st));  // ms_search: the search kernel alone
-    if (!forced) {
-      launch_k9_close_polylines(st, c->ds, g10, sd, sv_base, n_sv, c->k9_svseed.as<uint32_t>(), ent);
-      HIP_TRY(hipGetLastError());
-    } else {
-      HIP_TRY(hipMemcpyAsync(ent.cnt, forced->cnt, sizeof(uint32_t) * n_sv, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ent.pl, forced->pl, sizeof(uint32_t) * n_sv, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(ent.dist, forced->dist, sizeof(float) * n_sv, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipStreamSynchronize(st));  // (pageable host arrays of the caller)
-    }
-    HIP_TRY(hipEventRecord(c->eb[0], st));
-    // ---- the rule, the match graph, its components and their order
-    BUF_TRY(c->k9_acc.ensure(sizeof(uint32_t) * ((size_t)n_seeds + 1)));
-    BUF_TRY(c->k9_accoff.ensure(sizeof(uint32_t) * ((size_t)n_seeds + 1)));
-    BUF_TRY(c->k9_first.ensure(8 * (size_t)NP));
-    BUF_TRY(c->k9_ckey.ensure(8 * (size_t)NP));
-    BUF_TRY(c->k9_parent.ensure(4 * (size_t)NP));
-    BUF_TRY(c->k9_root.ensure(4 * (size_t)NP));
-    BUF_TRY(c->k9_rank.ensure(4 * (size_t)NP));
-    for (int k = 0; k < 2; k++) BUF_TRY(c->k9_key[k].ensure(8 * (size_t)NP));
-    const K9Graph g{c->k9_first.as<unsigned long long>(), c->k9_parent.as<uint32_t>(), c->k9_root.as<uint32_t>(),
-                    c->k9_ckey.as<unsigned long long>(), c->k9_rank.as<uint32_t>()};
-    unsigned long long* key[2] = {c->k9_key[0].as<unsigned long long>(), c->k9_key[1].as<unsigned long long>()};
-    HIP_TRY(hipEventRecord(c->ea[1], st));
-    launch_k9_init(st, NP, g);
-    launch_k9_refpoint_rule(st, c->ds, sd, b, n_seeds, sv_base, ent, c->k9_acc.as<uint32_t>(), g);
-    launch_k9_flatten(st, NP, g, ctr + 1);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k9_sort(c, g.ckey, key[0], NP));
-    launch_k9_rank(st, key[0], NP, g, ctr + 2);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(scan_queue_u32(c, c->k9_acc.as<uint32_t>(), c->k9_accoff.as<uint32_t>(), (size_t)n_seeds + 1, 0));
-    {
-      Readback rb(c);
-      const int ic = rb.add(ctr + 1, 2);
-      const int ia = rb.add(c->k9_accoff.as<uint32_t>() + n_seeds, 1);
-      const int iw = rb.add(c->b_scanchk.as<uint32_t>(), 1);
-      rb.clear_after(c->b_scanchk.as<uint32_t>());
-      BUF_TRY(rb.run());
-      if (*rb.item(iw)) return wrapped_error("accepted reference points");
-      n_nodes = rb.item(ic)[0];
-      n_sets = rb.item(ic)[1];
-      n_acc = *rb.item(ia);
-    }
-    if ((uint64_t)n_sets * V >= 0xffffffffull) {
-      g_err = "eg3d_match_polylines_closeness: the result has more than 2^32-2 rows (sets x views)";
-      return EG3D_ERR_CAPACITY;
-    }
-    BUF_TRY(c->k9_ref.ensure(sizeof(uint32_t) * std::max<size_t>(n_acc, 1)));
-    BUF_TRY(c->k9_rowoff.ensure(sizeof(uint32_t) * ((size_t)n_sets * V + 1)));
-    BUF_TRY(c->k9_plids.ensure(sizeof(uint32_t) * std::max<size_t>(n_nodes, 1)));
-    launch_k9_compact(st, c->k9_acc.as<uint32_t>(), c->k9_accoff.as<uint32_t>(), b, n_seeds, c->k9_ref.as<uint32_t>());
-    if (n_nodes) {
-      launch_k9_node_keys(st, c->ds, NP, g, key[0]);
-      HIP_TRY(hipGetLastError());
-      BUF_TRY(k9_sort(c, key[0], key[1], NP));
-      launch_k0_csr(st, key[1], n_nodes, n_sets * V, c->k9_rowoff.as<uint32_t>(), c->k9_plids.as<uint32_t>());
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->eb[1], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&ms_search, c->ea[0], c->eb[0]));
-    HIP_TRY(hipEventElapsedTime(&ms_comp, c->ea[1], c->eb[1]));
-  }
-  // ---- the result, library-owned
-  const auto t0 = std::chrono::steady_clock::now();
-  eg3d_polyline_matches m;
-  memset(&m, 0, sizeof(m));
-  const size_t n_rows1 = (size_t)n_sets * V + 1;
-  m.refpoints = (uint32_t*)malloc(sizeof(uint32_t) * std::max<size_t>(n_acc, 1));
-  m.row_off = (uint32_t*)malloc(sizeof(uint32_t) * n_rows1);
-  m.pl_ids = (uint32_t*)malloc(sizeof(uint32_t) * std::max<size_t>(n_nodes, 1));
-  hipError_t he = hipSuccess;
-  if (m.refpoints && m.row_off && m.pl_ids) {
-    m.row_off[0] = 0;
-    if (n_acc) he = hipMemcpyAsync(m.refpoints, c->k9_ref.p, sizeof(uint32_t) * n_acc, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && n_sets) he = hipMemcpyAsync(m.row_off, c->k9_rowoff.p, sizeof(uint32_t) * n_rows1, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && n_nodes) he = hipMemcpyAsync(m.pl_ids, c->k9_plids.p, sizeof(uint32_t) * n_nodes, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = es;
-  }
-  if (!(m.refpoints && m.row_off && m.pl_ids) || he != hipSuccess) {
-    g_err = he != hipSuccess ? std::string("eg3d_match_polylines_closeness: copy to the host: ") + hipGetErrorString(he)
-                             : std::string("eg3d_match_polylines_closeness: out of host memory");
-    eg3d_free_polyline_matches(&m);
-    return EG3D_ERR_HIP;
-  }
-  m.n_refpoints = n_acc;
-  m.n_sets = n_sets;
-  ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = m;
-  if (stats) {
-    stats->struct_size = (uint32_t)sizeof(eg3d_polymatch_stats);
-    stats->n_entries = n_sv;
-    stats->n_accepted = n_acc;
-    stats->n_nodes = n_nodes;
-    stats->n_sets = n_sets;
-    stats->ms_grid = ms_grid;
-    stats->ms_search = ms_search;
-    stats->ms_components = ms_comp;
-    stats->ms_copy = ms_copy;
-  }
-  return EG3D_OK;
-}
-extern "C" int eg3d_match_polylines_closeness(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint32_t e,
-                                              eg3d_polyline_matches* out, eg3d_polymatch_stats* stats) {
-  return polymatch_impl(c, seeds, b, e, nullptr, out, stats);
-}
-/* Tests only, not declared in include/eg3d.h (tests/test_gpu_polymatch.py).
- * eg3d_polymatch_test_entries: the per-entry results the last eg3d_match_polylines_closeness call on this context left on the
- * device (n = its stats.n_entries): polylines within 10 px, the first one's id and its distance.
- * eg3d_polymatch_test_rule: the matcher on the uploaded seeds [b, e) with the CALLER's per-entry results (one per track entry
- * of the range; a polyline id must lie inside its view) in place of the search: the rule, the graph and the order alone. */
-extern "C" int eg3d_polymatch_test_entries(eg3d_ctx* c, uint32_t n, uint32_t* cnt, uint32_t* pl, float* dist) {
-  if (!c || (size_t)n * 4 > c->k9_cnt.cap || (size_t)n * 4 > c->k9_pl.cap || (size_t)n * 4 > c->k9_dist.cap) {
-    g_err = "eg3d_polymatch_test_entries: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (n) {
-    HIP_TRY(hipMemcpy(cnt, c->k9_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pl, c->k9_pl.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dist, c->k9_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  }
-  return EG3D_OK;
-}
-extern "C" int eg3d_polymatch_test_rule(eg3d_ctx* c, uint32_t b, uint32_t e, const uint32_t* cnt, const uint32_t* pl,
-                                        const float* dist, eg3d_polyline_matches* out) {
-  if (!cnt || !pl || !dist) {
-    g_err = "eg3d_polymatch_test_rule: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  const K9Forced f{cnt, pl, dist};
-  return polymatch_impl(c, nullptr, b, e, &f, out, nullptr);
-}
-
-// ---- pipeline 1's polyline compatibility graph (K10, eg3d_k10_simgraph.hip) ---------------------------------------------------
-// Edge keys one chunk of the clique expansion writes when EG3D_SIMGRAPH_PAIR_BUDGET does not say.
-#ifndef EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
-#define EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT (1ull << 22)
-#endif
-
-extern "C" void eg3d_free_simgraph(eg3d_simgraph* g) {
-  if (!g) return;
-  free(g->node_view);
-  free(g->node_pl);
-  free(g->adj_off);
-  free(g->adj_node);
-  free(g->adj_w);
-  free(g->point_weight);
-  free(g->cp_off);
-  free(g->cp_view);
-  free(g->cp_pl);
-  free(g->cr_off);
-  free(g->cr_point);
-  memset(g, 0, sizeof(*g));
-}
-
-static int k10_sort_pairs(eg3d_ctx* c, const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin, uint32_t* vout,
-                          size_t n) {
-  size_t bytes = 0;
-  HIP_TRY(k8_sort_pairs(c->stream, nullptr, bytes, kin, kout, vin, vout, n));
-  BUF_TRY(c->k8_tmp.ensure(bytes));
-  HIP_TRY(k8_sort_pairs(c->stream, c->k8_tmp.p, bytes, kin, kout, vin, vout, n));
-  return EG3D_OK;
-}
-
-extern "C" int eg3d_similarity_graph(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint32_t e, eg3d_simgraph* out,
-                                     eg3d_simgraph_stats* stats) {
-  if (stats && stats->struct_size < sizeof(eg3d_simgraph_stats)) {
-    g_err = "eg3d_similarity_graph: stats->struct_size is smaller than this library's eg3d_simgraph_stats (" +
-            std::to_string(sizeof(eg3d_simgraph_stats)) + " bytes): set it to sizeof(eg3d_simgraph_stats)";
-    return EG3D_ERR_ARG;
-  }
-  if (!c || !out) {
-    g_err = "eg3d_similarity_graph: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  if (seeds) BUF_TRY(eg3d_upload_seeds(c, seeds));
-  if (b > e || e > c->n_seeds) {
-    g_err = "eg3d_similarity_graph: bad seed range (seeds uploaded?)";
-    return EG3D_ERR_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_pts = e - b;
-  const uint32_t sv_base = n_pts ? (*c->h_trk)[b] : 0, n_sv = n_pts ? (*c->h_trk)[e] - sv_base : 0;
-  const uint64_t budget = c->simgraph_pair_budget ? c->simgraph_pair_budget : EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT;
-  uint32_t n_pair = 0, n_nodes = 0, n_uniq = 0, n_kept = 0, n_chunks = 0;
-  uint64_t n_inst = 0;
-  float ms_grid = 0, ms_search = 0, ms_graph = 0, ms_weights = 0, ms_copy = 0;
-  if (n_sv && NP) {
-    K9Grid g10;
-    BUF_TRY(ensure_grid10(c, &g10, &ms_grid));
-    SeedsDev sd;
-    sd.trk_off = c->b_toff.as<uint32_t>();
-    sd.trk_view = c->b_tview.as<int32_t>();
-    sd.trk_xy = c->b_txy.as<float>();
-    // ---- the view ids, before anything indexes with them (K9's check)
-    BUF_TRY(c->k10_ctr.ensure(4 * sizeof(uint32_t)));  // [0] flags, [1] nodes, [2] distinct edges, [3] kept edges
-    BUF_TRY(c->k10_svseed.ensure(sizeof(uint32_t) * n_sv));
-    uint32_t* ctr = c->k10_ctr.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(uint32_t), st));
-    launch_k9_prep(st, sd, c->V, b, n_pts, sv_base, c->k10_svseed.as<uint32_t>(), ctr);
-    HIP_TRY(hipGetLastError());
-    {
-      BUF_TRY(ensure_mailbox(c));
-      Readback rb(c);
-      const int it = rb.add(ctr, 1);
-      BUF_TRY(rb.run());
-      if (*rb.item(it) & K9_FLAG_BAD_VIEW) {
-        g_err = "eg3d_similarity_graph: view id out of range";
-        return EG3D_ERR_ARG;
-      }
-    }
-    // ---- the search, list form: count, scan, fill
-    BUF_TRY(c->k10_cnt.ensure(sizeof(uint32_t) * ((size_t)n_sv + 1)));
-    BUF_TRY(c->k10_off.ensure(sizeof(uint32_t) * ((size_t)n_sv + 1)));
-    uint32_t* cnt = c->k10_cnt.as<uint32_t>();
-    uint32_t* off = c->k10_off.as<uint32_t>();
-    HIP_TRY(hipEventRecord(c->ea[0], st));
-    HIP_TRY(hipMemsetAsync(cnt + n_sv, 0, sizeof(uint32_t), st));
-    launch_k10_close_list(st, false, c->ds, g10, sd, sv_base, n_sv, c->k10_svseed.as<uint32_t>(), cnt, nullptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(scan_queue_u32(c, cnt, off, (size_t)n_sv + 1, 0));
-    {
-      Readback rb(c);
-      const int it = rb.add(off + n_sv, 1);
-      const int iw = rb.add(c->b_scanchk.as<uint32_t>(), 1);
-      rb.clear_after(c->b_scanchk.as<uint32_t>());
-      BUF_TRY(rb.run());
-      if (*rb.item(iw)) return wrapped_error("close polylines");
-      n_pair = *rb.item(it);
-    }
-    for (int k = 0; k < 2; k++) BUF_TRY(c->k10_pair[k].ensure(8 * std::max<size_t>(n_pair, 1)));
-    unsigned long long* pair[2] = {c->k10_pair[0].as<unsigned long long>(), c->k10_pair[1].as<unsigned long long>()};
-    launch_k10_close_list(st, true, c->ds, g10, sd, sv_base, n_sv, c->k10_svseed.as<uint32_t>(), nullptr, off, pair[0]);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->eb[0], st));
-    HIP_TRY(hipEventRecord(c->ea[1], st));
-    HIP_TRY(hipEventRecord(c->eb[1], st));  // (re-recorded below: both pairs are always defined)
-    HIP_TRY(hipEventRecord(c->ea[2], st));
-    HIP_TRY(hipEventRecord(c->eb[2], st));
-  }
-  if (n_pair) {
-    // ---- close_polylines, close_refpoints, the weights, the nodes
-    HIP_TRY(hipEventRecord(c->ea[1], st));
-    const uint32_t vis_words = (V + 31u) / 32u;
-    BUF_TRY(c->k10_crkey.ensure(8 * (size_t)n_pair));
-    BUF_TRY(c->k10_cpoff.ensure(4 * ((size_t)n_pts + 1)));
-    BUF_TRY(c->k10_cpview.ensure(4 * (size_t)n_pair));
-    BUF_TRY(c->k10_cppl.ensure(4 * (size_t)n_pair));
-    BUF_TRY(c->k10_croff.ensure(4 * ((size_t)NP + 1)));
-    BUF_TRY(c->k10_crpoint.ensure(4 * (size_t)n_pair));
-    BUF_TRY(c->k10_weight.ensure(4 * (size_t)n_pts));
-    BUF_TRY(c->k10_vis.ensure(4 * (size_t)n_pts * vis_words));
-    BUF_TRY(c->k10_npairs.ensure(8 * ((size_t)n_pts + 1)));
-    BUF_TRY(c->k10_pairoff.ensure(8 * ((size_t)n_pts + 1)));
-    for (int k = 0; k < 2; k++) BUF_TRY(c->k10_nkey[k].ensure(8 * (size_t)NP));
-    BUF_TRY(c->k10_nodeof.ensure(4 * (size_t)NP));
-    BUF_TRY(c->k10_nodeg.ensure(4 * (size_t)NP));
-    BUF_TRY(c->k10_nodeview.ensure(4 * (size_t)NP));
-    BUF_TRY(c->k10_nodepl.ensure(4 * (size_t)NP));
-    SeedsDev sd;
-    sd.trk_off = c->b_toff.as<uint32_t>();
-    sd.trk_view = c->b_tview.as<int32_t>();
-    sd.trk_xy = c->b_txy.as<float>();
-    uint32_t* ctr = c->k10_ctr.as<uint32_t>();
-    unsigned long long* const raw = c->k10_pair[0].as<unsigned long long>();
-    unsigned long long* const pair = c->k10_pair[1].as<unsigned long long>();    // point << 32 | g, ascending
-    unsigned long long* const crkey = c->k10_crkey.as<unsigned long long>();     // g << 32 | point, ascending
-    unsigned long long* const pair_off = c->k10_pairoff.as<unsigned long long>();
-    BUF_TRY(k9_sort(c, raw, pair, n_pair));
-    launch_k10_pairs(st, c->ds, pair, n_pair, c->k10_cpview.as<uint32_t>(), c->k10_cppl.as<uint32_t>(), raw);
-    launch_k10_row_off(st, pair, n_pair, b, n_pts, c->k10_cpoff.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k9_sort(c, raw, crkey, n_pair));
-    launch_k10_low_words(st, crkey, n_pair, c->k10_crpoint.as<uint32_t>());
-    launch_k10_row_off(st, crkey, n_pair, 0, NP, c->k10_croff.as<uint32_t>());
-    launch_k10_points(st, sd, b, n_pts, c->k10_cpoff.as<uint32_t>(), c->k10_cpview.as<uint32_t>(), vis_words,
-                      c->k10_weight.as<float>(), c->k10_vis.as<uint32_t>(), c->k10_npairs.as<unsigned long long>());
-    HIP_TRY(hipGetLastError());
-    {
-      size_t bytes = 0;
-      HIP_TRY(k10_scan_u64(st, nullptr, bytes, c->k10_npairs.as<unsigned long long>(), pair_off, (size_t)n_pts + 1));
-      BUF_TRY(c->k8_tmp.ensure(bytes));
-      HIP_TRY(k10_scan_u64(st, c->k8_tmp.p, bytes, c->k10_npairs.as<unsigned long long>(), pair_off, (size_t)n_pts + 1));
-    }
-    launch_k10_node_keys(st, NP, c->k10_croff.as<uint32_t>(), c->k10_crpoint.as<uint32_t>(), c->k10_nkey[0].as<unsigned long long>());
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k9_sort(c, c->k10_nkey[0].as<unsigned long long>(), c->k10_nkey[1].as<unsigned long long>(), NP));
-    launch_k10_nodes(st, c->ds, c->k10_nkey[1].as<unsigned long long>(), NP, c->k10_nodeof.as<uint32_t>(), c->k10_nodeg.as<uint32_t>(),
-                     c->k10_nodeview.as<uint32_t>(), c->k10_nodepl.as<uint32_t>(), ctr + 1);
-    HIP_TRY(hipGetLastError());
-    {
-      Readback rb(c);
-      const int in = rb.add(ctr + 1, 1);
-      const int ip = rb.add(pair_off + n_pts, 2);
-      BUF_TRY(rb.run());
-      n_nodes = *rb.item(in);
-      n_inst = (uint64_t)rb.item(ip)[0] | ((uint64_t)rb.item(ip)[1] << 32);
-    }
-    K10Graph g;
-    g.seed_begin = b;
-    g.n_pts = n_pts;
-    g.n_pl = NP;
-    g.vis_words = vis_words;
-    g.pair = pair;
-    g.cp_off = c->k10_cpoff.as<uint32_t>();
-    g.cr_off = c->k10_croff.as<uint32_t>();
-    g.cr_point = c->k10_crpoint.as<uint32_t>();
-    g.weight = c->k10_weight.as<float>();
-    g.vis = c->k10_vis.as<uint32_t>();
-    g.node_g = c->k10_nodeg.as<uint32_t>();
-    g.node_view = c->k10_nodeview.as<uint32_t>();
-    // ---- the distinct edges: the cliques a chunk of pair instances at a time, each chunk written behind the distinct keys
-    // so far (k10_edge[0]), the whole sorted (k10_edge[1]) and made distinct again (k10_edge[0])
-    for (uint64_t t0 = 0; t0 < n_inst; t0 += budget) {
-      const uint32_t n = (uint32_t)std::min<uint64_t>(budget, n_inst - t0);
-      const size_t total = (size_t)n_uniq + n;
-      BUF_TRY(c->k10_edge[0].ensure_keep(8 * total, 8 * (size_t)n_uniq, st));
-      BUF_TRY(c->k10_edge[1].ensure(8 * total));
-      unsigned long long* const ek0 = c->k10_edge[0].as<unsigned long long>();
-      unsigned long long* const ek1 = c->k10_edge[1].as<unsigned long long>();
-      launch_k10_expand(st, g, pair_off, c->k10_nodeof.as<uint32_t>(), t0, n, ek0 + n_uniq);
-      HIP_TRY(hipGetLastError());
-      BUF_TRY(k9_sort(c, ek0, ek1, total));
-      size_t bytes = 0;
-      HIP_TRY(k10_unique(st, nullptr, bytes, ek1, ek0, ctr + 2, total));
-      BUF_TRY(c->k8_tmp.ensure(bytes));
-      HIP_TRY(k10_unique(st, c->k8_tmp.p, bytes, ek1, ek0, ctr + 2, total));
-      Readback rb(c);
-      const int iu = rb.add(ctr + 2, 1);
-      BUF_TRY(rb.run());
-      n_uniq = *rb.item(iu);
-      n_chunks++;
-      if (n_uniq >= 0x80000000u) {
-        g_err = "eg3d_similarity_graph: the graph has 2^31 or more distinct edges (adjacency offsets are 32-bit)";
-        return EG3D_ERR_CAPACITY;
-      }
-    }
-    HIP_TRY(hipEventRecord(c->eb[1], st));
-    // ---- the edge weights and the adjacency
-    HIP_TRY(hipEventRecord(c->ea[2], st));
-    BUF_TRY(c->k10_adjoff.ensure(4 * ((size_t)n_nodes + 1)));
-    if (n_uniq) {
-      for (int k = 0; k < 2; k++) {
-        BUF_TRY(c->k10_dkey[k].ensure(16 * (size_t)n_uniq));
-        BUF_TRY(c->k10_dval[k].ensure(8 * (size_t)n_uniq));
-      }
-      launch_k10_edge_weights(st, g, c->k10_edge[0].as<unsigned long long>(), n_uniq, c->k10_dkey[0].as<unsigned long long>(),
-                              c->k10_dval[0].as<uint32_t>(), ctr + 3);
-      HIP_TRY(hipGetLastError());
-      BUF_TRY(k10_sort_pairs(c, c->k10_dkey[0].as<unsigned long long>(), c->k10_dkey[1].as<unsigned long long>(),
-                             c->k10_dval[0].as<uint32_t>(), c->k10_dval[1].as<uint32_t>(), 2 * (size_t)n_uniq));
-      Readback rb(c);
-      const int ik = rb.add(ctr + 3, 1);
-      BUF_TRY(rb.run());
-      n_kept = *rb.item(ik);
-      BUF_TRY(c->k10_adjnode.ensure(8 * std::max<size_t>(n_kept, 1)));
-      launch_k10_low_words(st, c->k10_dkey[1].as<unsigned long long>(), 2 * n_kept, c->k10_adjnode.as<uint32_t>());
-    }
-    // (directed keys that are not kept sort behind every node's: the offsets look at the kept ones only)
-    launch_k10_row_off(st, c->k10_dkey[1].as<unsigned long long>(), 2 * n_kept, 0, n_nodes, c->k10_adjoff.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->eb[2], st));
-  }
-  if (n_sv && NP) {
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&ms_search, c->ea[0], c->eb[0]));
-    HIP_TRY(hipEventElapsedTime(&ms_graph, c->ea[1], c->eb[1]));
-    HIP_TRY(hipEventElapsedTime(&ms_weights, c->ea[2], c->eb[2]));
-  }
-  // ---- the result, library-owned
-  const auto t0 = std::chrono::steady_clock::now();
-  eg3d_simgraph m;
-  memset(&m, 0, sizeof(m));
-  const size_t n_adj = 2 * (size_t)n_kept;
-  auto u32s = [](size_t n) { return (uint32_t*)calloc(std::max<size_t>(n, 1), sizeof(uint32_t)); };
-  m.node_view = u32s(n_nodes);
-  m.node_pl = u32s(n_nodes);
-  m.adj_off = u32s((size_t)n_nodes + 1);
-  m.adj_node = u32s(n_adj);
-  m.adj_w = (float*)u32s(n_adj);
-  m.point_weight = (float*)u32s(n_pts);
-  m.cp_off = u32s((size_t)n_pts + 1);
-  m.cp_view = u32s(n_pair);
-  m.cp_pl = u32s(n_pair);
-  m.cr_off = u32s((size_t)NP + 1);
-  m.cr_point = u32s(n_pair);
-  const bool have = m.node_view && m.node_pl && m.adj_off && m.adj_node && m.adj_w && m.point_weight && m.cp_off && m.cp_view &&
-                    m.cp_pl && m.cr_off && m.cr_point;
-  hipError_t he = hipSuccess;
-  if (have && n_pair) {
-    const struct { void* dst; const void* src; size_t n; } copies[] = {
-        {m.node_view, c->k10_nodeview.p, n_nodes}, {m.node_pl, c->k10_nodepl.p, n_nodes},
-        {m.adj_off, c->k10_adjoff.p, (size_t)n_nodes + 1}, {m.adj_node, c->k10_adjnode.p, n_adj},
-        {m.adj_w, c->k10_dval[1].p, n_adj}, {m.point_weight, c->k10_weight.p, n_pts},
-        {m.cp_off, c->k10_cpoff.p, (size_t)n_pts + 1}, {m.cp_view, c->k10_cpview.p, n_pair}, {m.cp_pl, c->k10_cppl.p, n_pair},
-        {m.cr_off, c->k10_croff.p, (size_t)NP + 1}, {m.cr_point, c->k10_crpoint.p, n_pair}};
-    for (const auto& cp : copies)
-      if (he == hipSuccess && cp.n) he = hipMemcpyAsync(cp.dst, cp.src, sizeof(uint32_t) * cp.n, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = es;
-  }
-  if (!have || he != hipSuccess) {
-    g_err = he != hipSuccess ? std::string("eg3d_similarity_graph: copy to the host: ") + hipGetErrorString(he)
-                             : std::string("eg3d_similarity_graph: out of host memory");
-    eg3d_free_simgraph(&m);
-    return EG3D_ERR_HIP;
-  }
-  m.n_nodes = n_nodes;
-  m.seed_begin = b;
-  m.n_points = n_pts;
-  m.n_polylines = NP;
-  ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = m;
-  if (stats) {
-    stats->struct_size = (uint32_t)sizeof(eg3d_simgraph_stats);
-    stats->n_entries = n_sv;
-    stats->n_nodes = n_nodes;
-    stats->n_edges = n_kept;
-    stats->n_pair_instances = n_inst;
-    stats->n_chunks = n_chunks;
-    stats->ms_grid = ms_grid;
-    stats->ms_search = ms_search;
-    stats->ms_graph = ms_graph;
-    stats->ms_weights = ms_weights;
-    stats->ms_copy = ms_copy;
-  }
-  return EG3D_OK;
-}
-
-// ---- pipeline 1's community detection (K11, eg3d_k11_louvain.hip) ----------------------------------------------------------------
-extern "C" void eg3d_free_communities(eg3d_communities* m) {
-  if (!m) return;
-  free(m->ids);
-  memset(m, 0, sizeof(*m));
-}
-
-static int k11_read_ctr(eg3d_ctx* c, uint64_t* v) {
+  r->n_seeds = e - b;
+  r->sv_base = r->n_seeds ? (*c->h_trk)[b] : 0;
+  r->n_sv = r->n_seeds ? (*c->h_trk)[e] - r->sv_base : 0;
+  r->active = r->n_sv && c->n_pl;
+  if (!r->active) return EG3D_OK;
+  BUF_TRY(ensure_grid10(c, &r->g10, &r->ms_grid));
+  WorkBuf &ctr = c->*ctr_of, &svseed = c->*svseed_of;
+  r->sd = seeds_dev(c);
+  // ---- the view ids, before anything indexes with them
+  BUF_TRY(ctr.ensure(4 * sizeof(uint32_t)));
+  BUF_TRY(svseed.ensure(sizeof(uint32_t) * r->n_sv));
+  HIP_TRY(hipMemsetAsync(ctr.p, 0, 4 * sizeof(uint32_t), c->stream));
+  launch_k9_prep(c->stream, r->sd, c->V, b, r->n_seeds, r->sv_base, svseed.as<uint32_t>(), ctr.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  BUF_TRY(ensure_mailbox(c));
   Readback rb(c);
-  const int it = rb.add(c->k11[K11B_CTR].p, 2 * K11_N_CTR);
+  const int it = rb.add(ctr.p, 1);
   BUF_TRY(rb.run());
-  memcpy(v, rb.item(it), sizeof(uint64_t) * K11_N_CTR);
-  return EG3D_OK;
-}
-// N = inside * M - sum of a_c^2, the squares as four sums of 32-bit limbs
-static __int128 k11_numer(const uint64_t* v, uint64_t M) {
-  unsigned __int128 sq = 0;
-  for (int l = 3; l >= 0; l--) sq = (sq << 32) + v[K11_C_LIMB0 + l];
-  return (__int128)((unsigned __int128)v[K11_C_INSIDE] * M) - (__int128)sq;
-}
-// (key0, vin) -> sorted (key1, val1) -> the distinct keys in key0 with their sums in `sums`; their number in ctr[K11_C_UNIQUE]
-static int k11_sort_reduce(eg3d_ctx* c, const unsigned long long* vin, unsigned long long* sums, size_t n) {
-  unsigned long long* const key0 = c->k11[K11B_KEY0].as<unsigned long long>();
-  unsigned long long* const key1 = c->k11[K11B_KEY1].as<unsigned long long>();
-  unsigned long long* const val1 = c->k11[K11B_VAL1].as<unsigned long long>();
-  unsigned long long* const n_out = c->k11[K11B_CTR].as<unsigned long long>() + K11_C_UNIQUE;
-  size_t bytes = 0;
-  HIP_TRY(k11_sort_pairs(c->stream, nullptr, bytes, key0, key1, vin, val1, n));
-  BUF_TRY(c->k8_tmp.ensure(bytes));
-  HIP_TRY(k11_sort_pairs(c->stream, c->k8_tmp.p, bytes, key0, key1, vin, val1, n));
-  bytes = 0;
-  HIP_TRY(k11_reduce_by_key(c->stream, nullptr, bytes, key1, val1, key0, sums, n_out, n));
-  BUF_TRY(c->k8_tmp.ensure(bytes));
-  HIP_TRY(k11_reduce_by_key(c->stream, c->k8_tmp.p, bytes, key1, val1, key0, sums, n_out, n));
+  if (*rb.item(it) & K9_FLAG_BAD_VIEW) {
+    g_err = std::string(who) + ": view id out of range";
+    return EG3D_ERR_ARG;
+  }
   return EG3D_OK;
 }
 
-extern "C" int eg3d_detect_communities(eg3d_ctx* c, const eg3d_simgraph* g, const eg3d_louvain_params* params, eg3d_communities* out,
-                                       eg3d_louvain_stats* stats) {
-  if (stats && stats->struct_size < sizeof(eg3d_louvain_stats)) {
-    g_err = "eg3d_detect_communities: stats->struct_size is smaller than this library's eg3d_louvain_stats (" +
-            std::to_string(sizeof(eg3d_louvain_stats)) + " bytes): set it to sizeof(eg3d_louvain_stats)";
-    return EG3D_ERR_ARG;
-  }
-  if (params && params->struct_size < sizeof(eg3d_louvain_params)) {
-    g_err = "eg3d_detect_communities: params->struct_size is smaller than this library's eg3d_louvain_params (" +
-            std::to_string(sizeof(eg3d_louvain_params)) + " bytes): set it to sizeof(eg3d_louvain_params)";
-    return EG3D_ERR_ARG;
-  }
-  if (!c || !g || !out) {
-    g_err = "eg3d_detect_communities: bad arguments";
-    return EG3D_ERR_ARG;
-  }
-  const uint32_t n_nodes = g->n_nodes;
-  if (n_nodes && !g->adj_off) {
-    g_err = "eg3d_detect_communities: adj_off is NULL";
-    return EG3D_ERR_ARG;
-  }
-  const uint32_t nnz0 = n_nodes ? g->adj_off[n_nodes] : 0;
-  if (nnz0 && (!g->adj_node || !g->adj_w)) {
-    g_err = "eg3d_detect_communities: adj_node or adj_w is NULL";
-    return EG3D_ERR_ARG;
-  }
-  if (n_nodes >= 0x80000000u || nnz0 >= 0x80000000u) {
-    g_err = "eg3d_detect_communities: 2^31 nodes or directed entries, or more (the integer sums are sized for fewer)";
-    return EG3D_ERR_CAPACITY;
-  }
-  const uint32_t max_phases = params && params->max_phases ? params->max_phases : 200u;
-  const uint32_t max_sweeps = params && params->max_sweeps ? params->max_sweeps : 1000u;
-  const double sweep_thr = params && params->sweep_threshold != 0.0 ? params->sweep_threshold : 1e-6;
-  const double phase_thr = params && params->phase_threshold != 0.0 ? params->phase_threshold : 1e-6;
-  if (!(sweep_thr > 0.0) || !(phase_thr > 0.0)) {
-    g_err = "eg3d_detect_communities: a threshold is negative or not a number";
-    return EG3D_ERR_ARG;
-  }
-  const uint32_t log2_slots = c->louvain_log2_slots ? c->louvain_log2_slots : (uint32_t)__builtin_ctz(K11_DEFAULT_SLOTS);
-  const auto now = [] { return std::chrono::steady_clock::now(); };
-  const auto ms_since = [](std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
-  };
-  uint32_t n_comm = 0, n_phases = 0, n_sweeps = 0;
-  uint64_t n_ovf_total = 0, M = 0;
-  __int128 N = 0;
-  float ms_upload = 0, ms_sweeps = 0, ms_coarsen = 0, ms_copy = 0;
-  if (n_nodes) {
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    BUF_TRY(ensure_mailbox(c));
-    auto t_stage = now();
-    DevBuf* const B = c->k11;
-    const size_t nv = (size_t)n_nodes + 1, ne = std::max<size_t>(nnz0, 1);
-    for (int k : {K11B_OFF0, K11B_OFF1, K11B_C, K11B_T, K11B_SIZE0, K11B_SIZE1, K11B_MEMBER, K11B_MINM, K11B_FLAG, K11B_RANK, K11B_CN,
-                  K11B_OVF, K11B_OCNT, K11B_OOFF})
-      BUF_TRY(B[k].ensure(4 * nv));
-    for (int k : {K11B_K, K11B_A0, K11B_A1, K11B_IDS}) BUF_TRY(B[k].ensure(8 * nv));
-    for (int k : {K11B_NBR0, K11B_NBR1, K11B_EROW0, K11B_EROW1, K11B_W}) BUF_TRY(B[k].ensure(4 * ne));
-    for (int k : {K11B_Q0, K11B_Q1, K11B_KEY0, K11B_KEY1, K11B_VAL0, K11B_VAL1}) BUF_TRY(B[k].ensure(8 * ne));
-    BUF_TRY(B[K11B_CTR].ensure(sizeof(uint64_t) * K11_N_CTR));
-    unsigned long long* const ctr = B[K11B_CTR].as<unsigned long long>();
-    uint64_t v[K11_N_CTR];
-    // ---- the caller's graph and its rules
-    HIP_TRY(hipMemcpyAsync(B[K11B_OFF0].p, g->adj_off, 4 * nv, hipMemcpyHostToDevice, st));
-    if (nnz0) {
-      HIP_TRY(hipMemcpyAsync(B[K11B_NBR0].p, g->adj_node, 4 * (size_t)nnz0, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(B[K11B_W].p, g->adj_w, 4 * (size_t)nnz0, hipMemcpyHostToDevice, st));
+int copy_out(hipStream_t st, const char* who, std::initializer_list<HostCopy> items) {
+  hipError_t e = hipSuccess;
+  bool oom = false;
+  for (const HostCopy& q : items) *q.dst = nullptr;
+  for (const HostCopy& q : items) {
+    const bool copy = q.src && q.bytes;
+    *q.dst = copy ? malloc(q.bytes) : calloc(std::max<size_t>(q.bytes, 1), 1);
+    if (!*q.dst) {
+      oom = true;
+      break;
     }
-    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(uint64_t) * K11_N_CTR, st));
-    launch_k11_validate(st, n_nodes, nnz0, B[K11B_OFF0].as<uint32_t>(), B[K11B_NBR0].as<uint32_t>(), B[K11B_W].as<float>(),
-                        B[K11B_EROW0].as<uint32_t>(), B[K11B_Q0].as<unsigned long long>(), ctr + K11_C_FLAGS);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k11_read_ctr(c, v));
-    if (const uint32_t bad = (uint32_t)v[K11_C_FLAGS]) {
-      const char* what = bad & K11_BAD_OFFSETS     ? "adj_off does not start at 0 or does not ascend"
-                         : bad & K11_BAD_NEIGHBOUR ? "a neighbour id is not below n_nodes"
-                         : bad & K11_SELF_LOOP     ? "a row lists its own node (a self-loop)"
-                         : bad & K11_BAD_ORDER     ? "the neighbours of a row are not strictly ascending"
-                         : bad & K11_BAD_WEIGHT    ? "a weight is not a finite number in (0, 1]"
-                         : bad & K11_ASYMMETRIC    ? "an entry has no reverse entry (the graph is not symmetric)"
-                                                   : "the two directions of an edge carry different weight bits";
-      g_err = std::string("eg3d_detect_communities: ") + what;
-      return EG3D_ERR_ARG;
-    }
-    int cur = 0;
-    const auto csr = [&](int k, uint32_t n, uint32_t nnz) {
-      return K11Csr{n, nnz, B[K11B_OFF0 + k].as<uint32_t>(), B[K11B_NBR0 + k].as<uint32_t>(), B[K11B_EROW0 + k].as<uint32_t>(),
-                    B[K11B_Q0 + k].as<unsigned long long>()};
-    };
-    K11Csr G = csr(cur, n_nodes, nnz0);
-    unsigned long long* const kdeg = B[K11B_K].as<unsigned long long>();
-    uint32_t* C = B[K11B_C].as<uint32_t>();
-    uint32_t* T = B[K11B_T].as<uint32_t>();
-    uint32_t* const member = B[K11B_MEMBER].as<uint32_t>();
-    uint32_t* const Cn = B[K11B_CN].as<uint32_t>();
-    launch_k11_members(st, n_nodes, G.off, member);
-    launch_k11_degrees(st, G, kdeg, C, ctr + K11_C_TOTAL);
-    HIP_TRY(hipGetLastError());
-    BUF_TRY(k11_read_ctr(c, v));
-    M = v[K11_C_TOTAL];
-    const double MM = (double)M * (double)M;
-    ms_upload = ms_since(t_stage);
-    // Renumbers the partition Cp of G by first appearance (Cn) and composes it into `member`; says whether Cp was the identity.
-    const auto renumber = [&](const uint32_t* Cp, uint32_t& n_new, bool& identity) -> int {
-      uint32_t* const minm = B[K11B_MINM].as<uint32_t>();
-      uint32_t* const rank = B[K11B_RANK].as<uint32_t>();
-      HIP_TRY(hipMemsetAsync(minm, 0xFF, 4 * (size_t)G.n, st));
-      HIP_TRY(hipMemsetAsync(ctr + K11_C_NOT_IDENTITY, 0, sizeof(uint64_t), st));
-      launch_k11_min_member(st, G.n, Cp, minm, ctr);
-      launch_k11_first_flags(st, G.n, Cp, minm, G.off, B[K11B_FLAG].as<uint32_t>());
-      HIP_TRY(hipGetLastError());
-      BUF_TRY(k8_scan(c, B[K11B_FLAG].as<uint32_t>(), rank, (size_t)G.n + 1));
-      launch_k11_relabel(st, G.n, Cp, minm, rank, Cn);
-      launch_k11_compose(st, n_nodes, Cn, member);
-      HIP_TRY(hipGetLastError());
-      Readback rb(c);
-      const int ic = rb.add(ctr + K11_C_NOT_IDENTITY, 2);
-      const int ir = rb.add(rank + G.n, 1);
-      BUF_TRY(rb.run());
-      identity = rb.item(ic)[0] == 0 && rb.item(ic)[1] == 0;
-      n_new = *rb.item(ir);
-      return EG3D_OK;
-    };
-    // a / size of the partition P into buffer pair `into`, and the numerator's sums into the counters
-    const auto totals_and_numer = [&](const uint32_t* P, int into) -> int {
-      unsigned long long* const a = B[K11B_A0 + into].as<unsigned long long>();
-      uint32_t* const size = B[K11B_SIZE0 + into].as<uint32_t>();
-      HIP_TRY(hipMemsetAsync(a, 0, 8 * (size_t)G.n, st));
-      HIP_TRY(hipMemsetAsync(size, 0, 4 * (size_t)G.n, st));
-      HIP_TRY(hipMemsetAsync(ctr + K11_C_INSIDE, 0, 5 * sizeof(uint64_t), st));
-      launch_k11_totals(st, G.n, P, kdeg, a, size);
-      launch_k11_inside(st, G, P, ctr);
-      launch_k11_squares(st, G.n, a, ctr);
-      HIP_TRY(hipGetLastError());
-      return k11_read_ctr(c, v);
-    };
-    if (!M) {  // no weight at all: every node with a row alone, numbered in order
-      t_stage = now();
-      bool identity;
-      BUF_TRY(renumber(C, n_comm, identity));
-      ms_coarsen += ms_since(t_stage);
-    }
-    for (uint32_t phase = 1; M && phase <= max_phases; phase++) {
-      t_stage = now();
-      if (phase > 1) launch_k11_degrees(st, G, kdeg, C, ctr + K11_C_TOTAL);  // (k and C = identity; the total is not read again)
-      int ia = 0;  // the buffer pair that holds a / size of C
-      BUF_TRY(totals_and_numer(C, ia));
-      const __int128 N0 = k11_numer(v, M);
-      __int128 Nprev = N0;
-      for (uint32_t sweep = 1; sweep <= max_sweeps; sweep++) {
-        const K11Part P{C, kdeg, B[K11B_A0 + ia].as<unsigned long long>(), B[K11B_SIZE0 + ia].as<uint32_t>(), M};
-        uint32_t* const ovf = B[K11B_OVF].as<uint32_t>();
-        HIP_TRY(hipMemsetAsync(ctr + K11_C_CHANGED, 0, 3 * sizeof(uint64_t), st));
-        launch_k11_targets(st, G, P, log2_slots, T, ovf, ctr);
-        HIP_TRY(hipGetLastError());
-        BUF_TRY(k11_read_ctr(c, v));
-        if (const uint32_t n_ovf = (uint32_t)v[K11_C_OVF_ROWS]) {
-          // rows whose communities do not fit the table: (row, community) keys of all of them, sorted and summed
-          const uint32_t n_oe = (uint32_t)v[K11_C_OVF_ENTRIES];
-          n_ovf_total += n_ovf;
-          launch_k11_ovf_counts(st, G, ovf, n_ovf, B[K11B_OCNT].as<uint32_t>());
-          HIP_TRY(hipGetLastError());
-          BUF_TRY(k8_scan(c, B[K11B_OCNT].as<uint32_t>(), B[K11B_OOFF].as<uint32_t>(), (size_t)n_ovf + 1));
-          launch_k11_ovf_expand(st, G, C, ovf, n_ovf, B[K11B_OOFF].as<uint32_t>(), B[K11B_KEY0].as<unsigned long long>(),
-                                B[K11B_VAL0].as<unsigned long long>());
-          HIP_TRY(hipGetLastError());
-          BUF_TRY(k11_sort_reduce(c, B[K11B_VAL0].as<unsigned long long>(), B[K11B_VAL0].as<unsigned long long>(), n_oe));
-          launch_k11_ovf_targets(st, P, ovf, n_ovf, B[K11B_KEY0].as<unsigned long long>(), B[K11B_VAL0].as<unsigned long long>(),
-                                 ctr + K11_C_UNIQUE, T, ctr);
-          HIP_TRY(hipGetLastError());
-        }
-        n_sweeps++;
-        BUF_TRY(totals_and_numer(T, 1 - ia));
-        if (!v[K11_C_CHANGED]) break;  // T == C
-        const __int128 Nnew = k11_numer(v, M);
-        if ((double)(Nnew - Nprev) < sweep_thr * MM) break;  // (T is dropped)
-        std::swap(C, T);
-        ia = 1 - ia;
-        Nprev = Nnew;
-      }
-      ms_sweeps += ms_since(t_stage);
-      t_stage = now();
-      n_phases++;
-      N = Nprev;
-      bool identity = false;
-      BUF_TRY(renumber(C, n_comm, identity));
-      const bool last = identity || (double)(Nprev - N0) < phase_thr * MM || phase == max_phases;
-      if (!last) {
-        // ---- the coarse graph: the entries keyed by (community of the row, community of the neighbour), sorted and summed
-        launch_k11_coarse_keys(st, G, Cn, B[K11B_KEY0].as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        BUF_TRY(k11_sort_reduce(c, G.q, B[K11B_Q0 + (1 - cur)].as<unsigned long long>(), G.nnz));
-        BUF_TRY(k11_read_ctr(c, v));
-        const uint32_t nnz2 = (uint32_t)v[K11_C_UNIQUE];
-        launch_k11_split_keys(st, B[K11B_KEY0].as<unsigned long long>(), nnz2, B[K11B_EROW0 + (1 - cur)].as<uint32_t>(),
-                              B[K11B_NBR0 + (1 - cur)].as<uint32_t>());
-        launch_k10_row_off(st, B[K11B_KEY0].as<unsigned long long>(), nnz2, 0, n_comm, B[K11B_OFF0 + (1 - cur)].as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        cur = 1 - cur;
-        G = csr(cur, n_comm, nnz2);
-      }
-      ms_coarsen += ms_since(t_stage);
-      if (last) break;
-    }
-    launch_k11_ids(st, n_nodes, member, B[K11B_IDS].as<int64_t>());
-    HIP_TRY(hipGetLastError());
+    if (copy && (e = hipMemcpyAsync(*q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
   }
-  // ---- the result, library-owned
-  const auto t0 = std::chrono::steady_clock::now();
-  int64_t* ids = (int64_t*)calloc(std::max<size_t>(n_nodes, 1), sizeof(int64_t));
-  if (!ids) {
-    g_err = "eg3d_detect_communities: out of host memory";
-    return EG3D_ERR_HIP;
+  const hipError_t es = hipStreamSynchronize(st);  // (also after a failure: no copy may still be writing what is freed)
+  if (e == hipSuccess) e = es;
+  if (!oom && e == hipSuccess) return EG3D_OK;
+  for (const HostCopy& q : items) {
+    free(*q.dst);
+    *q.dst = nullptr;
   }
-  if (n_nodes) {
-    hipError_t he = hipMemcpyAsync(ids, c->k11[K11B_IDS].p, sizeof(int64_t) * n_nodes, hipMemcpyDeviceToHost, c->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-    if (he != hipSuccess) {
-      g_err = std::string("eg3d_detect_communities: copy to the host: ") + hipGetErrorString(he);
-      free(ids);
-      return EG3D_ERR_HIP;
-    }
-  }
-  uint32_t n_isolated = 0;
-  for (uint32_t i = 0; i < n_nodes; i++) n_isolated += ids[i] < 0;
-  ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  out->n_nodes = n_nodes;
-  out->ids = ids;
-  out->n_communities = n_comm;
-  if (stats) {
-    stats->struct_size = (uint32_t)sizeof(eg3d_louvain_stats);
-    stats->n_phases = n_phases;
-    stats->n_sweeps = n_sweeps;
-    stats->n_communities = n_comm;
-    stats->n_isolated = n_isolated;
-    stats->n_overflow_rows = n_ovf_total;
-    stats->total_q = M;
-    stats->numer_hi = (uint64_t)((unsigned __int128)N >> 64);
-    stats->numer_lo = (uint64_t)(unsigned __int128)N;
-    stats->modularity = M ? (double)N / ((double)M * (double)M) : 0.0;
-    stats->ms_upload = ms_upload;
-    stats->ms_sweeps = ms_sweeps;
-    stats->ms_coarsen = ms_coarsen;
-    stats->ms_copy = ms_copy;
-  }
-  return EG3D_OK;
+  g_err = oom ? std::string(who) + ": out of host memory" : std::string(who) + ": copy to the host: " + hipGetErrorString(e);
+  return EG3D_ERR_HIP;
 }
+EG3D_API_END
+
 
 #ifdef EG3D_SECTION_TIMING
 // Tuning diagnostics, present only in builds made with -DEG3D_SECTION_TIMING (tools/section_timing*.py):
