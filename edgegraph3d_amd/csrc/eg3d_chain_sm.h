@@ -1169,8 +1169,8 @@ struct SmEnvSeq {
 // ... with the memory trips of the lane-private loops taken out of the dependent chains (what the engine kernel runs;
 // hostsim mode 3 runs it on the CPU against the oracle)
 struct SmEnvStream : SmEnvSeq {
-  // (the 2-view DLT stays in registers, SmEnvSeq::dlt: with its matrices in lane-private memory — dlt2_mem on a scratch
-  // array, which frees ~80 registers — a decomposition took 150 k clocks, 37 % of the engine's advance phase:
+  // (the 2-view DLT stays in registers, SmEnvSeq::dlt: with its matrices in a lane-private scratch array, which frees
+  // ~80 registers, a decomposition took 150 k clocks, 37 % of the engine's advance phase:
   // profiles/r05_experiments/engine_blocks_c3.txt)
   EG3D_HD int side_walk(const DevScene& s, Chain& c, int view, const PlRef& pl, const Obs& from, uint32_t direction, int lo,
                         int ci, int hi, bool towards_start, Pending* out) const {

@@ -49,10 +49,10 @@ namespace eg3d {
 #define EG3D_STAGE_VTX 512
 #define EG3D_STAGE_EPI 192
 // ---- the 2-view DLT on a GROUP OF 8 LANES (round 6) ---------------------------------------------------------------
-// The one-lane decomposition (svd4_smallest_v_mem) is a stream of ~8 000 vector instructions — ~230 per Jacobi
-// rotation, ~36 rotations — that a wavefront executes for ONE useful lane (a uniform section) or for the few
-// lanes of a look-ahead round: measured with the light timing build it was 19.5 % of k3b_expand's chain clocks on
-// C3' (profiles/r06_experiments/sections_light_c3.txt). Here lane k of the group holds ROW k of A (the four entries
+// The decomposition on one lane (svd4_smallest_v's operations, with the matrices in LDS) was a stream of ~8 000 vector
+// instructions — ~230 per Jacobi rotation, ~36 rotations — that a wavefront executed for ONE useful lane (a uniform
+// section) or for the few lanes of a look-ahead round: measured with the light timing build it was 19.5 % of k3b_expand's
+// chain clocks on C3' (profiles/r06_experiments/sections_light_c3.txt). Here lane k of the group holds ROW k of A (the four entries
 // At[0..3][k]) and, for k < 4, row k of V, in registers: a rotation's update of both columns is then ONE pass over
 // the lanes (6 instructions instead of 84 with their LDS loads and stores), and only what the arithmetic contract
 // orders — the sums over k of the dot product p and of the new squared norms a, b, which every sequential
@@ -237,9 +237,8 @@ struct CoopLds {
       f2 vtx[EG3D_STAGE_VTX];
       float epi[EG3D_STAGE_EPI][4];
     } walk;
-    // the matrices of up to 8 concurrent 2-view DLTs (look-ahead following: one per lane; a uniform section: slot 0)
-    double dlt_work[8][EG3D_DLT_WORK_DOUBLES];
-    // ... or, lane-group form (dlt2_grp8 below): per group of 8 lanes four staging rows for the in-order sums
+    // up to 8 concurrent 2-view DLTs (dlt2_grp8 above; look-ahead following: one per group of 8 lanes; a uniform
+    // section: group 0): per group four staging rows for the in-order sums
     DltGrpLds dltg;
   };
   int32_t la_m[8];               // look-ahead following: observations kept by step j

@@ -173,7 +173,7 @@ EG3D_HD bool add_observation_solve(const DevScene& s, const Chain& c, const Chai
 // the marked parallel sections split items across members, communicating through the chain's
 // scratch slice followed by sync(). TeamSeq (1 member) is the sequential semantics and what the
 // host instantiation uses; the GPU kernel uses a 64-lane wavefront (TeamWave in
-// eg3d_kernels.hip).
+// eg3d_k3b_expand.h).
 //
 // Solver hooks: gn_array() is ONE Gauss-Newton solve inside a uniform section; add_solves() is a
 // batch of B independent ADD solves, request j described by get(j, point, extra) -> wanted and
@@ -193,12 +193,8 @@ struct TeamSeq {
     return 0;
   }
   EG3D_HD uint32_t or_reduce(uint32_t v) const { return v; }
-  // the 2-view DLT of a uniform section (a wavefront team keeps the decomposition's matrices in LDS)
+  // the 2-view DLT of a uniform section (a wavefront team spreads the decomposition over a group of 8 lanes)
   EG3D_HD void dlt(const float* P1, float x1, float y1, const float* P2, float x2, float y2, double X0[3]) const {
-    dlt2(P1, x1, y1, P2, x2, y2, X0);
-  }
-  // ... and the one of the rarely taken 3-subset fallback
-  EG3D_HD void dlt_rare(const float* P1, float x1, float y1, const float* P2, float x2, float y2, double X0[3]) const {
     dlt2(P1, x1, y1, P2, x2, y2, X0);
   }
   // a value every member holds identically (a wavefront team keeps it in scalar registers)
@@ -274,8 +270,9 @@ struct TeamSeq {
     }
   }
 };
-// One member, but routed through the slot-based (parallel-capable) N-view step: lets the host
-// instantiation exercise exactly the code path the 64-lane team runs.
+// One member, but routed through the slot-based N-view step of stepn_chain (walks and triangulations of all starting
+// observations first, then the scan in observation order): the host instantiation checks that this form gives the
+// sequential one's results. No device team runs it: the 64-lane team takes the sequential branch (kSlotStep = false).
 struct TeamSeqSlots : TeamSeq {
   static constexpr bool kSlotStep = true;
 };
@@ -497,16 +494,6 @@ EG3D_HD_FLAT int stepn_chain(const Team& tm, const DevScene& s, Chain& c, const 
   return 0;
 }
 
-EG3D_HD bool new_point_from_list(Chain& c, ChainPt& np, const Obs* list, int m, const float X[3]) {
-  np.X[0] = X[0];
-  np.X[1] = X[1];
-  np.X[2] = X[2];
-  point_init(np);
-  if (!point_reserve(c, np, (uint32_t)m + 1)) return false;
-  for (int i = 0; i < m; i++)
-    if (!pool_append(c, np, list[i])) return false;
-  return true;
-}
 EG3D_HD bool new_point_from_tmp(Chain& c, ChainPt& np, int m, const float X[3]) {
   np.X[0] = X[0];
   np.X[1] = X[1];

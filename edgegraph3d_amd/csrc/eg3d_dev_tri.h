@@ -169,137 +169,6 @@ EG3D_HD void svd4_smallest_v(double At[4][EG3D_DLT_M], double out[4]) {
   for (int k = 0; k < 4; k++) out[k] = Vt[last][k];
 }
 
-// The same decomposition with the matrices in caller-provided MEMORY (work[0 .. 4M) = At, then Vt[16], then W[4]):
-// same operations in the same order => same bits. The expand kernel passes LDS: there the 80 vector registers of the
-// 6x4 form's At / Vt would sit on top of a chain's whole live state and push it out to scratch memory.
-template <class DP>
-EG3D_HD void svd4_smallest_v_mem(DP work, double out[4]) {
-  constexpr int M = EG3D_DLT_M;
-  DP At = work, Vt = work + 4 * M, W = work + 4 * M + 16;
-  for (int i = 0; i < 4; i++)
-    for (int k = 0; k < 4; k++) Vt[i * 4 + k] = (i == k) ? 1.0 : 0.0;
-  const double eps = 2.2204460492503131e-16 * 10;
-  for (int i = 0; i < 4; i++) {
-    double sd = 0;
-    for (int k = 0; k < M; k++) sd += At[i * M + k] * At[i * M + k];
-    W[i] = sd;
-  }
-#pragma unroll 1
-  for (int iter = 0; iter < 30; iter++) {
-    bool changed = false;
-#pragma unroll 1
-    for (int i = 0; i < 3; i++)
-#pragma unroll 1
-      for (int j = i + 1; j < 4; j++) {
-        // the two rows travel to registers ONCE per rotation (one memory round trip, then register arithmetic)
-        double ai[M], aj[M];
-        for (int k = 0; k < M; k++) {
-          ai[k] = At[i * M + k];
-          aj[k] = At[j * M + k];
-        }
-        double a = W[i], p = 0, b = W[j];
-        for (int k = 0; k < M; k++) p += ai[k] * aj[k];
-        {
-          const double ab = a * b, p2 = p * p, t = (eps * eps) * ab;
-          bool skip;
-          if (t > 1e-250 && p2 > t * 1.0000001)
-            skip = false;
-          else if (t > 1e-250 && p2 < t * 0.9999999)
-            skip = true;
-          else
-            skip = absd(p) <= eps * EG3D_SQRT(ab);
-          if (skip) continue;
-        }
-        p *= 2;
-        double beta = a - b, gamma = EG3D_SQRT(p * p + beta * beta);
-        double c, s;
-        if (beta < 0) {
-          double delta = (gamma - beta) * 0.5;
-          s = EG3D_SQRT(delta / gamma);
-          c = p / (gamma * s * 2);
-        } else {
-          c = EG3D_SQRT((gamma + beta) / (gamma * 2));
-          s = p / (gamma * c * 2);
-        }
-        a = 0;
-        b = 0;
-        for (int k = 0; k < M; k++) {
-          double t0 = c * ai[k] + s * aj[k];
-          double t1 = c * aj[k] - s * ai[k];
-          At[i * M + k] = t0;
-          At[j * M + k] = t1;
-          a += t0 * t0;
-          b += t1 * t1;
-        }
-        W[i] = a;
-        W[j] = b;
-        changed = true;
-        for (int k = 0; k < 4; k++) {
-          const double vi = Vt[i * 4 + k], vj = Vt[j * 4 + k];
-          double t0 = c * vi + s * vj;
-          double t1 = c * vj - s * vi;
-          Vt[i * 4 + k] = t0;
-          Vt[j * 4 + k] = t1;
-        }
-      }
-    if (!changed) break;
-  }
-  double Ws[4];
-  for (int i = 0; i < 4; i++) {
-    double sd = 0;
-    for (int k = 0; k < M; k++) sd += At[i * M + k] * At[i * M + k];
-    Ws[i] = EG3D_SQRT(sd);
-  }
-  // descending selection sort; track which row ends up last
-  int order[4] = {0, 1, 2, 3};
-  for (int i = 0; i < 3; i++) {
-    int j = i;
-    for (int k = i + 1; k < 4; k++)
-      if (Ws[j] < Ws[k]) j = k;
-    if (i != j) {
-      double tw = Ws[i];
-      Ws[i] = Ws[j];
-      Ws[j] = tw;
-      int to = order[i];
-      order[i] = order[j];
-      order[j] = to;
-    }
-  }
-  const int last = order[3];
-  for (int k = 0; k < 4; k++) out[k] = Vt[last * 4 + k];
-}
-#define EG3D_DLT_WORK_DOUBLES (4 * EG3D_DLT_M + 16 + 4)
-template <class DP>
-EG3D_HD void dlt2_mem(const float* P1, float x1, float y1, const float* P2, float x2, float y2, DP work, double X0[3]) {
-  constexpr int M = EG3D_DLT_M;
-  {
-    double x = x1, y = y1;
-    for (int k = 0; k < 4; k++) {
-      work[k * M + 0] = x * (double)P1[8 + k] - (double)P1[k];
-      work[k * M + 1] = y * (double)P1[8 + k] - (double)P1[4 + k];
-#if EG3D_DLT_ROWS == 3
-      work[k * M + 2] = x * (double)P1[4 + k] - y * (double)P1[k];
-#endif
-    }
-  }
-  {
-    double x = x2, y = y2;
-    for (int k = 0; k < 4; k++) {
-      work[k * M + EG3D_DLT_ROWS + 0] = x * (double)P2[8 + k] - (double)P2[k];
-      work[k * M + EG3D_DLT_ROWS + 1] = y * (double)P2[8 + k] - (double)P2[4 + k];
-#if EG3D_DLT_ROWS == 3
-      work[k * M + EG3D_DLT_ROWS + 2] = x * (double)P2[4 + k] - y * (double)P2[k];
-#endif
-    }
-  }
-  double v[4];
-  svd4_smallest_v_mem(work, v);
-  float h0 = (float)v[0], h1 = (float)v[1], h2 = (float)v[2], h3 = (float)v[3];
-  X0[0] = (double)(h0 / h3);
-  X0[1] = (double)(h1 / h3);
-  X0[2] = (double)(h2 / h3);
-}
-
 // 2-view DLT: per view the rows x*P(2,:)-P(0,:), y*P(2,:)-P(1,:) [, x*P(1,:)-y*P(0,:)] in double;
 // the homogeneous solution is rounded to float before the float division by w
 // (triangulation.cpp:216-224).

@@ -318,7 +318,7 @@ extern "C" int eg3d_probe_gn_dense(const float* cam_P, int n_views, const int32_
 
 // ---- the lane-group Gauss-Newton solver, request by request (tests/test_gpu_coop_gn.py): one single-wave block per window of
 // up to EG3D_COOP_REQ requests (request j on lane j, lanes without one pass want = false), coop_gn_groups called exactly as
-// k3b_expand calls it, with the template arguments of the product's instantiations (TeamWaveT, eg3d_kernels.hip) taken from
+// k3b_expand calls it, with the template arguments of the product's instantiations (TeamWaveT, eg3d_k3b_expand.h) taken from
 // the same macros. Verdict and solution of every request, and the window's long_refused, go back to the host.
 template <int KEEP, bool LONG_GN, int PRE_IT>
 __global__ void __launch_bounds__(64) k_probe_coop_gn(const float* cam_P, const Obs* obs, const int32_t* req_i, const float* req_f,

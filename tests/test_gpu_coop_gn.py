@@ -2,7 +2,7 @@
 request, against the oracle's one-lane em_GaussNewton — verdict equal, X bit for bit wherever valid. The windows
 (tests/coop_gn_cases.py) are built to reach what whole-pipeline parity only reaches by chance: every packing and group
 boundary, long requests of different lengths in one round, more long requests than a round takes, and a spread of
-convergence inside one window. Each template instantiation the product runs is checked (TeamWaveT, eg3d_kernels.hip), plus
+convergence inside one window. Each template instantiation the product runs is checked (TeamWaveT, eg3d_k3b_expand.h), plus
 the A/B forms its build switches select. The solver does not depend on the DLT form the suite runs twice for."""
 import collections
 import ctypes as C

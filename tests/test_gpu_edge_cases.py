@@ -311,7 +311,7 @@ def test_hypothesis_list_capacity_is_reported_not_truncated(monkeypatch):
 
 def test_slot_pool_size_does_not_matter_and_starvation_fails_loudly(monkeypatch):
     """The working slices of the expand stage are slots of a fixed arena, taken per XCD from a ring of slot ids
-    (eg3d_kernels.hip pool_pop / pool_push). More slots than waves can be resident change nothing; a pool SMALLER than
+    (eg3d_k3b_expand.h pool_pop / pool_push). More slots than waves can be resident change nothing; a pool SMALLER than
     the residency (forced: EG3D_SLOTS_PER_XCD, a test knob) makes the waves queue for the slots of their XCD: the
     cloud is still complete, or — if a wave exhausts its bounded wait — the call fails with an error; never a hang,
     never a cloud with chains missing."""

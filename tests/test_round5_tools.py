@@ -1,9 +1,12 @@
 """CPU-side checks of the round-5 infrastructure: the build guard reads the kernels' resource figures from the built
 library, the structure-tolerant comparator, and the oracle's convention switches (test hook)."""
 import os
+import shutil
+import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 from edgegraph3d_amd import api, build, host
 from oracle import binding as ob
@@ -78,3 +81,19 @@ def test_oracle_convention_switches_are_a_hook_and_default_off():
     assert rep["chains_in_both"] > 10 and rep["share_chains_identical"] > 0.3
     assert rep["points_X_bit_equal"] < rep["points_compared"]          # the start of Gauss-Newton really moved ...
     assert rep["share_points_within_tol"] > 0.99                        # ... and the solutions barely
+
+
+def test_a_removed_expand_switch_on_the_command_line_stops_the_build():
+    """The decided A/B switches of the expand kernel are gone (DESIGN_LOG.md): a variant build that still passes one
+    must fail in the preprocessor instead of building the product and timing it against itself. Preprocessing only."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("no hipcc")
+    cmd = ([hipcc] + [f for f in build.HIP_FLAGS if f != "-shared"]
+           + ["-I", build.INC_DIR, "-I", build.CSRC_DIR, "-I", build.HOST_DIR,
+              "-E", os.path.join(build.CSRC_DIR, "eg3d_kernels.hip"), "-o", os.devnull])
+    r = subprocess.run(cmd + ["-DEG3D_SIDE_WALK_BATCH=1"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    assert r.returncode != 0
+    assert "A/B switches" in r.stderr and "EG3D_SIDE_WALK_BATCH" in r.stderr and "DESIGN_LOG.md" in r.stderr, r.stderr
+    r = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr
