@@ -129,6 +129,45 @@ class LouvainStats(C.Structure):
                 ("ms_coarsen", C.c_float), ("ms_copy", C.c_float)]
 
 
+class FundParams(C.Structure):
+    """eg3d_fund_params: a field of 0 is its default."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("rng_seed", C.c_uint64), ("fit_budget", C.c_uint32),
+                ("stage_points", C.c_uint32)]
+
+
+class FundStats(C.Structure):
+    """eg3d_fund_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_pairs_valid", C.c_uint32), ("n_pairs_failed", C.c_uint32), ("n_chunks", C.c_uint32),
+                ("n_common_total", C.c_uint64), ("n_fits", C.c_uint64), ("n_fits_degenerate", C.c_uint64),
+                ("n_exact_medians", C.c_uint64), ("ms_upload", C.c_float), ("ms_lists", C.c_float), ("ms_samples", C.c_float),
+                ("ms_fits", C.c_float), ("ms_select", C.c_float), ("ms_refit", C.c_float), ("ms_copy", C.c_float)]
+
+
+def fund_call(fn, n_views, seeds, iterations, rng_seed, fit_budget, stage_points):
+    """What api.estimate_fundamental and host.estimate_fundamental share: `fn(n_views, seeds*, params*, F, valid, n_common,
+    stats*)` is the native call (the device index already bound). `seeds` is a POINTER(Seeds) / Seeds, or (trk_off, trk_view,
+    trk_xy). Returns rc, (F [V,V,9] f64, valid [V,V] u8, n_common [V,V] u32, stats dict)."""
+    keep = None
+    if isinstance(seeds, (tuple, list)):
+        off = np.ascontiguousarray(seeds[0], np.uint32)
+        view = np.ascontiguousarray(seeds[1] if len(seeds[1]) else [0], np.int32)
+        xy = np.ascontiguousarray(seeds[2] if len(seeds[2]) else [[0, 0]], np.float32)
+        keep = (off, view, xy)
+        seeds = C.pointer(Seeds(len(off) - 1, np_ptr(off, C.c_uint32), np_ptr(view, C.c_int32), np_ptr(xy, C.c_float)))
+    elif isinstance(seeds, Seeds):
+        seeds = C.pointer(seeds)
+    V = max(int(n_views), 0)
+    F = np.zeros((V, V, 9), np.float64)
+    valid = np.zeros((V, V), np.uint8)
+    ncom = np.zeros((V, V), np.uint32)
+    pr = FundParams(C.sizeof(FundParams), int(iterations), int(rng_seed), int(fit_budget), int(stage_points))
+    st = FundStats()
+    st.struct_size = C.sizeof(FundStats)
+    rc = fn(int(n_views), seeds, C.byref(pr), np_ptr(F, C.c_double), np_ptr(valid, C.c_uint8), np_ptr(ncom, C.c_uint32), C.byref(st))
+    del keep
+    return rc, (F, valid, ncom, {f[0]: getattr(st, f[0]) for f in FundStats._fields_})
+
+
 def simgraph_to_dict(g):
     """Numpy copies of every array of an eg3d_simgraph."""
     nn, npt, npl = int(g.n_nodes), int(g.n_points), int(g.n_polylines)

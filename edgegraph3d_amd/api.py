@@ -83,6 +83,8 @@ def lib():
                                               C.POINTER(D.Communities), C.POINTER(D.LouvainStats)]
         L.eg3d_free_communities.argtypes = [C.POINTER(D.Communities)]
         L.eg3d_free_communities.restype = None
+        L.eg3d_estimate_fundamental.argtypes = [C.c_int, C.c_int32, C.POINTER(D.Seeds), C.POINTER(D.FundParams), D.f64p, D.u8p,
+                                                D.u32p, C.POINTER(D.FundStats)]
         _LIB = L
     return _LIB
 
@@ -95,7 +97,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
     "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
     "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches", "eg3d_similarity_graph", "eg3d_free_simgraph",
-    "eg3d_detect_communities", "eg3d_free_communities",
+    "eg3d_detect_communities", "eg3d_free_communities", "eg3d_estimate_fundamental",
 ]
 
 
@@ -115,6 +117,18 @@ def check_polyline_sets(n_sets, row_off, pl_ids, n_views):
 
 def device_count():
     return int(lib().eg3d_device_count())
+
+
+def estimate_fundamental(n_views, seeds, iterations=0, rng_seed=0, fit_budget=0, stage_points=0, device=0):
+    """SURVEY N4 on the device (eg3d_estimate_fundamental, K12): the fundamental matrices of all ordered view pairs from
+    the tracks, before any Context exists. `seeds` is a seeds pointer (Synth.seeds) or (trk_off, trk_view, trk_xy); 0 in a
+    parameter is its default. Returns (F [V,V,9] f64, valid [V,V] u8, n_common [V,V] u32, stats dict) — bit for bit what
+    host.estimate_fundamental returns."""
+    L = lib()
+    rc, out = D.fund_call(lambda *a: L.eg3d_estimate_fundamental(int(device), *a), n_views, seeds, iterations, rng_seed,
+                          fit_budget, stage_points)
+    _check(rc, "eg3d_estimate_fundamental")
+    return out
 
 
 _HIP = None

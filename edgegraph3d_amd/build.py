@@ -213,6 +213,15 @@ RESOURCE_BOUNDS = {
     # the community detection (eg3d_detect_communities): no spills, no scratch (a substring: all of them). The sweep's hash
     # table is dynamic LDS (sized per launch, not in this figure); the only static LDS is k11_inside's one partial sum per wave
     "k11_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 32},
+    # the fundamental matrices (eg3d_estimate_fundamental): no scratch and no spilled SGPR in any of them, no static LDS (the
+    # selection's staging area is dynamic LDS, sized per launch) ...
+    "k12_": {"sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k12_keys": {"vgpr_spill_count": 0}, "k12_heads": {"vgpr_spill_count": 0}, "k12_compact": {"vgpr_spill_count": 0},
+    "k12_view_off": {"vgpr_spill_count": 0}, "k12_common": {"vgpr_spill_count": 0}, "k12_samples": {"vgpr_spill_count": 0},
+    "k12_select": {"vgpr_spill_count": 0}, "k12_final": {"vgpr_spill_count": 0},
+    # ... and the fit kernel, one wavefront per SIMD with both 9 x 9 matrices of the Jacobi in registers: what does not fit
+    # the 256 VGPRs is parked in AGPRs, which this figure counts (the build reports 90; a margin of a few registers)
+    "k12_fit": {"vgpr_spill_count": 96},
     "k2_epipolar_hits": {"vgpr_spill_count": 0},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }

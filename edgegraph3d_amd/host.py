@@ -262,6 +262,19 @@ def estimate_F(n_views, trk_off, trk_view, trk_xy, estimate=True, rng_seed=0):
     return F, valid, ncom, rc
 
 
+def estimate_fundamental(n_views, seeds, iterations=0, rng_seed=0, fit_budget=0, stage_points=0):
+    """The host statement of api.estimate_fundamental (eg3d_host_estimate_fundamental): the same arguments (fit_budget and
+    stage_points have no meaning here), the same return shape, the same bits — without a GPU."""
+    L = lib()
+    L.eg3d_host_estimate_fundamental.restype = C.c_int
+    L.eg3d_host_estimate_fundamental.argtypes = [C.c_int32, C.POINTER(D.Seeds), C.POINTER(D.FundParams), D.f64p, D.u8p, D.u32p,
+                                                 C.POINTER(D.FundStats)]
+    rc, out = D.fund_call(L.eg3d_host_estimate_fundamental, n_views, seeds, iterations, rng_seed, fit_budget, stage_points)
+    if rc != 0:
+        raise RuntimeError("eg3d_host_estimate_fundamental failed (%d)" % rc)
+    return out
+
+
 def png_edge_mask(path):
     w, h, p = C.c_int(), C.c_int(), D.u8p()
     rc = lib().eg3d_png_read_edge_mask(path.encode(), C.byref(w), C.byref(h), C.byref(p))

@@ -7,7 +7,8 @@
 //                                        with >= 10 common SfM points get a matrix, the others none (exact rule);
 //                                        the matrix is analytic from the cameras by default, or the build's own
 //                                        least-median-of-squares estimate from the tracks with --estimate-F
-//                                        (the reference's cv::findFundamentalMat(FM_LMEDS) is randomised OpenCV
+//                                        (on host threads; with --estimate-F-device too, on the GPU:
+//                                        eg3d_estimate_fundamental) (the reference's cv::findFundamentalMat(FM_LMEDS) is randomised OpenCV
 //                                        code: not reproducible)
 //     -> [pipeline 1] polyline matches of the similarity-graph matcher  (pipelines.cpp:219 -> :68-111)
 //     -> [pipeline 2] polyline matches by closeness to reference points (pipelines.cpp:223 -> :113-158)
@@ -29,7 +30,7 @@
 //   edge_matcher_refpoints --make-plgs <plgs.bin> <edge image 0.png> <edge image 1.png> ...
 //        builds the polyline graph of every binary edge image (view i = i-th image; SURVEY N2,
 //        edge_matcher.cpp:84-94 convert_edge_images_to_optimized_polyline_graphs) and writes the container
-//   edge_matcher_refpoints <dir>/input.json <dir>/plgs.bin <out.json> [--filter] [--estimate-F] [--all-pairs]
+//   edge_matcher_refpoints <dir>/input.json <dir>/plgs.bin <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs]
 //                          [--sets1 <polyline matches of pipeline 1>] [--sets2 <... of pipeline 2> | --match2]
 //        a match file is text: "eg3d-polyline-sets 1", then "<n_sets> <n_views>", then one line per (set, view):
 //        "<count> <polyline id> ..." with view-local ids (the reference's vector<set<ulong>> per match)
@@ -200,10 +201,10 @@ int main(int argc, char** argv) {
   if (argc >= 4 && std::strcmp(argv[1], "--make-synthetic") == 0) return make_synthetic(std::atoi(argv[2]), argv[3]);
   if (argc >= 4 && std::strcmp(argv[1], "--make-plgs") == 0) return make_plgs(argv[2], argc - 3, argv + 3);
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F] [--all-pairs] [--resident-dedup]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup]\n", argv[0]);
     return 2;
   }
-  bool do_filter = false, estimate_F = false, all_pairs = false;
+  bool do_filter = false, estimate_F = false, all_pairs = false, estimate_F_device = false;
   // --resident-dedup: every stage is matched device_only and deduplicated on the device against the claims of the stages
   // before it (eg3d_dedup_resident); only the survivors cross to the host. The output is the default path's, byte for byte.
   bool resident_dedup = false;
@@ -212,6 +213,7 @@ int main(int argc, char** argv) {
     do_filter |= std::strcmp(argv[a], "--filter") == 0;
     estimate_F |= std::strcmp(argv[a], "--estimate-F") == 0;
     all_pairs |= std::strcmp(argv[a], "--all-pairs") == 0;  // analytic F for every pair, ignoring the 10-point rule
+    estimate_F_device |= std::strcmp(argv[a], "--estimate-F-device") == 0;  // with --estimate-F: estimated on the device
     resident_dedup |= std::strcmp(argv[a], "--resident-dedup") == 0;
     if (std::strcmp(argv[a], "--sets1") == 0 && a + 1 < argc) sets_path[0] = argv[++a];
     else if (std::strcmp(argv[a], "--sets2") == 0 && a + 1 < argc) sets_path[1] = argv[++a];
@@ -273,7 +275,19 @@ int main(int argc, char** argv) {
   if (sc.n_views != V) return fail("views of the SfM file and of the polyline graphs differ");
   std::vector<double> F((size_t)V * V * 9);
   std::vector<uint8_t> Fv((size_t)V * V);
-  if (estimate_F) {
+  if (estimate_F && estimate_F_device) {  // the same estimator family on the device (eg3d_estimate_fundamental, K12)
+    eg3d_seeds tracks;
+    eg3d_sfm_seeds(sfm, &tracks);
+    eg3d_fund_params fp;
+    std::memset(&fp, 0, sizeof fp);
+    fp.struct_size = sizeof fp;
+    fp.rng_seed = 0xE63D2018ull;
+    eg3d_fund_stats fs;
+    std::memset(&fs, 0, sizeof fs);
+    fs.struct_size = sizeof fs;
+    if (eg3d_estimate_fundamental(0, V, &tracks, &fp, F.data(), Fv.data(), nullptr, &fs) != EG3D_OK) return fail("fundamental matrices");
+    if (fs.n_pairs_failed) std::printf("%u view pairs: estimate failed, left without a matrix\n", fs.n_pairs_failed);
+  } else if (estimate_F) {
     const int bad = eg3d_sfm_estimate_F(sfm, 1, 0xE63D2018ull, F.data(), Fv.data(), nullptr);
     if (bad < 0) return fail("fundamental matrices");
     if (bad > 0) std::printf("%d view pairs: estimate failed, left without a matrix\n", bad);
@@ -288,7 +302,9 @@ int main(int argc, char** argv) {
   size_t n_pairs = 0;
   for (uint8_t v : Fv) n_pairs += v;
   std::printf("fundamental matrices for %zu of %d ordered view pairs (%s)\n", n_pairs, V * (V - 1),
-              estimate_F ? "least-median-of-squares estimate from the tracks" : "analytic from the cameras");
+              estimate_F && estimate_F_device ? "least-median-of-squares estimate from the tracks, on the device"
+              : estimate_F                    ? "least-median-of-squares estimate from the tracks, on the host"
+                                              : "analytic from the cameras");
   sc.cam_P = eg3d_sfm_cam_P(sfm);
   sc.F = F.data();
   sc.F_valid = Fv.data();

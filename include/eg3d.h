@@ -528,6 +528,41 @@ int eg3d_detect_communities(eg3d_ctx*, const eg3d_simgraph* g, const eg3d_louvai
                             eg3d_louvain_stats* stats);
 void eg3d_free_communities(eg3d_communities*);
 
+/* ---- fundamental matrices from the tracks, on the device (row N4, K12) ---------------------------------------------------
+ * What generate_all_fundamental_matrices does before anything of the path can start: for every ORDERED pair of views the
+ * points seen from both (ascending id; a repeated view id counts once; a point's position on a view is its LAST listed
+ * observation with that id; entries with a view id outside [0, n_views) are ignored), and for pairs with at least 10 of
+ * them a least-median-of-squares estimate over `iterations` normalised 8-point samples with a refit on the inliers. The
+ * arithmetic is stated once, in csrc/eg3d_fund_core.h; include/eg3d_host.h's eg3d_host_estimate_fundamental is its plain
+ * host form and the DEFINITION of the result: F, F_valid, n_common, n_pairs_failed and n_fits_degenerate of the two are
+ * equal bit for bit, on any device, for any fit_budget and stage_points. (It is NOT the arithmetic of
+ * eg3d_host_estimate_F to the bit: the normalisation takes sqrt(dx*dx + dy*dy) where that one calls hypot. Nor is it
+ * OpenCV's LMedS, which is randomised: row N4 stays a documented non-parity.)
+ * The call needs no context — F is part of the scene eg3d_create takes — makes its own stream and buffers on `device` and
+ * frees all of them before it returns; the caller thread's current HIP device is the same after the call as before.
+ * Outputs are the caller's: F [V][V][9] with the convention of eg3d_scene.F (l_j = F[i][j] x_i), F_valid [V][V], n_common [V][V] (may be NULL); a pair without a matrix has F = 0, F_valid = 0.
+ * A pair with >= 10 common points whose every sample is degenerate (or has a non-finite median) counts in n_pairs_failed
+ * and gets F_valid = 0; the call still returns EG3D_OK. The fits of `fit_budget` (pair, iteration)s are held on the device
+ * at a time, in chunks of whole pairs (stats.n_chunks); the selection stages up to `stage_points` common points of a pair
+ * in LDS and reads longer pairs from memory, to the same result.
+ * EG3D_ERR_ARG (outputs and stats untouched): a struct_size smaller than the library's, n_views <= 0, seeds / F / F_valid
+ * NULL, a NULL track array with n_seeds > 0, trk_off not ascending from 0. EG3D_ERR_CAPACITY: more than 8192 views.
+ * EG3D_ERR_NODEVICE / EG3D_ERR_HIP as elsewhere. Any caller thread; concurrent calls are independent. */
+typedef struct eg3d_fund_params { uint32_t struct_size; /* caller sets it; smaller is refused */
+  uint32_t iterations /* 0 = 300 */; uint64_t rng_seed;
+  uint32_t fit_budget   /* fits held on the device at a time; 0 = default (2^20); raised to one pair's worth */;
+  uint32_t stage_points /* common points of a pair staged in LDS; 0 = default (1024, at most 4096); longer pairs are read from memory */;
+} eg3d_fund_params; /* NULL = defaults */
+typedef struct eg3d_fund_stats { uint32_t struct_size; /* caller sets it; smaller is refused */
+  uint32_t n_pairs_valid /* ordered pairs with a matrix */, n_pairs_failed, n_chunks /* 0 on the host */;
+  uint64_t n_common_total /* over the ordered pairs with >= 10 */, n_fits /* sample fits: those pairs x iterations */,
+  n_fits_degenerate /* of the sample fits */, n_exact_medians /* device only: medians the selection had to compute exactly */;
+  float ms_upload, ms_lists, ms_samples, ms_fits, ms_select /* with the inliers and the refit's normal matrix */,
+  ms_refit /* its solve and its median test */, ms_copy; } eg3d_fund_stats;
+int eg3d_estimate_fundamental(int device, int32_t n_views, const eg3d_seeds* seeds, const eg3d_fund_params* params /* NULL = defaults */,
+                              double* F /* [V][V][9] */, uint8_t* F_valid /* [V][V] */, uint32_t* n_common /* [V][V], may be NULL */,
+                              eg3d_fund_stats* stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

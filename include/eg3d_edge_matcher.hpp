@@ -58,6 +58,9 @@ typedef struct edge_matcher_input_params {
 
 struct EdgeMatchingOptions {
   bool estimate_F = false;  // fundamental matrices estimated from the tracks (own LMedS) instead of analytic from the cameras
+  // with estimate_F: the estimate runs on `device` (eg3d_estimate_fundamental, K12) instead of on host threads. The same
+  // estimator family, reproducible to the bit; not the matrices of the host call to the bit (include/eg3d.h). Off by default.
+  bool estimate_F_device = false;
   bool require_images = true;  // the photographs named by the SfM data must exist in images_folder (as parse_images fails without them)
   int device = 0;
   // edge_reconstruction_pipeline (pipelines.cpp:201-246) runs three pipelines; by default this build runs pipeline 3
@@ -286,7 +289,14 @@ inline bool generate_all_fundamental_matrices(const char* sfm_data_file, const S
   }
   std::vector<double> Fm((size_t)V * V * 9, 0.0);
   std::vector<uint8_t> valid((size_t)V * V, 0);
-  if (edge_matching_options().estimate_F) {
+  if (edge_matching_options().estimate_F && edge_matching_options().estimate_F_device) {
+    const eg3d_seeds tracks{(uint32_t)sfmd.numPoints_, off.data(), view.data(), xy.data()};
+    eg3d_fund_params fp{};
+    fp.struct_size = sizeof fp;
+    fp.rng_seed = 0xE63D2018ull;
+    if (eg3d_estimate_fundamental(edge_matching_options().device, V, &tracks, &fp, Fm.data(), valid.data(), nullptr, nullptr) != EG3D_OK)
+      return false;
+  } else if (edge_matching_options().estimate_F) {
     if (eg3d_host_estimate_F(V, (uint64_t)sfmd.numPoints_, off.data(), view.data(), xy.data(), 1, 0xE63D2018ull, Fm.data(), valid.data(),
                              nullptr) < 0)
       return false;

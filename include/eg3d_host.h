@@ -231,6 +231,15 @@ int eg3d_host_estimate_F(int n_views, uint64_t n_points, const uint32_t* trk_off
                          uint8_t* F_valid /* [V][V] */, uint32_t* n_common /* [V][V] or NULL */);
 int eg3d_sfm_estimate_F(const eg3d_sfm* s, int estimate, uint64_t rng_seed, double* F, uint8_t* F_valid,
                         uint32_t* n_common);
+/* The host statement of eg3d_estimate_fundamental (include/eg3d.h), and the definition of its result: the plain,
+ * sequential use of csrc/eg3d_fund_core.h, threaded over the pairs. The same validity rule and counts as
+ * eg3d_host_estimate_F; NOT the same matrices to the bit (its normalisation takes sqrt(dx*dx + dy*dy) instead of hypot,
+ * which makes it reproducible across hosts). Same arguments, outputs and stats as the device call (n_chunks,
+ * n_exact_medians and the times stay 0); EG3D_OK, or EG3D_ERR_ARG with nothing written. What a caller without a GPU uses
+ * to get the same bits. */
+int eg3d_host_estimate_fundamental(int32_t n_views, const eg3d_seeds* seeds, const eg3d_fund_params* params /* NULL = defaults */,
+                                   double* F /* [V][V][9] */, uint8_t* F_valid /* [V][V] */, uint32_t* n_common /* or NULL */,
+                                   eg3d_fund_stats* stats /* or NULL */);
 
 #ifdef __cplusplus
 }
