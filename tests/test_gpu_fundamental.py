@@ -1,7 +1,13 @@
 """-m gpu: eg3d_estimate_fundamental (K12) against its host statement, eg3d_host_estimate_fundamental, BIT FOR BIT: F
 (compared as uint64), F_valid, n_common, n_pairs_failed and n_fits_degenerate. The scenes are the synthetic ones and
 hand-made tracks (no scene is needed: the call has no context). The reference of every input is computed once on the host
-and shared by the two library forms the suite runs against; K12 does not depend on the DLT form."""
+and shared by the two library forms the suite runs against; K12 does not depend on the DLT form.
+
+Both sides of that comparison compile csrc/eg3d_fund_core.h, so it says nothing about the arithmetic. The named inputs of
+tests/fundamental_cases.py are therefore also compared with the independent reference of tests/fundamental_ref.py, within its
+TOL (tests/test_fundamental_ref.py does the same for the host statement and holds Synth(2)). The `bounds` input (n = 10:
+recurring subsets, the selection is tied by construction) and the `hostile` scene (null spaces of more than one dimension)
+stay bit-for-bit only: an independent reference has no single answer there."""
 import ctypes as C
 import os
 import re
@@ -10,8 +16,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import fundamental_cases as fc
 from edgegraph3d_amd import _cdefs as D
 from edgegraph3d_amd import api, host
+from fundamental_cases import full_tracks, rig, tracks
 
 pytestmark = pytest.mark.gpu
 
@@ -49,38 +57,6 @@ def synth_tracks(config):
     s = host.Synth(config)
     off, view, xy = s.seeds_np()
     return s.n_views, (off.copy(), view.copy(), xy.copy())
-
-
-# ---- hand-made tracks ---------------------------------------------------------------------------------------------------------
-def rig(n_views, n_points, seed):
-    """n_points 3-D points in front of n_views cameras on an arc, projected to float32 pixels with 0.3 px noise: xy[v][p]"""
-    rng = np.random.default_rng(seed)
-    X = np.concatenate([rng.uniform(-1.5, 1.5, (n_points, 2)), rng.uniform(5.0, 8.0, (n_points, 1))], 1)
-    xy = np.zeros((n_views, n_points, 2), np.float32)
-    for v in range(n_views):
-        a = 0.12 * v
-        R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-        t = np.array([-0.6 * v, 0.05 * v, 0.1 * v])
-        q = X @ R.T + t
-        xy[v] = (np.stack([900 * q[:, 0] / q[:, 2] + 640, 900 * q[:, 1] / q[:, 2] + 480], 1)
-                 + rng.normal(0, 0.3, (n_points, 2))).astype(np.float32)
-    return xy
-
-
-def tracks(per_point):
-    """per_point: for every point the list of (view, x, y) in track order -> (trk_off, trk_view, trk_xy)"""
-    off, view, xy = [0], [], []
-    for obs in per_point:
-        for v, x, y in obs:
-            view.append(v)
-            xy.append((x, y))
-        off.append(len(view))
-    return (np.asarray(off, np.uint32), np.asarray(view, np.int32), np.asarray(xy, np.float32).reshape(-1, 2))
-
-
-def full_tracks(xy, views_of=None):
-    V, n = xy.shape[:2]
-    return tracks([[(v, xy[v, p, 0], xy[v, p, 1]) for v in (views_of(p) if views_of else range(V))] for p in range(n)])
 
 
 # ---- scenes -------------------------------------------------------------------------------------------------------------------
@@ -174,6 +150,62 @@ def test_staging_and_the_selection_path():
     assert 0 < one[3]["n_exact_medians"] < 300 * 56
     assert one[3]["n_exact_medians"] == mem[3]["n_exact_medians"]
     print("exact medians per pair: %.1f" % (one[3]["n_exact_medians"] / 56.0))
+
+
+# ---- the named cases: the independent reference, and the boundaries of the kernels -------------------------------------------
+def check_case(name, **kw):
+    c = fc.case(name)
+    return check("case_" + name, c["V"], c["seeds"], **fc.kwargs(c), **kw)
+
+
+@pytest.mark.parametrize("name", list(fc.WELL_POSED) + ["synth0"])
+def test_cases_equal_the_independent_reference_and_the_host_bits(name):
+    """n63 .. n129: the wavefront boundaries of the ballot ranks (common points, inliers) and of the strides of 64, with
+    unequal lists (view i the longer one) and equal ones; empty_views: views without observations among 70; stage32,
+    stage_big: around the staging area; v2 / n65: the refit rejected / kept; few_inliers: no refit at all."""
+    got = check_case(name)
+    for (i, j), n in fc.case(name).get("n_common", {}).items():
+        assert got[2][i, j] == got[2][j, i] == n
+    worst, at = fc.assert_close_to_reference(name, got, "device")
+    print("%s: worst max|F - F_ref| / max|F_ref| = %.3g at %s" % (name, worst, at))
+
+
+def test_staging_boundary_31_32_33_points_around_a_staging_area_of_32():
+    one = check_case("stage32")
+    assert sorted({int(n) for n in one[2].ravel()}) == [0, 31, 32, 33] and one[3]["n_pairs_valid"] == 6
+    for stage_points in (32, 31, 33):
+        got = check_case("stage32", stage_points=stage_points)
+        assert np.array_equal(got[0].view(np.uint64), one[0].view(np.uint64)), stage_points
+
+
+@pytest.mark.parametrize("stage_points", [4096, 5000])
+def test_the_largest_staging_area(stage_points):
+    """1100 points: read from memory with the default staging area (1024), staged with the largest one (4096 points, 64 KB
+    of dynamic LDS); a larger request is clamped to it"""
+    one = check_case("stage_big")
+    assert one[2][0, 1] == 1100 and one[1][0, 1] and one[1][1, 0]
+    got = check_case("stage_big", stage_points=stage_points)
+    assert np.array_equal(got[0].view(np.uint64), one[0].view(np.uint64))
+    assert got[3]["n_exact_medians"] == one[3]["n_exact_medians"]
+
+
+def test_rectified_pair_frobenius_branch_and_threshold_clamp():
+    from test_fundamental_ref import rectified_properties
+    c = fc.rectified()
+    F, valid, ncom, st = check("rectified", c["V"], c["seeds"], **fc.kwargs(c))
+    rectified_properties(F, valid)
+
+
+@pytest.mark.parametrize("n,k,rng_seed,ok", fc.NAN_CASES)
+def test_median_among_a_non_finite_majority(n, k, rng_seed, ok):
+    """a handful of non-degenerate fits among 6000; their median is finite (k NaN points below n - n // 2) or 1e300 (from
+    there on: no matrix, although fits exist). The count path runs with best == 1e300, the exact median over keys that are
+    mostly 1e300."""
+    c = fc.nan_majority(n, k, rng_seed)
+    F, valid, ncom, st = check("nan_%d_%d" % (n, k), c["V"], c["seeds"], **fc.kwargs(c))
+    assert valid.tolist() == ([[0, 1], [1, 0]] if ok else [[0, 0], [0, 0]])
+    assert st["n_fits_degenerate"] == 12000 - sum(fc.clean_samples(n, k, rng_seed).values())
+    assert st["n_pairs_failed"] == (0 if ok else 2) and (st["n_exact_medians"] >= 2) == ok
 
 
 def test_two_calls_give_equal_bits_and_all_memory_comes_back():
