@@ -222,7 +222,9 @@ RESOURCE_BOUNDS = {
     # ... and the fit kernel, one wavefront per SIMD with both 9 x 9 matrices of the Jacobi in registers: what does not fit
     # the 256 VGPRs is parked in AGPRs, which this figure counts (the build reports 90; a margin of a few registers)
     "k12_fit": {"vgpr_spill_count": 96},
-    "k2_epipolar_hits": {"vgpr_spill_count": 0},
+    # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
+    # + the workgroup's claim (four counts and the base)
+    "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
 }
 

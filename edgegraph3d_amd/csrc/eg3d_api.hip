@@ -751,6 +751,8 @@ extern "C" int eg3d_clone(eg3d_ctx* parent, eg3d_ctx** out) {
   c->max_pl_vtx = parent->max_pl_vtx;
   c->stage_cap_pts = parent->stage_cap_pts;  // sizing hints only: the clone allocates its own staging area
   c->stage_cap_obs = parent->stage_cap_obs;
+  c->hits_per_list = parent->hits_per_list;
+  c->hits_learned = parent->hits_learned;
   *out = c;
   return EG3D_OK;
 }
@@ -867,9 +869,26 @@ namespace {
 struct BatchState {
   uint32_t b, e, n_seeds, sv_base, n_sv, n_tasks, n_lists, n_hits, n_hyp, n_chains, total_raw;
   uint32_t key0_base;  // added to key[0] of every point (polyline-set path: samples before this batch)
+  bool k2_single_pass;  // seed path: K2 claimed its hits from the cursor of b_ctr; hits_cap slots were there (k2_settle)
+  uint32_t hits_cap;
   StageAView a;
   SeedsDev sd;
 };
+
+// K2 of the seed path, queued on the stream: b_hits with room for B.hits_cap hits, the cursor zeroed.
+int launch_stage_a_k2(eg3d_ctx* c, BatchState& B) {
+  hipStream_t st = c->stream;
+  BUF_TRY(c->b_hits.ensure(sizeof(Obs) * ((size_t)B.hits_cap + 1)));
+  B.a.hits = c->b_hits.as<Obs>();
+  HIP_TRY(hipMemsetAsync(&c->b_ctr.as<Counters>()->hits_used, 0, sizeof(unsigned long long), st));
+  HIP_TRY(hipEventRecord(c->ea[2], st));
+  launch_k2(st, c->ds, B.sd, B.sv_base, B.n_tasks, c->b_task_seed.as<uint32_t>(), c->b_task_entry.as<uint32_t>(),
+            c->b_task_hit.as<uint32_t>(), c->b_task_list_off.as<uint32_t>(), c->b_raw_off.as<uint32_t>(),
+            c->b_cand_pl.as<uint32_t>(), c->b_cand_cnt.as<uint32_t>(), c->b_start_hits.as<Obs>(), c->b_list_cnt.as<uint32_t>(),
+            c->b_list_ptr.as<uint32_t>(), c->b_hits.as<Obs>(), B.hits_cap, c->tune.k2_stage_cap, c->b_ctr.as<Counters>());
+  HIP_TRY(hipEventRecord(c->eb[2], st));
+  return EG3D_OK;
+}
 
 // Stage A: K1 + task enumeration + K2. Leaves everything on the device.
 int run_stage_a(eg3d_ctx* c, BatchState& B, eg3d_stage_times* tm) {
@@ -918,18 +937,13 @@ int run_stage_a(eg3d_ctx* c, BatchState& B, eg3d_stage_times* tm) {
   BUF_TRY(c->b_list_cnt.ensure(sizeof(uint32_t) * (B.n_lists + 1)));
   BUF_TRY(c->b_list_ptr.ensure(sizeof(uint32_t) * (B.n_lists + 1)));
   HIP_TRY(hipMemsetAsync(c->b_list_cnt.as<uint32_t>() + B.n_lists, 0, sizeof(uint32_t), st));
-  HIP_TRY(hipEventRecord(c->ea[2], st));
-  launch_k2(st, false, c->ds, B.sd, B.b, B.n_seeds, B.sv_base, nt, c->b_task_off.as<uint32_t>(),
-            c->b_task_seed.as<uint32_t>(), c->b_task_entry.as<uint32_t>(), c->b_task_hit.as<uint32_t>(), c->b_task_list_off.as<uint32_t>(), c->b_raw_off.as<uint32_t>(),
-            c->b_cand_pl.as<uint32_t>(), c->b_cand_cnt.as<uint32_t>(), c->b_start_hits.as<Obs>(),
-            c->b_list_cnt.as<uint32_t>(), nullptr, nullptr);
-  BUF_TRY(scan_total_u32(c, c->b_list_cnt.as<uint32_t>(), c->b_list_ptr.as<uint32_t>(), B.n_lists + 1, B.n_hits, "epipolar hits"));
-  BUF_TRY(c->b_hits.ensure(sizeof(Obs) * (B.n_hits + 1)));
-  launch_k2(st, true, c->ds, B.sd, B.b, B.n_seeds, B.sv_base, nt, c->b_task_off.as<uint32_t>(),
-            c->b_task_seed.as<uint32_t>(), c->b_task_entry.as<uint32_t>(), c->b_task_hit.as<uint32_t>(), c->b_task_list_off.as<uint32_t>(), c->b_raw_off.as<uint32_t>(),
-            c->b_cand_pl.as<uint32_t>(), c->b_cand_cnt.as<uint32_t>(), c->b_start_hits.as<Obs>(),
-            c->b_list_cnt.as<uint32_t>(), c->b_list_ptr.as<uint32_t>(), c->b_hits.as<Obs>());
-  HIP_TRY(hipEventRecord(c->eb[2], st));
+  // b_hits: what the earlier calls of this context needed per list, or a first guess (C3' has 2.6 hits per list); K2
+  // finds out whether it was enough (k2_settle)
+  const uint64_t want = c->tune.hits_cap0 && !c->hits_learned ? c->tune.hits_cap0 : (uint64_t)((double)B.n_lists * c->hits_per_list) + 4096;
+  B.hits_cap = (uint32_t)std::min<uint64_t>(want, 0xffffffffull);
+  B.k2_single_pass = true;
+  B.n_hits = 0;
+  BUF_TRY(launch_stage_a_k2(c, B));
   StageAView& a = B.a;
   a.trk_off = B.sd.trk_off;
   a.trk_view = B.sd.trk_view;
@@ -946,6 +960,25 @@ int run_stage_a(eg3d_ctx* c, BatchState& B, eg3d_stage_times* tm) {
   a.hits = c->b_hits.as<Obs>();
   (void)tm;
   return EG3D_OK;
+}
+
+// K2's verdict on the size of b_hits, from the cursor value `used` a read-back brought (B.k2_single_pass). Enough: notes
+// what the next call should reserve, *again = false. Not enough: enlarges b_hits to what K2 asked for plus a margin and
+// queues K2 again; nothing has read the hits yet, and whatever was derived from the list counts is queued again by the caller.
+int k2_settle(eg3d_ctx* c, BatchState& B, unsigned long long used, bool* again) {
+  *again = false;
+  if (used > 0xffffffffull) return wrapped_error("epipolar hits");
+  if (used <= B.hits_cap) {
+    B.n_hits = (uint32_t)used;
+    if (B.n_lists) c->hits_per_list = std::max(c->hits_per_list, 1.0625 * (double)used / (double)B.n_lists);
+    c->hits_learned = true;
+    return EG3D_OK;
+  }
+  if (c->tune.trace_arena)
+    fprintf(stderr, "eg3d: epipolar hits: %llu claimed of %u: the buffer is enlarged and K2 runs again\n", used, B.hits_cap);
+  B.hits_cap = (uint32_t)std::min<unsigned long long>(used + used / 16 + 64, 0xffffffffull);
+  *again = true;
+  return launch_stage_a_k2(c, B);
 }
 
 // Caller-bound output arrays: malloc/realloc'ed runs that are handed to the caller as they are
@@ -1141,10 +1174,30 @@ int run_stage_b(eg3d_ctx* c, BatchState& B, UnitTurn& T, HostOut& H) {
   BUF_TRY(c->b_tasks.ensure(sizeof(TaskDesc) * (nt + 1)));
   BUF_TRY(c->b_nhyp.ensure(sizeof(uint32_t) * (nt + 1)));
   BUF_TRY(c->b_hyp_off.ensure(sizeof(uint32_t) * (nt + 1)));
-  HIP_TRY(hipMemsetAsync(c->b_nhyp.as<uint32_t>() + nt, 0, sizeof(uint32_t), st));
-  launch_task_setup(st, B.a, c->b_map_view.as<int32_t>(), c->b_map_entry.as<uint32_t>(), c->b_map_n.as<uint32_t>(),
-                    c->b_tasks.as<TaskDesc>(), c->b_nhyp.as<uint32_t>());
-  BUF_TRY(scan_total_u32(c, c->b_nhyp.as<uint32_t>(), c->b_hyp_off.as<uint32_t>(), nt + 1, B.n_hyp, "hypotheses"));
+  // The number of hypotheses and K2's cursor (seed path) come back in ONE read-back. A b_hits that was too small shows
+  // here, before anything has read a hit: K2 runs again with room (k2_settle), and the task setup behind it.
+  for (;;) {
+    HIP_TRY(hipMemsetAsync(c->b_nhyp.as<uint32_t>() + nt, 0, sizeof(uint32_t), st));
+    launch_task_setup(st, B.a, c->b_map_view.as<int32_t>(), c->b_map_entry.as<uint32_t>(), c->b_map_n.as<uint32_t>(),
+                      c->b_tasks.as<TaskDesc>(), c->b_nhyp.as<uint32_t>());
+    BUF_TRY(scan_queue_u32(c, c->b_nhyp.as<uint32_t>(), c->b_hyp_off.as<uint32_t>(), nt + 1, 0));
+    Readback rb(c);
+    const int it = rb.add(c->b_hyp_off.as<uint32_t>() + nt, 1);
+    const int iw = rb.add(c->b_scanchk.as<uint32_t>(), 1);
+    const int ih = B.k2_single_pass ? rb.add(&c->b_ctr.as<Counters>()->hits_used, 2) : -1;
+    rb.clear_after(c->b_scanchk.as<uint32_t>());
+    BUF_TRY(rb.run());
+    bool again = false;
+    if (ih >= 0) {
+      unsigned long long used;
+      memcpy(&used, rb.item(ih), sizeof(used));
+      BUF_TRY(k2_settle(c, B, used, &again));
+    }
+    if (again) continue;
+    if (*rb.item(iw)) return wrapped_error("hypotheses");
+    B.n_hyp = *rb.item(it);
+    break;
+  }
   // ---- K3a
   BUF_TRY(c->b_res.ensure(sizeof(HypResult) * (B.n_hyp + 1)));
   // K3a engine (eg3d_k3a_engine.h): single-wavefront blocks; the lanes of a wave that take work are limited when there
@@ -1764,6 +1817,8 @@ static void lane_share_inputs(eg3d_ctx* owner, eg3d_ctx* l) {
   l->chain_cap = std::max(l->chain_cap, owner->chain_cap);
   l->pool_cap = std::max(l->pool_cap, owner->pool_cap);
   l->arena_per_hyp = std::max(l->arena_per_hyp, owner->arena_per_hyp);
+  l->hits_per_list = std::max(l->hits_per_list, owner->hits_per_list);
+  l->hits_learned = l->hits_learned || owner->hits_learned;
   l->k3b_long_latched = l->k3b_long_latched || owner->k3b_long_latched;
 }
 static void lane_return_learned(eg3d_ctx* owner, const eg3d_ctx* l) {
@@ -1771,6 +1826,8 @@ static void lane_return_learned(eg3d_ctx* owner, const eg3d_ctx* l) {
   owner->chain_cap = std::max(l->chain_cap, owner->chain_cap);
   owner->pool_cap = std::max(l->pool_cap, owner->pool_cap);
   owner->arena_per_hyp = std::max(l->arena_per_hyp, owner->arena_per_hyp);
+  owner->hits_per_list = std::max(l->hits_per_list, owner->hits_per_list);
+  owner->hits_learned = l->hits_learned || owner->hits_learned;
   owner->k3b_long_latched = l->k3b_long_latched || owner->k3b_long_latched;
 }
 static int ensure_lanes(eg3d_ctx* c, int n) {
@@ -2179,7 +2236,12 @@ extern "C" int eg3d_candidates_run(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_
   B.b = b;
   B.e = e;
   BUF_TRY(run_stage_a(c, B, nullptr));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (bool again = true; again;) {
+    unsigned long long used = 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(&used, &c->b_ctr.as<Counters>()->hits_used, sizeof(used), hipMemcpyDeviceToHost));
+    BUF_TRY(k2_settle(c, B, used, &again));
+  }
   const uint32_t n_sv = B.n_sv, nt = B.n_tasks;
   std::vector<uint32_t> raw_off(n_sv + 1), cand_cnt(n_sv + 1), start_cnt(n_sv + 1), cand_pl(B.total_raw + 1),
       task_seed(nt + 1), task_entry(nt + 1), task_hit(nt + 1), task_list_off(nt + 1), list_cnt(B.n_lists + 1),
@@ -2197,7 +2259,7 @@ extern "C" int eg3d_candidates_run(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_
   DL(task_hit, b_task_hit, nt);
   DL(task_list_off, b_task_list_off, nt + 1);
   DL(list_cnt, b_list_cnt, B.n_lists);
-  DL(list_ptr, b_list_ptr, B.n_lists + 1);
+  DL(list_ptr, b_list_ptr, B.n_lists);
   DL(hits, b_hits, B.n_hits);
 #undef DL
   std::vector<uint32_t> o_cand_off(1, 0), o_cand_pl, o_start_off(1, 0), o_start_pl, o_start_seg, o_task_sv(nt),
@@ -2216,14 +2278,20 @@ extern "C" int eg3d_candidates_run(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_
     o_start_off.push_back((uint32_t)o_start_pl.size());
   }
   for (uint32_t t = 0; t < nt; t++) o_task_sv[t] = (*c->h_trk)[task_seed[t]] - B.sv_base + task_entry[t];
-  for (uint32_t h = 0; h < B.n_hits; h++) {
-    o_hit_pl[h] = hits[h].pl;
-    o_hit_seg[h] = hits[h].seg;
-    o_hit_xy[2 * h] = hits[h].x;
-    o_hit_xy[2 * h + 1] = hits[h].y;
+  // the tasks' regions of b_hits lie in the order the tasks claimed them: gathered here in (task, list) order, the CSR
+  // from the counts
+  std::vector<uint32_t> list_off(B.n_lists + 1, 0);
+  for (uint32_t l = 0, h = 0; l < B.n_lists; l++) {
+    for (uint32_t i = 0; i < list_cnt[l]; i++, h++) {
+      const Obs& o = hits[list_ptr[l] + i];
+      o_hit_pl[h] = o.pl;
+      o_hit_seg[h] = o.seg;
+      o_hit_xy[2 * h] = o.x;
+      o_hit_xy[2 * h + 1] = o.y;
+    }
+    list_off[l + 1] = h;
   }
   task_hit.resize(nt);
-  list_ptr.resize(B.n_lists + 1);
   task_list_off.resize(nt + 1);
   out->n_sv = n_sv;
   out->cand_off = dup_to_malloc(o_cand_off);
@@ -2236,7 +2304,7 @@ extern "C" int eg3d_candidates_run(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_
   out->task_sv = dup_to_malloc(o_task_sv);
   out->task_hit = dup_to_malloc(task_hit);
   out->task_list_off = dup_to_malloc(task_list_off);
-  out->list_off = dup_to_malloc(list_ptr);  // the exclusive scan of the counts is the CSR
+  out->list_off = dup_to_malloc(list_off);
   out->hit_pl = dup_to_malloc(o_hit_pl);
   out->hit_seg = dup_to_malloc(o_hit_seg);
   out->hit_xy = dup_to_malloc(o_hit_xy);
@@ -2480,7 +2548,7 @@ extern "C" int eg3d_probe_hyp_sections(eg3d_ctx* c, double* sum, double* slowest
     if (r[h].status & HYP_TRI) counts[1]++;
     if (r[h].status & HYP_D1) counts[2]++;
     if (r[h].status & HYP_D2) counts[3]++;
-    if (r[h].status & HYP_COMPAT) counts[4]++;
+    if (hyp_compatible(r[h].status, r[h].n1, r[h].n2)) counts[4]++;
     // list lengths (the per-section tick fields were retired): sum[0..1] = total n1, n2;
     // slowest[0..1] = longest n1, n2; sum[2] = hypotheses whose lists total >= 32 points
     sum[0] += r[h].n1;

@@ -144,6 +144,9 @@ struct HostGrids {
 //   EG3D_SLOTS_PER_XCD=n   tests: working slices of the expand stage per XCD (default: what can be resident + margin)
 //   EG3D_TRACE_ARENA=1     print the hypothesis arena's use per batch to stderr
 //   EG3D_ARENA_CAP0=n      initial hypothesis arena capacity (tests: forces the overflow-and-retry path)
+//   EG3D_K2_STAGE_CAP=n    tests: hits a wave of K2 stages in LDS (1 .. 128, default 128); a task with more sweeps twice
+//   EG3D_HITS_CAP0=n       tests: capacity of the epipolar-hit buffer until a K2 launch of the context has fitted (forces the
+//                          enlarge-and-run-again path)
 //   EG3D_MAX_SCRATCH_MB=n  tests: cut the chains of a batch into several K3b launches of at most n MB / slice size
 //                          chains each (default: one launch takes all chains — their working slices are slots)
 //   EG3D_NO_LPT=1          launch chains in identity order instead of longest-first (diagnostic)
@@ -181,6 +184,10 @@ struct Tunables {
   uint32_t arena_cap0 = 0, hyp_cap = 0;
   uint32_t chain_cap0 = 0, pool_cap0 = 0;  // EG3D_CHAIN_CAP0 / EG3D_POOL_CAP0 (tests): initial points / observation slots per chain,
                                            // small enough to force the relaunch-what-overflowed path several times
+  uint32_t k2_stage_cap = EG3D_K2_STAGE_MAX;  // EG3D_K2_STAGE_CAP (tests): hits a wave of K2 stages in LDS, 1 .. EG3D_K2_STAGE_MAX;
+                                              // a task with more takes the count-claim-write route
+  uint32_t hits_cap0 = 0;  // EG3D_HITS_CAP0 (tests): capacity of the epipolar-hit buffer until a K2 launch of the context has
+                           // fitted, small enough to force the enlarge-and-rerun path (0 = the first guess of run_stage_a)
   size_t max_scratch = 0;  // 0 = no limit
   uint32_t slots_per_xcd = 0;  // 0 = sized from the occupancy query
   bool use_lpt = true;
@@ -196,6 +203,8 @@ struct Tunables {
     if (const char* e = getenv("EG3D_ARENA_CAP0")) t.arena_cap0 = (uint32_t)std::max(16, atoi(e));
     if (const char* e = getenv("EG3D_CHAIN_CAP0")) t.chain_cap0 = (uint32_t)std::max(8, atoi(e));
     if (const char* e = getenv("EG3D_POOL_CAP0")) t.pool_cap0 = (uint32_t)std::max(64, atoi(e));
+    if (const char* e = getenv("EG3D_K2_STAGE_CAP")) t.k2_stage_cap = (uint32_t)std::min<int>(EG3D_K2_STAGE_MAX, std::max(1, atoi(e)));
+    if (const char* e = getenv("EG3D_HITS_CAP0")) t.hits_cap0 = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("EG3D_MAX_SCRATCH_MB")) t.max_scratch = (size_t)std::max(1, atoi(e)) << 20;
     if (const char* e = getenv("EG3D_NO_LPT")) t.use_lpt = !(e[0] == '1');
     if (const char* e = getenv("EG3D_TRACE_ARENA")) t.trace_arena = e[0] == '1';
@@ -292,6 +301,8 @@ struct eg3d_ctx {
   bool k3b_long_latched = false; // a launch of a few-views build met a solve of > 32 rows: the context runs the general builds from then on
   uint32_t max_pl_vtx = 0;  // vertices of the scene's longest valid polyline
   uint64_t stage_cap_pts = 0, stage_cap_obs = 0;
+  double hits_per_list = 4.0;  // epipolar-hit buffer: hits per list to reserve (learned from what K2 claimed; run_stage_a)
+  bool hits_learned = false;   // a K2 launch of this context (or of one it shares what it learned with) has fitted its buffer
   hipEvent_t ea[8], eb[8];  // begin/end events per stage: 1 K1, 2 K2, 3 K3a, 4 K3s, 5 K3b, 6 K4, 0 misc, 7 whole call
   hipEvent_t ecopy[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // D2H of the cloud: one per ring buffer (EG3D_D2H_RING <= 7)
   uint32_t chain_cap = 384, pool_cap = 0, hyp_cap = 160;

@@ -164,7 +164,7 @@ EG3D_HD bool select_task(const HypResult* res, uint32_t h0, uint32_t h1, ChainSe
   for (uint32_t h = h0; h < h1; h++) {
     const uint32_t st = res[h].status;
     if (st & HYP_D2) last_d2 = h;
-    if (st & HYP_COMPAT) {
+    if (hyp_compatible(st, res[h].n1, res[h].n2)) {
       if (winner != 0xffffffffu) return false;
       winner = h;
       src = last_d2;  // == h when the winner's own direction 2 is valid

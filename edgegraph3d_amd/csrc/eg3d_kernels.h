@@ -43,6 +43,7 @@ struct Counters {
   unsigned long long bytes;  // algorithmic bytes of polyline vertices touched
   uint32_t max_chain_ticks;  // k3b_expand: the longest time one chain held its wavefront (ticks of the constant-rate clock, wall_clock64)
   uint32_t pad_;
+  unsigned long long hits_used;  // k2_epipolar_hits: the cursor the tasks claim their region of the hits from
 };
 
 void launch_seed_prep(hipStream_t st, SeedsDev sd, uint32_t seed_begin, uint32_t n_seeds, uint32_t sv_base,
@@ -55,15 +56,14 @@ void launch_k1(hipStream_t st, DevScene s, SeedsDev sd, uint32_t sv_base, uint32
 void launch_task_fill(hipStream_t st, SeedsDev sd, uint32_t sv_base, uint32_t n_sv, const uint32_t* sv_seed,
                       const uint32_t* start_cnt, const uint32_t* task_off, uint32_t* task_seed, uint32_t* task_entry,
                       uint32_t* task_hit, uint32_t* task_k, const uint32_t* sv_vtx, Counters* ctr);
-#ifndef EG3D_K2_LDS
-#define EG3D_K2_LDS 0
-#endif
-// EG3D_K2_LDS=0 (default): one wavefront per task. =1: one workgroup per seed of [seed_begin, seed_begin + n_seeds)
-// with the candidate polylines staged in LDS; task_off = first task of each (seed, track entry).
-void launch_k2(hipStream_t st, bool fill, DevScene s, SeedsDev sd, uint32_t seed_begin, uint32_t n_seeds, uint32_t sv_base,
-               uint32_t n_tasks, const uint32_t* task_off, const uint32_t* task_seed, const uint32_t* task_entry,
-               const uint32_t* task_hit, const uint32_t* task_list_off, const uint32_t* raw_off, const uint32_t* cand_pl,
-               const uint32_t* cand_cnt, const Obs* start_hits, uint32_t* list_cnt, const uint32_t* list_ptr, Obs* hits);
+// K2 in one pass (eg3d_kernels.hip): one wavefront per task stages the task's hits in LDS (stage_cap <= EG3D_K2_STAGE_MAX per
+// wave), claims its region of `hits` from ctr->hits_used (zeroed by the caller) and writes list_cnt, list_ptr and the hits.
+// ctr->hits_used > hits_cap afterwards: `hits` was too small and is incomplete; enlarge it and launch again.
+#define EG3D_K2_STAGE_MAX 128u
+void launch_k2(hipStream_t st, DevScene s, SeedsDev sd, uint32_t sv_base, uint32_t n_tasks, const uint32_t* task_seed,
+               const uint32_t* task_entry, const uint32_t* task_hit, const uint32_t* task_list_off, const uint32_t* raw_off,
+               const uint32_t* cand_pl, const uint32_t* cand_cnt, const Obs* start_hits, uint32_t* list_cnt, uint32_t* list_ptr,
+               Obs* hits, uint32_t hits_cap, uint32_t stage_cap, Counters* ctr);
 // ---- pipelines 1-2 extractor: sets of potentially compatible polylines -> tasks ----
 // CSR over rows (set * V + view) of view-local polyline ids, ascending per row (device copies).
 struct SetsDev {

@@ -323,48 +323,50 @@ __global__ void k_task_fill(SeedsDev sd, uint32_t sv_base, uint32_t n_sv, const 
 }
 
 // ------------------------------------------------------------------ K2 ---------
-// One wavefront per task. For every other track entry: epipolar line of the start hit, then
-// all 64 lanes test consecutive segments of each candidate polyline; hits inside the
-// detection radius are compacted in segment order with __ballot + popcount. FILL=false
-// counts, FILL=true writes to the offsets produced by the scan of the counts.
-template <bool FILL>
-__global__ void __launch_bounds__(256) k2_epipolar_hits(DevScene s, SeedsDev sd, uint32_t sv_base, uint32_t n_tasks,
-                                                       const uint32_t* task_seed, const uint32_t* task_entry,
-                                                       const uint32_t* task_hit, const uint32_t* task_list_off,
-                                                       const uint32_t* raw_off, const uint32_t* cand_pl,
-                                                       const uint32_t* cand_cnt, const Obs* start_hits,
-                                                       uint32_t* list_cnt, const uint32_t* list_ptr, Obs* hits) {
-  const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  if (t >= n_tasks) return;
-  const uint32_t seed = task_seed[t], ea = task_entry[t], h = task_hit[t];
-  const uint32_t t0 = sd.trk_off[seed], k = sd.trk_off[seed + 1] - t0;
-  const uint32_t sv0 = t0 - sv_base;
-  const Obs hit = start_hits[raw_off[sv0 + ea] + h];
-  const int32_t start_view = sd.trk_view[t0 + ea];
-  float ix, iy;
-  seed_obs_in_view(sd, t0, k, start_view, ix, iy);
-  const float radius = dist(ix, iy, hit.x, hit.y) * 3.0f;
-  const float detsq = radius * radius;
-  const uint32_t lo = task_list_off[t];
-  const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  for (uint32_t i = 0; i < k; i++) {
+// One wavefront per task, ONE pass. For every other track entry: epipolar line of the start hit, then all 64 lanes test
+// consecutive segments of each candidate polyline; hits inside the detection radius are compacted in segment order with
+// __ballot + popcount. Where the hits of a task land in `hits` is decided only once the task knows how many it has, so
+// the sweep over the lists writes them to a per-wave LDS stage of `cap` <= EG3D_K2_STAGE_MAX hits; the four tasks of a
+// workgroup then claim their regions together, in task order, with ONE atomicAdd on the context's cursor
+// (Counters::hits_used), and every wave copies its stage out behind its claim. (One atomicAdd per task was measured first:
+// C3' has 119 k tasks per step, the returning atomics on the one address went through the memory side one at a time, and
+// the kernel took 1.47 ms - as long as both passes of the two-pass form - with 41 % fewer instructions.) A task that outgrows the
+// stage (or has more than 64 lists: the staged form keeps the count of list i in lane i) has been counted by that sweep
+// all the same; it claims, then sweeps again and writes straight to its region (DIRECT). The order of the tasks' regions
+// in `hits` depends on timing: everything downstream addresses hits through (list_ptr[l], list_cnt[l]) only.
+// A claim that ends beyond hits_cap writes no hit; the host sees the cursor in its next read-back, before anything has
+// read `hits`, enlarges the buffer and launches K2 again (run_stage_b).
+struct K2Task {
+  uint32_t t0, k, sv0, lo, lane;
+  int32_t start_view;
+  Obs hit;
+  float detsq;
+  unsigned long long lt_mask;
+};
+// DIRECT=false: hit number p of the task -> dst[p] (the LDS stage) while p < limit; count of list i -> list_cnt and lane
+// i & 63's my_cnt. DIRECT=true: dst = the task's region of `hits`, first hit of list i -> list_ptr. Returns the task's hits.
+template <bool DIRECT>
+__device__ __forceinline__ uint32_t k2_sweep(const DevScene& s, const SeedsDev& sd, const K2Task& T, const uint32_t* raw_off,
+                                             const uint32_t* cand_pl, const uint32_t* cand_cnt, Obs* dst, uint32_t limit,
+                                             uint32_t base, uint32_t* list_cnt, uint32_t* list_ptr, uint32_t& my_cnt) {
+  const uint32_t lane = T.lane, t0 = T.t0;
+  uint32_t tot = 0;
+  for (uint32_t i = 0; i < T.k; i++) {
     const int32_t cur_view = sd.trk_view[t0 + i];
     uint32_t cnt = 0;
-    if (cur_view == start_view) {
+    if (DIRECT && lane == 0) list_ptr[T.lo + i] = base + tot;
+    if (cur_view == T.start_view) {
       cnt = 1;
-      if (FILL && lane == 0) {
-        Obs o = hit;
+      if (lane == 0 && tot < limit) {
+        Obs o = T.hit;
         o.view = cur_view;
-        hits[list_ptr[lo + i]] = o;
+        dst[tot] = o;
       }
     } else {
       float la, lb, lc;
-      if (epiline(s.F, s.F_valid, s.n_views, start_view, cur_view, hit.x, hit.y, la, lb, lc)) {
+      if (epiline(s.F, s.F_valid, s.n_views, T.start_view, cur_view, T.hit.x, T.hit.y, la, lb, lc)) {
         const float sx = sd.trk_xy[2 * (t0 + i)], sy = sd.trk_xy[2 * (t0 + i) + 1];
-        const uint32_t cbase = raw_off[sv0 + i], ncand = cand_cnt[sv0 + i];
-        const uint32_t wbase = FILL ? list_ptr[lo + i] : 0;
-        if (FILL && list_ptr[lo + i + 1] == wbase) continue;  // the count pass found nothing for this list
+        const uint32_t cbase = raw_off[T.sv0 + i], ncand = cand_cnt[T.sv0 + i];
         // The segments of up to 64 candidate polylines are dealt to the lanes as ONE flat sequence (candidate-major,
         // segment-minor = the order of the per-candidate loops): polylines average ~25 vertices, so a pass per
         // candidate left 60 % of the lanes idle and paid its dependent look-ups (candidate id -> vertex range ->
@@ -385,17 +387,17 @@ __global__ void __launch_bounds__(256) k2_epipolar_hits(DevScene s, SeedsDev sd,
           // four chunks of 64 flat segments per trip: their owner searches and vertex loads are independent and in
           // flight together (one chunk at a time, a wave waited out one memory latency per chunk)
           constexpr int U = 4;
-          for (uint32_t base = 0; base < total; base += 64 * U) {
+          for (uint32_t fb = 0; fb < total; fb += 64 * U) {
             f2 v0[U], v1[U];
             uint32_t oid[U], seg[U];
             bool in[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
-              const uint32_t f = base + 64u * u + lane;
+              const uint32_t f = fb + 64u * u + lane;
               in[u] = f < total;
               oid[u] = seg[u] = 0;
               v0[u].x = v0[u].y = v1[u].x = v1[u].y = 0.f;
-              if (base + 64u * u < total) {  // wave-uniform
+              if (fb + 64u * u < total) {  // wave-uniform
                 uint32_t pos = 0;  // owner of flat segment f: the first lane whose inclusive count exceeds f
 #pragma unroll
                 for (uint32_t step = 32; step; step >>= 1) {
@@ -414,20 +416,21 @@ __global__ void __launch_bounds__(256) k2_epipolar_hits(DevScene s, SeedsDev sd,
             }
 #pragma unroll
             for (int u = 0; u < U; u++) {
-              if (base + 64u * u >= total) break;  // wave-uniform
+              if (fb + 64u * u >= total) break;  // wave-uniform
               bool ok = false;
               float hx = 0.f, hy = 0.f;
               if (in[u] && seg_line_hit(v1[u].x, v1[u].y, v0[u].x, v0[u].y, la, lb, lc, hx, hy))
-                ok = dist2(sx, sy, hx, hy) <= detsq;
+                ok = dist2(sx, sy, hx, hy) <= T.detsq;
               const unsigned long long mask = __ballot(ok);
-              if (FILL && ok) {
+              const uint32_t p = tot + cnt + __popcll(mask & T.lt_mask);
+              if (ok && p < limit) {
                 Obs o;
                 o.view = cur_view;
                 o.pl = oid[u];
                 o.seg = seg[u];
                 o.x = hx;
                 o.y = hy;
-                hits[wbase + cnt + __popcll(mask & lt_mask)] = o;
+                dst[p] = o;
               }
               cnt += __popcll(mask);
             }
@@ -435,7 +438,68 @@ __global__ void __launch_bounds__(256) k2_epipolar_hits(DevScene s, SeedsDev sd,
         }
       }
     }
-    if (!FILL && lane == 0) list_cnt[lo + i] = cnt;
+    if (!DIRECT) {
+      if (lane == 0) list_cnt[T.lo + i] = cnt;
+      if (lane == (i & 63u)) my_cnt = cnt;
+    }
+    tot += cnt;
+  }
+  return tot;
+}
+
+__global__ void __launch_bounds__(256) k2_epipolar_hits(DevScene s, SeedsDev sd, uint32_t sv_base, uint32_t n_tasks,
+                                                       const uint32_t* task_seed, const uint32_t* task_entry,
+                                                       const uint32_t* task_hit, const uint32_t* task_list_off,
+                                                       const uint32_t* raw_off, const uint32_t* cand_pl,
+                                                       const uint32_t* cand_cnt, const Obs* start_hits,
+                                                       uint32_t* list_cnt, uint32_t* list_ptr, Obs* hits,
+                                                       uint32_t hits_cap, uint32_t cap, Counters* ctr) {
+  __shared__ Obs stage_all[4][EG3D_K2_STAGE_MAX];
+  __shared__ uint32_t wave_total[4];
+  __shared__ unsigned long long block_base;
+  const uint32_t w = threadIdx.x >> 6;
+  const uint32_t t = blockIdx.x * 4u + w;
+  const bool live = t < n_tasks;  // (wave-uniform; the waves past the last task only take part in the claim)
+  Obs* stage = stage_all[w];
+  K2Task T;
+  T.lane = threadIdx.x & 63;
+  uint32_t limit = 0, total = 0, my_cnt = 0;
+  if (live) {
+    const uint32_t seed = task_seed[t], ea = task_entry[t], h = task_hit[t];
+    T.t0 = sd.trk_off[seed];
+    T.k = sd.trk_off[seed + 1] - T.t0;
+    T.sv0 = T.t0 - sv_base;
+    T.hit = start_hits[raw_off[T.sv0 + ea] + h];
+    T.start_view = sd.trk_view[T.t0 + ea];
+    float ix, iy;
+    seed_obs_in_view(sd, T.t0, T.k, T.start_view, ix, iy);
+    const float radius = dist(ix, iy, T.hit.x, T.hit.y) * 3.0f;
+    T.detsq = radius * radius;
+    T.lo = task_list_off[t];
+    T.lt_mask = (T.lane == 0) ? 0ull : (~0ull >> (64 - T.lane));
+    limit = T.k <= 64u ? cap : 0u;
+    total = k2_sweep<false>(s, sd, T, raw_off, cand_pl, cand_cnt, stage, limit, 0u, list_cnt, list_ptr, my_cnt);
+  }
+  if (T.lane == 0) wave_total[w] = total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long n = (unsigned long long)wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
+    block_base = n ? atomicAdd(&ctr->hits_used, n) : 0ull;
+  }
+  __syncthreads();
+  if (!live) return;
+  unsigned long long base = block_base;
+  for (uint32_t v = 0; v < w; v++) base += wave_total[v];
+  const bool fits = base + total <= (unsigned long long)hits_cap;
+  if (total <= limit) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (fits)
+      for (uint32_t j = T.lane; j < total; j += 64) hits[base + j] = stage[j];
+    const uint32_t excl = (uint32_t)wave_incl_scan((int)my_cnt) - my_cnt;
+    if (T.lane < T.k) list_ptr[T.lo + T.lane] = (uint32_t)base + excl;
+  } else if (fits) {
+    (void)k2_sweep<true>(s, sd, T, raw_off, cand_pl, cand_cnt, hits + base, 0xffffffffu, (uint32_t)base, list_cnt, list_ptr, my_cnt);
   }
 }
 
@@ -611,14 +675,7 @@ __device__ __forceinline__ uint32_t find_owner(const uint32_t* off, uint32_t n, 
 #define EG3D_K3A_WAVES 2 /* waves/SIMD the register allocation of K3a aims at: 256 VGPRs, nothing spills (at 3: 168 VGPRs,
                             86-102 spilled; same speed on C3', K3a 1.50 -> 1.30 ms on C2, half the L2<->fabric traffic) */
 #endif
-// compatible <=> direction 1 gave >= 2 points, or direction 2 is valid and gave >= 2
-// (compatible_new_plg_point, plg_matching.cpp:1276-1287)
-__global__ void k3a_finalize(uint32_t n_hyp, HypResult* res) {
-  const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= n_hyp) return;
-  const uint32_t st = res[h].status;
-  if ((st & HYP_D1) && (res[h].n1 >= 2 || ((st & HYP_D2) && res[h].n2 >= 2))) res[h].status = st | HYP_COMPAT;
-}
+// (which hypotheses are compatible is decided where it is asked, by k3s_select: hyp_compatible in eg3d_dev_follow.h)
 
 }  // namespace eg3d
 #include "eg3d_k3a_engine.h"
@@ -1231,19 +1288,14 @@ void launch_task_fill(hipStream_t st, SeedsDev sd, uint32_t sv_base, uint32_t n_
   hipLaunchKernelGGL(k_task_fill, blocks_for(n_sv, 256), dim3(256), 0, st, sd, sv_base, n_sv, sv_seed, start_cnt,
                      task_off, task_seed, task_entry, task_hit, task_k, sv_vtx, ctr);
 }
-void launch_k2(hipStream_t st, bool fill, DevScene s, SeedsDev sd, uint32_t seed_begin, uint32_t n_seeds, uint32_t sv_base,
-               uint32_t n_tasks, const uint32_t* task_off, const uint32_t* task_seed, const uint32_t* task_entry,
-               const uint32_t* task_hit, const uint32_t* task_list_off, const uint32_t* raw_off, const uint32_t* cand_pl,
-               const uint32_t* cand_cnt, const Obs* start_hits, uint32_t* list_cnt, const uint32_t* list_ptr, Obs* hits) {
-  if (!n_tasks || !n_seeds) return;
-  if (fill)
-    hipLaunchKernelGGL(k2_epipolar_hits<true>, blocks_for((uint64_t)n_tasks * 64, 256), dim3(256), 0, st, s, sd, sv_base,
-                       n_tasks, task_seed, task_entry, task_hit, task_list_off, raw_off, cand_pl, cand_cnt, start_hits,
-                       list_cnt, list_ptr, hits);
-  else
-    hipLaunchKernelGGL(k2_epipolar_hits<false>, blocks_for((uint64_t)n_tasks * 64, 256), dim3(256), 0, st, s, sd,
-                       sv_base, n_tasks, task_seed, task_entry, task_hit, task_list_off, raw_off, cand_pl, cand_cnt,
-                       start_hits, list_cnt, list_ptr, hits);
+void launch_k2(hipStream_t st, DevScene s, SeedsDev sd, uint32_t sv_base, uint32_t n_tasks, const uint32_t* task_seed,
+               const uint32_t* task_entry, const uint32_t* task_hit, const uint32_t* task_list_off, const uint32_t* raw_off,
+               const uint32_t* cand_pl, const uint32_t* cand_cnt, const Obs* start_hits, uint32_t* list_cnt, uint32_t* list_ptr,
+               Obs* hits, uint32_t hits_cap, uint32_t stage_cap, Counters* ctr) {
+  if (!n_tasks) return;
+  hipLaunchKernelGGL(k2_epipolar_hits, blocks_for((uint64_t)n_tasks * 64, 256), dim3(256), 0, st, s, sd, sv_base, n_tasks,
+                     task_seed, task_entry, task_hit, task_list_off, raw_off, cand_pl, cand_cnt, start_hits, list_cnt,
+                     list_ptr, hits, hits_cap, std::min<uint32_t>(std::max<uint32_t>(stage_cap, 1u), EG3D_K2_STAGE_MAX), ctr);
 }
 void launch_n1_samples(hipStream_t st, bool fill, DevScene s, SetsDev sets, uint32_t n_rows, uint32_t item_begin,
                        uint32_t n_items, uint32_t* sample_cnt, const uint32_t* sample_off, Obs* samples,
@@ -1284,7 +1336,6 @@ void launch_k3a_engine(hipStream_t st, uint32_t orient_waves, uint32_t follow_wa
   hipLaunchKernelGGL(k3a_orient, dim3(orient_waves), dim3(64), 0, st, s, a, tasks, hyp_off, n_hyp, res, hyp_cap, arena,
                      arena_cap, ctr, queue3, lanes_per_wave, items, queue3 + 2);
   hipLaunchKernelGGL(k3a_follow_spec, dim3(follow_waves), dim3(64), 0, st, s, res, follow_scratch, hyp_cap, arena, arena_cap, ctr, queue3 + 1, lanes_per_wave, items, queue3 + 2);
-  hipLaunchKernelGGL(k3a_finalize, blocks_for(n_hyp, 256), dim3(256), 0, st, n_hyp, res);
 }
 void launch_k3s(hipStream_t st, uint32_t n_tasks, const uint32_t* hyp_off, const HypResult* res, ChainSeed* per_task,
                 uint32_t* valid) {
