@@ -290,7 +290,8 @@ def device_source_fingerprint(defines=()):
     what a PMC profile under profiles/ was measured ON. tools/profile_summary.py records it beside the traffic figures;
     bench.py reports `roofline.traffic` only while it still matches (a changed kernel makes the committed figure stale:
     it is then reported as such, not as this run's traffic). Editing a comment does not change it. Of the eg3d_api* files
-    (eg3d_api.hip, the per-stage eg3d_api_*.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
+    (eg3d_api.hip, eg3d_api_match.hip, the per-stage eg3d_api_filter / _replay / _polymatch / _simgraph / _louvain /
+    _fundamental.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
     the preprocessor lines count — the macros that choose the kernel build, its default form and the slot-pool sizing;
     EG3D_EXTRA_HIPFLAGS and the `defines` of the build are part of the switches."""
     import hashlib

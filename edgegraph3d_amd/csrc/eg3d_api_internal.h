@@ -147,6 +147,8 @@ struct HostGrids {
 //   EG3D_K2_STAGE_CAP=n    tests: hits a wave of K2 stages in LDS (1 .. 128, default 128); a task with more sweeps twice
 //   EG3D_HITS_CAP0=n       tests: capacity of the epipolar-hit buffer until a K2 launch of the context has fitted (forces the
 //                          enlarge-and-run-again path)
+//   EG3D_STAGE_CAP0=n      tests: points the staging area of the expand stage holds (and n x the per-point guess of observations)
+//                          until an expand launch of the context has told what it needs (forces the size-it-and-repeat path)
 //   EG3D_MAX_SCRATCH_MB=n  tests: cut the chains of a batch into several K3b launches of at most n MB / slice size
 //                          chains each (default: one launch takes all chains — their working slices are slots)
 //   EG3D_NO_LPT=1          launch chains in identity order instead of longest-first (diagnostic)
@@ -188,6 +190,8 @@ struct Tunables {
                                               // a task with more takes the count-claim-write route
   uint32_t hits_cap0 = 0;  // EG3D_HITS_CAP0 (tests): capacity of the epipolar-hit buffer until a K2 launch of the context has
                            // fitted, small enough to force the enlarge-and-rerun path (0 = the first guess of run_stage_a)
+  uint32_t stage_cap0 = 0;  // EG3D_STAGE_CAP0 (tests): points of the expand stage's staging area while the context has learned
+                            // nothing (stage_cap_pts == 0), small enough to force the size-it-and-repeat path (0 = the first guess)
   size_t max_scratch = 0;  // 0 = no limit
   uint32_t slots_per_xcd = 0;  // 0 = sized from the occupancy query
   bool use_lpt = true;
@@ -205,6 +209,7 @@ struct Tunables {
     if (const char* e = getenv("EG3D_POOL_CAP0")) t.pool_cap0 = (uint32_t)std::max(64, atoi(e));
     if (const char* e = getenv("EG3D_K2_STAGE_CAP")) t.k2_stage_cap = (uint32_t)std::min<int>(EG3D_K2_STAGE_MAX, std::max(1, atoi(e)));
     if (const char* e = getenv("EG3D_HITS_CAP0")) t.hits_cap0 = (uint32_t)std::max(1, atoi(e));
+    if (const char* e = getenv("EG3D_STAGE_CAP0")) t.stage_cap0 = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("EG3D_MAX_SCRATCH_MB")) t.max_scratch = (size_t)std::max(1, atoi(e)) << 20;
     if (const char* e = getenv("EG3D_NO_LPT")) t.use_lpt = !(e[0] == '1');
     if (const char* e = getenv("EG3D_TRACE_ARENA")) t.trace_arena = e[0] == '1';
@@ -331,6 +336,15 @@ struct eg3d_ctx {
 
 EG3D_API_BEGIN
 int scan_exclusive_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one);  // (hipCUB, on c->b_scan_tmp)
+// (key, value) pairs by descending key, queued on the stream (hipCUB, on c->b_scan_tmp): the launch order of the expand stage
+int sort_pairs_desc_u32(eg3d_ctx* c, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n);
+// n elements of host memory into a device buffer made large enough, queued on `st`
+template <typename Buf, typename T>
+int upload(Buf& b, const T* src, size_t n, hipStream_t st) {
+  BUF_TRY(b.ensure(sizeof(T) * std::max<size_t>(n, 1)));
+  if (n) HIP_TRY(hipMemcpyAsync(b.p, src, sizeof(T) * n, hipMemcpyHostToDevice, st));
+  return EG3D_OK;
+}
 // ---- small read-backs through the mailbox ----------------------------------------------------------
 // b_scanchk: [0..3] "scan wrapped" flag words (ORed by k_scan_check, cleared by k_publish), [4..5] a saved
 // 64-bit counter.

@@ -1,5 +1,5 @@
 """-m gpu: ONE eg3d_match_* call cut into units that run concurrently on the context's internal lanes
-(eg3d_set_pipelining, eg3d_api.hip run_pipelined). The reference's parallel entry point runs the seeds of a call on its
+(eg3d_set_pipelining, eg3d_api_match.hip run_pipelined). The reference's parallel entry point runs the seeds of a call on its
 OpenMP team and appends in seed order (plg_matching_from_refpoints.cpp:83-104); the property checked here is the same:
 whatever the cutting and the number of lanes, the call's cloud is BYTE FOR BYTE the cloud of the uncut call (and that
 one is compared with the oracle), in the host arrays and in the device view alike."""

@@ -23,7 +23,8 @@ run() { # name, bench args, rocprof flags...
   local name=$1; local args=$2; shift 2
   rm -rf $out/prof_$name
   timeout -k 5 900 rocprofv3 "$@" -d $out/prof_$name -o $tag -- python bench.py $args > $out/prof_$name.out 2> $out/prof_$name.err
-  echo "pass $name rc=$?"
+  local rc=$?; echo "pass $name rc=$rc"
+  [ $rc -eq 0 ] || exit $rc  # (a pass that failed, faulted or ran out of time: nothing more is started on the GPU)
 }
 run kt "$kt_args" --kernel-trace --stats
 run serial "$pmc_args" --kernel-trace --stats
