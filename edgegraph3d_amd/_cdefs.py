@@ -40,6 +40,52 @@ class Candidates(C.Structure):
                 ("hit_pl", u32p), ("hit_seg", u32p), ("hit_xy", f32p), ("_owner", C.c_void_p)]
 
 
+class MatchedIntervals(C.Structure):
+    """eg3d_matched_intervals: the matched_polyline_intervals CSR of a graph (host or device pointers)."""
+    _fields_ = [("struct_size", C.c_uint32), ("on_device", C.c_int32), ("n_scene_polylines", C.c_uint64),
+                ("iv_off", C.c_void_p), ("iv_start_seg", C.c_void_p), ("iv_start_xy", C.c_void_p),
+                ("iv_end_seg", C.c_void_p), ("iv_end_xy", C.c_void_p)]
+
+
+class MatchedIntervalsArrays:
+    """Owns what an eg3d_matched_intervals points at. `g` is the dict of a host graph (host.replay_matches,
+    Context.replay_device) — numpy copies are kept here — or a DeviceGraph3D (Context.replay_device(to_host=False)),
+    whose arrays stay where they are: the context that built them must not have replaced them since."""
+
+    def __init__(self, g):
+        if isinstance(g, DeviceGraph3D):
+            self.a = None
+            self.c = MatchedIntervals(C.sizeof(MatchedIntervals), 1, int(g.n_scene_polylines), g.iv_off, g.iv_start_seg,
+                                      g.iv_start_xy, g.iv_end_seg, g.iv_end_xy)
+            return
+        pad = lambda k, t, w: np.ascontiguousarray(g[k], t).reshape(-1) if len(g[k]) else np.zeros(w, t)
+        self.a = {"iv_off": np.ascontiguousarray(g["iv_off"], np.uint64),
+                  "iv_start_seg": pad("iv_start_seg", np.uint32, 1), "iv_start_xy": pad("iv_start_xy", np.float32, 2),
+                  "iv_end_seg": pad("iv_end_seg", np.uint32, 1), "iv_end_xy": pad("iv_end_xy", np.float32, 2)}
+        a = self.a
+        self.c = MatchedIntervals(C.sizeof(MatchedIntervals), 0, int(g.get("n_scene_polylines", len(a["iv_off"]) - 1)),
+                                  a["iv_off"].ctypes.data, a["iv_start_seg"].ctypes.data, a["iv_start_xy"].ctypes.data,
+                                  a["iv_end_seg"].ctypes.data, a["iv_end_xy"].ctypes.data)
+
+
+class SetCandidates(C.Structure):
+    """eg3d_set_candidates (library-owned; eg3d_free_set_candidates)."""
+    _fields_ = [("n_tasks", C.c_uint32), ("task_view", i32p), ("task_pl", u32p), ("task_seg", u32p), ("task_xy", f32p),
+                ("list_off", u64p), ("hit_pl", u32p), ("hit_seg", u32p), ("hit_xy", f32p),
+                ("n_samples_skipped", C.c_uint64), ("n_hits_filtered", C.c_uint64), ("_owner", C.c_void_p)]
+
+
+def set_candidates_to_dict(c, n_views):
+    nt = int(c.n_tasks)
+    list_off = as_np(c.list_off, nt * n_views + 1, np.uint64)
+    nh = int(list_off[-1])
+    return {"n_tasks": nt, "task_view": as_np(c.task_view, nt, np.int32), "task_pl": as_np(c.task_pl, nt, np.uint32),
+            "task_seg": as_np(c.task_seg, nt, np.uint32), "task_xy": as_np(c.task_xy, 2 * nt, np.float32).reshape(nt, 2),
+            "list_off": list_off, "hit_pl": as_np(c.hit_pl, nh, np.uint32), "hit_seg": as_np(c.hit_seg, nh, np.uint32),
+            "hit_xy": as_np(c.hit_xy, 2 * nh, np.float32).reshape(nh, 2),
+            "n_samples_skipped": int(c.n_samples_skipped), "n_hits_filtered": int(c.n_hits_filtered)}
+
+
 class StageTimes(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_candidates", C.c_float), ("ms_epipolar", C.c_float),
                 ("ms_hypotheses", C.c_float), ("ms_select", C.c_float), ("ms_expand", C.c_float),

@@ -52,6 +52,13 @@ def lib():
         L.eg3d_match_polyline_sets.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32, C.c_int,
                                                C.POINTER(D.EdgePoints), C.POINTER(D.StageTimes)]
         L.eg3d_check_polyline_sets.argtypes = [C.POINTER(D.PolylineSets), C.c_int32]
+        L.eg3d_match_polyline_sets_matched.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32,
+                                                       C.POINTER(D.MatchedIntervals), C.c_int, C.POINTER(D.EdgePoints),
+                                                       C.POINTER(D.StageTimes)]
+        L.eg3d_polyline_set_candidates.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32,
+                                                   C.POINTER(D.MatchedIntervals), C.POINTER(D.SetCandidates)]
+        L.eg3d_free_set_candidates.argtypes = [C.POINTER(D.SetCandidates)]
+        L.eg3d_free_set_candidates.restype = None
         L.eg3d_last_device_output.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints)]
         L.eg3d_set_pipelining.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.eg3d_gn_filter.argtypes = [C.c_void_p, D.f32p, D.u32p, D.i32p, D.f32p, C.c_uint64, C.c_float, C.c_int,
@@ -94,6 +101,7 @@ EXPORTED_SYMBOLS = [
     "eg3d_last_error", "eg3d_device_count", "eg3d_dlt_rows", "eg3d_create", "eg3d_clone", "eg3d_destroy", "eg3d_get_grid", "eg3d_candidates_run",
     "eg3d_free_candidates", "eg3d_match_refpoints", "eg3d_free_edgepoints", "eg3d_upload_seeds",
     "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
+    "eg3d_match_polyline_sets_matched", "eg3d_polyline_set_candidates", "eg3d_free_set_candidates",
     "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
     "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
     "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches", "eg3d_similarity_graph", "eg3d_free_simgraph",
@@ -292,16 +300,24 @@ class Context:
         self.upload_seeds(seeds_ptr)
         return self.match_resident(begin, end, device_only)
 
-    def match_polyline_sets(self, n_sets, row_off, pl_ids, begin=0, end=None, device_only=False):
-        """Pipelines 1-2 extractor: sets = CSR over rows (set * V + view) of polyline ids."""
+    def match_polyline_sets(self, n_sets, row_off, pl_ids, begin=0, end=None, device_only=False, matched=None):
+        """Pipelines 1-2 extractor: sets = CSR over rows (set * V + view) of polyline ids. `matched`: the
+        graph whose matched intervals the extractor consults (eg3d_match_polyline_sets_matched) — the dict of a host graph
+        (host.replay_matches, replay_device) or the DeviceGraph3D of replay_device(to_host=False) on this context; samples
+        and epipolar hits inside a held interval are left out. None: no manager (eg3d_match_polyline_sets)."""
         if end is None:
             end = n_sets
         row_off = np.ascontiguousarray(row_off, np.uint32)
         pl_ids = np.ascontiguousarray(pl_ids if len(pl_ids) else [0], np.uint32)
         ps = D.PolylineSets(n_sets, D.np_ptr(row_off, C.c_uint32), D.np_ptr(pl_ids, C.c_uint32))
         e, tm = D.EdgePoints(), D.StageTimes()
-        rc = lib().eg3d_match_polyline_sets(self._h, C.byref(ps), begin, end, 1 if device_only else 0, C.byref(e),
-                                            C.byref(tm))
+        if matched is None:
+            rc = lib().eg3d_match_polyline_sets(self._h, C.byref(ps), begin, end, 1 if device_only else 0, C.byref(e),
+                                                C.byref(tm))
+        else:
+            m = matched if isinstance(matched, D.MatchedIntervalsArrays) else D.MatchedIntervalsArrays(matched)
+            rc = lib().eg3d_match_polyline_sets_matched(self._h, C.byref(ps), begin, end, C.byref(m.c),
+                                                        1 if device_only else 0, C.byref(e), C.byref(tm))
         _check(rc, "eg3d_match_polyline_sets")
         if device_only:
             d = {"n_points": int(e.n_points), "n_obs": int(e.n_obs), "n_tasks": int(e.n_tasks),
@@ -438,6 +454,26 @@ class Context:
         _check(lib().eg3d_candidates_run(self._h, seeds_ptr, begin, end, C.byref(c)), "eg3d_candidates_run")
         d = D.candidates_to_dict(c)
         lib().eg3d_free_candidates(C.byref(c))
+        return d
+
+    def polyline_set_candidates(self, n_sets, row_off, pl_ids, begin=0, end=None, matched=None):
+        """Stage A of the extractor alone (eg3d_polyline_set_candidates), in task order: the samples that became tasks
+        (task_view / task_pl / task_seg / task_xy), the hit lists as a CSR over task * n_views + view (list_off, hit_pl,
+        hit_seg, hit_xy; a hit's view is its list's) and n_samples_skipped / n_hits_filtered. `matched` as in
+        match_polyline_sets."""
+        if end is None:
+            end = n_sets
+        row_off = np.ascontiguousarray(row_off, np.uint32)
+        pl_ids = np.ascontiguousarray(pl_ids if len(pl_ids) else [0], np.uint32)
+        ps = D.PolylineSets(n_sets, D.np_ptr(row_off, C.c_uint32), D.np_ptr(pl_ids, C.c_uint32))
+        m = None
+        if matched is not None:
+            m = matched if isinstance(matched, D.MatchedIntervalsArrays) else D.MatchedIntervalsArrays(matched)
+        c = D.SetCandidates()
+        _check(lib().eg3d_polyline_set_candidates(self._h, C.byref(ps), begin, end, C.byref(m.c) if m else None, C.byref(c)),
+               "eg3d_polyline_set_candidates")
+        d = D.set_candidates_to_dict(c, self.n_views)
+        lib().eg3d_free_set_candidates(C.byref(c))
         return d
 
     def gn_filter(self, X, obs_off, obs_view, obs_xy, gn_max_mse=2.25, legacy_abs=False):

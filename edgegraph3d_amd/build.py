@@ -226,6 +226,19 @@ RESOURCE_BOUNDS = {
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},
     "k1_seed_candidates": {"vgpr_spill_count": 0},
+    # the extractor's stage A. <., false> (no manager): the figures of the kernels before they took the MATCHED parameter —
+    # the path every existing caller runs must not pay for the other one
+    "k_n1_samples<false, false>": {"vgpr_count": 26, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_samples<true, false>": {"vgpr_count": 20, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_hits<false, false>": {"vgpr_count": 38, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_hits<true, false>": {"vgpr_count": 40, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    # <., true> (matched intervals consulted; measured 42 / 45 / 46 / 47 VGPRs) and the table check (12): no LDS, no
+    # scratch, no spills; a margin of a few registers
+    "k_n1_samples<false, true>": {"vgpr_count": 48, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_samples<true, true>": {"vgpr_count": 50, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_hits<false, true>": {"vgpr_count": 52, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_hits<true, true>": {"vgpr_count": 52, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k_n1_check_intervals": {"vgpr_count": 16, "vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
 }
 
 # ... and of the lane-per-chain engine, present only in builds made with -DEG3D_WITH_K3C_ENGINE (build_hip_engine)

@@ -955,11 +955,12 @@ int run_batch(eg3d_ctx* c, uint32_t b, uint32_t e, UnitTurn& T, HostOut& H) {
 // Pipelines 1-2 extractor, stage A: sample the polylines of sets [set_b, set_e) and
 // collect the epipolar hits of every sample; then the common stage B. `sets` is already on the
 // device; h_row_off is its host copy of the row offsets.
-int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
-                   uint32_t set_e, UnitTurn& T, HostOut& H) {
+// `matched` (null: none) is the caller's interval table on the device: samples and hits inside a held interval are left out
+// (k_n1_samples / k_n1_hits <., true>); skip_cnt / drop_cnt (may be null) receive the per-polyline / per-task counts of them.
+int run_sets_stage_a(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
+                     uint32_t set_e, const IvTable* matched, WorkBuf* skip_cnt, WorkBuf* drop_cnt, BatchState& B) {
   hipStream_t st = c->stream;
   const uint32_t V = (uint32_t)c->V;
-  BatchState B;
   memset(&B, 0, sizeof(B));
   B.key0_base = 0;  // (key[0] = sample index of the CALL: the sink adds the samples of the units before this one)
   const uint32_t item_b = h_row_off[(size_t)set_b * V], item_e = h_row_off[(size_t)set_e * V];
@@ -970,8 +971,10 @@ int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, 
   BUF_TRY(c->b_raw_off.ensure(sizeof(uint32_t) * (n_items + 1)));
   HIP_TRY(hipMemsetAsync(c->b_raw_cnt.as<uint32_t>() + n_items, 0, sizeof(uint32_t), st));
   HIP_TRY(hipEventRecord(c->ea[1], st));
+  if (matched && skip_cnt) BUF_TRY(skip_cnt->ensure(sizeof(uint32_t) * (n_items + 1)));
   launch_n1_samples(st, false, c->ds, sets, n_rows_total, item_b, n_items, c->b_raw_cnt.as<uint32_t>(), nullptr, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, c->b_ctr.as<Counters>());
+                    nullptr, nullptr, nullptr, nullptr, nullptr, c->b_ctr.as<Counters>(), matched,
+                    matched && skip_cnt ? skip_cnt->as<uint32_t>() : nullptr);
   BUF_TRY(scan_total_u32(c, c->b_raw_cnt.as<uint32_t>(), c->b_raw_off.as<uint32_t>(), n_items + 1, B.n_tasks, "samples"));
   const uint32_t nt = B.n_tasks;
   if ((uint64_t)nt * V > 0x7fffffffull) {
@@ -985,11 +988,20 @@ int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, 
   launch_n1_samples(st, true, c->ds, sets, n_rows_total, item_b, n_items, nullptr, c->b_raw_off.as<uint32_t>(),
                     c->b_start_hits.as<Obs>(), c->b_task_seed.as<uint32_t>(), c->b_task_entry.as<uint32_t>(),
                     c->b_task_hit.as<uint32_t>(), c->b_task_list_off.as<uint32_t>(), c->b_task_k.as<uint32_t>(),
-                    c->b_ctr.as<Counters>());
+                    c->b_ctr.as<Counters>(), matched, nullptr);
   {
     const uint32_t last = nt * V;
     HIP_TRY(hipMemcpyAsync(c->b_task_list_off.as<uint32_t>() + nt, &last, sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // `last` leaves scope
+  }
+  if (matched) {  // (stage B clears the flags: a walk that did not advance is reported here)
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, &c->b_ctr.as<Counters>()->flags, sizeof(flags), hipMemcpyDeviceToHost));
+    if (flags & CTR_N1_NO_PROGRESS) {
+      g_err = "eg3d_match_polyline_sets_matched: the walk does not advance past a matched interval: the intervals do not "
+              "belong to this scene";
+      return EG3D_ERR_ARG;
+    }
   }
   HIP_TRY(hipEventRecord(c->eb[1], st));
   B.n_lists = nt * V;
@@ -997,14 +1009,29 @@ int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, 
   BUF_TRY(c->b_list_ptr.ensure(sizeof(uint32_t) * ((size_t)B.n_lists + 1)));
   HIP_TRY(hipMemsetAsync(c->b_list_cnt.as<uint32_t>() + B.n_lists, 0, sizeof(uint32_t), st));
   HIP_TRY(hipEventRecord(c->ea[2], st));
+  if (matched && drop_cnt) BUF_TRY(drop_cnt->ensure(sizeof(uint32_t) * (nt + 1)));
   launch_n1_hits(st, false, c->ds, sets, nt, c->b_start_hits.as<Obs>(), c->b_task_k.as<uint32_t>(),
-                 c->b_list_cnt.as<uint32_t>(), nullptr, nullptr, c->b_ctr.as<Counters>());
+                 c->b_list_cnt.as<uint32_t>(), nullptr, nullptr, c->b_ctr.as<Counters>(), matched,
+                 matched && drop_cnt ? drop_cnt->as<uint32_t>() : nullptr);
   BUF_TRY(scan_total_u32(c, c->b_list_cnt.as<uint32_t>(), c->b_list_ptr.as<uint32_t>(), (size_t)B.n_lists + 1, B.n_hits,
                          "epipolar hits"));
   BUF_TRY(c->b_hits.ensure(sizeof(Obs) * ((size_t)B.n_hits + 1)));
   launch_n1_hits(st, true, c->ds, sets, nt, c->b_start_hits.as<Obs>(), c->b_task_k.as<uint32_t>(),
-                 c->b_list_cnt.as<uint32_t>(), c->b_list_ptr.as<uint32_t>(), c->b_hits.as<Obs>(), c->b_ctr.as<Counters>());
+                 c->b_list_cnt.as<uint32_t>(), c->b_list_ptr.as<uint32_t>(), c->b_hits.as<Obs>(), c->b_ctr.as<Counters>(),
+                 matched, nullptr);
   HIP_TRY(hipEventRecord(c->eb[2], st));
+  return EG3D_OK;
+}
+
+int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
+                   uint32_t set_e, const IvTable* matched, UnitTurn& T, HostOut& H) {
+  hipStream_t st = c->stream;
+  const uint32_t V = (uint32_t)c->V;
+  BatchState B;
+  BUF_TRY(run_sets_stage_a(c, sets, h_row_off, n_rows_total, set_b, set_e, matched, nullptr, nullptr, B));
+  const uint32_t nt = B.n_tasks;
+  // every sample of the unit lies inside a held interval: nothing to launch, the unit only takes its turn
+  if (matched && !nt) return T.finish(0) ? EG3D_OK : EG3D_ERR_HIP;
   // identity view map: one row of V entries shared by every sample (StageAView::dense_k)
   {
     std::vector<int32_t> mv(V);
@@ -1370,8 +1397,74 @@ extern "C" int eg3d_check_polyline_sets(const eg3d_polyline_sets* ps, int32_t n_
   return EG3D_OK;
 }
 
-extern "C" int eg3d_match_polyline_sets(eg3d_ctx* c, const eg3d_polyline_sets* ps, uint32_t set_b, uint32_t set_e,
-                                        int device_only, eg3d_edgepoints* out, eg3d_stage_times* times) {
+// The caller's matched_polyline_intervals for the duration of ONE call: host arrays are uploaded into the WorkBufs here
+// (released with the call), device arrays are read in place. Everything is checked before anything is indexed with it:
+// what needs no scene on the host for host arrays (their total sizes the upload), then check_interval_row, one lane per
+// row, for both kinds. active: the table holds at least one interval.
+namespace {
+struct MatchedCall {
+  WorkBuf off, sseg, sxy, eseg, exy, bad;
+  IvTable dev{};
+  bool active = false;
+};
+int bad_matched(const char* what) {
+  g_err = std::string("eg3d_match_polyline_sets_matched: ") + what;
+  return EG3D_ERR_ARG;
+}
+int prepare_matched(eg3d_ctx* c, const eg3d_matched_intervals* m, MatchedCall& M) {
+  if (!m) return EG3D_OK;
+  if (m->struct_size != sizeof(eg3d_matched_intervals)) return bad_matched("struct_size is not sizeof(eg3d_matched_intervals)");
+  const uint32_t V = (uint32_t)c->V;
+  uint32_t n_pl = 0;
+  HIP_TRY(hipMemcpy(&n_pl, c->ds.view_pl_off + V, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (m->n_scene_polylines != n_pl) return bad_matched("n_scene_polylines is not the scene's number of polylines");
+  if (!m->iv_off) return bad_matched("iv_off is null");
+  hipStream_t st = c->stream;
+  uint64_t total = 0;
+  if (m->on_device) {
+    HIP_TRY(hipMemcpy(&total, m->iv_off + n_pl, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    M.dev.off = m->iv_off;
+    M.dev.start_seg = m->iv_start_seg;
+    M.dev.start_xy = m->iv_start_xy;
+    M.dev.end_seg = m->iv_end_seg;
+    M.dev.end_xy = m->iv_end_xy;
+  } else {
+    total = m->iv_off[n_pl];
+    for (uint32_t g = 0; g < n_pl; g++)
+      if (m->iv_off[g] > m->iv_off[g + 1] || m->iv_off[g + 1] > total) return bad_matched("iv_off is not ascending");
+  }
+  if (total && (!m->iv_start_seg || !m->iv_start_xy || !m->iv_end_seg || !m->iv_end_xy))
+    return bad_matched("an interval array is null");
+  if (!m->on_device) {
+    BUF_TRY(upload(M.off, m->iv_off, (size_t)n_pl + 1, st));
+    BUF_TRY(upload(M.sseg, m->iv_start_seg, total, st));
+    BUF_TRY(upload(M.sxy, m->iv_start_xy, 2 * total, st));
+    BUF_TRY(upload(M.eseg, m->iv_end_seg, total, st));
+    BUF_TRY(upload(M.exy, m->iv_end_xy, 2 * total, st));
+    M.dev.off = M.off.as<uint64_t>();
+    M.dev.start_seg = M.sseg.as<uint32_t>();
+    M.dev.start_xy = M.sxy.as<float>();
+    M.dev.end_seg = M.eseg.as<uint32_t>();
+    M.dev.end_xy = M.exy.as<float>();
+  }
+  BUF_TRY(M.bad.ensure(sizeof(uint32_t)));
+  HIP_TRY(hipMemsetAsync(M.bad.p, 0, sizeof(uint32_t), st));
+  launch_n1_check_intervals(st, c->ds, M.dev, total, n_pl, M.bad.as<uint32_t>());
+  uint32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, M.bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (also: the table is resident before any lane reads it)
+  if (bad)
+    return bad_matched("the intervals fail their checks (offsets ascending, segment indices inside their polyline, start "
+                       "segments strictly ascending within a row)");
+  M.active = total != 0;
+  return EG3D_OK;
+}
+// the checks and the upload of the sets, shared by the calls on polyline sets; `who` names the entry point in errors
+int prepare_sets(eg3d_ctx* c, const eg3d_polyline_sets* ps, SetsDev& sd);
+}  // namespace
+
+static int match_sets_call(eg3d_ctx* c, const eg3d_polyline_sets* ps, uint32_t set_b, uint32_t set_e,
+                           const eg3d_matched_intervals* m, int device_only, eg3d_edgepoints* out, eg3d_stage_times* times) {
   if (!c || !ps || !out || !ps->row_off || set_b > set_e || set_e > ps->n_sets) {
     g_err = "eg3d_match_polyline_sets: bad arguments";
     return EG3D_ERR_ARG;
@@ -1381,7 +1474,48 @@ extern "C" int eg3d_match_polyline_sets(eg3d_ctx* c, const eg3d_polyline_sets* p
     return EG3D_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
+  MatchedCall M;
+  BUF_TRY(prepare_matched(c, m, M));  // (before `out` is touched)
+  const IvTable* matched = M.active ? &M.dev : nullptr;
   memset(out, 0, sizeof(*out));
+  SetsDev sd;
+  BUF_TRY(prepare_sets(c, ps, sd));
+  const uint32_t V = (uint32_t)c->V;
+  const uint32_t n_rows = ps->n_sets * V;
+  const int lanes = lanes_for(c, device_only);
+  // units = runs of whole sets, bounded by the number of polylines (every sample owns V lists); with several lanes at
+  // least one unit per lane, balanced by the number of polylines
+  const uint32_t max_items = V >= 64 ? 2048u : 16384u;
+  std::vector<UnitRange> units;
+  {
+    auto cum = [&](uint32_t i) { return (double)ps->row_off[(size_t)i * V] + 1e-3 * (double)i; };
+    const uint32_t want = c->tune.units ? (uint32_t)c->tune.units : (uint32_t)lanes;
+    for (const UnitRange& r : cut_by_weight(set_b, set_e, want, cum))
+      for (uint32_t s0 = r.b; s0 < r.e;) {  // (a unit above the bound is cut into runs of whole sets within it)
+        uint32_t s1 = s0 + 1;
+        while (s1 < r.e && ps->row_off[(size_t)(s1 + 1) * V] - ps->row_off[(size_t)s0 * V] <= max_items) s1++;
+        units.push_back({s0, s1, cum(s1) - cum(s0)});
+        s0 = s1;
+      }
+  }
+  return match_call(c, device_only, true, units, lanes, out, times, [&](eg3d_ctx* lane, uint32_t u, UnitTurn& T, HostOut& H) {
+    return run_sets_batch(lane, sd, ps->row_off, n_rows, units[u].b, units[u].e, matched, T, H);
+  });
+}
+
+extern "C" int eg3d_match_polyline_sets(eg3d_ctx* c, const eg3d_polyline_sets* ps, uint32_t set_b, uint32_t set_e,
+                                        int device_only, eg3d_edgepoints* out, eg3d_stage_times* times) {
+  return match_sets_call(c, ps, set_b, set_e, nullptr, device_only, out, times);
+}
+
+extern "C" int eg3d_match_polyline_sets_matched(eg3d_ctx* c, const eg3d_polyline_sets* ps, uint32_t set_b, uint32_t set_e,
+                                                const eg3d_matched_intervals* m, int device_only, eg3d_edgepoints* out,
+                                                eg3d_stage_times* times) {
+  return match_sets_call(c, ps, set_b, set_e, m, device_only, out, times);
+}
+
+namespace {
+int prepare_sets(eg3d_ctx* c, const eg3d_polyline_sets* ps, SetsDev& sd) {
   const uint32_t V = (uint32_t)c->V;
   const uint32_t n_rows = ps->n_sets * V;
   const uint32_t n_ids = ps->row_off[n_rows];
@@ -1407,30 +1541,88 @@ extern "C" int eg3d_match_polyline_sets(eg3d_ctx* c, const eg3d_polyline_sets* p
   }
   BUF_TRY(upload(c->b_sets_off, ps->row_off, (size_t)n_rows + 1, c->stream));
   BUF_TRY(upload(c->b_sets_ids, ps->pl_ids, n_ids, c->stream));
-  SetsDev sd;
   sd.n_views = V;
   sd.row_off = c->b_sets_off.as<uint32_t>();
   sd.pl_ids = c->b_sets_ids.as<uint32_t>();
   HIP_TRY(hipStreamSynchronize(c->stream));  // the sets are resident before any lane reads them
-  const int lanes = lanes_for(c, device_only);
-  // units = runs of whole sets, bounded by the number of polylines (every sample owns V lists); with several lanes at
-  // least one unit per lane, balanced by the number of polylines
-  const uint32_t max_items = V >= 64 ? 2048u : 16384u;
-  std::vector<UnitRange> units;
-  {
-    auto cum = [&](uint32_t i) { return (double)ps->row_off[(size_t)i * V] + 1e-3 * (double)i; };
-    const uint32_t want = c->tune.units ? (uint32_t)c->tune.units : (uint32_t)lanes;
-    for (const UnitRange& r : cut_by_weight(set_b, set_e, want, cum))
-      for (uint32_t s0 = r.b; s0 < r.e;) {  // (a unit above the bound is cut into runs of whole sets within it)
-        uint32_t s1 = s0 + 1;
-        while (s1 < r.e && ps->row_off[(size_t)(s1 + 1) * V] - ps->row_off[(size_t)s0 * V] <= max_items) s1++;
-        units.push_back({s0, s1, cum(s1) - cum(s0)});
-        s0 = s1;
-      }
+  return EG3D_OK;
+}
+}  // namespace
+
+// Stage A of the extractor alone, the whole range as ONE batch on the context's own stream.
+extern "C" int eg3d_polyline_set_candidates(eg3d_ctx* c, const eg3d_polyline_sets* ps, uint32_t set_b, uint32_t set_e,
+                                            const eg3d_matched_intervals* m, eg3d_set_candidates* out) {
+  if (!c || !ps || !out || !ps->row_off || set_b > set_e || set_e > ps->n_sets) {
+    g_err = "eg3d_polyline_set_candidates: bad arguments";
+    return EG3D_ERR_ARG;
   }
-  return match_call(c, device_only, true, units, lanes, out, times, [&](eg3d_ctx* lane, uint32_t u, UnitTurn& T, HostOut& H) {
-    return run_sets_batch(lane, sd, ps->row_off, n_rows, units[u].b, units[u].e, T, H);
-  });
+  if ((uint64_t)ps->n_sets * (uint64_t)c->V > 0xffffffffull) {
+    g_err = "eg3d_polyline_set_candidates: too many rows";
+    return EG3D_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  MatchedCall M;
+  BUF_TRY(prepare_matched(c, m, M));
+  const IvTable* matched = M.active ? &M.dev : nullptr;
+  memset(out, 0, sizeof(*out));
+  SetsDev sd;
+  BUF_TRY(prepare_sets(c, ps, sd));
+  const uint32_t V = (uint32_t)c->V;
+  WorkBuf skip_cnt, drop_cnt;
+  BatchState B;
+  BUF_TRY(run_sets_stage_a(c, sd, ps->row_off, ps->n_sets * V, set_b, set_e, matched, &skip_cnt, &drop_cnt, B));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const uint32_t nt = B.n_tasks;
+  const uint32_t n_items = ps->row_off[(size_t)set_e * V] - ps->row_off[(size_t)set_b * V];
+  std::vector<Obs> samples(nt + 1), hits((size_t)B.n_hits + 1);
+  std::vector<uint32_t> list_ptr((size_t)B.n_lists + 1), skipped(n_items + 1), dropped(nt + 1);
+  if (nt) HIP_TRY(hipMemcpy(samples.data(), c->b_start_hits.p, sizeof(Obs) * nt, hipMemcpyDeviceToHost));
+  if (B.n_hits) HIP_TRY(hipMemcpy(hits.data(), c->b_hits.p, sizeof(Obs) * B.n_hits, hipMemcpyDeviceToHost));
+  // (list_ptr is the exclusive scan of the counts, its last entry the total: the lists lie in (task, view) order)
+  HIP_TRY(hipMemcpy(list_ptr.data(), c->b_list_ptr.p, sizeof(uint32_t) * ((size_t)B.n_lists + 1), hipMemcpyDeviceToHost));
+  if (matched && n_items) HIP_TRY(hipMemcpy(skipped.data(), skip_cnt.p, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost));
+  if (matched && nt) HIP_TRY(hipMemcpy(dropped.data(), drop_cnt.p, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost));
+  std::vector<int32_t> t_view(nt);
+  std::vector<uint32_t> t_pl(nt), t_seg(nt), h_pl(B.n_hits), h_seg(B.n_hits);
+  std::vector<float> t_xy((size_t)nt * 2), h_xy((size_t)B.n_hits * 2);
+  std::vector<uint64_t> list_off((size_t)B.n_lists + 1);
+  for (uint32_t i = 0; i < nt; i++) {
+    t_view[i] = (int32_t)samples[i].view;
+    t_pl[i] = samples[i].pl;
+    t_seg[i] = samples[i].seg;
+    t_xy[2 * (size_t)i] = samples[i].x;
+    t_xy[2 * (size_t)i + 1] = samples[i].y;
+  }
+  for (uint32_t i = 0; i < B.n_hits; i++) {
+    h_pl[i] = hits[i].pl;
+    h_seg[i] = hits[i].seg;
+    h_xy[2 * (size_t)i] = hits[i].x;
+    h_xy[2 * (size_t)i + 1] = hits[i].y;
+  }
+  for (size_t l = 0; l <= B.n_lists; l++) list_off[l] = list_ptr[l];
+  if (matched) {
+    for (uint32_t i = 0; i < n_items; i++) out->n_samples_skipped += skipped[i];
+    for (uint32_t i = 0; i < nt; i++) out->n_hits_filtered += dropped[i];
+  }
+  out->n_tasks = nt;
+  out->task_view = dup_to_malloc(t_view);
+  out->task_pl = dup_to_malloc(t_pl);
+  out->task_seg = dup_to_malloc(t_seg);
+  out->task_xy = dup_to_malloc(t_xy);
+  out->list_off = dup_to_malloc(list_off);
+  out->hit_pl = dup_to_malloc(h_pl);
+  out->hit_seg = dup_to_malloc(h_seg);
+  out->hit_xy = dup_to_malloc(h_xy);
+  out->_owner = (void*)1;
+  return EG3D_OK;
+}
+
+extern "C" void eg3d_free_set_candidates(eg3d_set_candidates* c) {
+  if (!c) return;
+  for (void* p : {(void*)c->task_view, (void*)c->task_pl, (void*)c->task_seg, (void*)c->task_xy, (void*)c->list_off,
+                  (void*)c->hit_pl, (void*)c->hit_seg, (void*)c->hit_xy})
+    free(p);
+  memset(c, 0, sizeof(*c));
 }
 
 extern "C" void eg3d_free_edgepoints(eg3d_edgepoints* e) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "eg3d_dev_pipeline.h"
+#include "eg3d_matched_core.h"
 
 namespace eg3d {
 
@@ -26,7 +27,8 @@ __device__ __forceinline__ void seed_obs_in_view(const SeedsDev& sd, uint32_t t0
 }
 
 enum : uint32_t { CTR_ARENA_OVERFLOW = 0x100u, CTR_SLOT_STARVED = 0x200u /* k3b_expand found no free working slice (internal) */,
-                  CTR_LONG_REFUSED = 0x400u /* the few-views build of k3b_expand met a solve of more than 32 rows (internal) */ };
+                  CTR_LONG_REFUSED = 0x400u /* the few-views build of k3b_expand met a solve of more than 32 rows (internal) */,
+                  CTR_N1_NO_PROGRESS = 0x800u /* k_n1_samples<., true>: a jump past a held interval did not advance (internal) */ };
 typedef uint64_t eg3d_off_t;  // element type of obs_off in the output cloud (include/eg3d.h)
 // arguments of k_publish: up to 6 runs of device words copied to the host mailbox, words cleared afterwards
 struct PubArgs {
@@ -76,10 +78,16 @@ struct SetsDev {
 void launch_n1_samples(hipStream_t st, bool fill, DevScene s, SetsDev sets, uint32_t n_rows, uint32_t item_begin,
                        uint32_t n_items, uint32_t* sample_cnt, const uint32_t* sample_off, Obs* samples,
                        uint32_t* task_seed, uint32_t* task_entry, uint32_t* task_hit, uint32_t* task_list_off,
-                       uint32_t* task_row0, Counters* ctr);
+                       uint32_t* task_row0, Counters* ctr, const IvTable* matched = nullptr, uint32_t* skip_cnt = nullptr);
 // one wavefront per (task, view): hits of the sample's epipolar line on the set's polylines of that view
 void launch_n1_hits(hipStream_t st, bool fill, DevScene s, SetsDev sets, uint32_t n_tasks, const Obs* samples,
-                    const uint32_t* task_row0, uint32_t* list_cnt, const uint32_t* list_ptr, Obs* hits, Counters* ctr);
+                    const uint32_t* task_row0, uint32_t* list_cnt, const uint32_t* list_ptr, Obs* hits, Counters* ctr,
+                    const IvTable* matched = nullptr, uint32_t* drop_cnt = nullptr);
+// `matched` (device pointers, checked by launch_n1_check_intervals) selects the MATCHED instantiations of both kernels:
+// samples and hits inside a held interval are left out (eg3d_matched_core.h). The count passes (fill = false) write, when
+// the pointer is given, skip_cnt[item] = samples skipped and drop_cnt[task] = hits dropped.
+// *bad (zeroed by the caller) becomes non-zero when a row of the table fails check_interval_row; total = iv.off[n_pl]
+void launch_n1_check_intervals(hipStream_t st, DevScene s, IvTable iv, uint64_t total, uint32_t n_pl, uint32_t* bad);
 void launch_task_setup(hipStream_t st, StageAView a, const int32_t* map_view, const uint32_t* map_entry,
                        const uint32_t* map_n, TaskDesc* tasks, uint32_t* n_hyp);
 // K3a as a request/serve engine (eg3d_k3a_engine.h): orient_waves / follow_waves single-wavefront blocks, of which

@@ -181,6 +181,33 @@ def replay_matches(scene_ptr, cloud):
     return d
 
 
+def is_matched(scene_ptr, graph, view, pl, seg, xy):
+    """PLGMatchesManager::is_matched for n points against the matched intervals of `graph` (a dict as returned by
+    replay_matches): int64 [n], -1 or the index within its row of the interval that contains the point
+    (eg3d_host_is_matched — the rule the kernels of Context.match_polyline_sets(matched=...) apply). Raises ValueError
+    when the intervals fail their checks or the extractor's walk would not advance past one of them."""
+    L = lib()
+    L.eg3d_host_is_matched.argtypes = [C.POINTER(D.Scene), C.POINTER(D.MatchedIntervals), C.c_uint64, D.i32p, D.u32p,
+                                       D.u32p, D.f32p, C.POINTER(C.c_int64)]
+    m = D.MatchedIntervalsArrays(graph)
+    view = np.ascontiguousarray(view, np.int32).reshape(-1)
+    n = len(view)
+    pad = lambda a, t, w: np.ascontiguousarray(a, t).reshape(-1) if n else np.zeros(w, t)
+    pl, seg, xy = pad(pl, np.uint32, 1), pad(seg, np.uint32, 1), pad(xy, np.float32, 2)
+    if n and (len(pl) != n or len(seg) != n or len(xy) != 2 * n):
+        raise ValueError("is_matched: view, pl, seg, xy differ in length")
+    out = np.full(max(n, 1), -1, np.int64)
+    rc = L.eg3d_host_is_matched(scene_ptr, C.byref(m.c), n, D.np_ptr(view if n else np.zeros(1, np.int32), C.c_int32),
+                                D.np_ptr(pl, C.c_uint32), D.np_ptr(seg, C.c_uint32), D.np_ptr(xy, C.c_float),
+                                D.np_ptr(out, C.c_int64))
+    if rc == -2:
+        raise ValueError("is_matched: the intervals do not belong to this scene (the walk would not advance past %d of the "
+                         "points)" % int((out[:n] <= -2).sum()))
+    if rc != 0:
+        raise ValueError("is_matched: bad intervals or points (%d)" % rc)
+    return out[:n]
+
+
 def write_compat_graph(path, graph):
     """Pipeline 1's compatibility graph (a dict as returned by Context.similarity_graph) as the text file the reference
     hands to its community detection (eg3d_host_write_compat_graph)."""

@@ -32,6 +32,7 @@
 //        edge_matcher.cpp:84-94 convert_edge_images_to_optimized_polyline_graphs) and writes the container
 //   edge_matcher_refpoints <dir>/input.json <dir>/plgs.bin <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs]
 //                          [--sets1 <polyline matches of pipeline 1>] [--sets2 <... of pipeline 2> | --match2]
+//                          [--refpoints-first]   (pipeline 3 first; pipelines 1-2 skip what it already matched)
 //        a match file is text: "eg3d-polyline-sets 1", then "<n_sets> <n_views>", then one line per (set, view):
 //        "<count> <polyline id> ..." with view-local ids (the reference's vector<set<ulong>> per match)
 //        (--make-synthetic also writes <dir>/sets1.txt and <dir>/sets2.txt: the polylines of 3-D curves 0-2 / 3-5)
@@ -201,7 +202,7 @@ int main(int argc, char** argv) {
   if (argc >= 4 && std::strcmp(argv[1], "--make-synthetic") == 0) return make_synthetic(std::atoi(argv[2]), argv[3]);
   if (argc >= 4 && std::strcmp(argv[1], "--make-plgs") == 0) return make_plgs(argv[2], argc - 3, argv + 3);
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup] [--refpoints-first]\n", argv[0]);
     return 2;
   }
   bool do_filter = false, estimate_F = false, all_pairs = false, estimate_F_device = false;
@@ -218,6 +219,13 @@ int main(int argc, char** argv) {
     if (std::strcmp(argv[a], "--sets1") == 0 && a + 1 < argc) sets_path[0] = argv[++a];
     else if (std::strcmp(argv[a], "--sets2") == 0 && a + 1 < argc) sets_path[1] = argv[++a];
   }
+  // --refpoints-first: pipeline 3 runs FIRST and the extractor of pipelines 1-2 consults the matched intervals its cloud
+  // leaves in the PLGMatchesManager (eg3d_match_polyline_sets_matched): 20 px samples and epipolar hits inside one start
+  // nothing. The intervals come from the replay of pipeline 3's cloud — on the device and read there in place with
+  // --resident-dedup (eg3d_replay_device), on the host otherwise (eg3d_host_replay_matches). Pipeline 3's cloud is then
+  // the first of the run's. Without the switch: the reference's order 1, 2, 3 and the output of earlier builds.
+  bool refpoints_first = false;
+  for (int a = 4; a < argc; a++) refpoints_first |= std::strcmp(argv[a], "--refpoints-first") == 0;
   // --match2: pipeline 2's polyline matches are computed on the device (eg3d_match_polylines_closeness) where --sets2 reads them
   bool match2 = false;
   for (int a = 4; a < argc; a++) match2 |= std::strcmp(argv[a], "--match2") == 0;
@@ -334,6 +342,59 @@ int main(int argc, char** argv) {
     first_stage = false;
     return true;
   };
+  // ---- pipeline 3 on the GPU (pipelines.cpp:160-176, :227); with --refpoints-first it also leaves the matched intervals
+  eg3d_seeds seeds;
+  eg3d_sfm_seeds(sfm, &seeds);
+  eg3d_graph3d held_host;
+  std::memset(&held_host, 0, sizeof(held_host));
+  eg3d_matched_intervals held;
+  std::memset(&held, 0, sizeof(held));
+  auto run_pipeline3 = [&]() -> int {
+    eg3d_edgepoints e;
+    if (eg3d_match_refpoints(ctx, &seeds, 0, seeds.n_seeds, resident_dedup ? 1 : 0, &e, &tm) != EG3D_OK)
+      return fail("eg3d_match_refpoints");
+    std::printf("matched %u reference points -> %llu edge-points (%llu observations) in %.2f ms on the GPU\n", seeds.n_seeds,
+                (unsigned long long)e.n_points, (unsigned long long)e.n_obs, tm.ms_total);
+    lap(resident_dedup ? "eg3d_match_refpoints (first call, device only)" : "eg3d_match_refpoints (first call, with the copy)");
+    if (refpoints_first) {
+      held.struct_size = (uint32_t)sizeof(held);
+      if (resident_dedup) {  // the whole cloud is still in HBM: replay it there, before the dedup compacts it
+        eg3d_device_graph3d dg;
+        eg3d_replay_stats rs;
+        std::memset(&rs, 0, sizeof(rs));
+        rs.struct_size = (uint32_t)sizeof(rs);
+        if (eg3d_replay_device(ctx, nullptr, &dg, nullptr, &rs) != EG3D_OK) return fail("eg3d_replay_device");
+        held.on_device = 1;
+        held.n_scene_polylines = dg.n_scene_polylines;
+        held.iv_off = dg.iv_off;
+        held.iv_start_seg = dg.iv_start_seg;
+        held.iv_start_xy = dg.iv_start_xy;
+        held.iv_end_seg = dg.iv_end_seg;
+        held.iv_end_xy = dg.iv_end_xy;
+        std::printf("  matches manager: %llu matched intervals (replayed on the device)\n", (unsigned long long)rs.n_intervals);
+      } else {
+        if (eg3d_host_replay_matches(&sc, &e, &held_host) != 0) return fail("eg3d_host_replay_matches");
+        held.n_scene_polylines = held_host.n_scene_polylines;
+        held.iv_off = held_host.iv_off;
+        held.iv_start_seg = held_host.iv_start_seg;
+        held.iv_start_xy = held_host.iv_start_xy;
+        held.iv_end_seg = held_host.iv_end_seg;
+        held.iv_end_xy = held_host.iv_end_xy;
+        std::printf("  matches manager: %llu matched intervals (replayed on the host)\n",
+                    (unsigned long long)held_host.iv_off[held_host.n_scene_polylines]);
+      }
+      lap("replay of pipeline 3's cloud (matched intervals)");
+    }
+    if (resident_dedup) {
+      if (!append_resident(e)) return fail("eg3d_dedup_resident");
+    } else {
+      all_stages.append(e);
+    }
+    eg3d_free_edgepoints(&e);
+    lap("append to the run's cloud");
+    return 0;
+  };
+  if (refpoints_first && run_pipeline3() != 0) return 1;
   // ---- pipelines 1 and 2 (pipelines.cpp:219-223): the extractor over the polyline matches of each stage, in
   // match order (one call takes all matches of a stage: eg3d_match_polyline_sets emits them set by set)
   for (int stage = 0; stage < 2; stage++) {
@@ -400,7 +461,8 @@ int main(int argc, char** argv) {
     ps.row_off = ms.row_off.data();
     ps.pl_ids = ms.ids.data();
     eg3d_edgepoints e;
-    if (eg3d_match_polyline_sets(ctx, &ps, 0, ms.n_sets, resident_dedup ? 1 : 0, &e, &tm) != EG3D_OK)
+    if (eg3d_match_polyline_sets_matched(ctx, &ps, 0, ms.n_sets, refpoints_first ? &held : nullptr, resident_dedup ? 1 : 0, &e,
+                                         &tm) != EG3D_OK)
       return fail("eg3d_match_polyline_sets");
     std::printf("pipeline %d: %u polyline matches -> %llu edge-points (%llu observations) in %.2f ms on the GPU\n", stage + 1,
                 ms.n_sets, (unsigned long long)e.n_points, (unsigned long long)e.n_obs, tm.ms_total);
@@ -411,24 +473,8 @@ int main(int argc, char** argv) {
     }
     eg3d_free_edgepoints(&e);
   }
-  // ---- pipeline 3 on the GPU (pipelines.cpp:160-176, :227)
-  eg3d_seeds seeds;
-  eg3d_sfm_seeds(sfm, &seeds);
-  {
-    eg3d_edgepoints e;
-    if (eg3d_match_refpoints(ctx, &seeds, 0, seeds.n_seeds, resident_dedup ? 1 : 0, &e, &tm) != EG3D_OK)
-      return fail("eg3d_match_refpoints");
-    std::printf("matched %u reference points -> %llu edge-points (%llu observations) in %.2f ms on the GPU\n", seeds.n_seeds,
-                (unsigned long long)e.n_points, (unsigned long long)e.n_obs, tm.ms_total);
-    lap(resident_dedup ? "eg3d_match_refpoints (first call, device only)" : "eg3d_match_refpoints (first call, with the copy)");
-    if (resident_dedup) {
-      if (!append_resident(e)) return fail("eg3d_dedup_resident");
-    } else {
-      all_stages.append(e);
-    }
-    eg3d_free_edgepoints(&e);
-    lap("append to the run's cloud");
-  }
+  if (!refpoints_first && run_pipeline3() != 0) return 1;
+  eg3d_host_free_graph3d(&held_host);
   eg3d_edgepoints pts = all_stages.view_as_edgepoints();
 
   // ---- filter_3d_points_close_2d_array + add_3dpoints_to_sfmd (pipelines.cpp:236-239; edge_matcher.cpp:150-158)

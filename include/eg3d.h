@@ -189,8 +189,9 @@ int eg3d_match_refpoints(eg3d_ctx* ctx, const eg3d_seeds* seeds, uint32_t seed_b
  * reference's vector<set<ulong>>). Every polyline of a set is sampled every 20 px from its start
  * to its end; each sample collects the hits of its epipolar line on the set's polylines of all
  * other views and goes through the same 3-view consensus + expand-all-views as a seed's starting
- * hit. As in the reference's parallel build the PLGMatchesManager is not consulted
- * (is_matched() == false: it is empty when pipelines 1-2 run and never updated inside the loop).
+ * hit. This call does not consult a PLGMatchesManager (is_matched() == false: the manager is empty when the
+ * reference's edge_matching() runs pipelines 1-2 and is never updated inside the loop);
+ * eg3d_match_polyline_sets_matched below does, for a caller that holds a filled one.
  * Output as eg3d_match_refpoints, in the reference's order (set, start view, polyline id, sample);
  * key = (sample index of the call, start view, 0, index in chain), in the host arrays and in the
  * device view (eg3d_last_device_output after device_only) alike. */
@@ -202,6 +203,51 @@ typedef struct eg3d_polyline_sets {
 } eg3d_polyline_sets;
 int eg3d_match_polyline_sets(eg3d_ctx* ctx, const eg3d_polyline_sets* sets, uint32_t set_begin, uint32_t set_end,
                              int device_only, eg3d_edgepoints* out, eg3d_stage_times* times);
+/* The same extractor for a caller whose PLGMatchesManager already holds matched intervals (pipeline 3 ran first, a re-run on
+ * new polyline matches, chains added between sets): plgmm.is_matched is asked where the reference asks it
+ * (polyline_matching.cpp:175 and :65; the rule with its quirks M1-M4: csrc/eg3d_matched_core.h).
+ *   - a 20 px sample inside a held interval never becomes a task; the walk goes on from
+ *     next_pl_point_by_distance(interval.end, pl.end, 20) (:186-189);
+ *   - an epipolar hit inside a held interval is dropped from its list.
+ * key[0] counts the samples that became tasks; order and everything else as eg3d_match_polyline_sets. `m` is the
+ * matched_polyline_intervals CSR of a host graph, struct eg3d_graph3d: host arrays, uploaded for the duration of the call; or of the
+ * eg3d_device_graph3d of eg3d_replay_device on ctx's device (read in place). m == NULL or a table without intervals: exactly
+ * eg3d_match_polyline_sets. The table is checked before anything is indexed with it (EG3D_ERR_ARG, `out` untouched):
+ * struct_size, n_scene_polylines, offsets ascending, both segment indices of every interval inside its polyline, start
+ * segments strictly ascending within a row. A walk that would not advance (an interval whose end lies behind the point it
+ * contains — the reference does not terminate on it) is refused as EG3D_ERR_ARG too: the intervals do not belong to
+ * this scene. */
+typedef struct eg3d_matched_intervals {
+  uint32_t struct_size;        /* sizeof(eg3d_matched_intervals) */
+  int32_t on_device;           /* pointers are HBM of ctx's device (an eg3d_device_graph3d), else host */
+  uint64_t n_scene_polylines;  /* must equal view_pl_off[V] */
+  const uint64_t* iv_off;      /* [n_scene_polylines + 1] */
+  const uint32_t* iv_start_seg;
+  const float* iv_start_xy;    /* [..][2] */
+  const uint32_t* iv_end_seg;
+  const float* iv_end_xy;
+} eg3d_matched_intervals;
+int eg3d_match_polyline_sets_matched(eg3d_ctx* ctx, const eg3d_polyline_sets* sets, uint32_t set_begin, uint32_t set_end,
+                                     const eg3d_matched_intervals* m /* NULL = none */, int device_only,
+                                     eg3d_edgepoints* out, eg3d_stage_times* times);
+/* Stage A of the extractor alone (as eg3d_candidates_run for seeds), in task order. Library-owned. */
+typedef struct eg3d_set_candidates {
+  uint32_t n_tasks;          /* samples that became tasks */
+  int32_t* task_view;        /* [n_tasks] */
+  uint32_t* task_pl;         /* [n_tasks] view-local polyline id */
+  uint32_t* task_seg;
+  float* task_xy;            /* [n_tasks][2] */
+  uint64_t* list_off;        /* [n_tasks * n_views + 1] hits of list task * n_views + view */
+  uint32_t* hit_pl;
+  uint32_t* hit_seg;
+  float* hit_xy;             /* [..][2] */
+  uint64_t n_samples_skipped;/* samples inside a held interval */
+  uint64_t n_hits_filtered;  /* epipolar hits inside a held interval */
+  void* _owner;
+} eg3d_set_candidates;
+int eg3d_polyline_set_candidates(eg3d_ctx* ctx, const eg3d_polyline_sets* sets, uint32_t set_begin, uint32_t set_end,
+                                 const eg3d_matched_intervals* m /* NULL = none */, eg3d_set_candidates* out);
+void eg3d_free_set_candidates(eg3d_set_candidates* c);
 /* The checks of `sets` that need no device and no scene (eg3d_match_polyline_sets runs them too, after its id-range
  * check): row_off ascending, ids strictly ascending within every row. EG3D_OK or EG3D_ERR_ARG (eg3d_last_error says
  * which). Usable without a GPU. */

@@ -85,6 +85,12 @@ struct EdgeMatchingOptions {
   std::string pipeline1_graph_file, pipeline1_communities_file;
   bool pipeline1_detect_communities = false;
   std::string pipeline1_communities_out_file;
+  // refpoints_first = true: pipeline 3 runs FIRST and the extractor of pipelines 2 and 1 consults what it matched (the
+  // PLGMatchesManager it filled): 20 px samples and epipolar hits inside an interval pipeline 3 already matched start
+  // nothing (find_new_3d_points_from_compatible_polylines_expandallviews_parallel with the manager, polyline_matching.cpp:
+  // 65,175). Pipeline 3's cloud then comes first in the output, pipelines 1-2's behind it. Off by default: the reference's
+  // order (1, 2, 3 — the manager is empty while pipelines 1-2 run) and the output of earlier builds.
+  bool refpoints_first = false;
   bool quiet = false;
   int skipped_pipelines = 0;  // bit 0: pipeline 1 (similarity graph), bit 1: pipeline 2 (closeness to refpoints) [out]
 };
@@ -343,7 +349,15 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
   // out of scope); pipeline 3
   const bool pipeline2 = edge_matching_options().run_pipeline2;
   edge_matching_options().skipped_pipelines = pipeline2 ? 1 : 3;
-  std::vector<new_3dpoint_plgp_matches> p3ds;
+  std::vector<new_3dpoint_plgp_matches> p3ds, p3ds_r;
+  const bool refpoints_first = edge_matching_options().refpoints_first;
+  if (refpoints_first) p3ds_r = plg_matching_from_refpoints_parallel(sfm_data, em.get(), cm.get(), plgmm);
+  auto extract = [&](const std::vector<std::set<unsigned long>>& sets) {
+    if (refpoints_first) return find_new_3d_points_from_compatible_polylines_expandallviews_parallel(sfm_data, em.get(), sets, plgmm);
+    auto cur = find_new_3d_points_from_compatible_polylines_expandallviews_parallel(sfm_data, em.get(), sets);
+    detail::throw_if_failed(em.get(), "find_new_3d_points_from_compatible_polylines_expandallviews_parallel");
+    return cur;
+  };
   bool pipeline1_ran = false;
   if (edge_matching_options().run_pipeline1) {
     const EdgeMatchingOptions& o = edge_matching_options();
@@ -372,9 +386,7 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
         throw Eg3dError(EG3D_ERR_ARG, "edge_matching: the communities file does not hold one id per node of the graph");
       for (const auto& potentially_compatible_polylines :
            compute_polyline_matches_from_nodes_component_ids(graph.polyline_matches_vector, sfm_data.numCameras_, component_ids)) {
-        const auto cur = find_new_3d_points_from_compatible_polylines_expandallviews_parallel(sfm_data, em.get(),
-                                                                                              potentially_compatible_polylines);
-        detail::throw_if_failed(em.get(), "find_new_3d_points_from_compatible_polylines_expandallviews_parallel");
+        const auto cur = extract(potentially_compatible_polylines);
         p3ds.insert(p3ds.end(), cur.begin(), cur.end());
       }
       pipeline1_ran = true;
@@ -388,17 +400,19 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
                            "reference's (INTEGRATION.md)\n");
     const auto pmctr_res = polyline_matching_closeness_to_refpoints(sfm_data, em.get());
     for (const auto& potentially_compatible_polylines : pmctr_res.second) {
-      const auto cur = find_new_3d_points_from_compatible_polylines_expandallviews_parallel(sfm_data, em.get(),
-                                                                                            potentially_compatible_polylines);
-      detail::throw_if_failed(em.get(), "find_new_3d_points_from_compatible_polylines_expandallviews_parallel");
+      const auto cur = extract(potentially_compatible_polylines);
       p3ds.insert(p3ds.end(), cur.begin(), cur.end());
     }
   } else if (!edge_matching_options().quiet && !pipeline1_ran)
     std::fprintf(stderr, "eg3d edge_matching: pipelines 1-2 (polyline matches of the similarity-graph / Louvain matchers) are not "
                          "part of this build; running pipeline 3 (reference points) only: the output may hold fewer edge-points "
                          "than the reference's (INTEGRATION.md)\n");
-  const std::vector<new_3dpoint_plgp_matches> p3ds_r = plg_matching_from_refpoints_parallel(sfm_data, em.get(), cm.get(), plgmm);
-  p3ds.insert(p3ds.end(), p3ds_r.begin(), p3ds_r.end());
+  if (!refpoints_first) {
+    p3ds_r = plg_matching_from_refpoints_parallel(sfm_data, em.get(), cm.get(), plgmm);
+    p3ds.insert(p3ds.end(), p3ds_r.begin(), p3ds_r.end());
+  } else {
+    p3ds.insert(p3ds.begin(), p3ds_r.begin(), p3ds_r.end());
+  }
   const std::vector<new_3dpoint_plgp_matches> filtered_p3ds =
       filter_3d_points_close_2d_array(sfm_data.numCameras_, sfm_data.imageWidth_, sfm_data.imageHeight_, p3ds);
   add_3dpoints_to_sfmd(sfm_data, filtered_p3ds);

@@ -152,6 +152,15 @@ typedef struct eg3d_graph3d {
 } eg3d_graph3d;
 int eg3d_host_replay_matches(const eg3d_scene* scene, const eg3d_edgepoints* pts, eg3d_graph3d* out);
 void eg3d_host_free_graph3d(eg3d_graph3d* g);
+/* PLGMatchesManager::is_matched (plg_matches_manager.cpp:54-85 with polyline_graph_2d.cpp:269-293; the rule the kernels
+ * of eg3d_match_polyline_sets_matched apply, csrc/eg3d_matched_core.h) for n points (view, view-local polyline, segment,
+ * xy[n][2]) against `intervals` (host arrays): out_index[i] = -1, or the index within its row of the interval that
+ * contains point i. Returns 0; -1 for bad arguments, a table that fails the checks of eg3d_match_polyline_sets_matched
+ * or a point that is not on its polyline's segments (nothing written); -2 when for some matched point the extractor's
+ * walk would not advance from the containing interval's end (out_index[i] = -2 - index for those points): the intervals
+ * do not belong to this scene. */
+int eg3d_host_is_matched(const eg3d_scene* scene, const eg3d_matched_intervals* intervals, uint64_t n, const int32_t* view,
+                         const uint32_t* pl, const uint32_t* seg, const float* xy, int64_t* out_index);
 
 /* ------------------------------ pipeline 1: the file seam of the community detection -- */
 /* The reference writes the weighted compatibility graph of polyline_matching_similarity_graph to a text file, runs Grappolo

@@ -87,6 +87,9 @@ struct PolyLineGraph2D {
     unsigned long polyline_id;
     pl_point plp;
   };
+  struct pl_interval {  // polyline::pl_interval (polyline_graph_2d.hpp): a matched stretch of one polyline
+    pl_point start, end;
+  };
   std::vector<polyline> polylines;
   std::vector<vec2> nodes_coords;
   // PolyLineGraph2D::is_valid_polyline (polyline_graph_2d.cpp:1141-1147)
@@ -120,9 +123,51 @@ class PLGMatchesManager {
     const uint64_t gpl = sc.view_pl_off[plg_id] + polyline_id;
     return {g_.iv_off[gpl], g_.iv_off[gpl + 1]};
   }
+  // The intervals as the table eg3d_match_polyline_sets_matched / eg3d_host_is_matched take (host arrays of get_plg3d();
+  // valid until the next replay). struct_size == 0: nothing has been replayed yet — no manager.
+  eg3d_matched_intervals matched_table() const {
+    eg3d_matched_intervals m;
+    std::memset(&m, 0, sizeof(m));
+    if (!g_.iv_off) return m;
+    m.struct_size = (uint32_t)sizeof(m);
+    m.n_scene_polylines = g_.n_scene_polylines;
+    m.iv_off = g_.iv_off;
+    m.iv_start_seg = g_.iv_start_seg;
+    m.iv_start_xy = g_.iv_start_xy;
+    m.iv_end_seg = g_.iv_end_seg;
+    m.iv_end_xy = g_.iv_end_xy;
+    return m;
+  }
+  // PLGMatchesManager::is_matched (plg_matches_manager.hpp:131, plg_matches_manager.cpp:54-85) against what the last
+  // replay left: true + the containing interval. The rule is the library's (eg3d_host_is_matched: the one the kernels
+  // of eg3d_match_polyline_sets_matched apply, quirks included). Throws Eg3dError for a point that is not on a segment
+  // of its polyline.
+  bool is_matched(const int plg_id, const unsigned long polyline_id, const PolyLineGraph2D::pl_point& plp,
+                  PolyLineGraph2D::pl_interval& pli_containing_point) const {
+    const eg3d_matched_intervals m = matched_table();
+    if (!m.struct_size) return false;
+    const int32_t view = plg_id;
+    const uint32_t pl = (uint32_t)polyline_id, seg = (uint32_t)plp.segment_index;
+    const float xy[2] = {plp.coords.x, plp.coords.y};
+    int64_t k = -1;
+    const int rc = polyline_id > 0xfffffffful || plp.segment_index > 0xfffffffful
+                       ? -1
+                       : eg3d_host_is_matched(&sc_, &m, 1, &view, &pl, &seg, xy, &k);
+    if (rc == -1) throw Eg3dError(EG3D_ERR_ARG, "PLGMatchesManager::is_matched: the point is not on its polyline");
+    if (k == -1) return false;
+    if (k < -1) k = -2 - k;  // (matched by an interval the extractor's walk would not get past: still the manager's answer)
+    const uint64_t at = g_.iv_off[sc_.view_pl_off[plg_id] + pl] + (uint64_t)k;
+    pli_containing_point.start = {g_.iv_start_seg[at], {g_.iv_start_xy[2 * at], g_.iv_start_xy[2 * at + 1]}};
+    pli_containing_point.end = {g_.iv_end_seg[at], {g_.iv_end_xy[2 * at], g_.iv_end_xy[2 * at + 1]}};
+    return true;
+  }
+  bool is_matched(const int plg_id, const PolyLineGraph2D::plg_point& plgp, PolyLineGraph2D::pl_interval& pli_containing_point) const {
+    return is_matched(plg_id, plgp.polyline_id, plgp.plp, pli_containing_point);
+  }
   // concatenates the batches of a run (seed order) and replays them
   int replay(const eg3d_scene& sc, const std::vector<eg3d_edgepoints>& parts) {
     eg3d_host_free_graph3d(&g_);
+    sc_ = sc;
     std::vector<float> X, xy;
     std::vector<uint32_t> pl, seg, key;
     std::vector<uint64_t> off(1, 0);
@@ -156,6 +201,7 @@ class PLGMatchesManager {
   int replay_chains(const eg3d_scene& sc, const std::vector<std::vector<new_3dpoint_plgp_matches>>& chains,
                     const std::vector<std::array<uint32_t, 3>>& chain_key) {
     eg3d_host_free_graph3d(&g_);
+    sc_ = sc;
     std::vector<float> X, xy;
     std::vector<uint32_t> pl, seg, key;
     std::vector<uint64_t> off(1, 0);
@@ -203,6 +249,7 @@ class PLGMatchesManager {
 
  private:
   eg3d_graph3d g_;
+  eg3d_scene sc_{};  // the scene of the last replay (the edge manager's: its arrays outlive the run)
 };
 
 // EdgeManager (edge_manager.hpp:54-73): the abstract base the path's entry points take (`const EdgeManager* em`, which
@@ -388,7 +435,10 @@ class PLGEdgeManager : public EdgeManager {
   // find_new_3d_points_from_compatible_polylines_expandallviews_parallel for ONE set of potentially
   // compatible polylines (per view: the reference's set<ulong> of polyline ids), as
   // pipelines.cpp:98,144 call it once per polyline match.
-  std::vector<new_3dpoint_plgp_matches> match_polyline_set(const std::vector<std::set<unsigned long>>& compat) {
+  // plgmm (may be null: no manager): the matches manager the extractor consults — samples and epipolar hits inside an
+  // interval it holds are left out (eg3d_match_polyline_sets_matched).
+  std::vector<new_3dpoint_plgp_matches> match_polyline_set(const std::vector<std::set<unsigned long>>& compat,
+                                                           const PLGMatchesManager* plgmm = nullptr) {
     std::vector<new_3dpoint_plgp_matches> res;
     if (!ctx_) return res;
     std::vector<uint32_t> row_off(1, 0), ids;
@@ -408,7 +458,11 @@ class PLGEdgeManager : public EdgeManager {
     ps.row_off = row_off.data();
     ps.pl_ids = ids.data();
     eg3d_edgepoints e;
-    status_ = eg3d_match_polyline_sets(ctx_, &ps, 0, 1, 0, &e, nullptr);
+    eg3d_matched_intervals m;
+    std::memset(&m, 0, sizeof(m));
+    if (plgmm) m = plgmm->matched_table();
+    status_ = m.struct_size ? eg3d_match_polyline_sets_matched(ctx_, &ps, 0, 1, &m, 0, &e, nullptr)
+                            : eg3d_match_polyline_sets(ctx_, &ps, 0, 1, 0, &e, nullptr);
     if (status_ == EG3D_OK) {
       res.reserve(e.n_points);
       for (uint64_t i = 0; i < e.n_points; i++) {
@@ -742,6 +796,19 @@ inline std::vector<new_3dpoint_plgp_matches> plg_matching_from_refpoints(const S
 inline std::vector<new_3dpoint_plgp_matches> find_new_3d_points_from_compatible_polylines_expandallviews_parallel(
     const SfMData&, PLGEdgeManager* em, const std::vector<std::set<unsigned long>>& potentially_compatible_polylines) {
   return em->match_polyline_set(potentially_compatible_polylines);
+}
+// ... with the reference's matches manager argument (polyline_matching.cpp:153): what plgmm holds — after
+// plg_matching_from_refpoints_parallel(sfmd, em, cm, plgmm), say — is consulted as the reference consults it: a 20 px sample
+// inside a held interval starts nothing and the walk goes on past the interval's end, an epipolar hit inside one is dropped.
+// As in the reference's parallel build, plgmm is not updated by this call. A manager that has replayed nothing behaves as
+// the overload above. Throws Eg3dError on failure.
+inline std::vector<new_3dpoint_plgp_matches> find_new_3d_points_from_compatible_polylines_expandallviews_parallel(
+    const SfMData&, PLGEdgeManager* em, const std::vector<std::set<unsigned long>>& potentially_compatible_polylines,
+    PLGMatchesManager& plgmm) {
+  auto res = em->match_polyline_set(potentially_compatible_polylines, &plgmm);
+  if (em->last_status() != EG3D_OK)
+    throw Eg3dError(em->last_status(), std::string("find_new_3d_points_from_compatible_polylines_expandallviews_parallel: ") + eg3d_last_error());
+  return res;
 }
 
 // polyline_matching_closeness_to_refpoints (include/edgegraph3d/matching/polyline_matching/polyline_matcher.hpp): plgs and
