@@ -109,7 +109,8 @@ def build_hip(force=False, out=None, defines=()):
         obj = os.path.join(odir, os.path.basename(src) + ".o")
         if force or _obj_stale(obj, obj + ".d", stamp):
             jobs.append([hipcc] + cflags + ["-MD", "-MF", obj + ".d", "-c", src, "-o", obj])
-    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, len(jobs))) as ex:
+    # one compiler per stale source, but no more at once than the machine's share of CPUs (MAX_JOBS, 16 unless set)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", "16"))))) as ex:
         list(ex.map(_run, jobs))
     tmp = out + ".tmp%d" % os.getpid()
     try:
@@ -302,7 +303,9 @@ def device_source_fingerprint(defines=()):
     """sha256 over the device CODE (sources with comments and blank lines removed) and the switches it is compiled with:
     what a PMC profile under profiles/ was measured ON. tools/profile_summary.py records it beside the traffic figures;
     bench.py reports `roofline.traffic` only while it still matches (a changed kernel makes the committed figure stale:
-    it is then reported as such, not as this run's traffic). Editing a comment does not change it. Of the eg3d_api* files
+    it is then reported as such, not as this run's traffic). Editing a comment does not change it; renaming a source or
+    moving a kernel to another file does (file names are hashed, each in front of its text). The kernels live in the
+    per-stage eg3d_k*.hip / eg3d_n1_sets.hip files and the headers they include. Of the eg3d_api* files
     (eg3d_api.hip, eg3d_api_match.hip, the per-stage eg3d_api_filter / _replay / _polymatch / _simgraph / _louvain /
     _fundamental.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
     the preprocessor lines count — the macros that choose the kernel build, its default form and the slot-pool sizing;

@@ -38,7 +38,7 @@ namespace eg3d {
 #define EG3D_GN_PRECHECK_IT 2
 #endif
 #ifndef EG3D_MANY_KEEP
-#define EG3D_MANY_KEEP 1 /* chunks of a long solve whose rows stay in registers between the passes of an iteration, many-views build (gn_round<KEEP>; eg3d_kernels.hip k3b_expand_many): 0 / 1 / 2 -> C4 step 1810 / 1774 / 1823 ms at 27 / 60 / 263 spilled VGPRs (round 5; round 4 had only measured 4 chunks at 2 waves per SIMD: slower) */
+#define EG3D_MANY_KEEP 1 /* chunks of a long solve whose rows stay in registers between the passes of an iteration, many-views build (gn_round<KEEP>; eg3d_k3_chains.hip k3b_expand_many): 0 / 1 / 2 -> C4 step 1810 / 1774 / 1823 ms at 27 / 60 / 263 spilled VGPRs (round 5; round 4 had only measured 4 chunks at 2 waves per SIMD: slower) */
 #endif
 #ifndef EG3D_K3B_HOIST
 #define EG3D_K3B_HOIST 1 /* k3b_expand's one-chunk rounds load a lane's observation once, before the iterations (gn_round's HOIST) instead of per iteration (0: rounds 4-5, when it measured as a loss; on the round-6 kernel: C3' 38.6 -> 38.2 ms, C2 4.23 -> 4.16, three runs each) */

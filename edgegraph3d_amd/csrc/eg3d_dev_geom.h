@@ -1,6 +1,6 @@
 // eg3d_dev_geom.h — 2-D geometry and polyline-walking primitives of the MI355X path.
 //
-// These are the per-lane building blocks of the gfx950 kernels in eg3d_kernels.hip. They are
+// These are the per-lane building blocks of the gfx950 kernels in the eg3d_k*.hip files. They are
 // written against flat device arrays (struct-of-arrays scene, CSR polylines) instead of the
 // reference's vector-of-struct graph. Each function names the reference behaviour it must
 // reproduce (file:line relative to the reference tree) — behaviour, not code: the layout,

@@ -1,8 +1,8 @@
 // eg3d_dev_pipeline.h — per-work-item bodies of the phase pipeline
 //   K1 seed_candidates -> K2 epipolar_hits -> T task_setup -> K3a hypotheses ->
 //   K3s select -> K3b expand -> K4 emit
-// Each function is the body one GPU lane runs for one item; the __global__ wrappers in
-// eg3d_kernels.hip only map thread ids to items. (The test-only host simulation under
+// Each function is the body one GPU lane runs for one item; the __global__ wrappers in the
+// per-stage eg3d_k*.hip files only map thread ids to items. (The test-only host simulation under
 // tests/hostsim drives the same bodies serially to debug logic without a GPU.)
 //
 // Reference behaviour covered here: the 3-view selection and uniqueness rule of
@@ -46,6 +46,20 @@ EG3D_HD int32_t track_view(const StageAView& a, uint32_t seed, uint32_t entry) {
 }
 EG3D_HD uint32_t track_n_views(const StageAView& a, const uint32_t* map_n, uint32_t seed) {
   return a.dense_k ? a.dense_k : map_n[seed - a.seed_begin];
+}
+
+// Owner of item x in a CSR: the largest t in [0, n) with off[t] <= x (off ascending, off[n] > x; empty rows are skipped by
+// the <=). K3a: the task of a hypothesis; N1: the row of a set's item.
+EG3D_HD uint32_t find_owner(const uint32_t* off, uint32_t n, uint32_t x) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= x)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
 }
 
 // view-indexed scatter of a seed's track: distinct views ascending, last entry wins (Q2-like,

@@ -283,12 +283,10 @@ __global__ void __launch_bounds__(K10_BLOCK) k10_edge_weights(K10Graph g, const 
 }
 
 // ------------------------------------------------------------ launch wrappers --
-static inline dim3 k10_blocks(uint64_t n, uint32_t per_block) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
-
 void launch_k10_close_list(hipStream_t st, bool fill, DevScene s, K9Grid g10, SeedsDev sd, uint32_t sv_base, uint32_t n_sv,
                            const uint32_t* sv_seed, uint32_t* cnt, const uint32_t* off, unsigned long long* pair) {
   if (!n_sv) return;
-  const dim3 grid = k10_blocks((uint64_t)n_sv * 64, K10_BLOCK);
+  const dim3 grid = blocks_for((uint64_t)n_sv * 64, K10_BLOCK);
   if (fill)
     hipLaunchKernelGGL(k10_close_list<true>, grid, dim3(K10_BLOCK), 0, st, s, g10, sd, sv_base, n_sv, sv_seed, cnt, off, pair);
   else
@@ -297,40 +295,40 @@ void launch_k10_close_list(hipStream_t st, bool fill, DevScene s, K9Grid g10, Se
 void launch_k10_pairs(hipStream_t st, DevScene s, const unsigned long long* pair, uint32_t n_pair, uint32_t* cp_view,
                       uint32_t* cp_pl, unsigned long long* swapped) {
   if (!n_pair) return;
-  hipLaunchKernelGGL(k10_pairs, k10_blocks(n_pair, K10_BLOCK), dim3(K10_BLOCK), 0, st, s, pair, n_pair, cp_view, cp_pl, swapped);
+  hipLaunchKernelGGL(k10_pairs, blocks_for(n_pair, K10_BLOCK), dim3(K10_BLOCK), 0, st, s, pair, n_pair, cp_view, cp_pl, swapped);
 }
 void launch_k10_row_off(hipStream_t st, const unsigned long long* keys, uint32_t n_keys, uint32_t base, uint32_t n_rows,
                         uint32_t* off) {
-  hipLaunchKernelGGL(k10_row_off, k10_blocks((uint64_t)n_rows + 1, K10_BLOCK), dim3(K10_BLOCK), 0, st, keys, n_keys, base, n_rows, off);
+  hipLaunchKernelGGL(k10_row_off, blocks_for((uint64_t)n_rows + 1, K10_BLOCK), dim3(K10_BLOCK), 0, st, keys, n_keys, base, n_rows, off);
 }
 void launch_k10_low_words(hipStream_t st, const unsigned long long* keys, uint32_t n, uint32_t* lo) {
   if (!n) return;
-  hipLaunchKernelGGL(k10_low_words, k10_blocks(n, K10_BLOCK), dim3(K10_BLOCK), 0, st, keys, n, lo);
+  hipLaunchKernelGGL(k10_low_words, blocks_for(n, K10_BLOCK), dim3(K10_BLOCK), 0, st, keys, n, lo);
 }
 void launch_k10_points(hipStream_t st, SeedsDev sd, uint32_t seed_begin, uint32_t n_pts, const uint32_t* cp_off,
                        const uint32_t* cp_view, uint32_t vis_words, float* weight, uint32_t* vis, unsigned long long* n_pairs) {
-  hipLaunchKernelGGL(k10_points, k10_blocks((uint64_t)n_pts + 1, K10_BLOCK), dim3(K10_BLOCK), 0, st, sd, seed_begin, n_pts, cp_off,
+  hipLaunchKernelGGL(k10_points, blocks_for((uint64_t)n_pts + 1, K10_BLOCK), dim3(K10_BLOCK), 0, st, sd, seed_begin, n_pts, cp_off,
                      cp_view, vis_words, weight, vis, n_pairs);
 }
 void launch_k10_node_keys(hipStream_t st, uint32_t n_pl, const uint32_t* cr_off, const uint32_t* cr_point, unsigned long long* key) {
   if (!n_pl) return;
-  hipLaunchKernelGGL(k10_node_keys, k10_blocks(n_pl, K10_BLOCK), dim3(K10_BLOCK), 0, st, n_pl, cr_off, cr_point, key);
+  hipLaunchKernelGGL(k10_node_keys, blocks_for(n_pl, K10_BLOCK), dim3(K10_BLOCK), 0, st, n_pl, cr_off, cr_point, key);
 }
 void launch_k10_nodes(hipStream_t st, DevScene s, const unsigned long long* key_sorted, uint32_t n_pl, uint32_t* node_of,
                       uint32_t* node_g, uint32_t* node_view, uint32_t* node_pl, uint32_t* n_nodes) {
   if (!n_pl) return;
-  hipLaunchKernelGGL(k10_nodes, k10_blocks(n_pl, K10_BLOCK), dim3(K10_BLOCK), 0, st, s, key_sorted, n_pl, node_of, node_g, node_view,
+  hipLaunchKernelGGL(k10_nodes, blocks_for(n_pl, K10_BLOCK), dim3(K10_BLOCK), 0, st, s, key_sorted, n_pl, node_of, node_g, node_view,
                      node_pl, n_nodes);
 }
 void launch_k10_expand(hipStream_t st, K10Graph g, const unsigned long long* pair_off, const uint32_t* node_of,
                        unsigned long long t0, uint32_t n, unsigned long long* out) {
   if (!n) return;
-  hipLaunchKernelGGL(k10_expand, k10_blocks(n, K10_BLOCK), dim3(K10_BLOCK), 0, st, g, pair_off, node_of, t0, n, out);
+  hipLaunchKernelGGL(k10_expand, blocks_for(n, K10_BLOCK), dim3(K10_BLOCK), 0, st, g, pair_off, node_of, t0, n, out);
 }
 void launch_k10_edge_weights(hipStream_t st, K10Graph g, const unsigned long long* edges, uint32_t n_edges,
                              unsigned long long* dkey, uint32_t* dval, uint32_t* n_kept) {
   if (!n_edges) return;
-  hipLaunchKernelGGL(k10_edge_weights, k10_blocks(n_edges, K10_BLOCK), dim3(K10_BLOCK), 0, st, g, edges, n_edges, dkey, dval, n_kept);
+  hipLaunchKernelGGL(k10_edge_weights, blocks_for(n_edges, K10_BLOCK), dim3(K10_BLOCK), 0, st, g, edges, n_edges, dkey, dval, n_kept);
 }
 
 hipError_t k10_scan_u64(hipStream_t st, void* tmp, size_t& tmp_bytes, const unsigned long long* in, unsigned long long* out, size_t n) {

@@ -1,4 +1,4 @@
-// eg3d_k3a_engine.h — K3a as a request/serve engine (gfx950 only; included by eg3d_kernels.hip).
+// eg3d_k3a_engine.h — K3a as a request/serve engine (gfx950 only; included by eg3d_k3_chains.hip).
 //
 // What the hypothesis stage computes is defined by eg3d_dev_follow.h (evaluate_hypothesis with HTeamSeq is the
 // sequential statement the host simulation runs; reference: plg_matching.cpp:51-265, 633-795, 1276-1287). This file

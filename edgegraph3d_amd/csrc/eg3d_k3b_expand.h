@@ -1,5 +1,5 @@
-// eg3d_k3b_expand.h — K3b, the expand stage, one wavefront per chain (gfx950 only; included by eg3d_kernels.hip after
-// its wave helpers and the K3a / K3s kernels).
+// eg3d_k3b_expand.h — K3b, the expand stage, one wavefront per chain (gfx950 only; included by eg3d_k3_chains.hip,
+// which instantiates k3b_expand_t and holds the launch wrappers).
 //
 // What the stage computes is stated sequentially by expand_chain with TeamSeq in eg3d_dev_expand.h (the host simulation
 // of the tests runs that). This file is how the GPU runs it: TeamWaveT, the 64-lane team; the slot pools that lend the

@@ -1,4 +1,4 @@
-// eg3d_k3c_engine.h — the expand stage as a LANE-PER-CHAIN engine (gfx950 only; included by eg3d_kernels.hip).
+// eg3d_k3c_engine.h — the expand stage as a LANE-PER-CHAIN engine (gfx950 only; included by eg3d_k3_chains.hip).
 //
 // k3b_expand (rounds 1-4) gives a chain a whole wavefront: its Gauss-Newton solves and candidate searches spread over
 // the 64 lanes, everything else — every side-walk step, every step of the chain following, every 2-view DLT, all the

@@ -312,54 +312,52 @@ __global__ void __launch_bounds__(K8_BLOCK) k8_iv_off(DevScene s, uint32_t n_pl,
 }
 
 // ------------------------------------------------------------ launch wrappers --
-static inline dim3 k8_blocks(uint64_t n, uint32_t per_block) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
-
 void launch_k8_pairs(hipStream_t st, CloudView in, DevScene s, unsigned long long* n_pairs, uint32_t* flags) {
   const uint64_t n = in.n_points > in.n_obs ? in.n_points : in.n_obs;
   if (!n) return;
-  hipLaunchKernelGGL(k8_pairs, k8_blocks(n, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, s, n_pairs, flags);
+  hipLaunchKernelGGL(k8_pairs, blocks_for(n, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, s, n_pairs, flags);
 }
 void launch_k8_node_claim(hipStream_t st, CloudView in, K8Table t) {
   if (!in.n_points) return;
-  hipLaunchKernelGGL(k8_node_claim, k8_blocks(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, t);
+  hipLaunchKernelGGL(k8_node_claim, blocks_for(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, t);
 }
 void launch_k8_node_resolve(hipStream_t st, CloudView in, K8Table t, uint32_t* first_of, uint32_t* is_first, uint32_t* last_of) {
   if (!in.n_points) return;
-  hipLaunchKernelGGL(k8_node_resolve, k8_blocks(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, t, first_of, is_first, last_of);
+  hipLaunchKernelGGL(k8_node_resolve, blocks_for(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, t, first_of, is_first, last_of);
 }
 void launch_k8_node_write(hipStream_t st, CloudView in, const uint32_t* first_of, const uint32_t* is_first, const uint32_t* rank,
                           const uint32_t* last_of, K8Graph g, unsigned long long* pair_key, uint32_t* pair_val) {
   if (!in.n_points) return;
-  hipLaunchKernelGGL(k8_node_write, k8_blocks(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, first_of, is_first, rank, last_of,
+  hipLaunchKernelGGL(k8_node_write, blocks_for(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, first_of, is_first, rank, last_of,
                      g, pair_key, pair_val);
 }
 void launch_k8_pl_heads(hipStream_t st, const unsigned long long* key_sorted, const uint32_t* val_sorted, uint64_t n_pairs,
                         uint32_t* creates) {
   if (!n_pairs) return;
-  hipLaunchKernelGGL(k8_pl_heads, k8_blocks(n_pairs, K8_BLOCK), dim3(K8_BLOCK), 0, st, key_sorted, val_sorted, n_pairs, creates);
+  hipLaunchKernelGGL(k8_pl_heads, blocks_for(n_pairs, K8_BLOCK), dim3(K8_BLOCK), 0, st, key_sorted, val_sorted, n_pairs, creates);
 }
 void launch_k8_pl_write(hipStream_t st, CloudView in, const uint32_t* first_of, const uint32_t* rank, const uint32_t* creates,
                         const uint32_t* pl_id, K8Graph g, unsigned long long* inc) {
   if (!in.n_points) return;
-  hipLaunchKernelGGL(k8_pl_write, k8_blocks(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, first_of, rank, creates, pl_id, g,
+  hipLaunchKernelGGL(k8_pl_write, blocks_for(in.n_points, K8_BLOCK), dim3(K8_BLOCK), 0, st, in, first_of, rank, creates, pl_id, g,
                      inc);
 }
 void launch_k8_conn(hipStream_t st, const unsigned long long* inc_sorted, uint64_t n_inc, uint64_t n_nodes, K8Graph g) {
   if (!n_inc) return;
-  hipLaunchKernelGGL(k8_conn, k8_blocks(n_inc, K8_BLOCK), dim3(K8_BLOCK), 0, st, inc_sorted, n_inc, n_nodes, g);
+  hipLaunchKernelGGL(k8_conn, blocks_for(n_inc, K8_BLOCK), dim3(K8_BLOCK), 0, st, inc_sorted, n_inc, n_nodes, g);
 }
 void launch_k8_iv(hipStream_t st, bool write, CloudView in, DevScene s, unsigned long long* map, const uint32_t* pos, K8Graph g) {
   if (!in.n_points) return;
   if (write)
-    hipLaunchKernelGGL(k8_iv<true>, k8_blocks(in.n_points, K8_BLOCK / 8), dim3(K8_BLOCK), 0, st, in, s, map, pos, g);
+    hipLaunchKernelGGL(k8_iv<true>, blocks_for(in.n_points, K8_BLOCK / 8), dim3(K8_BLOCK), 0, st, in, s, map, pos, g);
   else
-    hipLaunchKernelGGL(k8_iv<false>, k8_blocks(in.n_points, K8_BLOCK / 8), dim3(K8_BLOCK), 0, st, in, s, map, pos, g);
+    hipLaunchKernelGGL(k8_iv<false>, blocks_for(in.n_points, K8_BLOCK / 8), dim3(K8_BLOCK), 0, st, in, s, map, pos, g);
 }
 void launch_k8_seg_flags(hipStream_t st, const unsigned long long* map, uint64_t n_vtx, uint32_t* flag) {
-  hipLaunchKernelGGL(k8_seg_flags, k8_blocks(n_vtx + 1, K8_BLOCK), dim3(K8_BLOCK), 0, st, map, n_vtx, flag);
+  hipLaunchKernelGGL(k8_seg_flags, blocks_for(n_vtx + 1, K8_BLOCK), dim3(K8_BLOCK), 0, st, map, n_vtx, flag);
 }
 void launch_k8_iv_off(hipStream_t st, DevScene s, uint32_t n_pl, const uint32_t* pos, K8Graph g) {
-  hipLaunchKernelGGL(k8_iv_off, k8_blocks((uint64_t)n_pl + 1, K8_BLOCK), dim3(K8_BLOCK), 0, st, s, n_pl, pos, g);
+  hipLaunchKernelGGL(k8_iv_off, blocks_for((uint64_t)n_pl + 1, K8_BLOCK), dim3(K8_BLOCK), 0, st, s, n_pl, pos, g);
 }
 
 hipError_t k8_scan_u32(hipStream_t st, void* tmp, size_t& tmp_bytes, const uint32_t* in, uint32_t* out, size_t n) {

@@ -265,45 +265,43 @@ __global__ void __launch_bounds__(K9_BLOCK) k9_compact(const uint32_t* accept, c
 }
 
 // ------------------------------------------------------------ launch wrappers --
-static inline dim3 k9_blocks(uint64_t n, uint32_t per_block) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
-
 void launch_k9_prep(hipStream_t st, SeedsDev sd, int32_t n_views, uint32_t seed_begin, uint32_t n_seeds, uint32_t sv_base,
                     uint32_t* sv_seed, uint32_t* flags) {
   if (!n_seeds) return;
-  hipLaunchKernelGGL(k9_prep, k9_blocks(n_seeds, K9_BLOCK), dim3(K9_BLOCK), 0, st, sd, n_views, seed_begin, n_seeds, sv_base,
+  hipLaunchKernelGGL(k9_prep, blocks_for(n_seeds, K9_BLOCK), dim3(K9_BLOCK), 0, st, sd, n_views, seed_begin, n_seeds, sv_base,
                      sv_seed, flags);
 }
 void launch_k9_close_polylines(hipStream_t st, DevScene s, K9Grid g10, SeedsDev sd, uint32_t sv_base, uint32_t n_sv,
                                const uint32_t* sv_seed, K9Entries out) {
   if (!n_sv) return;
-  hipLaunchKernelGGL(k9_close_polylines, k9_blocks((uint64_t)n_sv * 64, K9_BLOCK), dim3(K9_BLOCK), 0, st, s, g10, sd, sv_base,
+  hipLaunchKernelGGL(k9_close_polylines, blocks_for((uint64_t)n_sv * 64, K9_BLOCK), dim3(K9_BLOCK), 0, st, s, g10, sd, sv_base,
                      n_sv, sv_seed, out);
 }
 void launch_k9_init(hipStream_t st, uint32_t n_pl, K9Graph g) {
   if (!n_pl) return;
-  hipLaunchKernelGGL(k9_init, k9_blocks(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, n_pl, g);
+  hipLaunchKernelGGL(k9_init, blocks_for(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, n_pl, g);
 }
 void launch_k9_refpoint_rule(hipStream_t st, DevScene s, SeedsDev sd, uint32_t seed_begin, uint32_t n_seeds, uint32_t sv_base,
                              K9Entries in, uint32_t* accept, K9Graph g) {
-  hipLaunchKernelGGL(k9_refpoint_rule, k9_blocks((uint64_t)n_seeds + 1, K9_BLOCK), dim3(K9_BLOCK), 0, st, s, sd, seed_begin,
+  hipLaunchKernelGGL(k9_refpoint_rule, blocks_for((uint64_t)n_seeds + 1, K9_BLOCK), dim3(K9_BLOCK), 0, st, s, sd, seed_begin,
                      n_seeds, sv_base, in, accept, g);
 }
 void launch_k9_flatten(hipStream_t st, uint32_t n_pl, K9Graph g, uint32_t* n_nodes) {
   if (!n_pl) return;
-  hipLaunchKernelGGL(k9_flatten, k9_blocks(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, n_pl, g, n_nodes);
+  hipLaunchKernelGGL(k9_flatten, blocks_for(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, n_pl, g, n_nodes);
 }
 void launch_k9_rank(hipStream_t st, const unsigned long long* ckey_sorted, uint32_t n_pl, K9Graph g, uint32_t* n_sets) {
   if (!n_pl) return;
-  hipLaunchKernelGGL(k9_rank, k9_blocks(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, ckey_sorted, n_pl, g, n_sets);
+  hipLaunchKernelGGL(k9_rank, blocks_for(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, ckey_sorted, n_pl, g, n_sets);
 }
 void launch_k9_node_keys(hipStream_t st, DevScene s, uint32_t n_pl, K9Graph g, unsigned long long* keys) {
   if (!n_pl) return;
-  hipLaunchKernelGGL(k9_node_keys, k9_blocks(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, s, n_pl, g, keys);
+  hipLaunchKernelGGL(k9_node_keys, blocks_for(n_pl, K9_BLOCK), dim3(K9_BLOCK), 0, st, s, n_pl, g, keys);
 }
 void launch_k9_compact(hipStream_t st, const uint32_t* accept, const uint32_t* off, uint32_t seed_begin, uint32_t n_seeds,
                        uint32_t* accepted) {
   if (!n_seeds) return;
-  hipLaunchKernelGGL(k9_compact, k9_blocks(n_seeds, K9_BLOCK), dim3(K9_BLOCK), 0, st, accept, off, seed_begin, n_seeds, accepted);
+  hipLaunchKernelGGL(k9_compact, blocks_for(n_seeds, K9_BLOCK), dim3(K9_BLOCK), 0, st, accept, off, seed_begin, n_seeds, accepted);
 }
 
 }  // namespace eg3d

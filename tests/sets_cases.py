@@ -8,7 +8,7 @@ set, most views present, dozens of samples per set. The reference's sets come fr
 missing, short polylines. Each family below is built to reach one branch of the extractor that curve-sized sets never do:
 
   tiny        hundreds of sets of 1-3 pieces of 20-60 px chord: one wavefront of 64 samples spans many sets (k_n1_hits)
-  one_view    sets whose rows are empty in every view but one (n1_row_of_item over runs of empty rows)
+  one_view    sets whose rows are empty in every view but one (k_n1_samples' find_owner over runs of empty rows)
   sparse      a 12-view rig, sets present in 1-3 views, empty sets at the ends of sub-ranges
   overlap     a polyline in several sets, sets that are supersets of others, a set repeated
   degenerate  ids of invalid polylines (stray vertices left in the input), of 0- and 1-vertex polylines and of loops

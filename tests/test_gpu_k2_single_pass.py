@@ -1,4 +1,4 @@
-"""-m gpu: the single-pass K2 (k2_epipolar_hits, eg3d_kernels.hip). One wavefront per task stages the task's epipolar hits
+"""-m gpu: the single-pass K2 (k2_epipolar_hits, eg3d_k1_k2_refpoints.hip). One wavefront per task stages the task's epipolar hits
 in LDS, claims its region of the hit buffer with one atomicAdd and copies the stage out; a task with more hits than the
 stage holds (EG3D_K2_STAGE_CAP, default 128) takes the count - claim - write route instead; a hit buffer that turns out
 too small (EG3D_HITS_CAP0 forces it) is enlarged by the host and K2 runs again. Where a task's hits lie in the buffer

@@ -40,6 +40,29 @@ def test_build_guard_reads_the_code_objects_and_the_bounds_hold():
     assert len(build.device_source_fingerprint()) == 16
 
 
+def test_kernel_code_diff_says_same_and_differs():
+    """tools/kernel_code_diff.py can say both things. A library against itself: every kernel `same`, exit 0. libeg3d.so
+    against libeg3d_dlt4x4.so (the other form of the DLT system): non-zero exit, the three k3b_expand_t instantiations among
+    the differing kernels, k6_compact_scan and k7_dedup_claim (no triangulation in them) among the same."""
+    if not os.path.exists(build.HIP_LIB):
+        build.build_hip()
+    if not os.path.exists(build.HIP_LIB_DLT4X4):
+        build.build_hip_dlt4x4()
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_code_diff as kd
+    a = kd.kernel_code(build.HIP_LIB)
+    lines, bad = kd.diff(a, a)
+    assert bad == 0 and len(lines) > 100 and all(l.startswith("same ") for l in lines[:-1]), lines[-1]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_code_diff.py"), build.HIP_LIB, build.HIP_LIB_DLT4X4],
+                       capture_output=True, text=True)
+    assert r.returncode == 1, r.stderr
+    verdict = {l[l.index("eg3d::"):]: l.split()[0] for l in r.stdout.splitlines() if "eg3d::" in l}
+    expand = [n for n in verdict if n.startswith("eg3d::k3b_expand_t<")]
+    assert len(expand) == 3 and all(verdict[n] == "differs" for n in expand), expand
+    assert verdict["eg3d::k6_compact_scan"] == "same" and verdict["eg3d::k7_dedup_claim"] == "same"
+    assert not [l for l in r.stdout.splitlines() if l.startswith("only ")]  # the two forms hold the same set of kernels
+
+
 def test_compare_by_chain_matches_chains_by_key_not_by_position():
     s = host.Synth(1)
     o = ob.Oracle(s.scene)
@@ -91,7 +114,7 @@ def test_a_removed_expand_switch_on_the_command_line_stops_the_build():
         pytest.skip("no hipcc")
     cmd = ([hipcc] + [f for f in build.HIP_FLAGS if f != "-shared"]
            + ["-I", build.INC_DIR, "-I", build.CSRC_DIR, "-I", build.HOST_DIR,
-              "-E", os.path.join(build.CSRC_DIR, "eg3d_kernels.hip"), "-o", os.devnull])
+              "-E", os.path.join(build.CSRC_DIR, "eg3d_k3_chains.hip"), "-o", os.devnull])
     r = subprocess.run(cmd + ["-DEG3D_SIDE_WALK_BATCH=1"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     assert r.returncode != 0
     assert "A/B switches" in r.stderr and "EG3D_SIDE_WALK_BATCH" in r.stderr and "DESIGN_LOG.md" in r.stderr, r.stderr

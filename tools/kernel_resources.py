@@ -27,21 +27,29 @@ def _demangle(names):
     return {n: n for n in names}
 
 
+def code_objects(lib, d):
+    """Extracts every gfx950 code object of `lib` into directory `d` (one per translation unit); returns their paths."""
+    fat = os.path.join(d, "fat.bin")
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
+    blob = open(fat, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"  # one bundle per translation unit, back to back in the section
+    starts = [m.start() for m in re.finditer(re.escape(magic), blob)]
+    out = []
+    for i, a in enumerate(starts):
+        part, co = os.path.join(d, "part%d.bin" % i), os.path.join(d, "dev%d.co" % i)
+        with open(part, "wb") as f:
+            f.write(blob[a:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        out.append(co)
+    return out
+
+
 def kernel_resources(lib):
-    """{demangled kernel name: {field: int}} for every kernel of the gfx950 code object in `lib`."""
+    """{demangled kernel name: {field: int}} for every kernel of the gfx950 code objects in `lib`."""
     notes = ""
     with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")
-        subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-        blob = open(fat, "rb").read()
-        magic = b"__CLANG_OFFLOAD_BUNDLE__"  # one bundle per translation unit, back to back in the section
-        starts = [m.start() for m in re.finditer(re.escape(magic), blob)]
-        for i, a in enumerate(starts):
-            part, co = os.path.join(d, "part%d.bin" % i), os.path.join(d, "dev%d.co" % i)
-            with open(part, "wb") as f:
-                f.write(blob[a:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-            subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        for co in code_objects(lib, d):
             notes += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True,
                                     check=True).stdout
     kernels, cur = {}, None
