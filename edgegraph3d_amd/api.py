@@ -230,6 +230,18 @@ class Context:
         """Sub-batches of one call kept in flight inside the library (eg3d_set_pipelining): lanes=1 switches it off."""
         _check(lib().eg3d_set_pipelining(self._h, lanes, units), "eg3d_set_pipelining")
 
+    def probe_k3a_walks(self):
+        """TEST-ONLY builds (variants/libeg3d_engine.so, timing builds): (walks the K3a walk service finished for a lane,
+        64-segment passes they took) of this context's match calls since the last probe. The product library carries no
+        probe: Eg3dError there."""
+        L = lib()
+        if not hasattr(L, "eg3d_probe_k3a_walks"):
+            raise Eg3dError("eg3d_probe_k3a_walks: not in this library (test-only builds carry it)")
+        L.eg3d_probe_k3a_walks.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        out = (C.c_ulonglong * 2)()
+        _check(L.eg3d_probe_k3a_walks(self._h, out), "eg3d_probe_k3a_walks")
+        return int(out[0]), int(out[1])
+
     def close(self):
         if self._h:
             lib().eg3d_destroy(self._h)

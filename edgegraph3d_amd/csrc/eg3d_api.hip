@@ -1071,6 +1071,23 @@ extern "C" int eg3d_probe_hyp_sections(eg3d_ctx* c, double* sum, double* slowest
 }
 
 #endif
+#if defined(EG3D_WITH_K3C_ENGINE) || defined(EG3D_SECTION_TIMING)
+// The K3a walk service's counters (eg3d_k3a_engine.h) of the match calls of this context since the last probe, summed over
+// the lanes the calls ran on: out2[0] = walks a wave finished for one of its lanes, out2[1] = the 64-segment passes they
+// took. Test-only builds (the engine variant, the timing builds): the product library carries no probe.
+extern "C" int eg3d_probe_k3a_walks(eg3d_ctx* c, unsigned long long* out2) {
+  if (!c || !out2) return EG3D_ERR_ARG;
+  out2[0] = out2[1] = 0;
+  std::vector<eg3d_ctx*> all = c->lanes;
+  if (all.empty()) all.push_back(c);
+  for (eg3d_ctx* l : all) {
+    out2[0] += l->k3a_walks_served;
+    out2[1] += l->k3a_walk_passes;
+    l->k3a_walks_served = l->k3a_walk_passes = 0;
+  }
+  return EG3D_OK;
+}
+#endif
 #if defined(EG3D_WITH_K3C_ENGINE) && (defined(EG3D_SECTION_TIMING) || defined(EG3D_K3C_TIMING))
 // ... and of the lane-per-chain engine (eg3d_k3c_engine.h g_k3c_dbg)
 namespace eg3d { int k3c_dbg_read(unsigned long long* out, int reset); }

@@ -258,6 +258,9 @@ struct eg3d_ctx {
       b_start_cnt, b_task_off, b_task_seed, b_task_entry, b_task_hit, b_task_k, b_task_list_off, b_list_cnt, b_list_ptr,
       b_hits, b_tasks, b_nhyp, b_hyp_off, b_res, b_arena, b_ctr, b_cs_task, b_valid, b_chain_off, b_chains,
       b_cscratch, b_couts, b_cpts, b_cobs, b_cpoff, b_cooff, b_scan_tmp, b_scanchk, b_cost, b_cidx, b_cost2, b_order, b_redo[2];
+  // K3a walk service (Counters::k3a_walks_served / k3a_walk_passes) of the units this lane ran since the last
+  // eg3d_probe_k3a_walks (test-only builds read them; the figures come with the counters' read-back in any case)
+  unsigned long long k3a_walks_served = 0, k3a_walk_passes = 0;
   WorkBuf o_X, o_off, o_view, o_pl, o_seg, o_xy, o_key;
   WorkBuf f_X, f_off, f_view, f_xy, f_Xo, f_inl;
   // eg3d_gn_filter_device / eg3d_compact_device / eg3d_filter_resident: histogram + flag word, block totals of the

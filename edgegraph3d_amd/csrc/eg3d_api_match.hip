@@ -444,6 +444,8 @@ int follow_and_select(eg3d_ctx* c, BatchState& B, HostOut& H) {
     if (B.n_hyp) c->arena_per_hyp = std::max(c->arena_per_hyp, 1.25 * (double)arena_cap / (double)B.n_hyp);
   }
   H.flags |= (hc.flags & 0xffu);
+  c->k3a_walks_served += hc.k3a_walks_served;
+  c->k3a_walk_passes += hc.k3a_walk_passes;
   BUF_TRY(c->b_chains.ensure(sizeof(ChainSeed) * (B.n_chains + 1)));
   launch_compact_chains(st, nt, c->b_cs_task.as<ChainSeed>(), c->b_valid.as<uint32_t>(), c->b_chain_off.as<uint32_t>(),
                         c->b_chains.as<ChainSeed>());

@@ -499,6 +499,82 @@ EG3D_HD uint32_t walk_by_line_pf(const PlRefT<VPtr>& pl, const PlPt& p, uint32_t
   return walk_by_line_run(pl, p, direction, la, lb, lc, bounded, min_d, max_d, W, out);
 }
 
+// walk_by_line in THREE PIECES, for callers that finish a long walk with many lanes (the walk service of the K3a
+// engine, eg3d_k3a_engine.h; on the host the loop over k of tests/walkcoop). walk_by_line above stays the definition:
+// the pieces make the same tests on the same operands, and the first decisive test in walking order decides, so the
+// result is the same bit for bit (tests/test_walk_coop.py).
+//   head     the direction check, the partial segment from the position and the first T whole segments — what the
+//            five-vertex window holds, no shift. Returns the decided status, or WALK_UNDECIDED and the continuation.
+//   body     the test of the k-th segment of the continuation: vertices next + step k and next + step (k + 1).
+//   resolve  from the first decisive test (or none): quasi-parallel stop, the hit with the [min, max] window of a
+//            bounded walk, or the extreme.
+enum : uint32_t { WALK_UNDECIDED = 0u };
+#define EG3D_WALK_HEAD_MAX 4 /* whole segments a VtxWindow holds */
+struct WalkCont {
+  int32_t next;  // vertex the first untested segment starts at
+  int32_t step;  // -1 towards the start, +1 towards the end
+  int32_t left;  // whole segments not tested yet (>= 1 when the head returns WALK_UNDECIDED)
+};
+// r: what seg_line_hit_guarded returned for the first decisive segment in walking order, 0 when none was decisive
+EG3D_HD uint32_t walk_resolve(uint32_t r, uint32_t seg, float hx, float hy, const PlPt& p, bool bounded, float min_d,
+                              float max_d, PlPt& out) {
+  if (r & 2u) return WALK_QUASIPARALLEL;
+  if (!(r & 1u)) return WALK_EXTREME;
+  out.seg = seg;
+  out.x = hx;
+  out.y = hy;
+  if (bounded) {
+    float dsq = dist2(hx, hy, p.x, p.y);
+    if (dsq < (min_d * min_d) || dsq > (max_d * max_d)) return WALK_BOUND;
+  }
+  return WALK_FOUND;
+}
+template <class VPtr>
+EG3D_HD uint32_t walk_seg_test(VPtr v, const WalkCont& c, int32_t k, float la, float lb, float lc, const LineDir& ld,
+                               uint32_t& seg, float& hx, float& hy) {
+  const int32_t i0 = c.next + c.step * k, i1 = i0 + c.step;
+  seg = (uint32_t)(i0 < i1 ? i0 : i1);
+  const f2 a = v[i0], b = v[i1];
+  return seg_line_hit_guarded(a.x, a.y, b.x, b.y, la, lb, lc, ld, hx, hy);
+}
+template <int T, class VPtr>
+EG3D_HD uint32_t walk_by_line_head(const PlRefT<VPtr>& pl, const PlPt& p, uint32_t direction, float la, float lb, float lc,
+                                   const LineDir& ld, bool bounded, float min_d, float max_d, PlPt& out, WalkCont& c) {
+  static_assert(T >= 1 && T <= EG3D_WALK_HEAD_MAX, "the head tests what the window holds");
+  VtxWindow<VPtr> W;
+  if (!walk_by_line_open(pl, p, direction, W)) return WALK_BAD_DIR;
+  const int32_t count = W.stepv < 0 ? W.first + 1 : (int32_t)pl.n - W.first;  // vertices ahead, as in walk_by_line_run
+  float hx = 0.0f, hy = 0.0f;
+  uint32_t seg = p.seg;
+  uint32_t r = seg_line_hit_guarded(p.x, p.y, W.w0.x, W.w0.y, la, lb, lc, ld, hx, hy);
+  int32_t k = 1;
+  if (!r && k < count) {
+    r = seg_line_hit_guarded(W.w0.x, W.w0.y, W.w1.x, W.w1.y, la, lb, lc, ld, hx, hy);
+    k = 2;
+    if (T >= 2 && !r && k < count) {
+      r = seg_line_hit_guarded(W.w1.x, W.w1.y, W.w2.x, W.w2.y, la, lb, lc, ld, hx, hy);
+      k = 3;
+      if (T >= 3 && !r && k < count) {
+        r = seg_line_hit_guarded(W.w2.x, W.w2.y, W.w3.x, W.w3.y, la, lb, lc, ld, hx, hy);
+        k = 4;
+        if (T >= 4 && !r && k < count) {
+          r = seg_line_hit_guarded(W.w3.x, W.w3.y, W.w4.x, W.w4.y, la, lb, lc, ld, hx, hy);
+          k = 5;
+        }
+      }
+    }
+    if (r) seg = (uint32_t)(W.stepv < 0 ? W.first - (k - 1) : W.first + (k - 1) - 1);
+  }
+  // (k - 1 whole segments tested; the next one starts at u[k - 1])
+  if (!r && k < count) {
+    c.next = W.first + W.stepv * (k - 1);
+    c.step = W.stepv;
+    c.left = count - k;
+    return WALK_UNDECIDED;
+  }
+  return walk_resolve(r, seg, hx, hy, p, bounded, min_d, max_d, out);
+}
+
 // Closest point of a whole polyline, first minimal segment wins (polyline_graph_2d.cpp:845-862).
 EG3D_HD float polyline_closest(const PlRef& pl, float px, float py, PlPt& out) {
   float bx, by;

@@ -124,6 +124,75 @@ __device__ __forceinline__ void k3a_serve(K3aShared& sh, const DevScene& s, uint
   __syncthreads();
 }
 
+// ---------------------------------------------------------------- the walk service --------
+// walk_by_line for the lanes with `want`, CALLED BY THE WHOLE WAVE (wave-uniform control flow; lanes without a walk
+// take part in the service). Each lane runs the head of its own walk (eg3d_dev_geom.h: the partial segment and the
+// EG3D_K3A_WALK_HEAD whole segments of the five-vertex window — the median walk ends there); the walks that are still
+// undecided are then finished one after the other, in lane order, by all 64 lanes: the owner's continuation and line go
+// out by v_readlane, lane k of a pass tests the k-th segment ahead, the first decisive lane in walking order decides,
+// passes repeat while the owner has segments left (at most ceil(left / 64)), and the owner alone resolves the result.
+// The same tests on the same operands in the same order as walk_by_line: the same result, bit for bit. (A lane's own
+// scan to the polyline's end — the wrong-direction halves of an orientation round — held its wave for 30-60 segment
+// tests where the mean walk needs 7.5.)
+#ifndef EG3D_K3A_WALK_HEAD
+#define EG3D_K3A_WALK_HEAD 4 /* whole segments a lane tests itself before it asks the wave */
+#endif
+struct K3aWalkStats {
+  uint32_t served = 0, passes = 0;  // per wave (uniform); added to Counters once, at exit
+};
+__device__ __forceinline__ uint32_t k3a_walk_coop(const DevScene& s, uint32_t lane, bool want, const PlRef& pl, const PlPt& p,
+                                                  uint32_t direction, float la, float lb, float lc, bool bounded, float min_d,
+                                                  float max_d, PlPt& out, K3aWalkStats& ws) {
+  uint32_t status = WALK_EXTREME;
+  WalkCont c;
+  c.next = c.left = 0;
+  c.step = 1;
+  LineDir ld;
+  ld.bx = ld.by = ld.bb = 0.0f;
+  bool pending = false;
+  if (want) {
+    ld = line_dir(la, lb);
+    status = walk_by_line_head<EG3D_K3A_WALK_HEAD>(pl, p, direction, la, lb, lc, ld, bounded, min_d, max_d, out, c);
+    pending = status == WALK_UNDECIDED;
+  }
+  unsigned long long pend = __ballot(pending);
+  while (pend) {
+    const int o = __ffsll((long long)pend) - 1;
+    pend &= pend - 1ull;
+    WalkCont oc;
+    oc.next = lane_bcast(c.next, o);
+    oc.step = lane_bcast(c.step, o);
+    oc.left = lane_bcast(c.left, o);
+    const f2* ov = s.vtx + lane_bcast((uint32_t)(pl.v - s.vtx), o);
+    const float ola = lane_bcast(la, o), olb = lane_bcast(lb, o), olc = lane_bcast(lc, o);
+    LineDir old;
+    old.bx = lane_bcast(ld.bx, o);
+    old.by = lane_bcast(ld.by, o);
+    old.bb = lane_bcast(ld.bb, o);
+    uint32_t rf = 0, sf = 0;
+    float xf = 0.0f, yf = 0.0f;
+    for (int32_t k0 = 0; k0 < oc.left; k0 += 64) {
+      ws.passes++;
+      const int32_t k = k0 + (int32_t)lane;
+      uint32_t r = 0, seg = 0;
+      float hx = 0.0f, hy = 0.0f;
+      if (k < oc.left) r = walk_seg_test(ov, oc, k, ola, olb, olc, old, seg, hx, hy);
+      const unsigned long long any = __ballot(r != 0);
+      if (any) {
+        const int f = __ffsll((long long)any) - 1;
+        rf = lane_bcast(r, f);
+        sf = lane_bcast(seg, f);
+        xf = lane_bcast(hx, f);
+        yf = lane_bcast(hy, f);
+        break;
+      }
+    }
+    ws.served++;
+    if (lane == (uint32_t)o) status = walk_resolve(rf, sf, xf, yf, p, bounded, min_d, max_d, out);
+  }
+  return status;
+}
+
 __device__ __forceinline__ HPoint k3a_point_of_slot(const K3aShared& sh, uint32_t slot) {
   HPoint hp;
   hp.X[0] = sh.resX[slot][0];
@@ -222,6 +291,7 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_orient(DevScene s, Sta
     sh.req[slot][2] = o;
     sh.reqM[slot] = 1u | ((uint32_t)q << 8) | (round_off << 10);
   };
+  K3aWalkStats wstat;
   K3A_T0();
 
   for (;;) {
@@ -369,38 +439,42 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_orient(DevScene s, Sta
       }
     }
     // ---- GEN: walk a round and issue its requests; with slots to spare, the rounds behind it too
+    // The loop over the rounds and the four walks of a round are WAVE-UNIFORM (a lane takes part while `gen` holds),
+    // so that every lane reaches the walk service (k3a_walk_coop) together; what a lane does in them, and in which
+    // order, is the lane-private loop this replaced.
     dead_round = 0xffffffffu;
-    if (st == K3A_GEN) {
-      uint32_t walkers = alive;  // the combinations this round is walked for
-      for (uint32_t round_off = 0;; round_off++) {
-        // +10 px on A; next epipolar hit (unbounded) on B / C for every direction a live combination uses
-        // (combination q = 2*b + c; the walk on C is made for the combinations whose walk on B found something)
-        uint32_t fl = 0, m = walkers;
-        const PlRef pa = L.polyline(s, 0);
-        PlPt q;
-        const uint32_t w = walk_by_distance_pf(pa, L.get(0), dirA, EG3D_FOLLOW_STEP, q);
+    bool gen = st == K3A_GEN;
+    uint32_t walkers = alive;  // the combinations this round is walked for
+    for (uint32_t round_off = 0; __ballot(gen); round_off++) {
+      // +10 px on A (lane-private: it is short); next epipolar hit (unbounded) on B / C for every direction a live
+      // combination uses (combination q = 2*b + c; the walk on C is made for the combinations whose walk on B found
+      // something)
+      uint32_t fl = 0, m = gen ? walkers : 0u;
+      PlPt q;
+      q.seg = 0;
+      q.x = q.y = 0.0f;
+      if (gen) {
+        const uint32_t w = walk_by_distance_pf(L.polyline(s, 0), L.get(0), dirA, EG3D_FOLLOW_STEP, q);
         if (w & WALK_BAD_DIR) fl |= 8u;
-        if (w & WALK_EXTREME) {
+        if (w & WALK_EXTREME)
           m = 0;
-        } else {
+        else
           L.set(0, q);
-          float la = 0.0f, lb = 0.0f, lc = 0.0f;
-          PlRef pk = pa;
+      }
 #pragma unroll 1
-          for (int idx = 0; idx < 4 && m; idx++) {
-            const int k = 1 + (idx >> 1), j = idx & 1;
-            const uint32_t users = k == 1 ? (3u << (2 * j)) : (5u << j);  // the combinations that walk (k, j)
-            if (j == 0) {
-              if (!epiline(s.F, s.F_valid, s.n_views, view[0], view[k], q.x, q.y, la, lb, lc)) {
-                m = 0;  // step3 fails here for every combination
-                break;
-              }
-              pk = L.polyline(s, k);
-            }
-            if (!(m & users)) continue;
-            PlPt r;
-            const uint32_t wr = walk_by_line_pf(pk, L.get(2 * k - 1 + j), k == 1 ? dirB[j] : dirC[j], la, lb, lc, false, 0.0f,
-                                                0.0f, r);
+      for (int k = 1; k <= 2; k++) {
+        float la = 0.0f, lb = 0.0f, lc = 0.0f;
+        // (step3 fails for every combination when a line is missing)
+        if (m && !epiline(s.F, s.F_valid, s.n_views, view[0], view[k], q.x, q.y, la, lb, lc)) m = 0;
+        const PlRef pk = L.polyline(s, k);
+#pragma unroll 1
+        for (int j = 0; j < 2; j++) {
+          const uint32_t users = k == 1 ? (3u << (2 * j)) : (5u << j);  // the combinations that walk (k, j)
+          const bool want = (m & users) != 0;
+          PlPt r;
+          const uint32_t wr = k3a_walk_coop(s, lane, want, pk, L.get(2 * k - 1 + j), k == 1 ? dirB[j] : dirC[j], la, lb, lc,
+                                            false, 0.0f, 0.0f, r, wstat);
+          if (want) {
             if (wr & WALK_BAD_DIR) fl |= 8u;
             if (wr & WALK_FOUND)
               L.set(2 * k - 1 + j, r);
@@ -408,55 +482,61 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_orient(DevScene s, Sta
               m &= ~users;
           }
         }
-        if (phase != K3A_REPLAY) flags |= fl;  // (the replay repeats steps whose flags are already counted)
-        if (round_off == 0) {
-          reqmask = m;
-          okmask = 0;
-          if (!m) {
-            if (phase == K3A_REPLAY) n1 = i_rep;  // (a replayed walk found nothing: cannot happen; the list ends there)
-            if (phase == K3A_ORIENT) {
-              alive = 0;
-              rounds++;
+      }
+      if (gen) {
+        bool more = false;
+        do {
+          if (phase != K3A_REPLAY) flags |= fl;  // (the replay repeats steps whose flags are already counted)
+          if (round_off == 0) {
+            reqmask = m;
+            okmask = 0;
+            if (!m) {
+              if (phase == K3A_REPLAY) n1 = i_rep;  // (a replayed walk found nothing: cannot happen; the list ends there)
+              if (phase == K3A_ORIENT) {
+                alive = 0;
+                rounds++;
+              }
+              st = K3A_END;
+              break;
             }
-            st = K3A_END;
-            break;
+            st = K3A_REQ;
+            while (reqmask && n_issued < K) {
+              const int qq = __ffs((int)reqmask) - 1;
+              reqmask &= reqmask - 1u;
+              issue(slot0 + n_issued, qq, 0u);
+              n_issued++;
+            }
+            if (reqmask) break;  // the rest of this round next iteration
+          } else {
+            if (!m) {
+              if (phase == K3A_REPLAY)
+                n1 = i_rep + round_off;
+              else
+                dead_round = round_off;
+              break;
+            }
+            uint32_t mm = m;
+            while (mm) {  // (fits: the look-ahead below checked the room)
+              const int qq = __ffs((int)mm) - 1;
+              mm &= mm - 1u;
+              issue(slot0 + n_issued, qq, round_off);
+              n_issued++;
+            }
           }
-          st = K3A_REQ;
-          while (reqmask && n_issued < K) {
-            const int qq = __ffs((int)reqmask) - 1;
-            reqmask &= reqmask - 1u;
-            issue(slot0 + n_issued, qq, 0u);
-            n_issued++;
-          }
-          if (reqmask) break;  // the rest of this round next iteration
-        } else {
-          if (!m) {
-            if (phase == K3A_REPLAY)
-              n1 = i_rep + round_off;
-            else
-              dead_round = round_off;
-            break;
-          }
-          uint32_t mm = m;
-          while (mm) {  // (fits: the look-ahead below checked the room)
-            const int qq = __ffs((int)mm) - 1;
-            mm &= mm - 1u;
-            issue(slot0 + n_issued, qq, round_off);
-            n_issued++;
-          }
-        }
-        // look ahead? a replay: its next step (known to succeed); the search: the next round of the combinations
-        // that are still walking, if there are at least two and their requests fit
-        const uint32_t cm = (uint32_t)__popc(m);
-        bool more;
-        if (phase == K3A_REPLAY)
-          more = i_rep + round_off + 1u < n1 && n_issued < K;
-        else if (phase == K3A_ORIENT)
-          more = cm >= 2u && n_issued + cm <= K && round_off < 14u;
+          // look ahead? a replay: its next step (known to succeed); the search: the next round of the combinations
+          // that are still walking, if there are at least two and their requests fit
+          const uint32_t cm = (uint32_t)__popc(m);
+          if (phase == K3A_REPLAY)
+            more = i_rep + round_off + 1u < n1 && n_issued < K;
+          else if (phase == K3A_ORIENT)
+            more = cm >= 2u && n_issued + cm <= K && round_off < 14u;
+          else
+            more = false;
+        } while (false);
+        if (more)
+          walkers = m;
         else
-          more = false;
-        if (!more) break;
-        walkers = m;
+          gen = false;
       }
     }
     // ---- REQ: requests of the round that are still to be issued (the first one of a new hypothesis; what did not fit)
@@ -535,6 +615,10 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_orient(DevScene s, Sta
     }
     K3A_T(2);
   }
+  if (lane == 0 && wstat.served) {
+    atomicAdd(&ctr->k3a_walks_served, wstat.served);
+    atomicAdd(&ctr->k3a_walk_passes, wstat.passes);
+  }
   K3A_TEND(0);
 }
 
@@ -549,54 +633,6 @@ template <class T>
 __device__ __forceinline__ T k3a_pick(const T a[3], int i) {
   return i == 0 ? a[0] : i == 1 ? a[1] : a[2];
 }
-// next request of a step: the base point's observations are entries 3..5 of the lane's positions, their views in
-// view3 (their polylines: the lane's cached polyline of that view). Returns the starting observation used and the
-// three new positions in the order the new point lists them (the starting observation, then the other two in index
-// order).
-__device__ __forceinline__ bool k3a_follow_request(const DevScene& s, const K3aLane& L, const int32_t view3[3],
-                                                   int st_start, const uint32_t dirs[3], const int32_t ids[3],
-                                                   int& st_used, PlPt sel_pt[3], uint32_t& fl) {
-#pragma unroll 1
-  for (int st = st_start; st < 3; st++) {
-    const int32_t sv = k3a_pick(view3, st);
-    const int sd = (sv == ids[0]) ? 0 : (sv == ids[1]) ? 1 : 2;
-    const PlRef ps = L.polyline(s, sd);
-    PlPt q;
-    const uint32_t w = walk_by_distance_pf(ps, L.get(3 + st), k3a_pick(dirs, sd), EG3D_FOLLOW_STEP, q);
-    if (w & WALK_BAD_DIR) fl |= 8u;
-    if (w & WALK_EXTREME) continue;
-    int found = 0;
-    PlPt r1 = q, r2 = q;
-#pragma unroll 1
-    for (int t = 0; t < 2; t++) {
-      const int i = t == 0 ? (st == 0 ? 1 : 0) : (st == 2 ? 1 : 2);
-      const int32_t cv = k3a_pick(view3, i);
-      float la, lb, lc;
-      if (!epiline(s.F, s.F_valid, s.n_views, sv, cv, q.x, q.y, la, lb, lc)) continue;
-      const int cd = (cv == ids[0]) ? 0 : (cv == ids[1]) ? 1 : 2;
-      const PlRef pk = L.polyline(s, cd);
-      PlPt r;
-      const uint32_t wr =
-          walk_by_line_pf(pk, L.get(3 + i), k3a_pick(dirs, cd), la, lb, lc, true, EG3D_FOLLOW_MIN, EG3D_FOLLOW_MAX, r);
-      if (wr & WALK_BAD_DIR) fl |= 8u;
-      if (wr & WALK_FOUND) {
-        found++;
-        if (t == 0)
-          r1 = r;
-        else
-          r2 = r;
-      }
-    }
-    if (found < 2) continue;
-    st_used = st;
-    sel_pt[0] = q;
-    sel_pt[1] = r1;
-    sel_pt[2] = r2;
-    return true;
-  }
-  return false;
-}
-
 __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_follow_spec(DevScene s, HypResult* res, HPoint* scratch,
                                                                       uint32_t cap, HPoint* arena, uint32_t arena_cap,
                                                                       Counters* ctr, uint32_t* queue, uint32_t lanes_per_wave,
@@ -621,6 +657,7 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_follow_spec(DevScene s
   // hypothesis' three (view, polyline) pairs
   int32_t cview[3] = {0, 0, 0};
   uint32_t cpl[3] = {0, 0, 0};
+  K3aWalkStats wstat;
   K3A_T0();
   for (;;) {
     while (!have && !exhausted) {
@@ -666,51 +703,103 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_follow_spec(DevScene s
     __syncthreads();
     uint32_t n_req = 0, end_fl = 0;
     bool ended = false;
+    // requests of this iteration: the step at hand and, speculatively, the ones behind it. Never beyond the
+    // probe of a list at capacity (one request past the last point that fits).
+    // A request of a step: the base point's observations are entries 3..5 of the lane's positions, their views in bview
+    // (their polylines: the lane's cached polyline of that view); each observation in turn is tried as the starting
+    // one — +10 px on it, bounded epipolar walks on the other two — and the first that finds both makes the request:
+    // the new point lists the starting observation first, then the other two in index order.
+    // The loops over the requests and over a request's starting observations are ONE WAVE-UNIFORM loop (a turn = one
+    // starting observation of the request a lane is generating: the +10 px walk, lane-private, and the two bounded
+    // epipolar walks through the walk service), so that every lane reaches the service together; what a lane does, and
+    // in which order, is what its own nested loops did (stepn3 of eg3d_dev_follow.h).
+    uint32_t lim = 0, fl = 0;
+    int32_t bview[3] = {cview[0], cview[1], cview[2]};
+    uint32_t bpl[3] = {cpl[0], cpl[1], cpl[2]};
+    int st = st_start;
     if (have) {
-      // requests of this iteration: the step at hand and, speculatively, the ones behind it. Never beyond the
-      // probe of a list at capacity (one request past the last point that fits).
       const uint32_t total = n_init + n_new;
       const uint32_t room = total < cap ? cap - total : 0u;
-      const uint32_t lim = K < room + 1u ? K : room + 1u;
-      int32_t bview[3] = {cview[0], cview[1], cview[2]};
-      uint32_t bpl[3] = {cpl[0], cpl[1], cpl[2]};
+      lim = K < room + 1u ? K : room + 1u;
       L.set(3, L.get(0));
       L.set(4, L.get(1));
       L.set(5, L.get(2));
-      int st0 = st_start;
-      while (n_req < lim) {
-        int st_used = 0;
-        PlPt sel_pt[3];
-        uint32_t fl = 0;
-        if (!k3a_follow_request(s, L, bview, st0, dirs, ids, st_used, sel_pt, fl)) {
+    }
+    bool act = have;  // (lim >= 1)
+    if (act && st >= 3) {  // the step's last starting observation was the one that failed
+      ended = true;
+      act = false;
+    }
+    while (__ballot(act)) {
+      bool go = false;
+      int32_t sv = 0;
+      PlPt q;
+      q.seg = 0;
+      q.x = q.y = 0.0f;
+      if (act) {
+        sv = k3a_pick(bview, st);
+        const int sd = (sv == ids[0]) ? 0 : (sv == ids[1]) ? 1 : 2;
+        const uint32_t w = walk_by_distance_pf(L.polyline(s, sd), L.get(3 + st), k3a_pick(dirs, sd), EG3D_FOLLOW_STEP, q);
+        if (w & WALK_BAD_DIR) fl |= 8u;
+        go = !(w & WALK_EXTREME);
+      }
+      int found = 0;
+      PlPt r1 = q, r2 = q;
+#pragma unroll 1
+      for (int t = 0; t < 2; t++) {
+        const int i = t == 0 ? (st == 0 ? 1 : 0) : (st == 2 ? 1 : 2);
+        const int32_t cv = k3a_pick(bview, i);
+        float la = 0.0f, lb = 0.0f, lc = 0.0f;
+        const bool want = go && epiline(s.F, s.F_valid, s.n_views, sv, cv, q.x, q.y, la, lb, lc);
+        const int cd = (cv == ids[0]) ? 0 : (cv == ids[1]) ? 1 : 2;
+        PlPt r;
+        const uint32_t wr = k3a_walk_coop(s, lane, want, L.polyline(s, cd), L.get(3 + i), k3a_pick(dirs, cd), la, lb, lc, true,
+                                          EG3D_FOLLOW_MIN, EG3D_FOLLOW_MAX, r, wstat);
+        if (want) {
+          if (wr & WALK_BAD_DIR) fl |= 8u;
+          if (wr & WALK_FOUND) {
+            found++;
+            if (t == 0)
+              r1 = r;
+            else
+              r2 = r;
+          }
+        }
+      }
+      if (act) {
+        if (found == 2) {  // the request of starting observation st: the new point lists it first, then the other two in index order
+          const uint32_t slot = slot0 + n_req;
+          int32_t nview[3];
+          uint32_t npl[3];
+          const int sel_idx[3] = {st, st == 0 ? 1 : 0, st == 2 ? 1 : 2};
+          const PlPt sel_pt[3] = {q, r1, r2};
+          for (int k = 0; k < 3; k++) {
+            nview[k] = k3a_pick(bview, sel_idx[k]);
+            npl[k] = k3a_pick(bpl, sel_idx[k]);
+            Obs o;
+            o.view = (uint32_t)nview[k];
+            o.pl = npl[k];
+            o.seg = sel_pt[k].seg;
+            o.x = sel_pt[k].x;
+            o.y = sel_pt[k].y;
+            sh.req[slot][k] = o;
+          }
+          sh.reqM[slot] = 1u | ((uint32_t)st << 8) | (fl << 16);
+          n_req++;
+          // the next request starts from this one's observations
+          for (int k = 0; k < 3; k++) {
+            bview[k] = nview[k];
+            bpl[k] = npl[k];
+            L.set(3 + k, sel_pt[k]);
+          }
+          st = 0;
+          fl = 0;
+          if (n_req >= lim) act = false;
+        } else if (++st >= 3) {  // no observation left to start from
           ended = true;
           end_fl = fl;
-          break;
+          act = false;
         }
-        const uint32_t slot = slot0 + n_req;
-        int32_t nview[3];
-        uint32_t npl[3];
-        const int sel_idx[3] = {st_used, st_used == 0 ? 1 : 0, st_used == 2 ? 1 : 2};
-        for (int k = 0; k < 3; k++) {
-          nview[k] = k3a_pick(bview, sel_idx[k]);
-          npl[k] = k3a_pick(bpl, sel_idx[k]);
-          Obs o;
-          o.view = (uint32_t)nview[k];
-          o.pl = npl[k];
-          o.seg = sel_pt[k].seg;
-          o.x = sel_pt[k].x;
-          o.y = sel_pt[k].y;
-          sh.req[slot][k] = o;
-        }
-        sh.reqM[slot] = 1u | ((uint32_t)st_used << 8) | (fl << 16);
-        n_req++;
-        // the next request starts from this one's observations
-        for (int k = 0; k < 3; k++) {
-          bview[k] = nview[k];
-          bpl[k] = npl[k];
-          L.set(3 + k, sel_pt[k]);
-        }
-        st0 = 0;
       }
     }
     K3A_T(0);
@@ -804,6 +893,10 @@ __global__ void __launch_bounds__(64, EG3D_K3A_WAVES) k3a_follow_spec(DevScene s
       }
     }
     K3A_T(2);
+  }
+  if (lane == 0 && wstat.served) {
+    atomicAdd(&ctr->k3a_walks_served, wstat.served);
+    atomicAdd(&ctr->k3a_walk_passes, wstat.passes);
   }
   K3A_TEND(1);
 }

@@ -39,6 +39,10 @@ struct Counters {
   uint32_t max_chain_ticks;  // k3b_expand: the longest time one chain held its wavefront (ticks of the constant-rate clock, wall_clock64)
   uint32_t pad_;
   unsigned long long hits_used;  // k2_epipolar_hits: the cursor the tasks claim their region of the hits from
+  // K3a walk service (eg3d_k3a_engine.h): walks the wave finished for a lane, and the 64-segment passes that took; every
+  // wavefront adds its totals once, at exit (read by eg3d_probe_k3a_walks in the test-only builds)
+  uint32_t k3a_walks_served;
+  uint32_t k3a_walk_passes;
 };
 // grid of a launch with one lane (or one wave's worth of lanes) per item: ceil(n / per_block) blocks
 inline dim3 blocks_for(uint64_t n, uint32_t per_block) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
