@@ -1,0 +1,138 @@
+"""The C ABI as ctypes sees it: one table per library, function name -> (restype, argtypes), covering every function
+of include/eg3d.h, include/eg3d_host.h and include/eg3d_rccl.h, and bind(), which applies a table to a CDLL. Written by
+hand; tests/test_abi.py reads the headers and holds every row (and every struct mirror of _cdefs.py) to them."""
+import ctypes as C
+
+from . import _cdefs as D
+
+P = C.POINTER
+vp, cstr, i32, u32, i64p = C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, P(C.c_int64)
+u64, f32, intp = C.c_uint64, C.c_float, P(C.c_int)
+f32p, f64p, u8p, u32p, i32p, u64p = D.f32p, D.f64p, D.u8p, D.u32p, D.i32p, D.u64p
+
+# include/eg3d.h (libeg3d.so, libeg3d_dlt4x4.so); a context handle (eg3d_ctx*) is a void pointer here
+EG3D = {
+    "eg3d_last_error": (cstr, []),
+    "eg3d_device_count": (i32, []),
+    "eg3d_dlt_rows": (i32, []),
+    "eg3d_create": (i32, [P(D.Scene), i32, P(vp)]),
+    "eg3d_destroy": (None, [vp]),
+    "eg3d_clone": (i32, [vp, P(vp)]),
+    "eg3d_get_grid": (i32, [vp, i32, i32, u32p, u32p, P(u32p), P(u32p)]),
+    "eg3d_candidates_run": (i32, [vp, P(D.Seeds), u32, u32, P(D.Candidates)]),
+    "eg3d_free_candidates": (None, [P(D.Candidates)]),
+    "eg3d_match_refpoints": (i32, [vp, P(D.Seeds), u32, u32, i32, P(D.EdgePoints), P(D.StageTimes)]),
+    "eg3d_match_polyline_sets": (i32, [vp, P(D.PolylineSets), u32, u32, i32, P(D.EdgePoints), P(D.StageTimes)]),
+    "eg3d_match_polyline_sets_matched": (i32, [vp, P(D.PolylineSets), u32, u32, P(D.MatchedIntervals), i32, P(D.EdgePoints),
+                                               P(D.StageTimes)]),
+    "eg3d_polyline_set_candidates": (i32, [vp, P(D.PolylineSets), u32, u32, P(D.MatchedIntervals), P(D.SetCandidates)]),
+    "eg3d_free_set_candidates": (None, [P(D.SetCandidates)]),
+    "eg3d_check_polyline_sets": (i32, [P(D.PolylineSets), C.c_int32]),
+    "eg3d_free_edgepoints": (None, [P(D.EdgePoints)]),
+    "eg3d_upload_seeds": (i32, [vp, P(D.Seeds)]),
+    "eg3d_match_resident": (i32, [vp, u32, u32, i32, P(D.EdgePoints), P(D.StageTimes)]),
+    "eg3d_set_pipelining": (i32, [vp, i32, i32]),
+    "eg3d_last_device_output": (i32, [vp, P(D.DeviceEdgePoints)]),
+    "eg3d_gn_filter": (i32, [vp, f32p, u32p, i32p, f32p, u64, f32, i32, f32p, u8p, f32p]),
+    "eg3d_context_info": (i32, [vp, P(C.c_int32), P(C.c_int32)]),
+    "eg3d_gn_filter_device": (i32, [vp, P(D.DeviceEdgePoints), vp, f32, i32, vp, vp, u64p, u64p, f32p]),
+    "eg3d_compact_device": (i32, [vp, P(D.DeviceEdgePoints), vp, vp, C.c_int32, P(D.DeviceEdgePoints)]),
+    "eg3d_filter_resident": (i32, [vp, f32, i32, i32, u64p, i32, P(D.EdgePoints), P(D.DeviceEdgePoints), P(D.FilterStats)]),
+    "eg3d_dedup_device": (i32, [vp, P(D.DeviceEdgePoints), u64, i32, vp, u64p]),
+    "eg3d_dedup_resident": (i32, [vp, u64, i32, i32, f32, i32, i32, u64p, i32, P(D.EdgePoints), P(D.DeviceEdgePoints),
+                                  P(D.DedupStats)]),
+    "eg3d_replay_device": (i32, [vp, P(D.DeviceEdgePoints), P(D.DeviceGraph3D), P(D.Graph3D), P(D.ReplayStats)]),
+    "eg3d_free_graph3d": (None, [P(D.Graph3D)]),
+    "eg3d_match_polylines_closeness": (i32, [vp, P(D.Seeds), u32, u32, P(D.PolylineMatches), P(D.PolymatchStats)]),
+    "eg3d_free_polyline_matches": (None, [P(D.PolylineMatches)]),
+    "eg3d_similarity_graph": (i32, [vp, P(D.Seeds), u32, u32, P(D.Simgraph), P(D.SimgraphStats)]),
+    "eg3d_free_simgraph": (None, [P(D.Simgraph)]),
+    "eg3d_detect_communities": (i32, [vp, P(D.Simgraph), P(D.LouvainParams), P(D.Communities), P(D.LouvainStats)]),
+    "eg3d_free_communities": (None, [P(D.Communities)]),
+    "eg3d_estimate_fundamental": (i32, [i32, C.c_int32, P(D.Seeds), P(D.FundParams), f64p, u8p, u32p, P(D.FundStats)]),
+}
+
+# include/eg3d_host.h (libeg3d_host.so); the eg3d_synth*, eg3d_plg* and eg3d_sfm* handles are void pointers here
+EG3D_HOST = {
+    "eg3d_synth_default_config": (None, [P(D.SynthConfig), i32]),
+    "eg3d_synth_create": (vp, [P(D.SynthConfig)]),
+    "eg3d_synth_scene": (P(D.Scene), [vp]),
+    "eg3d_synth_seeds": (P(D.Seeds), [vp]),
+    "eg3d_synth_seed_truth": (f32p, [vp]),
+    "eg3d_synth_total_segments": (u64, [vp]),
+    "eg3d_synth_polyline_curve": (u32p, [vp]),
+    "eg3d_synth_n_curves": (i32, [vp]),
+    "eg3d_synth_destroy": (None, [vp]),
+    "eg3d_synth_points": (i32, [vp, u64, u64, P(f32p), P(u32p), P(i32p), P(f32p)]),
+    "eg3d_host_free": (None, [vp]),
+    "eg3d_synth_camera": (i32, [vp, i32, f32p, f32p, f32p, f32p, f32p]),
+    "eg3d_plg_write": (i32, [cstr, P(D.Scene)]),
+    "eg3d_plg_read": (vp, [cstr]),
+    "eg3d_plg_scene": (P(D.Scene), [vp]),
+    "eg3d_plg_destroy": (None, [vp]),
+    "eg3d_plg_build_from_mask": (i32, [u8p, i32, i32, P(D.PlgView)]),
+    "eg3d_png_read_edge_mask": (i32, [cstr, intp, intp, P(u8p)]),
+    "eg3d_plg_build_from_png": (i32, [cstr, intp, intp, P(D.PlgView)]),
+    "eg3d_plg_view_free": (None, [P(D.PlgView)]),
+    "eg3d_plg_build_views_from_png": (i32, [P(cstr), i32, intp, intp, P(D.PlgView)]),
+    "eg3d_plg_from_views": (vp, [i32, i32, i32, P(D.PlgView)]),
+    "eg3d_host_build_grid": (i32, [P(D.Scene), i32, f32, u32p, u32p, P(u32p), P(u32p), u32p]),
+    "eg3d_host_filter_close_2d": (i32, [i32, i32, i32, P(D.EdgePoints), u8p]),
+    "eg3d_host_observation_filter": (i32, [i32, u32p, u64, u64, i32, u8p]),
+    "eg3d_host_gather_plan": (i32, [i32, u64p, u64p, u64p, u64p, u64p]),
+    "eg3d_host_gather_place": (i32, [P(D.EdgePoints), u64, u64, P(D.EdgePoints)]),
+    "eg3d_host_replay_matches": (i32, [P(D.Scene), P(D.EdgePoints), P(D.Graph3D)]),
+    "eg3d_host_free_graph3d": (None, [P(D.Graph3D)]),
+    "eg3d_host_is_matched": (i32, [P(D.Scene), P(D.MatchedIntervals), u64, i32p, u32p, u32p, f32p, i64p]),
+    "eg3d_host_write_compat_graph": (i32, [cstr, P(D.Simgraph)]),
+    "eg3d_host_read_communities": (i32, [cstr, P(i64p), u64p]),
+    "eg3d_host_write_communities": (i32, [cstr, i64p, u64]),
+    "eg3d_host_sets_from_communities": (i32, [P(D.Simgraph), i64p, u64, C.c_int32, P(D.PolylineSets)]),
+    "eg3d_host_free_polyline_sets": (None, [P(D.PolylineSets)]),
+    "eg3d_sfm_read_json": (vp, [cstr]),
+    "eg3d_sfm_write_json": (i32, [vp, cstr, cstr]),
+    "eg3d_host_camera_model": (i32, [u64, f32p, f32p, f32p, f32p, f32p]),
+    "eg3d_host_json_double_text": (i32, [C.c_double, cstr, i32]),
+    "eg3d_host_json_number_text": (i32, [cstr, cstr, i32]),
+    "eg3d_host_json_cached_power": (i32, [i32, u64p, intp]),
+    "eg3d_sfm_create": (vp, [i32, i32, i32]),
+    "eg3d_sfm_destroy": (None, [vp]),
+    "eg3d_sfm_n_views": (i32, [vp]),
+    "eg3d_sfm_n_points": (u64, [vp]),
+    "eg3d_sfm_cam_P": (f32p, [vp]),
+    "eg3d_sfm_image_path": (cstr, [vp, i32]),
+    "eg3d_sfm_image_size": (i32, [vp, intp, intp]),
+    "eg3d_sfm_set_camera": (i32, [vp, i32, f32, f32, f32, f32p, f32p, cstr]),
+    "eg3d_sfm_seeds": (i32, [vp, P(D.Seeds)]),
+    "eg3d_sfm_points": (f32p, [vp]),
+    "eg3d_sfm_add_point": (i32, [vp, f32p, i32, i32p, f32p]),
+    "eg3d_sfm_add_edgepoints": (i32, [vp, P(D.EdgePoints), u8p]),
+    "eg3d_sfm_remove_outliers": (i32, [vp, u8p]),
+    "eg3d_sfm_set_point_coords": (i32, [vp, f32p]),
+    "eg3d_sfm_analytic_F": (i32, [vp, f64p, u8p]),
+    "eg3d_host_estimate_F": (i32, [i32, u64, u32p, i32p, f32p, i32, u64, f64p, u8p, u32p]),
+    "eg3d_sfm_estimate_F": (i32, [vp, i32, u64, f64p, u8p, u32p]),
+    "eg3d_host_estimate_fundamental": (i32, [C.c_int32, P(D.Seeds), P(D.FundParams), f64p, u8p, u32p, P(D.FundStats)]),
+}
+
+# include/eg3d_rccl.h (libeg3d_rccl.so); communicator, gather handle and stream are void pointers here
+EG3D_RCCL = {
+    "eg3d_comm_unique_id": (i32, [vp]),
+    "eg3d_comm_init": (i32, [vp, i32, i32, i32, P(vp)]),
+    "eg3d_comm_query": (i32, [vp, intp, intp, intp]),
+    "eg3d_comm_destroy": (None, [vp]),
+    "eg3d_gather_create": (vp, [i32]),
+    "eg3d_gather_destroy": (None, [vp]),
+    "eg3d_gather_set_mode": (i32, [vp, i32]),
+    "eg3d_gather_set_chunk_bytes": (i32, [vp, u64]),
+    "eg3d_allgather_edgepoints": (i32, [vp, vp, i32, i32, vp, P(D.DeviceEdgePoints), P(D.DeviceEdgePoints), u64p, u64p]),
+    "eg3d_concat_edgepoints": (i32, [vp, i32, P(D.DeviceEdgePoints), vp, P(D.DeviceEdgePoints)]),
+}
+
+
+def bind(lib, table):
+    """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib

@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
+from ._cabi import EG3D, bind
 
 _LIB = None
 
@@ -33,80 +34,12 @@ def lib():
         if not os.path.exists(path):
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
-        L = C.CDLL(path)
-        L.eg3d_last_error.restype = C.c_char_p
-        L.eg3d_device_count.restype = C.c_int
-        L.eg3d_dlt_rows.restype = C.c_int
-        L.eg3d_create.argtypes = [C.POINTER(D.Scene), C.c_int, C.POINTER(C.c_void_p)]
-        L.eg3d_destroy.argtypes = [C.c_void_p]
-        L.eg3d_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.eg3d_get_grid.argtypes = [C.c_void_p, C.c_int, C.c_int, D.u32p, D.u32p, C.POINTER(D.u32p), C.POINTER(D.u32p)]
-        L.eg3d_candidates_run.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32, C.POINTER(D.Candidates)]
-        L.eg3d_free_candidates.argtypes = [C.POINTER(D.Candidates)]
-        L.eg3d_match_refpoints.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32, C.c_int,
-                                           C.POINTER(D.EdgePoints), C.POINTER(D.StageTimes)]
-        L.eg3d_free_edgepoints.argtypes = [C.POINTER(D.EdgePoints)]
-        L.eg3d_upload_seeds.argtypes = [C.c_void_p, C.POINTER(D.Seeds)]
-        L.eg3d_match_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(D.EdgePoints),
-                                          C.POINTER(D.StageTimes)]
-        L.eg3d_match_polyline_sets.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32, C.c_int,
-                                               C.POINTER(D.EdgePoints), C.POINTER(D.StageTimes)]
-        L.eg3d_check_polyline_sets.argtypes = [C.POINTER(D.PolylineSets), C.c_int32]
-        L.eg3d_match_polyline_sets_matched.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32,
-                                                       C.POINTER(D.MatchedIntervals), C.c_int, C.POINTER(D.EdgePoints),
-                                                       C.POINTER(D.StageTimes)]
-        L.eg3d_polyline_set_candidates.argtypes = [C.c_void_p, C.POINTER(D.PolylineSets), C.c_uint32, C.c_uint32,
-                                                   C.POINTER(D.MatchedIntervals), C.POINTER(D.SetCandidates)]
-        L.eg3d_free_set_candidates.argtypes = [C.POINTER(D.SetCandidates)]
-        L.eg3d_free_set_candidates.restype = None
-        L.eg3d_last_device_output.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints)]
-        L.eg3d_set_pipelining.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.eg3d_gn_filter.argtypes = [C.c_void_p, D.f32p, D.u32p, D.i32p, D.f32p, C.c_uint64, C.c_float, C.c_int,
-                                     D.f32p, D.u8p, D.f32p]
-        L.eg3d_context_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.eg3d_gn_filter_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.c_void_p, C.c_float, C.c_int,
-                                            C.c_void_p, C.c_void_p, D.u64p, D.u64p, D.f32p]
-        L.eg3d_compact_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.POINTER(D.DeviceEdgePoints)]
-        L.eg3d_filter_resident.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, D.u64p, C.c_int,
-                                           C.POINTER(D.EdgePoints), C.POINTER(D.DeviceEdgePoints), C.POINTER(D.FilterStats)]
-        L.eg3d_dedup_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.c_uint64, C.c_int, C.c_void_p, D.u64p]
-        L.eg3d_dedup_resident.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, D.u64p,
-                                          C.c_int, C.POINTER(D.EdgePoints), C.POINTER(D.DeviceEdgePoints),
-                                          C.POINTER(D.DedupStats)]
-        L.eg3d_replay_device.argtypes = [C.c_void_p, C.POINTER(D.DeviceEdgePoints), C.POINTER(D.DeviceGraph3D),
-                                         C.POINTER(D.Graph3D), C.POINTER(D.ReplayStats)]
-        L.eg3d_free_graph3d.argtypes = [C.POINTER(D.Graph3D)]
-        L.eg3d_free_graph3d.restype = None
-        L.eg3d_match_polylines_closeness.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32,
-                                                     C.POINTER(D.PolylineMatches), C.POINTER(D.PolymatchStats)]
-        L.eg3d_free_polyline_matches.argtypes = [C.POINTER(D.PolylineMatches)]
-        L.eg3d_free_polyline_matches.restype = None
-        L.eg3d_similarity_graph.argtypes = [C.c_void_p, C.POINTER(D.Seeds), C.c_uint32, C.c_uint32, C.POINTER(D.Simgraph),
-                                            C.POINTER(D.SimgraphStats)]
-        L.eg3d_free_simgraph.argtypes = [C.POINTER(D.Simgraph)]
-        L.eg3d_free_simgraph.restype = None
-        L.eg3d_detect_communities.argtypes = [C.c_void_p, C.POINTER(D.Simgraph), C.POINTER(D.LouvainParams),
-                                              C.POINTER(D.Communities), C.POINTER(D.LouvainStats)]
-        L.eg3d_free_communities.argtypes = [C.POINTER(D.Communities)]
-        L.eg3d_free_communities.restype = None
-        L.eg3d_estimate_fundamental.argtypes = [C.c_int, C.c_int32, C.POINTER(D.Seeds), C.POINTER(D.FundParams), D.f64p, D.u8p,
-                                                D.u32p, C.POINTER(D.FundStats)]
-        _LIB = L
+        _LIB = bind(C.CDLL(path), EG3D)
     return _LIB
 
 
-# every symbol include/eg3d.h declares (checked by tests/test_abi.py without a GPU)
-EXPORTED_SYMBOLS = [
-    "eg3d_last_error", "eg3d_device_count", "eg3d_dlt_rows", "eg3d_create", "eg3d_clone", "eg3d_destroy", "eg3d_get_grid", "eg3d_candidates_run",
-    "eg3d_free_candidates", "eg3d_match_refpoints", "eg3d_free_edgepoints", "eg3d_upload_seeds",
-    "eg3d_match_resident", "eg3d_gn_filter", "eg3d_last_device_output", "eg3d_match_polyline_sets", "eg3d_check_polyline_sets", "eg3d_set_pipelining",
-    "eg3d_match_polyline_sets_matched", "eg3d_polyline_set_candidates", "eg3d_free_set_candidates",
-    "eg3d_gn_filter_device", "eg3d_compact_device", "eg3d_filter_resident", "eg3d_context_info",
-    "eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_replay_device", "eg3d_free_graph3d",
-    "eg3d_match_polylines_closeness", "eg3d_free_polyline_matches", "eg3d_similarity_graph", "eg3d_free_simgraph",
-    "eg3d_detect_communities", "eg3d_free_communities", "eg3d_estimate_fundamental",
-]
+# every symbol include/eg3d.h declares (tests/test_abi.py holds the table to the header without a GPU)
+EXPORTED_SYMBOLS = list(EG3D)
 
 
 def _check(rc, what):

@@ -74,6 +74,21 @@ class StepPlan:
         return (self.n_total + self.batch - 1) // self.batch
 
 
+_GATHER_LIB = None
+
+
+def gather_lib():
+    """libeg3d_rccl.so with include/eg3d_rccl.h declared on it. Loaded on first use, never on import: it brings librccl
+    into the process, which only a caller of the exchange wants."""
+    global _GATHER_LIB
+    if _GATHER_LIB is None:
+        import ctypes as C
+        import os
+        from ._cabi import EG3D_RCCL, bind
+        _GATHER_LIB = bind(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_rccl.so")), EG3D_RCCL)
+    return _GATHER_LIB
+
+
 class RcclCloudGather:
     """The C-ABI exchange step (include/eg3d_rccl.h: eg3d_allgather_edgepoints in libeg3d_rccl.so) on an
     RCCL communicator created by the same library (eg3d_comm_init: hipSetDevice + ncclCommInitRank); the
@@ -87,11 +102,7 @@ class RcclCloudGather:
         self.C, self.D = C, D
         self.world, self.rank = world, rank
         self.g, self.comm = None, None
-        pkg = os.path.dirname(os.path.abspath(__file__))
-        self.G = C.CDLL(os.path.join(pkg, "libeg3d_rccl.so"))
-        self.G.eg3d_comm_unique_id.argtypes = [C.c_void_p]
-        self.G.eg3d_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        self.G.eg3d_comm_destroy.argtypes = [C.c_void_p]
+        self.G = gather_lib()
         uid = (C.c_ubyte * 128)()
         if rank == 0:
             rc = self.G.eg3d_comm_unique_id(uid)
@@ -108,7 +119,6 @@ class RcclCloudGather:
         if rc != 0:
             raise RuntimeError("eg3d_comm_init (hipSetDevice + ncclCommInitRank) failed (%d) on rank %d" % (rc, rank))
         # pre-flight, part 1: what RCCL itself reports about the communicator must be what the launcher started
-        self.G.eg3d_comm_query.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         n_, r_, d_ = C.c_int(-1), C.c_int(-1), C.c_int(-1)
         rc = self.G.eg3d_comm_query(self.comm, C.byref(n_), C.byref(r_), C.byref(d_))
         self.comm_info = {"ncclCommCount": n_.value, "ncclCommUserRank": r_.value, "ncclCommCuDevice": d_.value}
@@ -119,12 +129,6 @@ class RcclCloudGather:
             self.close()
             raise RuntimeError("RCCL pre-flight: the communicator reports %s, expected %d ranks / rank %d / device %d"
                                % (self.comm_info, world, rank, device_index))
-        self.G.eg3d_gather_create.restype = C.c_void_p
-        self.G.eg3d_gather_create.argtypes = [C.c_int]
-        self.G.eg3d_gather_destroy.argtypes = [C.c_void_p]
-        self.G.eg3d_allgather_edgepoints.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                                     C.POINTER(D.DeviceEdgePoints), C.POINTER(D.DeviceEdgePoints),
-                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         self.g = self.G.eg3d_gather_create(device_index)
         if not self.g:
             self.close()  # do not leak the communicator
@@ -132,7 +136,6 @@ class RcclCloudGather:
         self.stream = C.c_void_p(stream_ptr) if stream_ptr else None
         self.rank_points = (C.c_uint64 * world)()
         self.rank_obs = (C.c_uint64 * world)()
-        self.G.eg3d_gather_set_mode.argtypes = [C.c_void_p, C.c_int]
         self.mode = "bcast" if os.environ.get("EG3D_GATHER_MODE", "")[:1] in ("b", "1") else "sendrecv"
         self.selftest = None
         if world > 1 and dist.get_backend() == "nccl":
@@ -295,7 +298,6 @@ class HostCloudGather:
         pbase = np.zeros(world, np.uint64)
         obase = np.zeros(world, np.uint64)
         tp, to = C.c_uint64(), C.c_uint64()
-        self.H.eg3d_host_gather_plan.argtypes = [C.c_int, D.u64p, D.u64p, D.u64p, D.u64p, D.u64p]
         rc = self.H.eg3d_host_gather_plan(world, D.np_ptr(counts, C.c_uint64), D.np_ptr(pbase, C.c_uint64),
                                           D.np_ptr(obase, C.c_uint64), C.byref(tp), C.byref(to))
         if rc != 0:
@@ -306,7 +308,6 @@ class HostCloudGather:
                  "obs_seg": np.zeros(to, np.uint32), "obs_xy": np.zeros((to, 2), np.float32)}
         whole_c = D.EdgePointsArrays(whole)
         whole_c.c.n_points, whole_c.c.n_obs = tp, to
-        self.H.eg3d_host_gather_place.argtypes = [C.POINTER(D.EdgePoints), C.c_uint64, C.c_uint64, C.POINTER(D.EdgePoints)]
         dtypes = {"X": np.float32, "obs_off": np.uint64, "key": np.uint32, "obs_view": np.int32, "obs_pl": np.uint32,
                   "obs_seg": np.uint32, "obs_xy": np.float32}
         for r in range(world):

@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
+from ._cabi import EG3D_HOST, bind
 
 _LIB = None
 
@@ -15,48 +16,7 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_host.so")
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
-        L = C.CDLL(path)
-        L.eg3d_synth_default_config.argtypes = [C.POINTER(D.SynthConfig), C.c_int]
-        L.eg3d_synth_create.argtypes = [C.POINTER(D.SynthConfig)]
-        L.eg3d_synth_create.restype = C.c_void_p
-        L.eg3d_synth_scene.argtypes = [C.c_void_p]
-        L.eg3d_synth_scene.restype = C.POINTER(D.Scene)
-        L.eg3d_synth_seeds.argtypes = [C.c_void_p]
-        L.eg3d_synth_seeds.restype = C.POINTER(D.Seeds)
-        L.eg3d_synth_seed_truth.argtypes = [C.c_void_p]
-        L.eg3d_synth_seed_truth.restype = D.f32p
-        L.eg3d_synth_total_segments.argtypes = [C.c_void_p]
-        L.eg3d_synth_total_segments.restype = C.c_uint64
-        L.eg3d_synth_destroy.argtypes = [C.c_void_p]
-        L.eg3d_synth_polyline_curve.argtypes = [C.c_void_p]
-        L.eg3d_synth_polyline_curve.restype = D.u32p
-        L.eg3d_synth_n_curves.argtypes = [C.c_void_p]
-        L.eg3d_synth_points.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(D.f32p), C.POINTER(D.u32p),
-                                        C.POINTER(D.i32p), C.POINTER(D.f32p)]
-        L.eg3d_host_free.argtypes = [C.c_void_p]
-        L.eg3d_host_build_grid.argtypes = [C.POINTER(D.Scene), C.c_int, C.c_float, D.u32p, D.u32p,
-                                           C.POINTER(D.u32p), C.POINTER(D.u32p), D.u32p]
-        L.eg3d_host_filter_close_2d.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(D.EdgePoints), D.u8p]
-        L.eg3d_host_observation_filter.argtypes = [C.c_int, D.u32p, C.c_uint64, C.c_uint64, C.c_int, D.u8p]
-        L.eg3d_host_replay_matches.argtypes = [C.POINTER(D.Scene), C.POINTER(D.EdgePoints), C.POINTER(D.Graph3D)]
-        L.eg3d_host_free_graph3d.argtypes = [C.POINTER(D.Graph3D)]
-        L.eg3d_plg_build_from_mask.argtypes = [D.u8p, C.c_int, C.c_int, C.POINTER(D.PlgView)]
-        L.eg3d_plg_build_from_png.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(D.PlgView)]
-        L.eg3d_png_read_edge_mask.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(D.u8p)]
-        L.eg3d_plg_view_free.argtypes = [C.POINTER(D.PlgView)]
-        L.eg3d_plg_from_views.restype = C.c_void_p
-        L.eg3d_plg_from_views.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(D.PlgView)]
-        L.eg3d_plg_scene.restype = C.POINTER(D.Scene)
-        L.eg3d_plg_scene.argtypes = [C.c_void_p]
-        L.eg3d_plg_destroy.argtypes = [C.c_void_p]
-        L.eg3d_host_write_compat_graph.argtypes = [C.c_char_p, C.POINTER(D.Simgraph)]
-        L.eg3d_host_read_communities.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_uint64)]
-        L.eg3d_host_write_communities.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_uint64]
-        L.eg3d_host_sets_from_communities.argtypes = [C.POINTER(D.Simgraph), C.POINTER(C.c_int64), C.c_uint64, C.c_int32,
-                                                      C.POINTER(D.PolylineSets)]
-        L.eg3d_host_free_polyline_sets.argtypes = [C.POINTER(D.PolylineSets)]
-        L.eg3d_host_free_polyline_sets.restype = None
-        _LIB = L
+        _LIB = bind(C.CDLL(path), EG3D_HOST)
     return _LIB
 
 
@@ -186,9 +146,6 @@ def is_matched(scene_ptr, graph, view, pl, seg, xy):
     replay_matches): int64 [n], -1 or the index within its row of the interval that contains the point
     (eg3d_host_is_matched — the rule the kernels of Context.match_polyline_sets(matched=...) apply). Raises ValueError
     when the intervals fail their checks or the extractor's walk would not advance past one of them."""
-    L = lib()
-    L.eg3d_host_is_matched.argtypes = [C.POINTER(D.Scene), C.POINTER(D.MatchedIntervals), C.c_uint64, D.i32p, D.u32p,
-                                       D.u32p, D.f32p, C.POINTER(C.c_int64)]
     m = D.MatchedIntervalsArrays(graph)
     view = np.ascontiguousarray(view, np.int32).reshape(-1)
     n = len(view)
@@ -197,9 +154,9 @@ def is_matched(scene_ptr, graph, view, pl, seg, xy):
     if n and (len(pl) != n or len(seg) != n or len(xy) != 2 * n):
         raise ValueError("is_matched: view, pl, seg, xy differ in length")
     out = np.full(max(n, 1), -1, np.int64)
-    rc = L.eg3d_host_is_matched(scene_ptr, C.byref(m.c), n, D.np_ptr(view if n else np.zeros(1, np.int32), C.c_int32),
-                                D.np_ptr(pl, C.c_uint32), D.np_ptr(seg, C.c_uint32), D.np_ptr(xy, C.c_float),
-                                D.np_ptr(out, C.c_int64))
+    rc = lib().eg3d_host_is_matched(scene_ptr, C.byref(m.c), n, D.np_ptr(view if n else np.zeros(1, np.int32), C.c_int32),
+                                    D.np_ptr(pl, C.c_uint32), D.np_ptr(seg, C.c_uint32), D.np_ptr(xy, C.c_float),
+                                    D.np_ptr(out, C.c_int64))
     if rc == -2:
         raise ValueError("is_matched: the intervals do not belong to this scene (the walk would not advance past %d of the "
                          "points)" % int((out[:n] <= -2).sum()))
@@ -270,10 +227,6 @@ def estimate_F(n_views, trk_off, trk_view, trk_xy, estimate=True, rng_seed=0):
     """SURVEY N4 (geometric_utilities.cpp:754-820): fundamental matrices of all ordered view pairs from the
     point tracks; pairs with fewer than 10 common points are invalid. Returns (F [V,V,9] f64, valid [V,V] u8,
     n_common [V,V] u32, pairs whose estimate failed). estimate=False: validity rule and counts only."""
-    L = lib()
-    L.eg3d_host_estimate_F.restype = C.c_int
-    L.eg3d_host_estimate_F.argtypes = [C.c_int, C.c_uint64, D.u32p, D.i32p, D.f32p, C.c_int, C.c_uint64, D.f64p,
-                                       D.u8p, D.u32p]
     off = np.ascontiguousarray(trk_off, np.uint32)
     view = np.ascontiguousarray(trk_view, np.int32)
     xy = np.ascontiguousarray(trk_xy, np.float32)
@@ -281,9 +234,9 @@ def estimate_F(n_views, trk_off, trk_view, trk_xy, estimate=True, rng_seed=0):
     F = np.zeros((V, V, 9), np.float64)
     valid = np.zeros((V, V), np.uint8)
     ncom = np.zeros((V, V), np.uint32)
-    rc = L.eg3d_host_estimate_F(V, len(off) - 1, D.np_ptr(off, C.c_uint32), D.np_ptr(view, C.c_int32),
-                                D.np_ptr(xy, C.c_float), 1 if estimate else 0, rng_seed, D.np_ptr(F, C.c_double),
-                                D.np_ptr(valid, C.c_uint8), D.np_ptr(ncom, C.c_uint32))
+    rc = lib().eg3d_host_estimate_F(V, len(off) - 1, D.np_ptr(off, C.c_uint32), D.np_ptr(view, C.c_int32),
+                                    D.np_ptr(xy, C.c_float), 1 if estimate else 0, rng_seed, D.np_ptr(F, C.c_double),
+                                    D.np_ptr(valid, C.c_uint8), D.np_ptr(ncom, C.c_uint32))
     if rc < 0:
         raise RuntimeError("eg3d_host_estimate_F failed (%d)" % rc)
     return F, valid, ncom, rc
@@ -292,11 +245,7 @@ def estimate_F(n_views, trk_off, trk_view, trk_xy, estimate=True, rng_seed=0):
 def estimate_fundamental(n_views, seeds, iterations=0, rng_seed=0, fit_budget=0, stage_points=0):
     """The host statement of api.estimate_fundamental (eg3d_host_estimate_fundamental): the same arguments (fit_budget and
     stage_points have no meaning here), the same return shape, the same bits — without a GPU."""
-    L = lib()
-    L.eg3d_host_estimate_fundamental.restype = C.c_int
-    L.eg3d_host_estimate_fundamental.argtypes = [C.c_int32, C.POINTER(D.Seeds), C.POINTER(D.FundParams), D.f64p, D.u8p, D.u32p,
-                                                 C.POINTER(D.FundStats)]
-    rc, out = D.fund_call(L.eg3d_host_estimate_fundamental, n_views, seeds, iterations, rng_seed, fit_budget, stage_points)
+    rc, out = D.fund_call(lib().eg3d_host_estimate_fundamental, n_views, seeds, iterations, rng_seed, fit_budget, stage_points)
     if rc != 0:
         raise RuntimeError("eg3d_host_estimate_fundamental failed (%d)" % rc)
     return out

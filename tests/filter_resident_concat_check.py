@@ -11,16 +11,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from edgegraph3d_amd import _cdefs as D  # noqa: E402
 from edgegraph3d_amd import api, host  # noqa: E402
+from edgegraph3d_amd._cabi import EG3D_RCCL, bind  # noqa: E402
 from edgegraph3d_amd.cloudnp import np_compact, same_cloud  # noqa: E402
 
 
 def main():
-    G = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(api.__file__)), "libeg3d_rccl.so"))
-    G.eg3d_gather_create.restype = C.c_void_p
-    G.eg3d_gather_create.argtypes = [C.c_int]
-    G.eg3d_gather_destroy.argtypes = [C.c_void_p]
-    G.eg3d_concat_edgepoints.argtypes = [C.c_void_p, C.c_int, C.POINTER(D.DeviceEdgePoints), C.c_void_p,
-                                         C.POINTER(D.DeviceEdgePoints)]
+    G = bind(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(api.__file__)), "libeg3d_rccl.so")), EG3D_RCCL)
     s = host.Synth(2)
     a = api.Context(s.scene)
     a.upload_seeds(s.seeds)

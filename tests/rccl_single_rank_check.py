@@ -19,13 +19,13 @@ def main():
     import ctypes as C
     import os
     from edgegraph3d_amd import _cdefs as D
+    from edgegraph3d_amd._cabi import EG3D_RCCL, bind
     pkg = os.path.dirname(os.path.abspath(api.__file__))
-    G = C.CDLL(os.path.join(pkg, "libeg3d_rccl.so"))
+    G = bind(C.CDLL(os.path.join(pkg, "libeg3d_rccl.so")), EG3D_RCCL)
     hip = C.CDLL("/opt/rocm/lib/libamdhip64.so")
     uid = (C.c_ubyte * 128)()
     assert G.eg3d_comm_unique_id(uid) == 0
     comm = C.c_void_p()
-    G.eg3d_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     assert G.eg3d_comm_init(uid, 1, 0, 0, C.byref(comm)) == 0
     # default: the small scene; EG3D_GATHER_CHECK="<config> <seed_begin> <seed_end>" for a large one (ad hoc, e.g.
     # "4 0 8192": a whole multi-chunk C4 step, a 7 GB cloud through pack / all-gather / unpack)
@@ -37,11 +37,6 @@ def main():
     want = ctx.match_resident(b, e)
     ctx.match_resident(b, e, device_only=True)
     local = ctx.last_device_output()
-    G.eg3d_gather_create.restype = C.c_void_p
-    G.eg3d_allgather_edgepoints.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                            C.POINTER(D.DeviceEdgePoints), C.POINTER(D.DeviceEdgePoints),
-                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    G.eg3d_gather_destroy.argtypes = [C.c_void_p]
     g = G.eg3d_gather_create(0)
     out = D.DeviceEdgePoints()
     rp, ro = (C.c_uint64 * 1)(), (C.c_uint64 * 1)()
@@ -75,8 +70,6 @@ def main():
         assert np.array_equal(fetch(o.obs_seg, mm, np.uint32), w["obs_seg"]), label
         assert np.array_equal(fetch(o.obs_xy, 2 * mm, np.uint32), w["obs_xy"].view(np.uint32).ravel()), label
 
-    G.eg3d_concat_edgepoints.argtypes = [C.c_void_p, C.c_int, C.POINTER(D.DeviceEdgePoints), C.c_void_p,
-                                         C.POINTER(D.DeviceEdgePoints)]
     span = e - b
     for cuts in ((0.1, 0.1, 0.55), (0.5,), (0.0, 0.33, 0.34, 0.9)):
         edges = [b] + [b + int(span * c) for c in cuts] + [e]
@@ -99,7 +92,6 @@ def main():
     alias[1] = ctx.last_device_output()
     assert G.eg3d_concat_edgepoints(g, 2, alias, None, C.byref(D.DeviceEdgePoints())) == -1
     G.eg3d_gather_destroy(g)
-    G.eg3d_comm_destroy.argtypes = [C.c_void_p]
     G.eg3d_comm_destroy(comm)
     ctx.close()
     # the pre-flight check bench.py --gpus N runs before trusting the exchange (edgegraph3d_amd/distributed.py): its

@@ -39,9 +39,10 @@ def worker(rank, world, idfile):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     from edgegraph3d_amd import _cdefs as D
     from edgegraph3d_amd import api, host
+    from edgegraph3d_amd._cabi import EG3D_RCCL, bind
     from edgegraph3d_amd.distributed import shard_ranges_balanced
     pkg = os.path.dirname(os.path.abspath(api.__file__))
-    G = C.CDLL(os.path.join(pkg, "libeg3d_rccl.so"))
+    G = bind(C.CDLL(os.path.join(pkg, "libeg3d_rccl.so")), EG3D_RCCL)
     hip = C.CDLL("libamdhip64.so")
     uid = UniqueId()
     if rank == 0:
@@ -56,14 +57,7 @@ def worker(rank, world, idfile):
             time.sleep(0.1)
         C.memmove(C.byref(uid), open(idfile, "rb").read(), 128)
     comm = C.c_void_p()
-    G.eg3d_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     assert G.eg3d_comm_init(C.byref(uid), world, rank, rank, C.byref(comm)) == 0   # hipSetDevice(rank) + ncclCommInitRank
-    G.eg3d_gather_create.restype = C.c_void_p
-    G.eg3d_gather_create.argtypes = [C.c_int]
-    G.eg3d_allgather_edgepoints.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                            C.POINTER(D.DeviceEdgePoints), C.POINTER(D.DeviceEdgePoints),
-                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    G.eg3d_gather_destroy.argtypes = [C.c_void_p]
     g = G.eg3d_gather_create(rank)
     assert g
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -105,8 +99,6 @@ def worker(rank, world, idfile):
         assert sum(rp) == n and sum(ro) == m
         print("rank %d: %s ok (%d points, per rank %s)" % (rank, label, n, list(rp)), flush=True)
 
-    G.eg3d_gather_set_mode.argtypes = [C.c_void_p, C.c_int]
-    G.eg3d_gather_set_chunk_bytes.argtypes = [C.c_void_p, C.c_uint64]
     hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
 
     def to_dev(a):
@@ -185,7 +177,6 @@ def worker(rank, world, idfile):
     assert rc == -4, rc
     print("rank %d: incomplete rank reported to every rank (rc -4)" % rank, flush=True)
     G.eg3d_gather_destroy(g)
-    G.eg3d_comm_destroy.argtypes = [C.c_void_p]
     G.eg3d_comm_destroy(comm)
     ctx.close()
 

@@ -24,21 +24,9 @@ EDGES = os.path.join(HERE, "golden", "dtu006_edges")
 F_PX, PPX, PPY = 2890.0, 823.0, 619.0
 
 
-def _sfm():
-    L = host.lib()
-    L.eg3d_sfm_create.restype = C.c_void_p
-    L.eg3d_sfm_create.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.eg3d_sfm_set_camera.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, D.f32p, D.f32p, C.c_char_p]
-    L.eg3d_sfm_analytic_F.argtypes = [C.c_void_p, D.f64p, D.u8p]
-    L.eg3d_sfm_cam_P.argtypes = [C.c_void_p]
-    L.eg3d_sfm_cam_P.restype = D.f32p
-    L.eg3d_sfm_destroy.argtypes = [C.c_void_p]
-    return L
-
-
 def lookat_cameras(centres, target, width, height):
     """P [V,16] f32 and analytic F [V,V,9] f64 of look-at cameras (x right, y down, z forward)."""
-    L = _sfm()
+    L = host.lib()
     V = len(centres)
     h = L.eg3d_sfm_create(V, width, height)
     for v, Cw in enumerate(centres):

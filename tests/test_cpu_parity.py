@@ -51,47 +51,6 @@ def test_oracle_threads_do_not_change_output():
     assert rep["ok"] and rep["bitexact_X"]
 
 
-def subprocess_nm(path):
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return [l.split()[-1] for l in out.splitlines() if " T " in l]
-
-
-def test_abi_library_exports_every_declared_symbol():
-    """The C-ABI library loads without a GPU and exports every symbol include/eg3d.h declares."""
-    import os
-    import re
-    if not os.path.exists(api.lib_path()):
-        from edgegraph3d_amd import build
-        build.build_hip()
-    L = C.CDLL(api.lib_path())
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, "include", "eg3d.h")).read()
-    declared = set(re.findall(r"\b(eg3d_[a-z_0-9]+)\s*\(", hdr))
-    assert declared == set(api.EXPORTED_SYMBOLS), declared ^ set(api.EXPORTED_SYMBOLS)
-    for name in declared:
-        assert hasattr(L, name), name
-    # no test hooks in the product library: the probes live in tests/probe/libeg3d_probe.so
-    exported = subprocess_nm(api.lib_path())
-    assert not [n for n in exported if "probe" in n or "internal" in n], exported
-    H = host.lib()
-    hhdr = open(os.path.join(root, "include", "eg3d_host.h")).read()
-    host_syms = set(re.findall(r"\b(eg3d_(?:synth|host|sfm|plg)_[a-z_0-9A-Z]+)\s*\(", hhdr))
-    assert len(host_syms) > 24
-    for name in host_syms:
-        assert hasattr(H, name), name
-    # the RCCL gather library (include/eg3d_rccl.h): symbol table only — loading it would pull
-    # /opt/rocm's librccl into a process that may already hold the torch wheel's ROCm runtime
-    import subprocess
-    syms = subprocess.run(["nm", "-D", "--defined-only", os.path.join(os.path.dirname(api.lib_path()), "libeg3d_rccl.so")],
-                          capture_output=True, text=True, check=True).stdout
-    rhdr = open(os.path.join(root, "include", "eg3d_rccl.h")).read()
-    rsyms = set(re.findall(r"\b(eg3d_(?:gather|allgather|comm|concat)_[a-z_0-9]+)\s*\(", rhdr))
-    assert len(rsyms) == 10  # gather create / destroy / set_mode / set_chunk_bytes, allgather, concat, comm unique_id / init / query / destroy
-    for name in rsyms:
-        assert re.search(r"\b%s\b" % name, syms), name
-
-
 def test_no_gpu_means_loud_failure():
     """Without a device the product refuses to run (no CPU fallback)."""
     if api.device_count() > 0:
@@ -108,7 +67,6 @@ def test_inconsistent_scenes_are_refused_before_any_device_is_touched():
     import ctypes as C
     from edgegraph3d_amd import api
     L = api.lib()
-    L.eg3d_last_error.restype = C.c_char_p
     s = host.Synth(0)
     base = s.scene_np()
 

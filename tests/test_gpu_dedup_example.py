@@ -1,26 +1,20 @@
 """-m gpu: examples/edge_matcher_refpoints --resident-dedup. All three stages (polyline matches of pipelines 1 and 2, the
 reference points) matched device-only, each deduplicated on the device against the claims of the stages before it, only
 the survivors copied: the JSON written must be the default path's, byte for byte, with and without --filter."""
-import os
 import re
 import subprocess
 
 import pytest
 
+import cbuild
 import forms
 
 pytestmark = pytest.mark.gpu
 
 
 def test_resident_dedup_writes_the_same_json(eg3d_form, tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
     lib = forms.lib_path(eg3d_form)
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", os.path.dirname(lib),
-                           "-l:" + os.path.basename(lib), "-L", pkg, "-leg3d_host", "-Wl,-rpath," + os.path.dirname(lib),
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=lib)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "1", d])
     common = [d + "/input.json", d + "/plgs.bin"]

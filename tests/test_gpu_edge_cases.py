@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import cbuild
 from edgegraph3d_amd import _cdefs as D
 from edgegraph3d_amd import api, host
 from parity_util import compare_edgepoints
@@ -401,21 +402,6 @@ def _concat_clouds(parts):
 def _check_example_outputs_against_oracle(d, doc, doc_f, sets_files=()):
     from oracle import binding as ob
     H = host.lib()
-    H.eg3d_sfm_read_json.restype = C.c_void_p
-    H.eg3d_sfm_read_json.argtypes = [C.c_char_p]
-    H.eg3d_sfm_destroy.argtypes = [C.c_void_p]
-    H.eg3d_sfm_n_views.argtypes = [C.c_void_p]
-    H.eg3d_sfm_cam_P.argtypes = [C.c_void_p]
-    H.eg3d_sfm_cam_P.restype = D.f32p
-    H.eg3d_sfm_seeds.argtypes = [C.c_void_p, C.POINTER(D.Seeds)]
-    H.eg3d_sfm_points.argtypes = [C.c_void_p]
-    H.eg3d_sfm_points.restype = D.f32p
-    H.eg3d_sfm_analytic_F.argtypes = [C.c_void_p, D.f64p, D.u8p]
-    H.eg3d_plg_read.restype = C.c_void_p
-    H.eg3d_plg_read.argtypes = [C.c_char_p]
-    H.eg3d_plg_scene.restype = C.POINTER(D.Scene)
-    H.eg3d_plg_scene.argtypes = [C.c_void_p]
-    H.eg3d_plg_destroy.argtypes = [C.c_void_p]
     sfm = H.eg3d_sfm_read_json((d + "/input.json").encode())
     plg = H.eg3d_plg_read((d + "/plgs.bin").encode())
     assert sfm and plg
@@ -493,12 +479,7 @@ def test_cpp_end_to_end_example(tmp_path):
     import os
     import re
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "1", d])
     out = subprocess.run([exe, d + "/input.json", d + "/plgs.bin", d + "/out.json", "--all-pairs"], capture_output=True,

@@ -16,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cbuild
 import fundamental_cases as fc
 from edgegraph3d_amd import _cdefs as D
 from edgegraph3d_amd import api, host
@@ -275,12 +276,7 @@ def test_end_to_end_the_example_and_python_report_the_same_cloud(tmp_path):
     with --estimate-F --estimate-F-device on the files of the same scene (the example links the default library: the
     Python side of this comparison uses it too, whichever form the test runs under)."""
     import forms
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "2", d])
     out = subprocess.run([exe, d + "/input.json", d + "/plgs.bin", d + "/out.json", "--estimate-F", "--estimate-F-device"],

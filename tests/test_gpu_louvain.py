@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cbuild
 import louvain_ref as L
 import polymatch_ref as pref
 import simgraph_ref as sref
@@ -291,19 +292,10 @@ def test_end_to_end_without_a_file():
 
 
 # ---- the seams ----------------------------------------------------------------------------------------------------------------
-def _gxx(src, exe, extra=()):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + list(extra) + ["-I", os.path.join(root, "include"), os.path.join(root, src),
-                           "-L", pkg, "-leg3d", "-leg3d_host", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib",
-                           "-lamdhip64", "-o", exe])
-
-
 def test_example_with_louvain_writes_the_restatements_ids(tmp_path):
     """examples/edge_matcher_refpoints.cpp on --make-synthetic scene 2: --louvain out.txt needs no --communities, writes the
     restatement's ids, and pipeline 1's extractor runs in front of the rest: the output differs from the run without it."""
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    _gxx(os.path.join("examples", "edge_matcher_refpoints.cpp"), exe)
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "2", d])
     s = _synth(2)[0]
@@ -325,8 +317,7 @@ def test_example_with_louvain_writes_the_restatements_ids(tmp_path):
 def test_refapi_compute_communities(tmp_path):
     """compute_communities of include/eg3d_refapi.hpp (tests/refapi/louvain_check.cpp) on config 1: both files hold the
     restatement's text, the returned ids are the restatement's, and SimilarityGraph::communities passes its parameters on."""
-    exe = str(tmp_path / "louvain_check")
-    _gxx(os.path.join("tests", "refapi", "louvain_check.cpp"), exe, ["-pthread"])
+    exe = cbuild.build_caller("tests/refapi/louvain_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     s = _synth(1)[0]
     g_want, want = _simgraph_want(1, 0, s.n_seeds)
     assert g_want["n_nodes"] >= 10
@@ -348,10 +339,8 @@ def test_edge_matching_detects_pipeline_1s_communities(tmp_path):
     the same inputs give, and the communities file holds the restatement's ids on that graph."""
     import png_util
     import real_scene as rs
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    _gxx(os.path.join("examples", "edge_matcher_refpoints.cpp"), exe)
-    chk = str(tmp_path / "edge_matching_louvain_check")
-    _gxx(os.path.join("tests", "refapi", "edge_matching_louvain_check.cpp"), chk, ["-pthread"])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
+    chk = cbuild.build_caller("tests/refapi/edge_matching_louvain_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "1", d])
     _, sc, _ = _synth(1)

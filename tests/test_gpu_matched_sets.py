@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import cbuild
 import matched_ref as R
 import sets_cases as cases
 from edgegraph3d_amd import _cdefs as D
@@ -459,13 +460,7 @@ def test_refapi_manager_and_overload(tmp_path, eg3d_form):
     import os
     import subprocess
     assert api.device_count() >= 1
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "matched_sets_check")
-    lib = os.path.splitext(os.path.basename(api.lib_path()))[0][3:]  # (the library of the form under test)
-    subprocess.check_call(["g++", "-std=c++17", "-pthread", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "refapi", "matched_sets_check.cpp"), "-L", pkg, "-l" + lib, "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("tests/refapi/matched_sets_check.cpp", tmp_path)  # (links the library of the form under test)
     out = subprocess.run([exe], env=dict(os.environ, EG3D_LIB=""), capture_output=True, text=True, check=True).stdout
     lines = [l.split() for l in out.split("\n") if l]
     s = host.Synth(0)
@@ -521,14 +516,8 @@ def test_example_refpoints_first(eg3d_form, tmp_path):
     import re
     import subprocess
     import forms
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
     lib = forms.lib_path(eg3d_form)
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", os.path.dirname(lib),
-                           "-l:" + os.path.basename(lib), "-L", pkg, "-leg3d_host", "-Wl,-rpath," + os.path.dirname(lib),
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=lib)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "0", d])
     args = [d + "/input.json", d + "/plgs.bin"]

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import cbuild
 from edgegraph3d_amd import api, host
 from parity_util import compare_edgepoints
 
@@ -387,12 +388,7 @@ def test_reference_surface_shim_on_gpu(have_gpu, tmp_path):
     on clones — equals one direct C-ABI call bit for bit (tests/refapi/refapi_check.cpp)."""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "refapi_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "refapi", "refapi_check.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("tests/refapi/refapi_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     out = subprocess.run([exe, "1"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "\nOK points=" in "\n" + out.stdout, out.stdout + out.stderr
 

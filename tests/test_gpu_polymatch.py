@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cbuild
 import polymatch_cases as pc
 import polymatch_ref as ref
 from edgegraph3d_amd import _cdefs as D
@@ -211,12 +212,7 @@ def _write_sets(path, n_views, r):
 def test_example_match2_equals_sets2_of_the_restatement(tmp_path):
     """examples/edge_matcher_refpoints.cpp on --make-synthetic scene 2: --match2 writes the JSON the same run writes when
     --sets2 hands it the restatement's sets; both flags together are refused."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "2", d])
     y = Synth(2)
@@ -287,12 +283,7 @@ def test_view_id_outside_the_rig():
 def test_refapi_function_equals_the_restatement(tmp_path):
     """polyline_matching_closeness_to_refpoints of include/eg3d_refapi.hpp (tests/refapi/polymatch_check.cpp) on config 1:
     the pair it returns is the restatement's, match by match and view by view."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "polymatch_check")
-    subprocess.check_call(["g++", "-std=c++17", "-pthread", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "refapi", "polymatch_check.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("tests/refapi/polymatch_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     out = subprocess.run([exe, "1"], env=dict(os.environ, EG3D_LIB=""), capture_output=True, text=True, check=True).stdout
     lines = out.split("\n")
     y = Synth(1)

@@ -303,20 +303,3 @@ def test_graph_released_by_the_library_itself(eg3d_form, small):
     finally:
         ctx.close()
 
-
-# ---- 6. the ctypes mirrors against the header ----
-@pytest.mark.parametrize("mirror, ctype", [(D.ReplayStats, "eg3d_replay_stats"), (D.DeviceGraph3D, "eg3d_device_graph3d")])
-def test_mirrors_match_the_header(eg3d_form, tmp_path, mirror, ctype):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    fields = [f[0] for f in mirror._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "eg3d.h"\nint main(void) {\n'
-                   '  printf("%%zu\\n", sizeof(%s));\n' % ctype
-                   + "".join('  printf("%%zu\\n", offsetof(%s, %s));\n' % (ctype, f) for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)],
-                   check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got[0] == C.sizeof(mirror)
-    assert got[1:] == [getattr(mirror, f).offset for f in fields]
-    assert hasattr(api.lib(), "eg3d_replay_device") and hasattr(api.lib(), "eg3d_free_graph3d")

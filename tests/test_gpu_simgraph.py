@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cbuild
 import polymatch_cases as pc
 import polymatch_ref as pref
 import simgraph_cases as sc
@@ -243,12 +244,7 @@ def test_example_writes_the_restatements_graph_file(tmp_path):
     """examples/edge_matcher_refpoints.cpp on --make-synthetic scene 2: --match1-graph writes the restatement's text; with
     --communities (the restatement's components) pipeline 1's extractor runs in front of the rest, and the output differs
     from the run without it."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     d = str(tmp_path)
     subprocess.check_call([exe, "--make-synthetic", "2", d])
     y = Synth(2)
@@ -268,12 +264,7 @@ def test_example_writes_the_restatements_graph_file(tmp_path):
 def test_refapi_functions_equal_the_restatement(tmp_path):
     """The pipeline 1 functions of include/eg3d_refapi.hpp (tests/refapi/simgraph_check.cpp) on config 1: the graph file,
     close_polylines, close_refpoints and the sets from community ids are the restatement's."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "simgraph_check")
-    subprocess.check_call(["g++", "-std=c++17", "-pthread", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "refapi", "simgraph_check.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("tests/refapi/simgraph_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     y = Synth(1)
     V = y.scene["n_views"]
     want = _want(y.name, y.scene, y.seeds, 0, y.s.n_seeds)

@@ -15,24 +15,6 @@ from oracle import binding as ob
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _sfm_lib():
-    L = host.lib()
-    L.eg3d_sfm_read_json.restype = C.c_void_p
-    L.eg3d_sfm_read_json.argtypes = [C.c_char_p]
-    L.eg3d_sfm_write_json.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-    L.eg3d_sfm_destroy.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_views.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_points.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_points.restype = C.c_uint64
-    L.eg3d_sfm_cam_P.argtypes = [C.c_void_p]
-    L.eg3d_sfm_cam_P.restype = D.f32p
-    L.eg3d_sfm_seeds.argtypes = [C.c_void_p, C.POINTER(D.Seeds)]
-    L.eg3d_sfm_points.argtypes = [C.c_void_p]
-    L.eg3d_sfm_points.restype = D.f32p
-    L.eg3d_sfm_add_edgepoints.argtypes = [C.c_void_p, C.POINTER(D.EdgePoints), D.u8p]
-    return L
-
-
 def _openmvg_doc(base=10):
     R = [[1, 0, 0], [0, 1, 0], [0, 0, 1]]
     views, extr = [], []
@@ -52,7 +34,7 @@ def _openmvg_doc(base=10):
 
 
 def test_openmvg_json_round_trip():
-    L = _sfm_lib()
+    L = host.lib()
     with tempfile.TemporaryDirectory() as d:
         p_in, p_out = os.path.join(d, "in.json"), os.path.join(d, "out.json")
         json.dump(_openmvg_doc(), open(p_in, "w"))
@@ -129,12 +111,6 @@ def test_polyline_graph_container_round_trip():
     """EG3DPLG1 container (edgegraph3d_amd/host/plg_file.cpp): the polyline graphs of all views
     written and read back are identical, including invalid / empty polylines and node ids."""
     L = host.lib()
-    L.eg3d_plg_write.argtypes = [C.c_char_p, C.POINTER(D.Scene)]
-    L.eg3d_plg_read.restype = C.c_void_p
-    L.eg3d_plg_read.argtypes = [C.c_char_p]
-    L.eg3d_plg_scene.restype = C.POINTER(D.Scene)
-    L.eg3d_plg_scene.argtypes = [C.c_void_p]
-    L.eg3d_plg_destroy.argtypes = [C.c_void_p]
     s = host.Synth(1)
     sc = s.scene_np()
     with tempfile.TemporaryDirectory() as d:
@@ -163,7 +139,7 @@ def test_polyline_graph_container_round_trip():
 def test_openmvg_reader_rejects_malformed_files_instead_of_crashing():
     """A variant / truncated OpenMVG file (non-pinhole intrinsic without focal_length, short
     rotation, missing observation coordinates, absurd nesting) makes eg3d_sfm_read_json return NULL."""
-    L = _sfm_lib()
+    L = host.lib()
     import copy
 
     def reads(doc, raw=None):
@@ -208,12 +184,7 @@ def test_analytic_fundamental_matrices_satisfy_the_epipolar_constraint():
     geometric_utilities.cpp:824-843): the projection of any 3-D point into j lies on the line of its
     projection into i. Checked in float64 from the float camera matrices, through the oracle's
     epiline primitive, and against the synthetic generator's own F (same rig => same matrices)."""
-    L = _sfm_lib()
-    L.eg3d_sfm_create.restype = C.c_void_p
-    L.eg3d_sfm_create.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.eg3d_sfm_set_camera.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, D.f32p, D.f32p, C.c_char_p]
-    L.eg3d_sfm_analytic_F.argtypes = [C.c_void_p, D.f64p, D.u8p]
-    L.eg3d_synth_camera.argtypes = [C.c_void_p, C.c_int, D.f32p, D.f32p, D.f32p, D.f32p, D.f32p]
+    L = host.lib()
     s = host.Synth(1)
     sc = s.scene_np()
     V = sc["n_views"]

@@ -132,29 +132,8 @@ def driver(tmp_path_factory):
     d.save()
 
 
-def _lib():
-    L = host.lib()
-    L.eg3d_host_json_double_text.argtypes = [C.c_double, C.c_char_p, C.c_int]
-    L.eg3d_host_json_number_text.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    L.eg3d_host_json_cached_power.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
-    L.eg3d_sfm_read_json.restype = C.c_void_p
-    L.eg3d_sfm_read_json.argtypes = [C.c_char_p]
-    L.eg3d_sfm_write_json.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-    L.eg3d_sfm_destroy.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_views.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_points.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_points.restype = C.c_uint64
-    L.eg3d_sfm_cam_P.argtypes = [C.c_void_p]
-    L.eg3d_sfm_cam_P.restype = D.f32p
-    L.eg3d_sfm_seeds.argtypes = [C.c_void_p, C.POINTER(D.Seeds)]
-    L.eg3d_sfm_points.argtypes = [C.c_void_p]
-    L.eg3d_sfm_points.restype = D.f32p
-    L.eg3d_sfm_add_point.argtypes = [C.c_void_p, D.f32p, C.c_int, D.i32p, D.f32p]
-    return L
-
-
 def test_cached_powers_of_grisu_equal_the_librarys(driver, tmp_path):
-    L = _lib()
+    L = host.lib()
     ref = [tuple(int(x) for x in ln.split()) for ln in driver.output("powers").decode().splitlines()]
     assert len(ref) == 87
     for i in range(87):
@@ -164,7 +143,7 @@ def test_cached_powers_of_grisu_equal_the_librarys(driver, tmp_path):
 
 
 def test_doubles_print_exactly_as_the_librarys_writer(driver, tmp_path):
-    L = _lib()
+    L = host.lib()
     rng = np.random.default_rng(1)
     n = 100000
     vals = np.concatenate([
@@ -188,7 +167,7 @@ def test_number_literals_are_reprinted_as_reader_plus_writer_do(driver, tmp_path
     """Numbers of `views` / `intrinsics` / `control_points` are copied from the input file: the reference parses them
     (its vendored reader defaults to full precision) and prints what it parsed. Literals whose magnitude underflows
     the double range are out of contract (the vendored library returns garbage for them)."""
-    L = _lib()
+    L = host.lib()
     rng = np.random.default_rng(2)
     lits = []
     for i in range(40000):
@@ -265,7 +244,7 @@ def _f32(x):
 
 
 def test_written_file_is_byte_identical_to_the_reference_writers_and_reader_indexes_like_the_parser(driver, tmp_path):
-    L = _lib()
+    L = host.lib()
     text, pose_of_view = _hand_written_openmvg()
     p_in = str(tmp_path / "in.json")
     open(p_in, "w").write(text)

@@ -1,9 +1,7 @@
 """CPU: the restatement of K11 (tests/louvain_ref.py, the definition of eg3d_detect_communities) on hand graphs and against
-checks that do not share its code; the library side that needs no device (symbols, struct mirrors, refusals, the communities
-file). The planted partitions use seeds 0-4 of louvain_ref.planted: all five recover the blocks exactly."""
+checks that do not share its code; the library side that needs no device (refusals, the communities file; symbols and
+struct mirrors: tests/test_abi.py). The planted partitions use seeds 0-4 of louvain_ref.planted: all five recover the blocks exactly."""
 import ctypes as C
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -11,7 +9,7 @@ import pytest
 
 import louvain_ref as L
 from edgegraph3d_amd import _cdefs as D
-from edgegraph3d_amd import api, build, host
+from edgegraph3d_amd import api, host
 
 _RUNS = {}   # per graph name: (graph, result), computed once and never modified
 
@@ -24,32 +22,6 @@ def _run(name, make):
 
 
 # ---- library checks ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("libname", ["HIP_LIB", "HIP_LIB_DLT4X4"])
-def test_abi_symbols_in_both_libraries(libname):
-    path = getattr(build, libname)
-    if not os.path.exists(path):
-        (build.build_hip if libname == "HIP_LIB" else build.build_hip_dlt4x4)()
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name in ("eg3d_detect_communities", "eg3d_free_communities"):
-        assert name in exported and name in api.EXPORTED_SYMBOLS, name
-
-
-def test_struct_mirrors_match_the_header(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pairs = [("eg3d_louvain_params", D.LouvainParams), ("eg3d_communities", D.Communities), ("eg3d_louvain_stats", D.LouvainStats)]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "eg3d.h"\nint main(void) {\n'
-                   + "".join('  printf(" %%zu", sizeof(%s));\n' % c for c, _ in pairs)
-                   + "".join('  printf(" %%zu", offsetof(%s, %s));\n' % (c, f[0]) for c, m in pairs for f in m._fields_)
-                   + "  return 0;\n}\n")
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", exe])
-    nums = [int(t) for t in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    want = [C.sizeof(m) for _, m in pairs] + [getattr(m, f[0]).offset for _, m in pairs for f in m._fields_]
-    assert nums == want
-
-
 def test_null_context_and_small_structs_are_refused():
     lib = api.lib()
     n, off, node, w = L.two_triangles()

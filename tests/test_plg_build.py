@@ -10,6 +10,7 @@ import zlib
 import numpy as np
 import pytest
 
+import cbuild
 from edgegraph3d_amd import host
 from oracle import binding as ob
 from png_util import read_png_edge_mask
@@ -202,22 +203,12 @@ def test_example_builds_the_container_from_edge_images(tmp_path):
     import ctypes as C
     import subprocess
     from edgegraph3d_amd import _cdefs as D
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pkg = os.path.join(root, "edgegraph3d_amd")
-    exe = str(tmp_path / "edge_matcher_refpoints")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "examples", "edge_matcher_refpoints.cpp"), "-L", pkg, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib", "-L", "/opt/rocm/lib", "-lamdhip64", "-o", exe])
+    exe = cbuild.build_caller("examples/edge_matcher_refpoints.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     files = sorted(glob.glob(os.path.join(EDGES, "*.png")))[:3]
     out = str(tmp_path / "plgs.bin")
     r = subprocess.run([exe, "--make-plgs", out] + files, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     L = host.lib()
-    L.eg3d_plg_read.restype = C.c_void_p
-    L.eg3d_plg_read.argtypes = [C.c_char_p]
-    L.eg3d_plg_scene.restype = C.POINTER(D.Scene)
-    L.eg3d_plg_scene.argtypes = [C.c_void_p]
-    L.eg3d_plg_destroy.argtypes = [C.c_void_p]
     g = L.eg3d_plg_read(out.encode())
     assert g
     sc = L.eg3d_plg_scene(g).contents
@@ -290,10 +281,6 @@ def test_all_views_at_once_equals_one_view_at_a_time(tmp_path):
     import ctypes as C
     from edgegraph3d_amd import _cdefs as D
     L = host.lib()
-    L.eg3d_plg_build_views_from_png.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                C.POINTER(D.PlgView)]
-    L.eg3d_plg_build_from_png.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(D.PlgView)]
-    L.eg3d_plg_view_free.argtypes = [C.POINTER(D.PlgView)]
     files = sorted(glob.glob(os.path.join(EDGES, "*.png")))[:9]
     arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
     views = (D.PlgView * len(files))()

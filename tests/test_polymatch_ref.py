@@ -147,16 +147,6 @@ def test_abi_small_struct_size_is_refused_before_anything_else():
     L.eg3d_free_polyline_matches(None)
 
 
-def test_abi_stats_mirror_has_the_size_of_the_c_struct(tmp_path):
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "eg3d.h"\nint main(void) { printf("%zu %zu\\n", '
-                   'sizeof(eg3d_polymatch_stats), sizeof(eg3d_polyline_matches)); return 0; }\n')
-    exe = tmp_path / "sz"
-    assert os.system("cc -I %s -o %s %s" % (build.INC_DIR, exe, src)) == 0
-    a, b = os.popen(str(exe)).read().split()
-    assert int(a) == C.sizeof(D.PolymatchStats) and int(b) == C.sizeof(D.PolylineMatches)
-
-
 def test_restatement_result_passes_check_polyline_sets():
     """The restatement's sets on the hand-built rule scene are a valid eg3d_polyline_sets (the device result must equal them:
     tests/test_gpu_polymatch.py)."""

@@ -9,17 +9,15 @@ import subprocess
 
 import pytest
 
+import cbuild
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GLM = "/root/reference/external/glm"
-PKG = os.path.join(ROOT, "edgegraph3d_amd")
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(GLM, "glm")), reason="the reference tree is not present (build container only)")
 def test_glm_adapters_compile_against_the_vendored_glm_and_round_trip(tmp_path):
-    exe = str(tmp_path / "glm_adapter_check")
-    subprocess.check_call(["g++", "-std=c++17", "-w", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", GLM,
-                           os.path.join(ROOT, "tests", "refapi", "glm_adapter_check.cpp"), "-L", PKG, "-leg3d", "-leg3d_host",
-                           "-Wl,-rpath," + PKG, "-L", "/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = cbuild.build_caller("tests/refapi/glm_adapter_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB, extra=("-w", "-I", GLM))
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and "GLM-ADAPTER-OK" in out.stdout, out.stdout + out.stderr
 

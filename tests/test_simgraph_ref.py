@@ -2,8 +2,6 @@
 are worked out here, the rank key of the node numbering, and the host side of the file seam (libeg3d_host.so) against the
 restatement."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +9,7 @@ import pytest
 import simgraph_cases as sc
 import simgraph_ref as ref
 from edgegraph3d_amd import _cdefs as D
-from edgegraph3d_amd import api, build, host
+from edgegraph3d_amd import api, host
 
 F32 = np.float32
 ONE, W23, W37 = F32(1), F32(2) / F32(3), F32(3) / F32(7)   # an int divided by a float, as compute_refpoint_weight
@@ -163,34 +161,6 @@ def test_communities_to_sets(tmp_path):
         host.read_communities(path)
     with pytest.raises(RuntimeError):
         host.read_communities(str(tmp_path / "missing.txt"))
-
-
-@pytest.mark.parametrize("libname", ["HIP_LIB", "HIP_LIB_DLT4X4"])
-def test_abi_symbols_in_both_libraries(libname):
-    path = getattr(build, libname)
-    if not os.path.exists(path):
-        (build.build_hip if libname == "HIP_LIB" else build.build_hip_dlt4x4)()
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    for name in ("eg3d_similarity_graph", "eg3d_free_simgraph"):
-        assert name in exported and name in api.EXPORTED_SYMBOLS, name
-
-
-def test_struct_mirrors_match_the_header(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "eg3d.h"\nint main(void) {\n'
-                   '  printf("%zu %zu", sizeof(eg3d_simgraph), sizeof(eg3d_simgraph_stats));\n'
-                   + "".join('  printf(" %%zu", offsetof(eg3d_simgraph, %s));\n' % f[0] for f in D.Simgraph._fields_)
-                   + "".join('  printf(" %%zu", offsetof(eg3d_simgraph_stats, %s));\n' % f[0] for f in D.SimgraphStats._fields_)
-                   + "  return 0;\n}\n")
-    exe = str(tmp_path / "sz")
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", exe])
-    nums = [int(t) for t in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
-    want = [C.sizeof(D.Simgraph), C.sizeof(D.SimgraphStats)]
-    want += [getattr(D.Simgraph, f[0]).offset for f in D.Simgraph._fields_]
-    want += [getattr(D.SimgraphStats, f[0]).offset for f in D.SimgraphStats._fields_]
-    assert nums == want
 
 
 def test_abi_small_struct_size_is_refused_before_anything_else():

@@ -17,6 +17,7 @@ sys.path.insert(0, ROOT)
 import torch  # device storage for the batch clouds of the concat leg; initialised BEFORE libeg3d.so loads its HIP runtime
 torch.cuda.init()
 from edgegraph3d_amd import _cdefs as D, api, host  # noqa: E402
+from edgegraph3d_amd.distributed import gather_lib  # noqa: E402
 
 n_seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
@@ -80,11 +81,7 @@ A.close()
 B.close()
 torch.cuda.synchronize()
 # ---- eg3d_concat_edgepoints of the batch clouds == the one-call cloud (checked through the per-batch digests)
-G = C.CDLL(os.path.join(ROOT, "edgegraph3d_amd", "libeg3d_rccl.so"))
-G.eg3d_gather_create.restype = C.c_void_p
-G.eg3d_gather_create.argtypes = [C.c_int]
-G.eg3d_gather_destroy.argtypes = [C.c_void_p]
-G.eg3d_concat_edgepoints.argtypes = [C.c_void_p, C.c_int, C.POINTER(D.DeviceEdgePoints), C.c_void_p, C.POINTER(D.DeviceEdgePoints)]
+G = gather_lib()
 g = G.eg3d_gather_create(0)
 parts = (D.DeviceEdgePoints * len(keep))()
 for i, (t, nb, no) in enumerate(keep):

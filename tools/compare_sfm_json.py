@@ -31,14 +31,6 @@ from edgegraph3d_amd import _cdefs as D, host  # noqa: E402
 def read_cloud(path):
     """(X [N,3] float32, trk_off [N+1], trk_view, trk_xy [M,2]) of an OpenMVG JSON through the library's own reader."""
     L = host.lib()
-    L.eg3d_sfm_read_json.restype = C.c_void_p
-    L.eg3d_sfm_read_json.argtypes = [C.c_char_p]
-    L.eg3d_sfm_destroy.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_points.argtypes = [C.c_void_p]
-    L.eg3d_sfm_n_points.restype = C.c_uint64
-    L.eg3d_sfm_seeds.argtypes = [C.c_void_p, C.POINTER(D.Seeds)]
-    L.eg3d_sfm_points.argtypes = [C.c_void_p]
-    L.eg3d_sfm_points.restype = D.f32p
     h = L.eg3d_sfm_read_json(path.encode())
     if not h:
         raise SystemExit("cannot read %s as OpenMVG sfm_data JSON" % path)
