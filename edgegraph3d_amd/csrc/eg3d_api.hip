@@ -56,18 +56,19 @@ void dev_free(void* p, size_t bytes) {
 int DevBuf::ensure_keep(size_t bytes, size_t keep, hipStream_t st) {
   if (bytes <= cap && p) return EG3D_OK;
   if (!p || !keep) return ensure(bytes);
-  DevBuf q;
-  q.cap = bytes + bytes / 2;
-  BUF_TRY(dev_alloc(&q.p, q.cap));
-  hipError_t e = hipMemcpyAsync(q.p, p, keep, hipMemcpyDeviceToDevice, st);
+  void* q = nullptr;
+  const size_t q_cap = bytes + bytes / 2;
+  BUF_TRY(dev_alloc(&q, q_cap));
+  hipError_t e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
-    q.release();
+    dev_free(q, q_cap);
     g_err = std::string("growing a device buffer: ") + hipGetErrorString(e);
     return EG3D_ERR_HIP;
   }
   release();
-  *this = q;
+  p = q;
+  cap = q_cap;
   return EG3D_OK;
 }
 EG3D_API_END
@@ -155,22 +156,23 @@ int scan_total_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus
 }
 EG3D_API_END
 
-// K0: one uniform grid of the scene on the device (the scene's polylines are already resident: c->ds): count the (cell,
+// K0: one uniform grid of the scene `sc` on the device (its polylines are already resident: sc.ds), queued on c's stream
+// with c's scratch — in eg3d_create `sc` is the scene being made, which the context does not share yet: count the (cell,
 // polyline) pairs of every polyline, exclusive scan, write them as 64-bit keys, radix sort, unique, CSR. The temporaries (24 B
 // per pair) belong to the caller, which frees them once the stream has drained.
 struct GridTemps {
-  WorkBuf cnt, off, keys, keys2, n;  // n: [0] unique keys, [1] samples outside the image (summed over the builds)
+  DevBuf cnt, off, keys, keys2, n;  // n: [0] unique keys, [1] samples outside the image (summed over the builds)
 };
-template <typename Buf>  // (the 30 px and 4 px grids are scene handles, the 10 px map belongs to HostGrids)
-static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t, Buf& g_off, Buf& g_ids, uint32_t* out_w,
-                             uint32_t* out_h, uint32_t* dropped) {
+static int build_grid_device(eg3d_ctx* c, const SceneFacts& sc, float cell, GridTemps& t, DevBuf& g_off, DevBuf& g_ids,
+                             uint32_t* out_w, uint32_t* out_h, uint32_t* dropped) {
   hipStream_t st = c->stream;
-  const int V = c->V;
+  const int V = sc.V;
+  const uint32_t NP = sc.n_pl;
   if (!t.n.p) {
     BUF_TRY(t.n.ensure(2 * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(t.n.p, 0, 2 * sizeof(uint32_t), st));
   }
-  const int map_w = (int)std::ceil(c->W / cell), map_h = (int)std::ceil(c->H / cell);  // (as host/grid_build.cpp: float division)
+  const int map_w = (int)std::ceil(sc.W / cell), map_h = (int)std::ceil(sc.H / cell);  // (as host/grid_build.cpp: float division)
   *out_w = (uint32_t)map_w;
   *out_h = (uint32_t)map_h;
   const unsigned long long total_cells = (unsigned long long)V * (unsigned long long)map_w * (unsigned long long)map_h;
@@ -181,7 +183,7 @@ static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t,
   BUF_TRY(t.cnt.ensure(sizeof(uint32_t) * ((size_t)NP + 1)));
   BUF_TRY(t.off.ensure(sizeof(uint32_t) * ((size_t)NP + 1)));
   HIP_TRY(hipMemsetAsync(t.cnt.as<uint32_t>() + NP, 0, sizeof(uint32_t), st));
-  launch_k0_pairs(st, false, c->ds, NP, cell, map_w, map_h, t.cnt.as<uint32_t>(), nullptr, nullptr, t.n.as<uint32_t>() + 1);
+  launch_k0_pairs(st, false, sc.ds, NP, cell, map_w, map_h, t.cnt.as<uint32_t>(), nullptr, nullptr, t.n.as<uint32_t>() + 1);
   uint32_t n_pairs = 0;
   BUF_TRY(scan_total_u32(c, t.cnt.as<uint32_t>(), t.off.as<uint32_t>(), (size_t)NP + 1, n_pairs, "(cell, polyline) entries of the grids"));
   BUF_TRY(g_off.ensure(sizeof(uint32_t) * ((size_t)total_cells + 1)));
@@ -190,7 +192,7 @@ static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t,
     if (n_pairs) {
       BUF_TRY(t.keys.ensure(sizeof(unsigned long long) * (size_t)n_pairs));
       BUF_TRY(t.keys2.ensure(sizeof(unsigned long long) * (size_t)n_pairs));
-      launch_k0_pairs(st, true, c->ds, NP, cell, map_w, map_h, nullptr, t.off.as<uint32_t>(), t.keys.as<unsigned long long>(), nullptr);
+      launch_k0_pairs(st, true, sc.ds, NP, cell, map_w, map_h, nullptr, t.off.as<uint32_t>(), t.keys.as<unsigned long long>(), nullptr);
       int end_bit = EG3D_K0_PL_BITS_HOST;
       while (end_bit < 64 && (total_cells >> (end_bit - EG3D_K0_PL_BITS_HOST)) != 0) end_bit++;
       size_t tmp = 0;
@@ -219,52 +221,42 @@ static int build_grid_device(eg3d_ctx* c, uint32_t NP, float cell, GridTemps& t,
   }
   return EG3D_OK;
 }
-// The 30 px and 4 px grids of eg3d_create.
-static int build_grids_device(eg3d_ctx* c, uint32_t NP) {
+// eg3d_create: the 30 px and 4 px grids on the device.
+static int build_grids_device(eg3d_ctx* c, Scene& s) {
   GridTemps t;
-  for (int which = 0; which < 2; which++) {
-    DevBuf& g_off = which == 0 ? c->b_g30o : c->b_g4o;
-    DevBuf& g_ids = which == 0 ? c->b_g30i : c->b_g4i;
-    BUF_TRY(build_grid_device(c, NP, which == 0 ? 30.0f : 4.0f, t, g_off, g_ids, &c->gw[which], &c->gh[which], &c->grid_dropped));
-    c->hg->d_off[which] = g_off.as<uint32_t>();
-    c->hg->d_ids[which] = g_ids.as<uint32_t>();
-    c->hg->cells_per_view[which] = c->gw[which] * c->gh[which];
-  }
+  for (int which = 0; which < 2; which++)
+    BUF_TRY(build_grid_device(c, s, which == 0 ? 30.0f : 4.0f, t, s.g_off[which], s.g_ids[which], &s.gw[which], &s.gh[which],
+                              &s.grid_dropped));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the temporaries go away
   return EG3D_OK;
 }
 int eg3d::api::ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms) {
-  HostGrids& hg = *c->hg;
-  std::lock_guard<std::mutex> lk(hg.mu);
-  if (!hg.built10) {
+  Scene& s = *c->scene;
+  std::lock_guard<std::mutex> lk(s.mu);
+  if (!s.built10) {
     const auto t0 = std::chrono::steady_clock::now();
     // (the build runs on the calling context's stream and scratch; `mu` only keeps a second context of the family from
     // building the same map at the same time)
     GridTemps t;
-    WorkBuf& g_off = hg.g10o;
-    WorkBuf& g_ids = hg.g10i;
     uint32_t dropped = 0;
-    int rc = build_grid_device(c, c->n_pl, 10.0f, t, g_off, g_ids, &hg.w10, &hg.h10, &dropped);
+    int rc = build_grid_device(c, s, 10.0f, t, s.g_off[2], s.g_ids[2], &s.w10, &s.h10, &dropped);
     if (rc == EG3D_OK && hipStreamSynchronize(c->stream) != hipSuccess) {
       g_err = "eg3d_match_polylines_closeness: building the 10 px map failed";
       rc = EG3D_ERR_HIP;
     }
     if (rc != EG3D_OK) {
       (void)hipStreamSynchronize(c->stream);
-      g_off.release();
-      g_ids.release();
+      s.g_off[2].release();
+      s.g_ids[2].release();
       return rc;
     }
-    hg.d_off[2] = g_off.as<uint32_t>();
-    hg.d_ids[2] = g_ids.as<uint32_t>();
-    hg.cells_per_view[2] = hg.w10 * hg.h10;
-    hg.built10 = true;
+    s.built10 = true;
     if (ms) *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
-  out->w = (int32_t)hg.w10;
-  out->h = (int32_t)hg.h10;
-  out->off = hg.d_off[2];
-  out->ids = hg.d_ids[2];
+  out->w = (int32_t)s.w10;
+  out->h = (int32_t)s.h10;
+  out->off = s.d_off(2);
+  out->ids = s.d_ids(2);
   return EG3D_OK;
 }
 
@@ -284,11 +276,6 @@ extern "C" int eg3d_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
-}
-
-static std::vector<DevBuf*> scene_bufs(eg3d_ctx* c) {
-  return {&c->b_bbo,  &c->b_bb,  &c->b_camP, &c->b_F,   &c->b_Fv,   &c->b_vpo,  &c->b_pvo, &c->b_vtx,
-          &c->b_pls,  &c->b_ple, &c->b_g30o, &c->b_g30i, &c->b_g4o, &c->b_g4i};
 }
 
 // Everything about a scene that can be checked on the host, before a device is touched: the library indexes
@@ -346,6 +333,290 @@ static int validate_scene(const eg3d_scene* sc) {
   return EG3D_OK;
 }
 
+// ---- eg3d_create, step by step (the list is at the end) ---------------------------------------------------------------------
+int eg3d::api::make_own_resources(eg3d_ctx* c, StreamPrio prio) {
+  if (prio == StreamPrio::plain) {
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  } else {
+    int least = 0, greatest = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const int priority = prio == StreamPrio::greatest ? greatest : prio == StreamPrio::middle ? (least + greatest) / 2 : least;
+    HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, priority));
+  }
+  for (int i = 0; i < 8; i++) {
+    HIP_TRY(hipEventCreate(&c->ea[i]));
+    HIP_TRY(hipEventCreate(&c->eb[i]));
+  }
+  for (int i = 0; i < 7; i++) HIP_TRY(hipEventCreateWithFlags(&c->ecopy[i], hipEventDisableTiming));
+  return EG3D_OK;
+}
+
+// An invalid polyline (pl_valid == 0) is one the reference has invalidated: it keeps its id but its
+// coordinates are cleared (polyline_graph_2d.cpp:1047-1058, Q8). The ABI tolerates a caller that
+// leaves vertices on such a polyline; the device must not see them (the polyline-sets path takes
+// raw polyline ids), so they are dropped here: compacted vertex array, zero-length slices.
+namespace {
+struct SceneVertices {
+  std::vector<uint32_t> pvo_c;
+  std::vector<float> vtx_c;
+  const uint32_t* pvo = nullptr;  // the caller's arrays, or the compacted ones above
+  const float* vtx = nullptr;
+};
+}  // namespace
+static void drop_invalid_vertices(const eg3d_scene* sc, uint32_t NP, SceneVertices& a) {
+  a.pvo = sc->pl_vtx_off;
+  a.vtx = sc->vtx_xy;
+  bool stray = false;
+  for (uint32_t p = 0; p < NP && !stray; p++) stray = !sc->pl_valid[p] && sc->pl_vtx_off[p + 1] > sc->pl_vtx_off[p];
+  if (!stray) return;
+  a.pvo_c.assign(1, 0);
+  for (uint32_t p = 0; p < NP; p++) {
+    if (sc->pl_valid[p])
+      a.vtx_c.insert(a.vtx_c.end(), sc->vtx_xy + 2 * (size_t)sc->pl_vtx_off[p], sc->vtx_xy + 2 * (size_t)sc->pl_vtx_off[p + 1]);
+    a.pvo_c.push_back((uint32_t)(a.vtx_c.size() / 2));
+  }
+  if (a.vtx_c.empty()) a.vtx_c.assign(2, 0.f);
+  a.pvo = a.pvo_c.data();
+  a.vtx = a.vtx_c.data();
+}
+
+static int upload_scene_arrays(eg3d_ctx* c, Scene& s, const eg3d_scene* sc, const SceneVertices& a) {
+  const size_t V = (size_t)s.V;
+  // (A plain shorthand now: it destroys nothing, the caller's guard does. It keeps its name and first line because
+  // build.device_source_fingerprint() hashes the preprocessor lines of this file, and the committed PMC profile
+  // (profiles/pmc_traffic.json) is valid for exactly that hash; whoever regenerates the profile can write the calls out.)
+#define UP(buf, ptr, n)                                        \
+  BUF_TRY(upload(s.buf, ptr, (size_t)(n), c->stream))
+  UP(camP, sc->cam_P, V * 16);
+  UP(F, sc->F, V * V * 9);
+  UP(Fv, sc->F_valid, V * V);
+  UP(vpo, sc->view_pl_off, V + 1);
+  UP(pvo, a.pvo, (size_t)s.n_pl + 1);
+  UP(vtx, a.vtx, (size_t)s.n_vtx * 2);
+  UP(pls, sc->pl_start, s.n_pl);
+  UP(ple, sc->pl_end, s.n_pl);
+#undef UP
+  DevScene& d = s.ds;
+  d.n_views = s.V;
+  d.width = s.W;
+  d.height = s.H;
+  d.cam_P = s.camP.as<float>();
+  d.F = s.F.as<double>();
+  d.F_valid = s.Fv.as<uint8_t>();
+  d.view_pl_off = s.vpo.as<uint32_t>();
+  d.pl_vtx_off = s.pvo.as<uint32_t>();
+  d.vtx = s.vtx.as<f2>();
+  d.pl_start = s.pls.as<uint32_t>();
+  d.pl_end = s.ple.as<uint32_t>();
+  return EG3D_OK;
+}
+
+// bounding boxes of blocks of EG3D_BB_SEGS segments (the pre-test of the expand stage's closest-point scans)
+static int upload_block_boxes(eg3d_ctx* c, Scene& s, const SceneVertices& a) {
+  const uint32_t NP = s.n_pl;
+  std::vector<uint32_t> bbo(NP + 1, 0);
+  std::vector<float> bb;
+  for (uint32_t p = 0; p < NP; p++) {
+    const uint32_t v0 = a.pvo[p], v1 = a.pvo[p + 1];
+    const uint32_t nseg = v1 > v0 + 1 ? v1 - v0 - 1 : 0;
+    for (uint32_t s0 = 0; s0 < nseg; s0 += EG3D_BB_SEGS) {
+      const uint32_t s1 = std::min(nseg, s0 + (uint32_t)EG3D_BB_SEGS);
+      float x0 = a.vtx[2 * (size_t)(v0 + s0)], y0 = a.vtx[2 * (size_t)(v0 + s0) + 1], x1 = x0, y1 = y0;
+      for (uint32_t i = s0 + 1; i <= s1; i++) {
+        const float x = a.vtx[2 * (size_t)(v0 + i)], y = a.vtx[2 * (size_t)(v0 + i) + 1];
+        x0 = std::min(x0, x);
+        y0 = std::min(y0, y);
+        x1 = std::max(x1, x);
+        y1 = std::max(y1, y);
+      }
+      bb.insert(bb.end(), {x0, y0, x1, y1});
+    }
+    bbo[p + 1] = (uint32_t)(bb.size() / 4);
+  }
+  if (bb.empty()) bb.assign(4, 0.f);
+  BUF_TRY(upload(s.bbo, bbo.data(), bbo.size(), c->stream));
+  BUF_TRY(upload(s.bb, bb.data(), bb.size(), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // `bbo` / `bb` go out of scope
+  s.ds.pl_bb_off = s.bbo.as<uint32_t>();
+  s.ds.pl_bb = s.bb.as<float>();
+  return EG3D_OK;
+}
+
+// Runs `work` on up to `n` threads, the caller included (at most EG3D_COPY_THREADS and what the machine has; when no more
+// threads can be started, those that did start and the calling thread do what is left).
+template <typename Work>
+static void run_on_threads(unsigned n, Work work) {
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  const int nthr = (int)std::min<unsigned>(std::min<unsigned>(hw, EG3D_COPY_THREADS), n);
+  std::vector<std::thread> th;
+  try {
+    for (int t = 1; t < nthr; t++) th.emplace_back(work);
+  } catch (...) {
+  }
+  work();
+  for (auto& t : th) t.join();
+}
+
+// EG3D_GRID_ON_HOST=1 (diagnostic): the host builder instead of K0 — the 2 x V builds are independent
+// (polyLine_2d_map.cpp:40-58 constructs one map per view), so they run on a few host threads; serially, as until round 5,
+// this was 2x the whole hot path of a dtu006-sized job (90 ms for C3', 0.87 s for C4). The per-view arrays are kept for
+// eg3d_get_grid; the device CSR over (view, cell) is assembled on the same threads.
+static int build_grids_host(eg3d_ctx* c, Scene& s, const eg3d_scene* sc) {
+  const int V = s.V;
+  struct GridJob {
+    uint32_t w = 0, h = 0, dropped = 0, *o = nullptr, *i = nullptr;
+    int rc = 0;
+  };
+  std::vector<GridJob> jobs((size_t)2 * V);
+  struct FreeJobs {
+    std::vector<GridJob>& j;
+    ~FreeJobs() {
+      for (auto& g : j) {
+        free(g.o);
+        free(g.i);
+      }
+    }
+  } free_jobs{jobs};
+  std::atomic<int> next{0};
+  run_on_threads((unsigned)(2 * V), [&]() {
+    for (int j; (j = next.fetch_add(1)) < 2 * V;) {
+      GridJob& g = jobs[(size_t)j];
+      // (the 4 px grids first: they are the long jobs)
+      g.rc = eg3d_host_build_grid(sc, j % V, j < V ? 4.0f : 30.0f, &g.w, &g.h, &g.o, &g.i, &g.dropped);
+    }
+  });
+  for (auto& g : jobs)
+    if (g.rc != 0) {
+      g_err = "eg3d_create: grid construction failed";
+      return EG3D_ERR_ARG;
+    }
+  for (int which = 0; which < 2; which++) {
+    const auto job_of = [&](int v) -> const GridJob& { return jobs[(size_t)(which == 0 ? V + v : v)]; };
+    s.h_off[which].resize((size_t)V);
+    s.h_ids[which].resize((size_t)V);
+    std::vector<size_t> id_base((size_t)V + 1, 0), off_base((size_t)V + 1, 0);
+    for (int v = 0; v < V; v++) {
+      const GridJob& g = job_of(v);
+      s.h_off[which][(size_t)v].assign(g.o, g.o + (size_t)g.w * g.h + 1);
+      s.h_ids[which][(size_t)v].assign(g.i, g.i + g.o[(size_t)g.w * g.h]);
+      s.gw[which] = g.w;
+      s.gh[which] = g.h;
+      s.grid_dropped += g.dropped;
+      id_base[(size_t)v + 1] = id_base[(size_t)v] + g.o[(size_t)g.w * g.h];
+      off_base[(size_t)v + 1] = off_base[(size_t)v] + (size_t)g.w * g.h;
+    }
+    s.have[which] = true;
+    if (id_base[(size_t)V] > 0xffffffffull) {
+      g_err = "eg3d_create: the grids of this scene hold more than 2^32-1 (cell, polyline) entries";
+      return EG3D_ERR_CAPACITY;
+    }
+    std::vector<uint32_t> off(off_base[(size_t)V] + 1), ids(std::max<size_t>(id_base[(size_t)V], 1));
+    off[0] = 0;
+    std::atomic<int> nextv{0};
+    run_on_threads((unsigned)V, [&]() {
+      for (int v; (v = nextv.fetch_add(1)) < V;) {
+        const GridJob& g = job_of(v);
+        const size_t nc = (size_t)g.w * g.h;
+        const uint32_t base = (uint32_t)id_base[(size_t)v];
+        uint32_t* dst = off.data() + off_base[(size_t)v] + 1;
+        for (size_t cc = 0; cc < nc; cc++) dst[cc] = base + g.o[cc + 1];
+        if (g.o[nc]) memcpy(ids.data() + id_base[(size_t)v], g.i, sizeof(uint32_t) * g.o[nc]);
+      }
+    });
+    BUF_TRY(upload(s.g_off[which], off.data(), off.size(), c->stream));
+    BUF_TRY(upload(s.g_ids[which], ids.data(), ids.size(), c->stream));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) {  // `off`/`ids` go out of scope
+      g_err = "eg3d_create: uploading the grids failed";
+      return EG3D_ERR_HIP;
+    }
+  }
+  return EG3D_OK;
+}
+
+// grids (row a3), one CSR over (view, cell) per cell size: built on the DEVICE (K0) from the polylines just uploaded
+static int build_grids(eg3d_ctx* c, Scene& s, const eg3d_scene* sc) {
+  BUF_TRY(c->tune.grid_on_host ? build_grids_host(c, s, sc) : build_grids_device(c, s));
+  DevScene& d = s.ds;
+  d.g30_w = (int)s.gw[0];
+  d.g30_h = (int)s.gh[0];
+  d.g4_w = (int)s.gw[1];
+  d.g4_h = (int)s.gh[1];
+  d.g30_off = s.d_off(0);
+  d.g30_ids = s.d_ids(0);
+  d.g4_off = s.d_off(1);
+  d.g4_ids = s.d_ids(1);
+  return EG3D_OK;
+}
+
+// every camera entry that is not zero lies in 2^-100 .. 2^100 (NaN fails)
+static void flag_cams_mid_range(Scene& s, const eg3d_scene* sc) {
+  bool mid = true;
+  for (size_t v = 0; v < (size_t)s.V && mid; v++)
+    for (int k = 0; k < 12 && mid; k++) {
+      const float p = sc->cam_P[v * 16 + k];
+      if (p != 0.0f) {
+        const float a = p < 0 ? -p : p;
+        mid = a >= 7.888609052210118e-31f && a <= 1.2676506002282294e+30f;
+      }
+    }
+  s.ds.cams_mid_range = mid ? 1 : 0;
+}
+
+// What the expand stage starts from: the scene's longest polyline, the context's first capacities, and the slot pools
+// sized from the occupancy query.
+static int size_pools_and_slots(eg3d_ctx* c, Scene& s, const eg3d_scene* sc) {
+  // the longest valid polyline of the scene (a scene whose polylines all fit the side walks' LDS staging area, and
+  // that has few views, runs the smaller build of the expand kernel: launch_k3b)
+  for (uint32_t p = 0; p < s.n_pl; p++)
+    if (sc->pl_valid[p]) s.max_pl_vtx = std::max(s.max_pl_vtx, sc->pl_vtx_off[p + 1] - sc->pl_vtx_off[p]);
+  // observation slots per chain (blocks double when they fill, so budget ~3x the live count);
+  // grown automatically when a chain overflows
+  // (many-view scenes: points carry ~V/3 observations and blocks are relocated as they double — C4 settles at 196 608; starting
+  // at 24 576 as until round 6 cost the first call three extra rounds of the expand stage)
+  Learned& L = c->learned;
+  L.pool_cap = std::min<uint32_t>(131072, 768u * (uint32_t)std::min(s.V, 128));
+  if (L.pool_cap < 6144) L.pool_cap = 6144;
+  if (c->tune.pool_cap0) L.pool_cap = c->tune.pool_cap0;
+  if (c->tune.chain_cap0) L.chain_cap = c->tune.chain_cap0;
+  const int device = s.device;
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  s.n_simd = (uint32_t)prop.multiProcessorCount * 4;
+  if (hipDeviceGetAttribute(&s.wall_clock_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess) s.wall_clock_khz = 0;
+  // working-slice slots per XCD: what can be resident (occupancy query x CUs of an XCD) plus a margin —
+  // the occupancy API may be one block per CU off, and a pool must never be smaller than the residency
+  const int per_cu = k3b_blocks_per_cu();
+  if (per_cu < 1) {
+    g_err = "eg3d_create: occupancy query of the expand kernel failed";
+    return EG3D_ERR_HIP;
+  }
+  // XCDs of THIS device: 8 on the whole MI355X (32 CUs each), fewer when the GPU is partitioned (CPX: one XCD of 32
+  // CUs appears as a device, DPX / QPX: four / two) — all its blocks then draw from the pools of those XCDs only, so a
+  // pool is sized for CUs / XCDs compute units, not for an eighth of whatever the device reports
+  const uint32_t cus = (uint32_t)prop.multiProcessorCount;
+  const uint32_t n_xcd = std::min(8u, std::max(1u, cus / 32u));
+  // (at least 40: an XCD of 38 CUs on a part with fewer than 8 XCDs would be undersized by the estimate cus / 32 — the
+  // pools cost a few tens of MB more on gfx950, where an XCD has 32)
+  const uint32_t cus_per_xcd = std::max<uint32_t>((cus + n_xcd - 1u) / n_xcd, 40u);
+  s.slots_per_xcd = ((uint32_t)per_cu + 1u) * cus_per_xcd + 16u;
+  if (c->tune.slots_per_xcd) s.slots_per_xcd = c->tune.slots_per_xcd;  // tests / experiments
+  // (the lane-per-chain engine is an opt-in second form: only a context that asks for it depends on its kernel)
+  if (c->tune.k3b_engine != 0) {
+#ifdef EG3D_WITH_K3C_ENGINE
+    s.k3c_per_cu = k3c_blocks_per_cu();
+    if (s.k3c_per_cu < 1) {
+      g_err = "eg3d_create: occupancy query of the expand engine failed";
+      return EG3D_ERR_HIP;
+    }
+#else
+    g_err = "eg3d_create: EG3D_K3B_ENGINE=1, but this library was built without the lane-per-chain engine "
+            "(-DEG3D_WITH_K3C_ENGINE: edgegraph3d_amd/variants/libeg3d_engine.so)";
+    return EG3D_ERR_ARG;
+#endif
+  }
+  return EG3D_OK;
+}
+
 extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
   if (!sc || !out) {
     g_err = "eg3d_create: bad arguments";
@@ -362,375 +633,54 @@ extern "C" int eg3d_create(const eg3d_scene* sc, int device, eg3d_ctx** out) {
     return EG3D_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(device));
-  eg3d_ctx* c = new eg3d_ctx();
-  c->device = device;
+  // (declared in this order: a failing exit first drains and destroys the context, then lets the scene's arrays go)
+  auto scene = std::make_shared<Scene>();
+  CtxGuard guard(new eg3d_ctx(), eg3d_destroy);
+  eg3d_ctx* c = guard.get();
+  Scene& s = *scene;
+  s.device = c->device = device;  // (the context's own copy: eg3d_destroy works on a context that shares no scene yet)
+  s.V = sc->n_views;
+  s.W = sc->width;
+  s.H = sc->height;
+  c->seeds = std::make_shared<Seeds>(device);
   c->tune = Tunables::from_env();
-  if (const char* e = getenv("EG3D_COMPACT_NT")) c->compact_nt = e[0] == '1';
-  if (const char* e = getenv("EG3D_REPLAY_TABLE_BITS")) c->replay_table_bits = std::min(40, std::max(0, atoi(e)));
-  if (const char* e = getenv("EG3D_SIMGRAPH_PAIR_BUDGET")) c->simgraph_pair_budget = std::min(1ull << 31, strtoull(e, nullptr, 10));
-  if (const char* e = getenv("EG3D_LOUVAIN_TABLE_SLOTS")) {
-    const unsigned long long want = std::min<unsigned long long>(K11_MAX_SLOTS, std::max<unsigned long long>(K11_MIN_SLOTS, strtoull(e, nullptr, 10)));
-    while ((1ull << c->louvain_log2_slots) < want) c->louvain_log2_slots++;
-  }
-  if (c->tune.hyp_cap) c->hyp_cap = c->tune.hyp_cap;
-  c->hg = std::make_shared<HostGrids>();
-  if (c->tune.lane_priorities) {
-    int least = 0, greatest = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest));
-  } else
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  for (int i = 0; i < 8; i++) {
-    HIP_TRY(hipEventCreate(&c->ea[i]));
-    HIP_TRY(hipEventCreate(&c->eb[i]));
-  }
-  for (int i = 0; i < 7; i++) HIP_TRY(hipEventCreateWithFlags(&c->ecopy[i], hipEventDisableTiming));
-  const int V = sc->n_views;
-  c->V = V;
-  c->W = sc->width;
-  c->H = sc->height;
-  const uint32_t NP = sc->view_pl_off[V];
-  // An invalid polyline (pl_valid == 0) is one the reference has invalidated: it keeps its id but its
-  // coordinates are cleared (polyline_graph_2d.cpp:1047-1058, Q8). The ABI tolerates a caller that
-  // leaves vertices on such a polyline; the device must not see them (the polyline-sets path takes
-  // raw polyline ids), so they are dropped here: compacted vertex array, zero-length slices.
-  std::vector<uint32_t> pvo_c;
-  std::vector<float> vtx_c;
-  const uint32_t* pvo_up = sc->pl_vtx_off;
-  const float* vtx_up = sc->vtx_xy;
-  {
-    bool stray = false;
-    for (uint32_t p = 0; p < NP && !stray; p++) stray = !sc->pl_valid[p] && sc->pl_vtx_off[p + 1] > sc->pl_vtx_off[p];
-    if (stray) {
-      pvo_c.assign(1, 0);
-      for (uint32_t p = 0; p < NP; p++) {
-        if (sc->pl_valid[p])
-          vtx_c.insert(vtx_c.end(), sc->vtx_xy + 2 * (size_t)sc->pl_vtx_off[p], sc->vtx_xy + 2 * (size_t)sc->pl_vtx_off[p + 1]);
-        pvo_c.push_back((uint32_t)(vtx_c.size() / 2));
-      }
-      if (vtx_c.empty()) vtx_c.assign(2, 0.f);
-      pvo_up = pvo_c.data();
-      vtx_up = vtx_c.data();
-    }
-  }
-  const uint32_t NV = pvo_up[NP];
-  c->n_pl = NP;
-  c->n_vtx = NV;
-  int rc;
-#define UP(buf, ptr, n)                                        \
-  if ((rc = upload(c->buf, ptr, (size_t)(n), c->stream)) != EG3D_OK) { \
-    eg3d_destroy(c);                                           \
-    return rc;                                                 \
-  }
-  UP(b_camP, sc->cam_P, (size_t)V * 16);
-  UP(b_F, sc->F, (size_t)V * V * 9);
-  UP(b_Fv, sc->F_valid, (size_t)V * V);
-  UP(b_vpo, sc->view_pl_off, V + 1);
-  UP(b_pvo, pvo_up, NP + 1);
-  UP(b_vtx, vtx_up, (size_t)NV * 2);
-  UP(b_pls, sc->pl_start, NP);
-  UP(b_ple, sc->pl_end, NP);
-  {
-    // bounding boxes of blocks of EG3D_BB_SEGS segments (the pre-test of the expand stage's closest-point scans)
-    std::vector<uint32_t> bbo(NP + 1, 0);
-    std::vector<float> bb;
-    for (uint32_t p = 0; p < NP; p++) {
-      const uint32_t a = pvo_up[p], b = pvo_up[p + 1];
-      const uint32_t nseg = b > a + 1 ? b - a - 1 : 0;
-      for (uint32_t s0 = 0; s0 < nseg; s0 += EG3D_BB_SEGS) {
-        const uint32_t s1 = std::min(nseg, s0 + (uint32_t)EG3D_BB_SEGS);
-        float x0 = vtx_up[2 * (size_t)(a + s0)], y0 = vtx_up[2 * (size_t)(a + s0) + 1], x1 = x0, y1 = y0;
-        for (uint32_t i = s0 + 1; i <= s1; i++) {
-          const float x = vtx_up[2 * (size_t)(a + i)], y = vtx_up[2 * (size_t)(a + i) + 1];
-          x0 = std::min(x0, x);
-          y0 = std::min(y0, y);
-          x1 = std::max(x1, x);
-          y1 = std::max(y1, y);
-        }
-        bb.insert(bb.end(), {x0, y0, x1, y1});
-      }
-      bbo[p + 1] = (uint32_t)(bb.size() / 4);
-    }
-    if (bb.empty()) bb.assign(4, 0.f);
-    UP(b_bbo, bbo.data(), bbo.size());
-    UP(b_bb, bb.data(), bb.size());
-    HIP_TRY(hipStreamSynchronize(c->stream));  // `bbo` / `bb` go out of scope
-  }
-#undef UP
-  DevScene& d = c->ds;
-  d.n_views = V;
-  d.width = sc->width;
-  d.height = sc->height;
-  d.cam_P = c->b_camP.as<float>();
-  d.F = c->b_F.as<double>();
-  d.F_valid = c->b_Fv.as<uint8_t>();
-  d.view_pl_off = c->b_vpo.as<uint32_t>();
-  d.pl_vtx_off = c->b_pvo.as<uint32_t>();
-  d.vtx = c->b_vtx.as<f2>();
-  d.pl_start = c->b_pls.as<uint32_t>();
-  d.pl_end = c->b_ple.as<uint32_t>();
-  d.pl_bb_off = c->b_bbo.as<uint32_t>();
-  d.pl_bb = c->b_bb.as<float>();
-  // grids (row a3), one CSR over (view, cell) per cell size: built on the DEVICE (K0, build_grids_device) from the polylines
-  // just uploaded. EG3D_GRID_ON_HOST=1 (diagnostic) runs the host builder instead — the 2 x V builds are independent
-  // (polyLine_2d_map.cpp:40-58 constructs one map per view), so they run on a few host threads; serially, as until round 5,
-  // this was 2x the whole hot path of a dtu006-sized job (90 ms for C3', 0.87 s for C4).
-  c->hg->device = device;
-  c->hg->n_views = V;
-  if (!c->tune.grid_on_host) {
-    if ((rc = build_grids_device(c, NP)) != EG3D_OK) {
-      eg3d_destroy(c);
-      return rc;
-    }
-  } else {
-    struct GridJob {
-      uint32_t w = 0, h = 0, dropped = 0, *o = nullptr, *i = nullptr;
-      int rc = 0;
-    };
-    std::vector<GridJob> jobs((size_t)2 * V);
-    std::atomic<int> next{0};
-    auto work = [&]() {
-      for (int j; (j = next.fetch_add(1)) < 2 * V;) {
-        GridJob& g = jobs[(size_t)j];
-        // (the 4 px grids first: they are the long jobs)
-        g.rc = eg3d_host_build_grid(sc, j % V, j < V ? 4.0f : 30.0f, &g.w, &g.h, &g.o, &g.i, &g.dropped);
-      }
-    };
-    {
-      const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-      const int nthr = (int)std::min<unsigned>(std::min<unsigned>(hw, EG3D_COPY_THREADS), (unsigned)(2 * V));
-      std::vector<std::thread> th;
-      try {
-        for (int t = 1; t < nthr; t++) th.emplace_back(work);
-      } catch (...) {  // no more threads: the calling thread does what is left
-      }
-      work();
-      for (auto& t : th) t.join();
-    }
-    bool ok = true;
-    for (auto& g : jobs) ok = ok && g.rc == 0;
-    // the per-view arrays are copied for eg3d_get_grid; the device CSR over (view, cell) is assembled on the same threads
-    struct FreeJobs {
-      std::vector<GridJob>& j;
-      ~FreeJobs() {
-        for (auto& g : j) {
-          free(g.o);
-          free(g.i);
-        }
-      }
-    } free_jobs{jobs};
-    for (int which = 0; which < 2 && ok; which++) {
-      c->hg->h_off[which].resize((size_t)V);
-      c->hg->h_ids[which].resize((size_t)V);
-      for (int v = 0; v < V; v++) {
-        const GridJob& g = jobs[(size_t)(which == 0 ? V + v : v)];
-        c->hg->h_off[which][(size_t)v].assign(g.o, g.o + (size_t)g.w * g.h + 1);
-        c->hg->h_ids[which][(size_t)v].assign(g.i, g.i + g.o[(size_t)g.w * g.h]);
-      }
-      c->hg->have[which] = true;
-    }
-    for (int which = 0; which < 2 && ok; which++) {
-      std::vector<size_t> id_base((size_t)V + 1, 0), off_base((size_t)V + 1, 0);
-      for (int v = 0; v < V; v++) {
-        const GridJob& g = jobs[(size_t)(which == 0 ? V + v : v)];
-        c->gw[which] = g.w;
-        c->gh[which] = g.h;
-        c->grid_dropped += g.dropped;
-        id_base[(size_t)v + 1] = id_base[(size_t)v] + g.o[(size_t)g.w * g.h];
-        off_base[(size_t)v + 1] = off_base[(size_t)v] + (size_t)g.w * g.h;
-      }
-      if (id_base[(size_t)V] > 0xffffffffull) {
-        g_err = "eg3d_create: the grids of this scene hold more than 2^32-1 (cell, polyline) entries";
-        eg3d_destroy(c);
-        return EG3D_ERR_CAPACITY;
-      }
-      std::vector<uint32_t> off(off_base[(size_t)V] + 1), ids(std::max<size_t>(id_base[(size_t)V], 1));
-      off[0] = 0;
-      std::atomic<int> nextv{0};
-      auto fill = [&]() {
-        for (int v; (v = nextv.fetch_add(1)) < V;) {
-          const GridJob& g = jobs[(size_t)(which == 0 ? V + v : v)];
-          const size_t nc = (size_t)g.w * g.h;
-          const uint32_t base = (uint32_t)id_base[(size_t)v];
-          uint32_t* dst = off.data() + off_base[(size_t)v] + 1;
-          for (size_t cc = 0; cc < nc; cc++) dst[cc] = base + g.o[cc + 1];
-          if (g.o[nc]) memcpy(ids.data() + id_base[(size_t)v], g.i, sizeof(uint32_t) * g.o[nc]);
-        }
-      };
-      {
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        const int nthr = (int)std::min<unsigned>(std::min<unsigned>(hw, EG3D_COPY_THREADS), (unsigned)V);
-        std::vector<std::thread> th;
-        try {
-          for (int t = 1; t < nthr; t++) th.emplace_back(fill);
-        } catch (...) {
-        }
-        fill();
-        for (auto& t : th) t.join();
-      }
-      if (which == 0) {
-        if ((rc = upload(c->b_g30o, off.data(), off.size(), c->stream)) == EG3D_OK) rc = upload(c->b_g30i, ids.data(), ids.size(), c->stream);
-      } else {
-        if ((rc = upload(c->b_g4o, off.data(), off.size(), c->stream)) == EG3D_OK) rc = upload(c->b_g4i, ids.data(), ids.size(), c->stream);
-      }
-      if (rc == EG3D_OK && hipStreamSynchronize(c->stream) != hipSuccess) {  // `off`/`ids` go out of scope
-        g_err = "eg3d_create: uploading the grids failed";
-        rc = EG3D_ERR_HIP;
-      }
-      if (rc != EG3D_OK) ok = false;
-    }
-    if (!ok) {
-      if (rc == EG3D_OK) {
-        g_err = "eg3d_create: grid construction failed";
-        rc = EG3D_ERR_ARG;
-      }
-      eg3d_destroy(c);
-      return rc;
-    }
-  }
-  d.g30_w = (int)c->gw[0];
-  d.g30_h = (int)c->gh[0];
-  d.g4_w = (int)c->gw[1];
-  d.g4_h = (int)c->gh[1];
-  d.g30_off = c->b_g30o.as<uint32_t>();
-  d.g30_ids = c->b_g30i.as<uint32_t>();
-  d.g4_off = c->b_g4o.as<uint32_t>();
-  d.g4_ids = c->b_g4i.as<uint32_t>();
-  {
-    bool mid = true;
-    for (size_t v = 0; v < (size_t)V && mid; v++)
-      for (int k = 0; k < 12 && mid; k++) {
-        const float p = sc->cam_P[v * 16 + k];
-        if (p != 0.0f) {
-          const float a = p < 0 ? -p : p;
-          mid = a >= 7.888609052210118e-31f && a <= 1.2676506002282294e+30f;  // 2^-100 .. 2^100 (NaN fails)
-        }
-      }
-    d.cams_mid_range = mid ? 1 : 0;
-  }
-  // the longest valid polyline of the scene (a scene whose polylines all fit the side walks' LDS staging area, and
-  // that has few views, runs the smaller build of the expand kernel: launch_k3b)
-  c->max_pl_vtx = 0;
-  for (uint32_t p = 0; p < NP; p++)
-    if (sc->pl_valid[p]) c->max_pl_vtx = std::max(c->max_pl_vtx, sc->pl_vtx_off[p + 1] - sc->pl_vtx_off[p]);
-  // observation slots per chain (blocks double when they fill, so budget ~3x the live count);
-  // grown automatically when a chain overflows
-  // (many-view scenes: points carry ~V/3 observations and blocks are relocated as they double — C4 settles at 196 608; starting
-  // at 24 576 as until round 6 cost the first call three extra rounds of the expand stage)
-  c->pool_cap = std::min<uint32_t>(131072, 768u * (uint32_t)std::min(V, 128));
-  if (c->pool_cap < 6144) c->pool_cap = 6144;
-  if (c->tune.pool_cap0) c->pool_cap = c->tune.pool_cap0;
-  if (c->tune.chain_cap0) c->chain_cap = c->tune.chain_cap0;
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  c->n_simd = (uint32_t)prop.multiProcessorCount * 4;
-  if (hipDeviceGetAttribute(&c->wall_clock_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess) c->wall_clock_khz = 0;
-  {
-    // working-slice slots per XCD: what can be resident (occupancy query x CUs of an XCD) plus a margin —
-    // the occupancy API may be one block per CU off, and a pool must never be smaller than the residency
-    const int per_cu = k3b_blocks_per_cu();
-    if (per_cu < 1) {
-      g_err = "eg3d_create: occupancy query of the expand kernel failed";
-      eg3d_destroy(c);
-      return EG3D_ERR_HIP;
-    }
-    // XCDs of THIS device: 8 on the whole MI355X (32 CUs each), fewer when the GPU is partitioned (CPX: one XCD of 32
-    // CUs appears as a device, DPX / QPX: four / two) — all its blocks then draw from the pools of those XCDs only, so a
-    // pool is sized for CUs / XCDs compute units, not for an eighth of whatever the device reports
-    const uint32_t cus = (uint32_t)prop.multiProcessorCount;
-    const uint32_t n_xcd = std::min(8u, std::max(1u, cus / 32u));
-    // (at least 40: an XCD of 38 CUs on a part with fewer than 8 XCDs would be undersized by the estimate cus / 32 — the
-    // pools cost a few tens of MB more on gfx950, where an XCD has 32)
-    const uint32_t cus_per_xcd = std::max<uint32_t>((cus + n_xcd - 1u) / n_xcd, 40u);
-    c->slots_per_xcd = ((uint32_t)per_cu + 1u) * cus_per_xcd + 16u;
-    if (c->tune.slots_per_xcd) c->slots_per_xcd = c->tune.slots_per_xcd;  // tests / experiments
-    // (the lane-per-chain engine is an opt-in second form: only a context that asks for it depends on its kernel)
-    if (c->tune.k3b_engine != 0) {
-#ifdef EG3D_WITH_K3C_ENGINE
-      c->k3c_per_cu = k3c_blocks_per_cu();
-      if (c->k3c_per_cu < 1) {
-        g_err = "eg3d_create: occupancy query of the expand engine failed";
-        eg3d_destroy(c);
-        return EG3D_ERR_HIP;
-      }
-#else
-      g_err = "eg3d_create: EG3D_K3B_ENGINE=1, but this library was built without the lane-per-chain engine "
-              "(-DEG3D_WITH_K3C_ENGINE: edgegraph3d_amd/variants/libeg3d_engine.so)";
-      eg3d_destroy(c);
-      return EG3D_ERR_ARG;
-#endif
-    }
-  }
+  if (c->tune.hyp_cap) c->learned.hyp_cap = c->tune.hyp_cap;
+  BUF_TRY(make_own_resources(c, c->tune.lane_priorities ? StreamPrio::greatest : StreamPrio::plain));
+  SceneVertices vertices;
+  s.n_pl = sc->view_pl_off[s.V];
+  drop_invalid_vertices(sc, s.n_pl, vertices);
+  s.n_vtx = vertices.pvo[s.n_pl];
+  BUF_TRY(upload_scene_arrays(c, s, sc, vertices));
+  BUF_TRY(upload_block_boxes(c, s, vertices));
+  BUF_TRY(build_grids(c, s, sc));
+  flag_cams_mid_range(s, sc);
+  BUF_TRY(size_pools_and_slots(c, s, sc));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  // from here on the scene buffers belong to the (shareable) owner, not to this context
-  c->scene_owner = std::make_shared<DevOwner>();
-  c->scene_owner->device = device;
-  for (DevBuf* b : scene_bufs(c)) c->scene_owner->bufs.push_back(*b);
-  *out = c;
+  share_scene(c, std::move(scene));
+  *out = guard.release();
   return EG3D_OK;
 }
 
 /* A second context on the same device that SHARES the parent's immutable scene (cameras, F,
  * polylines, grids) and its currently resident seeds, with its own stream, events and work
  * buffers: the way to keep several independent batches in flight (one host thread per context). */
+int eg3d::api::clone_ctx(eg3d_ctx* parent, StreamPrio prio, eg3d_ctx** out) {
+  HIP_TRY(hipSetDevice(parent->device));
+  CtxGuard c(new eg3d_ctx(), eg3d_destroy);
+  share_scene(c.get(), parent->scene);
+  c->seeds = parent->seeds;
+  c->tune = parent->tune;
+  c->learned = parent->learned;
+  BUF_TRY(make_own_resources(c.get(), prio));
+  *out = c.release();
+  return EG3D_OK;
+}
 extern "C" int eg3d_clone(eg3d_ctx* parent, eg3d_ctx** out) {
   if (!parent || !out) {
     g_err = "eg3d_clone: bad arguments";
     return EG3D_ERR_ARG;
   }
-  HIP_TRY(hipSetDevice(parent->device));
-  eg3d_ctx* c = new eg3d_ctx();
-  c->device = parent->device;
-  c->tune = parent->tune;
-  c->compact_nt = parent->compact_nt;
-  c->replay_table_bits = parent->replay_table_bits;
-  c->simgraph_pair_budget = parent->simgraph_pair_budget;
-  c->louvain_log2_slots = parent->louvain_log2_slots;
-  c->n_pl = parent->n_pl;
-  c->n_vtx = parent->n_vtx;
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  for (int i = 0; i < 8; i++) {
-    HIP_TRY(hipEventCreate(&c->ea[i]));
-    HIP_TRY(hipEventCreate(&c->eb[i]));
-  }
-  for (int i = 0; i < 7; i++) HIP_TRY(hipEventCreateWithFlags(&c->ecopy[i], hipEventDisableTiming));
-  c->V = parent->V;
-  c->W = parent->W;
-  c->H = parent->H;
-  c->ds = parent->ds;
-  {
-    std::vector<DevBuf*> src = scene_bufs(parent), dst = scene_bufs(c);
-    for (size_t i = 0; i < src.size(); i++) *dst[i] = *src[i];
-  }
-  c->scene_owner = parent->scene_owner;
-  c->hg = parent->hg;
-  for (int k = 0; k < 2; k++) {
-    c->gw[k] = parent->gw[k];
-    c->gh[k] = parent->gh[k];
-  }
-  c->grid_dropped = parent->grid_dropped;
-  c->n_seeds = parent->n_seeds;
-  c->h_trk = parent->h_trk;
-  c->b_toff = parent->b_toff;
-  c->b_tview = parent->b_tview;
-  c->b_txy = parent->b_txy;
-  c->seeds_owner = parent->seeds_owner;
-  c->chain_cap = parent->chain_cap;
-  c->pool_cap = parent->pool_cap;
-  c->hyp_cap = parent->hyp_cap;
-  c->n_simd = parent->n_simd;
-  c->wall_clock_khz = parent->wall_clock_khz;
-  c->arena_per_hyp = parent->arena_per_hyp;
-  c->slots_per_xcd = parent->slots_per_xcd;
-  c->k3c_per_cu = parent->k3c_per_cu;
-  c->k3b_long_latched = parent->k3b_long_latched;
-  c->max_pl_vtx = parent->max_pl_vtx;
-  c->stage_cap_pts = parent->stage_cap_pts;  // sizing hints only: the clone allocates its own staging area
-  c->stage_cap_obs = parent->stage_cap_obs;
-  c->hits_per_list = parent->hits_per_list;
-  c->hits_learned = parent->hits_learned;
-  *out = c;
-  return EG3D_OK;
+  return clone_ctx(parent, StreamPrio::plain, out);
 }
 
 extern "C" void eg3d_destroy(eg3d_ctx* c) {
@@ -739,10 +689,6 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
   c->lanes.clear();
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (!c->scene_owner)  // creation failed half-way: the scene buffers are still this context's
-    for (DevBuf* b : scene_bufs(c)) b->release();
-  c->scene_owner.reset();
-  c->seeds_owner.reset();
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->mbox) (void)hipHostFree(c->mbox);
   for (int i = 0; i < 8; i++) {
@@ -752,7 +698,9 @@ extern "C" void eg3d_destroy(eg3d_ctx* c) {
   for (int i = 0; i < 7; i++)
     if (c->ecopy[i]) (void)hipEventDestroy(c->ecopy[i]);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;  // (the work buffers release themselves: nothing is queued on the stream any more)
+  // (nothing is queued on the stream any more: the work buffers release themselves, and the scene and the seeds go with
+  // the last context that shares them)
+  delete c;
 }
 
 extern "C" int eg3d_get_grid(eg3d_ctx* c, int view, int which, uint32_t* ncols, uint32_t* nrows,
@@ -761,35 +709,35 @@ extern "C" int eg3d_get_grid(eg3d_ctx* c, int view, int which, uint32_t* ncols, 
     g_err = "eg3d_get_grid: bad arguments";
     return EG3D_ERR_ARG;
   }
-  HostGrids& hg = *c->hg;
+  Scene& s = *c->scene;
   {
-    std::lock_guard<std::mutex> lk(hg.mu);
-    if (which == 2 && !hg.built10) {
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (which == 2 && !s.built10) {
       g_err = "eg3d_get_grid: the 10 px map does not exist before the first eg3d_match_polylines_closeness call";
       return EG3D_ERR_ARG;
     }
-    if (!hg.have[which]) {  // first request for this cell size: fetch the device CSR and cut it into per-view CSRs
-      HIP_TRY(hipSetDevice(hg.device));
-      const size_t cpv = hg.cells_per_view[which], V = (size_t)hg.n_views;
+    if (!s.have[which]) {  // first request for this cell size: fetch the device CSR and cut it into per-view CSRs
+      HIP_TRY(hipSetDevice(s.device));
+      const size_t cpv = s.cells_per_view(which), V = (size_t)s.V;
       std::vector<uint32_t> off(V * cpv + 1);
-      HIP_TRY(hipMemcpy(off.data(), hg.d_off[which], sizeof(uint32_t) * off.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(off.data(), s.d_off(which), sizeof(uint32_t) * off.size(), hipMemcpyDeviceToHost));
       std::vector<uint32_t> all(std::max<size_t>(off.back(), 1));
-      if (off.back()) HIP_TRY(hipMemcpy(all.data(), hg.d_ids[which], sizeof(uint32_t) * off.back(), hipMemcpyDeviceToHost));
-      hg.h_off[which].resize(V);
-      hg.h_ids[which].resize(V);
+      if (off.back()) HIP_TRY(hipMemcpy(all.data(), s.d_ids(which), sizeof(uint32_t) * off.back(), hipMemcpyDeviceToHost));
+      s.h_off[which].resize(V);
+      s.h_ids[which].resize(V);
       for (size_t v = 0; v < V; v++) {
         const uint32_t base = off[v * cpv];
-        hg.h_off[which][v].resize(cpv + 1);
-        for (size_t cc = 0; cc <= cpv; cc++) hg.h_off[which][v][cc] = off[v * cpv + cc] - base;
-        hg.h_ids[which][v].assign(all.begin() + base, all.begin() + off[(v + 1) * cpv]);
+        s.h_off[which][v].resize(cpv + 1);
+        for (size_t cc = 0; cc <= cpv; cc++) s.h_off[which][v][cc] = off[v * cpv + cc] - base;
+        s.h_ids[which][v].assign(all.begin() + base, all.begin() + off[(v + 1) * cpv]);
       }
-      hg.have[which] = true;
+      s.have[which] = true;
     }
   }
-  *ncols = which == 2 ? hg.w10 : c->gw[which];
-  *nrows = which == 2 ? hg.h10 : c->gh[which];
-  *cell_off = hg.h_off[which][(size_t)view].data();
-  *ids = hg.h_ids[which][(size_t)view].data();
+  *ncols = which == 2 ? s.w10 : c->gw[which];
+  *nrows = which == 2 ? s.h10 : c->gh[which];
+  *cell_off = s.h_off[which][(size_t)view].data();
+  *ids = s.h_ids[which][(size_t)view].data();
   return EG3D_OK;
 }
 
@@ -819,24 +767,17 @@ extern "C" int eg3d_upload_seeds(eg3d_ctx* c, const eg3d_seeds* s) {
       g_err = "eg3d_upload_seeds: view id out of range";
       return EG3D_ERR_ARG;
     }
-  // fresh buffers: the previous ones may still be in use by clones of this context
-  c->seeds_owner.reset();
-  c->b_toff = c->b_tview = c->b_txy = DevBuf();
-  c->n_seeds = 0;
-  auto owner = std::make_shared<DevOwner>();
-  owner->device = c->device;
-  int rc = upload(c->b_toff, s->trk_off, n + 1, c->stream);
-  if (rc == EG3D_OK) rc = upload(c->b_tview, s->trk_view, m, c->stream);
-  if (rc == EG3D_OK) rc = upload(c->b_txy, s->trk_xy, (size_t)m * 2, c->stream);
-  owner->bufs = {c->b_toff, c->b_tview, c->b_txy};
-  if (rc != EG3D_OK) {
-    c->b_toff = c->b_tview = c->b_txy = DevBuf();
-    return rc;
-  }
+  // A fresh object: the previous one may still be in use by clones of this context. The context lets go of it first (its
+  // arrays are freed before the new ones are allocated when nobody else holds them) and has no seeds if the upload fails.
+  c->seeds = std::make_shared<Seeds>(c->device);
+  auto fresh = std::make_shared<Seeds>(c->device);
+  BUF_TRY(upload(fresh->toff, s->trk_off, n + 1, c->stream));
+  BUF_TRY(upload(fresh->tview, s->trk_view, m, c->stream));
+  BUF_TRY(upload(fresh->txy, s->trk_xy, (size_t)m * 2, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->seeds_owner = owner;
-  c->h_trk = std::make_shared<std::vector<uint32_t>>(s->trk_off, s->trk_off + n + 1);
-  c->n_seeds = n;
+  fresh->trk_off.assign(s->trk_off, s->trk_off + n + 1);
+  fresh->n_seeds = n;
+  c->seeds = std::move(fresh);
   return EG3D_OK;
 }
 
@@ -935,25 +876,25 @@ int check_struct_size(const char* who, const char* type_name, size_t got, size_t
 }
 
 int open_seed_range(eg3d_ctx* c, const char* who, const eg3d_seeds* seeds, uint32_t b, uint32_t e, const void* out,
-                    WorkBuf eg3d_ctx::*ctr_of, WorkBuf eg3d_ctx::*svseed_of, SeedRange* r) {
+                    DevBuf eg3d_ctx::*ctr_of, DevBuf eg3d_ctx::*svseed_of, SeedRange* r) {
   if (!c || !out) {
     g_err = std::string(who) + ": bad arguments";
     return EG3D_ERR_ARG;
   }
   if (seeds) BUF_TRY(eg3d_upload_seeds(c, seeds));
-  if (b > e || e > c->n_seeds) {
+  if (b > e || e > c->seeds->n_seeds) {
     g_err = std::string(who) + ": bad seed range (seeds uploaded?)";
     return EG3D_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
   r->n_seeds = e - b;
-  r->sv_base = r->n_seeds ? (*c->h_trk)[b] : 0;
-  r->n_sv = r->n_seeds ? (*c->h_trk)[e] - r->sv_base : 0;
+  r->sv_base = r->n_seeds ? c->seeds->trk_off[b] : 0;
+  r->n_sv = r->n_seeds ? c->seeds->trk_off[e] - r->sv_base : 0;
   r->active = r->n_sv && c->n_pl;
   if (!r->active) return EG3D_OK;
   BUF_TRY(ensure_grid10(c, &r->g10, &r->ms_grid));
-  WorkBuf &ctr = c->*ctr_of, &svseed = c->*svseed_of;
-  r->sd = seeds_dev(c);
+  DevBuf &ctr = c->*ctr_of, &svseed = c->*svseed_of;
+  r->sd = c->seeds->dev();
   // ---- the view ids, before anything indexes with them
   BUF_TRY(ctr.ensure(4 * sizeof(uint32_t)));
   BUF_TRY(svseed.ensure(sizeof(uint32_t) * r->n_sv));

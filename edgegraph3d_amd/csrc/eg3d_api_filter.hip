@@ -83,7 +83,7 @@ static int compact_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, con
   BUF_TRY(c->c_xy.ensure(8 * no));
   CloudOut o{c->c_X.as<float>(), c->c_off.as<eg3d_off_t>(), c->c_view.as<int32_t>(), c->c_pl.as<uint32_t>(),
              c->c_seg.as<uint32_t>(), c->c_xy.as<float>(), c->c_key.as<uint32_t>()};
-  launch_compact_scatter(st, in, keep_dev, X_new_dev, min_obs, blk, o, c->compact_nt);
+  launch_compact_scatter(st, in, keep_dev, X_new_dev, min_obs, blk, o, c->tune.compact_nt);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->eb[0], st));
   HIP_TRY(hipStreamSynchronize(st));

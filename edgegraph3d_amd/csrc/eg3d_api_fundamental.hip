@@ -1,5 +1,5 @@
 // eg3d_api_fundamental.hip — the fundamental matrices from the tracks on the device (K12, eg3d_k12_fundamental.hip).
-// Context-free: F is part of the scene eg3d_create takes, so the call makes its own stream, events and WorkBufs and
+// Context-free: F is part of the scene eg3d_create takes, so the call makes its own stream, events and DevBufs and
 // releases them when it returns, whichever way.
 #include "eg3d_api_internal.h"
 #include "eg3d_fund_core.h"
@@ -10,7 +10,7 @@ namespace {
 struct FundCall {
   hipStream_t st = nullptr;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  WorkBuf toff, tview, txy, key[2], val[2], flag, pos, ckey, cxy, voff, ncom, has, has_rank, size, size_off, pts, pairs, idx, fits, refits,
+  DevBuf toff, tview, txy, key[2], val[2], flag, pos, ckey, cxy, voff, ncom, has, has_rank, size, size_off, pts, pairs, idx, fits, refits,
       normals, sel, err, inl, F, valid, ctr, tmp;
   ~FundCall() {
     for (hipEvent_t e : ev)

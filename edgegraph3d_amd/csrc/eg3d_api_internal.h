@@ -1,5 +1,6 @@
 // eg3d_api_internal.h — what the host drivers of the C ABI (eg3d_api*.hip) share: the error string, the device buffer
-// types, the context, the small read-backs and one copy of each idiom the stages repeat. Host only; no kernel lives here.
+// type, the knobs, the context and what it shares (Scene, Seeds) or has learned, the small read-backs and one copy of each
+// idiom the stages repeat. Host only; no kernel lives here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,11 +51,16 @@ EG3D_API_BEGIN
 int dev_alloc(void** p, size_t bytes);
 void dev_free(void* p, size_t bytes);
 
-// A device block and its size: a plain, copyable HANDLE. It frees nothing by itself — the scene and seed buffers are
-// handles, copied into clones and lanes and released by the DevOwner the contexts share.
+// A device block that belongs to the object it is a member of: no copies, released with its owner. Every device buffer of
+// the library is one — a context's work and result buffers, the scene's and the seeds' arrays (Scene, Seeds), the
+// temporaries of a grid build — so no list of them exists anywhere.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= cap && p) return EG3D_OK;
     return replace(std::max<size_t>(bytes + bytes / 4, 256));
@@ -86,54 +92,8 @@ struct DevBuf {
   }
 };
 
-// A device block that belongs to the object it is a member of: the same interface, no copies, released with its owner.
-// Every work and result buffer of a context is one, so no list of them exists anywhere.
-struct WorkBuf : private DevBuf {
-  WorkBuf() = default;
-  WorkBuf(const WorkBuf&) = delete;
-  WorkBuf& operator=(const WorkBuf&) = delete;
-  ~WorkBuf() { release(); }
-  using DevBuf::as;
-  using DevBuf::cap;
-  using DevBuf::ensure;
-  using DevBuf::ensure_exact;
-  using DevBuf::ensure_keep;
-  using DevBuf::p;
-  using DevBuf::release;
-};
-
-// Device allocations shared by a context and its clones (immutable scene / resident seeds): freed
-// when the last context referring to them goes away.
-struct DevOwner {
-  int device = 0;
-  std::vector<DevBuf> bufs;
-  ~DevOwner() {
-    (void)hipSetDevice(device);
-    for (DevBuf& b : bufs) b.release();
-  }
-};
-// Host copies of the grids for eg3d_get_grid (per view CSR with view-local offsets). The grids live on the device (K0 builds
-// them there); the copies are made by the first eg3d_get_grid call that asks for a cell size — tests do, the hot path never.
-// Index 2 is the 10 px map of the polyline matcher (eg3d_match_polylines_closeness): no context has it until the first such
-// call on the context or on one of its clones builds it (ensure_grid10, under `mu`); it then belongs to this object, which
-// the context and its clones share, and goes away with the last of them — always inside eg3d_destroy, after its
-// hipSetDevice: g10o / g10i (like every WorkBuf of a context) rely on that and set no device of their own.
-struct HostGrids {
-  std::mutex mu;
-  bool have[3] = {false, false, false};
-  std::vector<std::vector<uint32_t>> h_off[3], h_ids[3];
-  // where to fetch them from (device arrays of the shared, immutable scene)
-  int device = 0, n_views = 0;
-  const uint32_t* d_off[3] = {nullptr, nullptr, nullptr};
-  const uint32_t* d_ids[3] = {nullptr, nullptr, nullptr};
-  uint32_t cells_per_view[3] = {0, 0, 0};
-  bool built10 = false;
-  uint32_t w10 = 0, h10 = 0;
-  WorkBuf g10o, g10i;  // the 10 px map's device arrays (d_off[2] / d_ids[2] point into them)
-};
-
-// Test / tuning knobs, read from the environment ONCE when a context is created (eg3d_create; clones
-// inherit them) — the hot path never calls getenv:
+// Test / tuning knobs, ALL of them, read from the environment ONCE when a context is created (eg3d_create calls from_env; a
+// clone copies the struct) — nothing else in the library calls getenv:
 //   EG3D_K3A_ENGINE_WAVES=n  wavefronts per SIMD the K3a engine launches (default 2 = what its 256-VGPR build allows)
 //   EG3D_K3A_ENGINE_LANES=n  lanes of a K3a wavefront that take work (default: 64, fewer for small batches)
 #ifndef EG3D_K3B_ENGINE_DEFAULT
@@ -195,6 +155,13 @@ struct Tunables {
   size_t max_scratch = 0;  // 0 = no limit
   uint32_t slots_per_xcd = 0;  // 0 = sized from the occupancy query
   bool use_lpt = true;
+  bool compact_nt = false;  // EG3D_COMPACT_NT=1: non-temporal loads of the compaction's source
+  int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (tests): a node table of 2^bits slots, raised to the smallest power of
+                              // two above the number of lookups; 0 = the default, about twice that
+  uint64_t simgraph_pair_budget = 0;  // EG3D_SIMGRAPH_PAIR_BUDGET (tests): edge keys one chunk of the clique expansion may
+                                      // write; 0 = EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
+  uint32_t louvain_log2_slots = 0;  // EG3D_LOUVAIN_TABLE_SLOTS (tests): slots of the sweep's per-wave LDS table, raised to a
+                                    // power of two in 16 .. 1024; 0 = K11_DEFAULT_SLOTS
   static Tunables from_env() {
     Tunables t;
     if (const char* e = getenv("EG3D_K3A_ENGINE_WAVES")) t.k3a_engine_waves = atoi(e);
@@ -222,6 +189,13 @@ struct Tunables {
     if (const char* e = getenv("EG3D_LANE_PRIORITIES")) t.lane_priorities = atoi(e);
     if (const char* e = getenv("EG3D_UNIT_RAMP")) t.unit_ramp = std::min(16.0, std::max(1.0 / 16.0, atof(e)));
     if (const char* e = getenv("EG3D_PIPELINE_UNITS")) t.units = std::min(4096, std::max(0, atoi(e)));
+    if (const char* e = getenv("EG3D_COMPACT_NT")) t.compact_nt = e[0] == '1';
+    if (const char* e = getenv("EG3D_REPLAY_TABLE_BITS")) t.replay_table_bits = std::min(40, std::max(0, atoi(e)));
+    if (const char* e = getenv("EG3D_SIMGRAPH_PAIR_BUDGET")) t.simgraph_pair_budget = std::min(1ull << 31, strtoull(e, nullptr, 10));
+    if (const char* e = getenv("EG3D_LOUVAIN_TABLE_SLOTS")) {
+      const unsigned long long want = std::min<unsigned long long>(K11_MAX_SLOTS, std::max<unsigned long long>(K11_MIN_SLOTS, strtoull(e, nullptr, 10)));
+      while ((1ull << t.louvain_log2_slots) < want) t.louvain_log2_slots++;
+    }
     return t;
   }
 };
@@ -230,93 +204,138 @@ struct Tunables {
 enum K11Buf { K11B_OFF0, K11B_OFF1, K11B_NBR0, K11B_NBR1, K11B_EROW0, K11B_EROW1, K11B_Q0, K11B_Q1, K11B_W, K11B_K, K11B_C, K11B_T,
               K11B_A0, K11B_A1, K11B_SIZE0, K11B_SIZE1, K11B_MEMBER, K11B_MINM, K11B_FLAG, K11B_RANK, K11B_CN, K11B_OVF, K11B_OCNT,
               K11B_OOFF, K11B_KEY0, K11B_KEY1, K11B_VAL0, K11B_VAL1, K11B_IDS, K11B_CTR, K11B_COUNT };
+
+// What the scene fixes, as plain values and device addresses (no ownership). Scene holds the original; every context
+// carries a copy (share_scene), so that the drivers read c->V, c->ds, ... without a second indirection.
+struct SceneFacts {
+  int device = 0;
+  int V = 0, W = 0, H = 0;
+  DevScene ds;
+  uint32_t n_pl = 0, n_vtx = 0;  // polylines and vertices of the scene as uploaded
+  uint32_t max_pl_vtx = 0;       // vertices of the scene's longest valid polyline
+  uint32_t gw[2] = {0, 0}, gh[2] = {0, 0};  // the 30 px and 4 px grids
+  uint32_t grid_dropped = 0;
+  uint32_t n_simd = 0;         // SIMDs of the device (4 per CU): sizes the K3a engine's launch
+  int wall_clock_khz = 0;      // rate of wall_clock64() on the device (hipDeviceAttributeWallClockRate)
+  uint32_t slots_per_xcd = 0;  // working slices of the expand stage per XCD (b_cscratch: 8 XCDs x slots_per_xcd slices)
+  int k3c_per_cu = 0;          // resident blocks per CU of the lane-per-chain engine (occupancy query)
+};
+// The immutable scene: eg3d_create makes one, the context, its clones and their lanes share it through a shared_ptr, and it
+// goes away with the last of them. It owns the device arrays `ds` points into, and the host copies of the grids for
+// eg3d_get_grid (per view CSR with view-local offsets). The grids live on the device (K0 builds them there); the copies are
+// made by the first eg3d_get_grid call that asks for a cell size — tests do, the hot path never. Index 2 is the 10 px map of
+// the polyline matcher (eg3d_match_polylines_closeness): nobody has it until the first such call on any context of the
+// family builds it (ensure_grid10, under `mu`).
+struct Scene : SceneFacts {
+  DevBuf camP, F, Fv, vpo, pvo, vtx, pls, ple, bbo, bb;
+  DevBuf g_off[3], g_ids[3];  // 30 px, 4 px, 10 px
+  std::mutex mu;              // guards what follows
+  bool have[3] = {false, false, false};
+  std::vector<std::vector<uint32_t>> h_off[3], h_ids[3];
+  bool built10 = false;
+  uint32_t w10 = 0, h10 = 0;
+  const uint32_t* d_off(int which) const { return g_off[which].as<uint32_t>(); }
+  const uint32_t* d_ids(int which) const { return g_ids[which].as<uint32_t>(); }
+  uint32_t cells_per_view(int which) const { return which == 2 ? w10 * h10 : gw[which] * gh[which]; }
+  ~Scene() { (void)hipSetDevice(device); }  // (the last owner may be on any thread; the buffers go right after this body)
+};
+// The resident seeds, immutable once uploaded: eg3d_upload_seeds builds a fresh object and swaps the context's pointer, so
+// clones and lanes still matching the old seeds are not disturbed; the arrays go away with the last of them.
+struct Seeds {
+  const int device;
+  explicit Seeds(int device_) : device(device_) {}
+  uint32_t n_seeds = 0;
+  std::vector<uint32_t> trk_off = {0};  // host copy: ranges are cut and checked with it
+  DevBuf toff, tview, txy;
+  SeedsDev dev() const {  // as the kernels take them
+    SeedsDev sd;
+    sd.trk_off = toff.as<uint32_t>();
+    sd.trk_view = tview.as<int32_t>();
+    sd.trk_xy = txy.as<float>();
+    return sd;
+  }
+  ~Seeds() { (void)hipSetDevice(device); }
+};
+// What a context has learned about the sizes the scene needs (capacities only grow). A clone starts from its parent's by
+// one assignment; lanes take the owner's and give theirs back through merge.
+struct Learned {
+  uint32_t chain_cap = 384, pool_cap = 0, hyp_cap = 160;
+  double arena_per_hyp = 16.0;  // hypothesis arena: points per hypothesis to reserve (learned from overflows)
+  double hits_per_list = 4.0;   // epipolar-hit buffer: hits per list to reserve (learned from what K2 claimed; run_stage_a)
+  bool hits_learned = false;    // a K2 launch of this context (or of one it shares what it learned with) has fitted its buffer
+  bool k3b_long_latched = false;  // a launch of a few-views build met a solve of > 32 rows: the general builds from then on
+  uint64_t stage_cap_pts = 0, stage_cap_obs = 0;  // staging area of the expand stage (b_stage_*: grow-only)
+  // stage_cap_* are copied with the rest at clone time and NOT merged: they are sizing hints only — every context allocates
+  // its own staging area and learns its need from its own launches. (hyp_cap is fixed by EG3D_HYP_CAP at eg3d_create.)
+  void merge(const Learned& o) {
+    chain_cap = std::max(chain_cap, o.chain_cap);
+    pool_cap = std::max(pool_cap, o.pool_cap);
+    arena_per_hyp = std::max(arena_per_hyp, o.arena_per_hyp);
+    hits_per_list = std::max(hits_per_list, o.hits_per_list);
+    hits_learned = hits_learned || o.hits_learned;
+    k3b_long_latched = k3b_long_latched || o.k3b_long_latched;
+  }
+};
 EG3D_API_END
 
 // (an internal header: only the eg3d_api*.hip include it, and they are written in these namespaces)
 using namespace eg3d;
 using namespace eg3d::api;
 
-struct eg3d_ctx {
-  int device = 0;
+// A context is four kinds of state, each in one place: the scene it shares (`scene`, with SceneFacts as plain copies), the
+// seeds it shares until the next upload (`seeds`), what it was told and what it has learned (`tune`, `learned`), and what
+// it owns alone — the stream, the events and every buffer below. eg3d_clone is written in exactly these terms.
+struct eg3d_ctx : SceneFacts {
+  std::shared_ptr<Scene> scene;  // (set by share_scene alone)
+  std::shared_ptr<const Seeds> seeds;  // (never null once the context is made: no seeds = an object with none)
   Tunables tune;
+  Learned learned;
   hipStream_t stream = nullptr;
-  int V = 0, W = 0, H = 0;
-  DevScene ds;
-  DevBuf b_camP, b_F, b_Fv, b_vpo, b_pvo, b_vtx, b_pls, b_ple, b_g30o, b_g30i, b_g4o, b_g4i, b_bbo, b_bb;
-  std::shared_ptr<DevOwner> scene_owner;  // owns b_camP .. b_g4i
-  // host copies of the grids for eg3d_get_grid (per view CSR with view-local offsets)
-  std::shared_ptr<HostGrids> hg;
-  uint32_t gw[2] = {0, 0}, gh[2] = {0, 0};
-  uint32_t grid_dropped = 0;
-  // resident seeds
-  uint32_t n_seeds = 0;
-  std::shared_ptr<std::vector<uint32_t>> h_trk;
-  DevBuf b_toff, b_tview, b_txy;
-  std::shared_ptr<DevOwner> seeds_owner;  // owns b_toff, b_tview, b_txy
   // work buffers
-  WorkBuf b_sv_seed, b_map_view, b_map_entry, b_map_n, b_raw_cnt, b_raw_off, b_cand_pl, b_start_hits, b_cand_cnt,
+  DevBuf b_sv_seed, b_map_view, b_map_entry, b_map_n, b_raw_cnt, b_raw_off, b_cand_pl, b_start_hits, b_cand_cnt,
       b_start_cnt, b_task_off, b_task_seed, b_task_entry, b_task_hit, b_task_k, b_task_list_off, b_list_cnt, b_list_ptr,
       b_hits, b_tasks, b_nhyp, b_hyp_off, b_res, b_arena, b_ctr, b_cs_task, b_valid, b_chain_off, b_chains,
       b_cscratch, b_couts, b_cpts, b_cobs, b_cpoff, b_cooff, b_scan_tmp, b_scanchk, b_cost, b_cidx, b_cost2, b_order, b_redo[2];
   // K3a walk service (Counters::k3a_walks_served / k3a_walk_passes) of the units this lane ran since the last
   // eg3d_probe_k3a_walks (test-only builds read them; the figures come with the counters' read-back in any case)
   unsigned long long k3a_walks_served = 0, k3a_walk_passes = 0;
-  WorkBuf o_X, o_off, o_view, o_pl, o_seg, o_xy, o_key;
-  WorkBuf f_X, f_off, f_view, f_xy, f_Xo, f_inl;
+  DevBuf o_X, o_off, o_view, o_pl, o_seg, o_xy, o_key;
+  DevBuf f_X, f_off, f_view, f_xy, f_Xo, f_inl;
   // eg3d_gn_filter_device / eg3d_compact_device / eg3d_filter_resident: histogram + flag word, block totals of the
   // compaction, the compacted cloud (valid until the next compaction), X_out / inlier of eg3d_filter_resident
-  WorkBuf r_hist, r_blk, r_Xo, r_inl, c_X, c_off, c_view, c_pl, c_seg, c_xy, c_key;
-  bool compact_nt = false;  // EG3D_COMPACT_NT=1 (read by eg3d_create): non-temporal loads of the compaction's source
+  DevBuf r_hist, r_blk, r_Xo, r_inl, c_X, c_off, c_view, c_pl, c_seg, c_xy, c_key;
   // eg3d_dedup_device / eg3d_dedup_resident: the claim map (this context's own; created on first use), the kept count +
   // flag word, the mask of eg3d_dedup_resident
-  WorkBuf d_first, d_cnt, d_keep;
+  DevBuf d_first, d_cnt, d_keep;
   bool dedup_valid = false;   // the claim map holds the claims of the earlier calls (false: it is filled before use)
-  WorkBuf prim_tmp;  // scratch of the post stages' rocPRIM primitives (prim_call: K8 .. K11; the pipeline's scans keep b_scan_tmp)
+  DevBuf prim_tmp;  // scratch of the post stages' rocPRIM primitives (prim_call: K8 .. K11; the pipeline's scans keep b_scan_tmp)
   // eg3d_replay_device (K8). Work: counters + flag word, the node table (slot / last), per point the first point of its
   // node, flags, their scans, the last point of a node, the sort buffers, the interval claim map over
   // the scene's segments with its flags and scan. Result (valid until the next replay): the arrays of eg3d_graph3d.
-  WorkBuf k8_cnt, k8_slot, k8_last, k8_firstof, k8_flag, k8_rank, k8_lastof, k8_plid, k8_key[2], k8_val[2], k8_map, k8_sflag, k8_pos;
-  WorkBuf g_nodeX, g_nodept, g_pls, g_ple, g_conoff, g_conpl, g_ivoff, g_ivss, g_ivsxy, g_ives, g_ivexy;
+  DevBuf k8_cnt, k8_slot, k8_last, k8_firstof, k8_flag, k8_rank, k8_lastof, k8_plid, k8_key[2], k8_val[2], k8_map, k8_sflag, k8_pos;
+  DevBuf g_nodeX, g_nodept, g_pls, g_ple, g_conoff, g_conpl, g_ivoff, g_ivss, g_ivsxy, g_ives, g_ivexy;
   // eg3d_match_polylines_closeness (K9). Work: entry -> seed, the per-entry search results, the accept flags and their scan,
   // the match graph over the scene's polylines, the sort buffers, counters + flag word. Result on the device: the accepted
   // ids, row_off, pl_ids (copied to the caller's library-owned arrays at the end of the call).
-  WorkBuf k9_svseed, k9_cnt, k9_pl, k9_dist, k9_acc, k9_accoff, k9_first, k9_parent, k9_root, k9_ckey, k9_rank, k9_key[2], k9_ctr,
+  DevBuf k9_svseed, k9_cnt, k9_pl, k9_dist, k9_acc, k9_accoff, k9_first, k9_parent, k9_root, k9_ckey, k9_rank, k9_key[2], k9_ctr,
       k9_ref, k9_rowoff, k9_plids;
   // eg3d_similarity_graph (K10). Work: entry -> seed, the per-entry counts and their scan, the (point, polyline) pairs and
   // their swapped form (two sort buffers each way), the CSRs and columns of close_polylines / close_refpoints, the weights,
   // the visibility rows, the pair counts and their 64-bit scan, the node tables, the edge keys (k10_edge: the unique list
   // with the current chunk behind it, and the sort's output), the directed keys and weights, counters + flag word.
-  WorkBuf k10_svseed, k10_cnt, k10_off, k10_pair[2], k10_crkey, k10_cpoff, k10_cpview, k10_cppl, k10_croff, k10_crpoint, k10_weight, k10_vis,
+  DevBuf k10_svseed, k10_cnt, k10_off, k10_pair[2], k10_crkey, k10_cpoff, k10_cpview, k10_cppl, k10_croff, k10_crpoint, k10_weight, k10_vis,
       k10_npairs, k10_pairoff, k10_nkey[2], k10_nodeof, k10_nodeg, k10_nodeview, k10_nodepl, k10_edge[2], k10_dkey[2], k10_dval[2],
       k10_adjoff, k10_adjnode, k10_ctr;
   // eg3d_detect_communities (K11): the graph of the current and of the next phase, the partition and its totals, the
   // renumbering, the overflow rows, two (key, value) sort buffers, the ids, the counters (K11Buf names them).
-  WorkBuf k11[K11B_COUNT];
-  uint32_t louvain_log2_slots = 0;  // EG3D_LOUVAIN_TABLE_SLOTS (read by eg3d_create; tests): slots of the sweep's per-wave LDS
-                                    // table, raised to a power of two in 16 .. 1024; 0 = K11_DEFAULT_SLOTS
-  uint64_t simgraph_pair_budget = 0;  // EG3D_SIMGRAPH_PAIR_BUDGET (read by eg3d_create; tests): edge keys one chunk of the clique
-                                      // expansion may write; 0 = EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
-  int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (read by eg3d_create; tests): a node table of 2^bits slots, raised to the
-                              // smallest power of two above the number of lookups; 0 = the default, about twice that
-  uint32_t n_pl = 0, n_vtx = 0;  // polylines and vertices of the scene as uploaded
-  WorkBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
-  WorkBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
+  DevBuf k11[K11B_COUNT];
+  DevBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
+  DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
   // and the staging area finished chains are packed into (sized from the previous launches; grow-only)
-  WorkBuf b_pools, b_stage_pts, b_stage_obs, b_stage_used;
-  uint32_t slots_per_xcd = 0;
-  int k3c_per_cu = 0;            // resident blocks per CU of the lane-per-chain engine (occupancy query)
-  bool k3b_long_latched = false; // a launch of a few-views build met a solve of > 32 rows: the context runs the general builds from then on
-  uint32_t max_pl_vtx = 0;  // vertices of the scene's longest valid polyline
-  uint64_t stage_cap_pts = 0, stage_cap_obs = 0;
-  double hits_per_list = 4.0;  // epipolar-hit buffer: hits per list to reserve (learned from what K2 claimed; run_stage_a)
-  bool hits_learned = false;   // a K2 launch of this context (or of one it shares what it learned with) has fitted its buffer
-  hipEvent_t ea[8], eb[8];  // begin/end events per stage: 1 K1, 2 K2, 3 K3a, 4 K3s, 5 K3b, 6 K4, 0 misc, 7 whole call
+  DevBuf b_pools, b_stage_pts, b_stage_obs, b_stage_used;
+  hipEvent_t ea[8] = {}, eb[8] = {};  // begin/end events per stage: 1 K1, 2 K2, 3 K3a, 4 K3s, 5 K3b, 6 K4, 0 misc, 7 whole call
   hipEvent_t ecopy[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // D2H of the cloud: one per ring buffer (EG3D_D2H_RING <= 7)
-  uint32_t chain_cap = 384, pool_cap = 0, hyp_cap = 160;
-  uint32_t n_simd = 0;  // SIMDs of the device (4 per CU): sizes the K3a engine's launch
-  int wall_clock_khz = 0;  // rate of wall_clock64() on the device (hipDeviceAttributeWallClockRate)
-  double arena_per_hyp = 16.0;  // hypothesis arena: points per hypothesis to reserve (learned from overflows)
   void* pinned = nullptr;  // the ring of pinned host buffers the D2H copies of a cloud go through (ensure_d2h_ring)
   size_t pinned_cap = 0, ring_chunk = 0;
   // mailbox for the small read-backs of a step (scan totals, counters): pinned host memory mapped into the
@@ -338,6 +357,20 @@ struct eg3d_ctx {
 };
 
 EG3D_API_BEGIN
+inline void share_scene(eg3d_ctx* c, std::shared_ptr<Scene> s) {  // the ONE place a context's copies of SceneFacts are filled
+  static_cast<SceneFacts&>(*c) = *s;
+  c->scene = std::move(s);
+}
+// What a context owns alone from its first moment: its stream, of the given priority (`plain`: no priority asked for), the
+// 16 timing events and the 7 copy events. Whoever makes a context — eg3d_create, clone_ctx — holds it in a CtxGuard until
+// it is whole: every failing exit in between is a plain return, and eg3d_destroy frees what was made.
+enum class StreamPrio { plain, greatest, middle, least };
+int make_own_resources(eg3d_ctx* c, StreamPrio prio);
+using CtxGuard = std::unique_ptr<eg3d_ctx, void (*)(eg3d_ctx*)>;
+// eg3d_clone with the stream priority chosen: share the scene, share the seeds, copy `tune` and `learned`, make own
+// resources. Public clones are `plain`; the lanes of a call (ensure_lanes) ask for theirs.
+int clone_ctx(eg3d_ctx* parent, StreamPrio prio, eg3d_ctx** out);
+
 int scan_exclusive_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one);  // (hipCUB, on c->b_scan_tmp)
 // (key, value) pairs by descending key, queued on the stream (hipCUB, on c->b_scan_tmp): the launch order of the expand stage
 int sort_pairs_desc_u32(eg3d_ctx* c, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n);
@@ -381,7 +414,7 @@ int wrapped_error(const char* what);
 int scan_total_u32(eg3d_ctx* c, const uint32_t* in, uint32_t* out, size_t n_plus_one, uint32_t& total, const char* what);
 
 // The 10 px map of the polyline matcher, built by the first call that needs it on this context or a clone of it and shared
-// by all of them from then on (HostGrids). eg3d_create neither builds nor allocates it.
+// by all of them from then on (Scene). eg3d_create neither builds nor allocates it.
 int ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms);
 CloudView cloud_view(const eg3d_device_edgepoints* d);
 int check_cloud(const eg3d_device_edgepoints* d, const char* who, bool all_arrays);
@@ -391,7 +424,7 @@ int device_flags_error(const char* who, uint32_t flags);
 // The two-call form of a rocPRIM primitive (eg3d_k8_replay.h .. eg3d_k11_louvain.h): ask for the scratch size, make room
 // in `tmp`, call again. A failure is reported under the primitive's `name`.
 template <typename... P, typename... A>
-int prim_call(hipStream_t st, WorkBuf& tmp, const char* name, hipError_t (*prim)(hipStream_t, void*, size_t&, P...), A... a) {
+int prim_call(hipStream_t st, DevBuf& tmp, const char* name, hipError_t (*prim)(hipStream_t, void*, size_t&, P...), A... a) {
   size_t bytes = 0;
   hipError_t e = prim(st, nullptr, bytes, a...);
   if (e == hipSuccess) {
@@ -423,15 +456,6 @@ inline int reduce_by_key_u64(eg3d_ctx* c, const u64* kin, const u64* vin, u64* k
 // A caller's stats / params struct must be at least this library's: "<who>: <arg>->struct_size is smaller than ..."
 int check_struct_size(const char* who, const char* type_name, size_t got, size_t want, const char* arg = "stats");
 
-// The resident seeds as the kernels take them.
-inline SeedsDev seeds_dev(const eg3d_ctx* c) {
-  SeedsDev sd;
-  sd.trk_off = c->b_toff.as<uint32_t>();
-  sd.trk_view = c->b_tview.as<int32_t>();
-  sd.trk_xy = c->b_txy.as<float>();
-  return sd;
-}
-
 // How eg3d_match_polylines_closeness and eg3d_similarity_graph begin: the argument checks (messages prefixed with `who`),
 // the optional seed upload, the range check, and — when the range has track entries and the scene polylines (`active`) —
 // the 10 px map, the counters `ctr` (4 words, zeroed; [0] flags) and the entry -> seed map `svseed` of launch_k9_prep,
@@ -444,7 +468,7 @@ struct SeedRange {
   float ms_grid = 0;
 };
 int open_seed_range(eg3d_ctx* c, const char* who, const eg3d_seeds* seeds, uint32_t b, uint32_t e, const void* out,
-                    WorkBuf eg3d_ctx::*ctr_of, WorkBuf eg3d_ctx::*svseed_of, SeedRange* r);
+                    DevBuf eg3d_ctx::*ctr_of, DevBuf eg3d_ctx::*svseed_of, SeedRange* r);
 
 // Library-owned result arrays: each *dst is allocated (at least one byte) and filled from the device on `st`; an array
 // with no source or nothing to copy is zero-filled instead. The stream is synchronised even after a failure, so that no

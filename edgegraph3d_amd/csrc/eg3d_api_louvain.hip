@@ -62,7 +62,7 @@ extern "C" int eg3d_detect_communities(eg3d_ctx* c, const eg3d_simgraph* g, cons
     g_err = "eg3d_detect_communities: a threshold is negative or not a number";
     return EG3D_ERR_ARG;
   }
-  const uint32_t log2_slots = c->louvain_log2_slots ? c->louvain_log2_slots : (uint32_t)__builtin_ctz(K11_DEFAULT_SLOTS);
+  const uint32_t log2_slots = c->tune.louvain_log2_slots ? c->tune.louvain_log2_slots : (uint32_t)__builtin_ctz(K11_DEFAULT_SLOTS);
   const auto now = [] { return std::chrono::steady_clock::now(); };
   const auto ms_since = [](std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -76,7 +76,7 @@ extern "C" int eg3d_detect_communities(eg3d_ctx* c, const eg3d_simgraph* g, cons
     hipStream_t st = c->stream;
     BUF_TRY(ensure_mailbox(c));
     auto t_stage = now();
-    WorkBuf* const B = c->k11;
+    DevBuf* const B = c->k11;
     const size_t nv = (size_t)n_nodes + 1, ne = std::max<size_t>(nnz0, 1);
     for (int k : {K11B_OFF0, K11B_OFF1, K11B_C, K11B_T, K11B_SIZE0, K11B_SIZE1, K11B_MEMBER, K11B_MINM, K11B_FLAG, K11B_RANK, K11B_CN,
                   K11B_OVF, K11B_OCNT, K11B_OOFF})

@@ -88,11 +88,11 @@ void fill_stage_a_view(const eg3d_ctx* c, BatchState& B) {
 int run_stage_a(eg3d_ctx* c, BatchState& B) {
   hipStream_t st = c->stream;
   B.n_seeds = B.e - B.b;
-  B.sv_base = (*c->h_trk)[B.b];
-  B.n_sv = (*c->h_trk)[B.e] - B.sv_base;
-  B.sd = seeds_dev(c);
+  B.sv_base = c->seeds->trk_off[B.b];
+  B.n_sv = c->seeds->trk_off[B.e] - B.sv_base;
+  B.sd = c->seeds->dev();
   const uint32_t n_sv = B.n_sv;
-  for (WorkBuf* w : {&c->b_sv_seed, &c->b_map_view, &c->b_map_entry, &c->b_raw_cnt, &c->b_raw_off, &c->b_cand_cnt, &c->b_start_cnt,
+  for (DevBuf* w : {&c->b_sv_seed, &c->b_map_view, &c->b_map_entry, &c->b_raw_cnt, &c->b_raw_off, &c->b_cand_cnt, &c->b_start_cnt,
                      &c->b_task_off})  // (one 32-bit word per track entry)
     BUF_TRY(w->ensure(sizeof(uint32_t) * (n_sv + 1)));
   BUF_TRY(c->b_map_n.ensure(sizeof(uint32_t) * (B.n_seeds + 1)));
@@ -113,7 +113,7 @@ int run_stage_a(eg3d_ctx* c, BatchState& B) {
   HIP_TRY(hipEventRecord(c->eb[1], st));
   BUF_TRY(scan_total_u32(c, c->b_start_cnt.as<uint32_t>(), c->b_task_off.as<uint32_t>(), n_sv + 1, B.n_tasks, "tasks"));
   const uint32_t nt = B.n_tasks;
-  for (WorkBuf* w : {&c->b_task_seed, &c->b_task_entry, &c->b_task_hit, &c->b_task_k, &c->b_task_list_off})
+  for (DevBuf* w : {&c->b_task_seed, &c->b_task_entry, &c->b_task_hit, &c->b_task_k, &c->b_task_list_off})
     BUF_TRY(w->ensure(sizeof(uint32_t) * (nt + 1)));
   HIP_TRY(hipMemsetAsync(c->b_task_k.as<uint32_t>() + nt, 0, sizeof(uint32_t), st));
   launch_task_fill(st, B.sd, B.sv_base, n_sv, c->b_sv_seed.as<uint32_t>(), c->b_start_cnt.as<uint32_t>(),
@@ -125,7 +125,7 @@ int run_stage_a(eg3d_ctx* c, BatchState& B) {
   HIP_TRY(hipMemsetAsync(c->b_list_cnt.as<uint32_t>() + B.n_lists, 0, sizeof(uint32_t), st));
   // b_hits: what the earlier calls of this context needed per list, or a first guess (C3' has 2.6 hits per list); K2
   // finds out whether it was enough (k2_settle)
-  const uint64_t want = c->tune.hits_cap0 && !c->hits_learned ? c->tune.hits_cap0 : (uint64_t)((double)B.n_lists * c->hits_per_list) + 4096;
+  const uint64_t want = c->tune.hits_cap0 && !c->learned.hits_learned ? c->tune.hits_cap0 : (uint64_t)((double)B.n_lists * c->learned.hits_per_list) + 4096;
   B.hits_cap = (uint32_t)std::min<uint64_t>(want, 0xffffffffull);
   B.k2_single_pass = true;
   B.n_hits = 0;
@@ -142,8 +142,8 @@ int k2_settle(eg3d_ctx* c, BatchState& B, unsigned long long used, bool* again) 
   if (used > 0xffffffffull) return wrapped_error("epipolar hits");
   if (used <= B.hits_cap) {
     B.n_hits = (uint32_t)used;
-    if (B.n_lists) c->hits_per_list = std::max(c->hits_per_list, 1.0625 * (double)used / (double)B.n_lists);
-    c->hits_learned = true;
+    if (B.n_lists) c->learned.hits_per_list = std::max(c->learned.hits_per_list, 1.0625 * (double)used / (double)B.n_lists);
+    c->learned.hits_learned = true;
     return EG3D_OK;
   }
   if (c->tune.trace_arena)
@@ -393,12 +393,12 @@ int follow_and_select(eg3d_ctx* c, BatchState& B, HostOut& H) {
   else
     while (eng_lanes > 8 && (uint64_t)eng_waves_max * (eng_lanes / 2) >= B.n_hyp) eng_lanes /= 2;
   const uint32_t eng_waves = std::max<uint32_t>(1, std::min<uint32_t>(eng_waves_max, (B.n_hyp + eng_lanes - 1) / eng_lanes));
-  BUF_TRY(c->b_fscratch.ensure(sizeof(HPoint) * std::min<uint32_t>(c->hyp_cap, EG3D_K3A_STAGE_POINTS) * ((size_t)eng_waves * 64)));
+  BUF_TRY(c->b_fscratch.ensure(sizeof(HPoint) * std::min<uint32_t>(c->learned.hyp_cap, EG3D_K3A_STAGE_POINTS) * ((size_t)eng_waves * 64)));
   BUF_TRY(c->b_queue.ensure(4 * sizeof(uint32_t)));
   BUF_TRY(c->b_items.ensure(sizeof(uint32_t) * 2 * ((size_t)B.n_hyp + 1)));
   // hypothesis arena: 16 points per hypothesis to start with (the seed path uses 0.4-11.6, the polyline-set path 23-24: its
   // first call overflows once), more once an attempt of this context has overflowed (it is redone with room)
-  uint32_t arena_cap = std::max<uint32_t>(1u << 16, std::min<uint64_t>((uint64_t)((double)B.n_hyp * c->arena_per_hyp) + 1, 1ull << 26));
+  uint32_t arena_cap = std::max<uint32_t>(1u << 16, std::min<uint64_t>((uint64_t)((double)B.n_hyp * c->learned.arena_per_hyp) + 1, 1ull << 26));
   if (c->tune.arena_cap0) arena_cap = c->tune.arena_cap0;  // tests: force the overflow-and-retry path
   Counters hc;
   BUF_TRY(c->b_cs_task.ensure(sizeof(ChainSeed) * (nt + 1)));
@@ -410,7 +410,7 @@ int follow_and_select(eg3d_ctx* c, BatchState& B, HostOut& H) {
     HIP_TRY(hipEventRecord(c->ea[3], st));
     HIP_TRY(hipMemsetAsync(c->b_queue.p, 0, 4 * sizeof(uint32_t), st));
     launch_k3a_engine(st, eng_waves, eng_waves, eng_lanes, c->ds, B.a, c->b_tasks.as<TaskDesc>(), c->b_hyp_off.as<uint32_t>(),
-                      B.n_hyp, c->b_res.as<HypResult>(), c->b_fscratch.as<HPoint>(), c->hyp_cap, c->b_arena.as<HPoint>(),
+                      B.n_hyp, c->b_res.as<HypResult>(), c->b_fscratch.as<HPoint>(), c->learned.hyp_cap, c->b_arena.as<HPoint>(),
                       arena_cap, c->b_ctr.as<Counters>(), c->b_queue.as<uint32_t>(), c->b_items.as<uint32_t>());
     HIP_TRY(hipEventRecord(c->eb[3], st));
     // ---- K3s and the chain scan are queued right behind K3a; K3a's counters (arena overflow?) and the
@@ -441,7 +441,7 @@ int follow_and_select(eg3d_ctx* c, BatchState& B, HostOut& H) {
       return EG3D_ERR_CAPACITY;
     }
     arena_cap = std::max<uint32_t>(arena_cap * 2, hc.arena_used + (hc.arena_used >> 2));
-    if (B.n_hyp) c->arena_per_hyp = std::max(c->arena_per_hyp, 1.25 * (double)arena_cap / (double)B.n_hyp);
+    if (B.n_hyp) c->learned.arena_per_hyp = std::max(c->learned.arena_per_hyp, 1.25 * (double)arena_cap / (double)B.n_hyp);
   }
   H.flags |= (hc.flags & 0xffu);
   c->k3a_walks_served += hc.k3a_walks_served;
@@ -509,7 +509,7 @@ void launch_engine(eg3d_ctx* c, const BatchState& B, const ExpandState& X) {
              c->b_map_entry.as<uint32_t>(), c->b_map_n.as<uint32_t>(), X.L, c->b_cscratch.as<unsigned char>(), X.stage,
              c->b_couts.as<ChainOut>(), c->b_cpts.as<uint32_t>(), c->b_cobs.as<uint32_t>(), c->b_ctr.as<Counters>(),
              c->b_order.as<uint32_t>(), c->b_queue.as<uint32_t>(),
-             (c->tune.k3b_full || c->k3b_long_latched || (c->V > EG3D_SMALL_SCENE_VIEWS_HOST && !c->tune.assume_short)) ? 1 : 0);
+             (c->tune.k3b_full || c->learned.k3b_long_latched || (c->V > EG3D_SMALL_SCENE_VIEWS_HOST && !c->tune.assume_short)) ? 1 : 0);
 }
 #else
 bool engine_selected(const eg3d_ctx*) { return false; }
@@ -523,7 +523,7 @@ void launch_engine(eg3d_ctx*, const BatchState&, const ExpandState&) {}
 int prepare_expand(eg3d_ctx* c, const BatchState& B, ExpandState& X) {
   hipStream_t st = c->stream;
   // capacities can grow between chunks (overflow -> retry below), so the layout is per chunk
-  X.L = chain_layout(c->chain_cap, c->pool_cap, (uint32_t)c->V);
+  X.L = chain_layout(c->learned.chain_cap, c->learned.pool_cap, (uint32_t)c->V);
   const ChainLayout& L = X.L;
   if (!X.redo_n) {
     const size_t max_scratch = c->tune.max_scratch, left = B.n_chains - X.c0;
@@ -554,14 +554,14 @@ int prepare_expand(eg3d_ctx* c, const BatchState& B, ExpandState& X) {
     const uint64_t guess_pts = 96ull * nc;
     const uint64_t per_pt = (uint64_t)std::min(100, std::max(8, c->V / 2));
     // (EG3D_STAGE_CAP0, tests: until the context has learned a need the area holds that few points, whatever is allocated)
-    const bool cap0 = c->tune.stage_cap0 && !c->stage_cap_pts;
+    const bool cap0 = c->tune.stage_cap0 && !c->learned.stage_cap_pts;
     X.stage_lim_pts = cap0 ? (uint64_t)c->tune.stage_cap0 : ~0ull;
     X.stage_lim_obs = cap0 ? (uint64_t)c->tune.stage_cap0 * per_pt : ~0ull;
-    const uint64_t want_pts = cap0 ? X.stage_lim_pts : std::max<uint64_t>(c->stage_cap_pts, guess_pts);
+    const uint64_t want_pts = cap0 ? X.stage_lim_pts : std::max<uint64_t>(c->learned.stage_cap_pts, guess_pts);
     // (the first guess is capped at 8 GB of observations: a launch that needs more reports its exact need and is
     // repeated once — better than reserving tens of GB per context on a guess for a many-view scene)
     const uint64_t want_obs = cap0 ? X.stage_lim_obs
-                                   : std::max<uint64_t>(c->stage_cap_obs, std::min<uint64_t>(guess_pts * per_pt, (8ull << 30) / sizeof(Obs)));
+                                   : std::max<uint64_t>(c->learned.stage_cap_obs, std::min<uint64_t>(guess_pts * per_pt, (8ull << 30) / sizeof(Obs)));
     BUF_TRY(c->b_stage_pts.ensure(sizeof(StagePt) * (size_t)want_pts));
     BUF_TRY(c->b_stage_obs.ensure(sizeof(Obs) * (size_t)want_obs));
     BUF_TRY(c->b_stage_used.ensure(2 * sizeof(unsigned long long)));
@@ -575,7 +575,7 @@ int prepare_expand(eg3d_ctx* c, const BatchState& B, ExpandState& X) {
   stage.used = c->b_stage_used.as<unsigned long long>();
   BUF_TRY(c->b_couts.ensure(sizeof(ChainOut) * (nc + 1)));
   // (per chain: its points and observations and their scans; the cost, its index and the sorted pair of the launch order)
-  for (WorkBuf* w : {&c->b_cpts, &c->b_cobs, &c->b_cpoff, &c->b_cooff, &c->b_cost, &c->b_cidx, &c->b_cost2, &c->b_order})
+  for (DevBuf* w : {&c->b_cpts, &c->b_cobs, &c->b_cpoff, &c->b_cooff, &c->b_cost, &c->b_cidx, &c->b_cost2, &c->b_order})
     BUF_TRY(w->ensure(sizeof(uint32_t) * (nc + 1)));
   HIP_TRY(hipMemsetAsync(c->b_cpts.as<uint32_t>() + nc, 0, sizeof(uint32_t), st));
   HIP_TRY(hipMemsetAsync(c->b_cobs.as<uint32_t>() + nc, 0, sizeof(uint32_t), st));
@@ -603,7 +603,7 @@ int launch_expand(eg3d_ctx* c, const BatchState& B, bool device_only, ExpandStat
   // long-request path. Few views normally means none (one observation per view), and the smaller builds run; a point
   // that repeats a view can exceed it — the kernel then raises CTR_LONG_REFUSED and the chunk is redone with the general
   // build (k3b_full latched for the context), like the capacity overflows below.
-  const bool general = c->tune.k3b_full || c->k3b_long_latched || c->max_pl_vtx > EG3D_STAGE_VTX_HOST;
+  const bool general = c->tune.k3b_full || c->learned.k3b_long_latched || c->max_pl_vtx > EG3D_STAGE_VTX_HOST;
   if (X.engine)
     launch_engine(c, B, X);
   else
@@ -664,11 +664,11 @@ int judge_expand(eg3d_ctx* c, HostOut& H, ExpandState& X, Expand* verdict) {
   if (hc.flags & CTR_LONG_REFUSED) {
     // a point of a few-views scene carries more than 32 observations (a view repeated on a track): valid input — the
     // general build solves it. Latch it for the context, restore the byte counter and redo this chunk.
-    if (c->k3b_long_latched) {
+    if (c->learned.k3b_long_latched) {
       g_err = "eg3d: internal: the general build of the expand kernel refused a solve";
       return EG3D_ERR_HIP;
     }
-    c->k3b_long_latched = true;
+    c->learned.k3b_long_latched = true;
     if (c->tune.trace_arena) fprintf(stderr, "eg3d: expand launch of %u chains redone: a solve of more than 32 rows -> general build\n", nc);
     return redo_whole_chunk(c, X, true);
   }
@@ -684,21 +684,21 @@ int judge_expand(eg3d_ctx* c, HostOut& H, ExpandState& X, Expand* verdict) {
     if (c->tune.trace_arena)
       fprintf(stderr, "eg3d: expand launch of %u chains redone: staging area %zu points / %zu observations, needed %u / %u\n", nc,
               (size_t)stage.cap_pts, (size_t)stage.cap_obs, np, no);
-    c->stage_cap_pts = std::max<uint64_t>(c->stage_cap_pts, std::max<uint64_t>(np, X.stage_used[0]) + np / 16 + 64);
-    c->stage_cap_obs = std::max<uint64_t>(c->stage_cap_obs, std::max<uint64_t>(no, X.stage_used[1]) + no / 16 + 64);
+    c->learned.stage_cap_pts = std::max<uint64_t>(c->learned.stage_cap_pts, std::max<uint64_t>(np, X.stage_used[0]) + np / 16 + 64);
+    c->learned.stage_cap_obs = std::max<uint64_t>(c->learned.stage_cap_obs, std::max<uint64_t>(no, X.stage_used[1]) + no / 16 + 64);
     return redo_whole_chunk(c, X, true);  // (every chain of the chunk again: what was packed does not fit the area as it is)
   }
   // a chain outgrew its working slice: enlarge the capacities (kept for later calls) and redo
   // this chunk; results of the overflowing attempt are discarded
-  const bool can_grow = ((hc.flags & EG3D_FLAG_CHAIN_OVERFLOW) && c->chain_cap < 8192) ||
-                        ((hc.flags & EG3D_FLAG_OBS_OVERFLOW) && c->pool_cap < (1u << 20));
+  const bool can_grow = ((hc.flags & EG3D_FLAG_CHAIN_OVERFLOW) && c->learned.chain_cap < 8192) ||
+                        ((hc.flags & EG3D_FLAG_OBS_OVERFLOW) && c->learned.pool_cap < (1u << 20));
   if (!can_grow) {  // nothing overflowed — or what did cannot grow any further: the call ends with the flag raised
     X.redo_n = 0;
     *verdict = Expand::done;
     return EG3D_OK;
   }
-  if (hc.flags & EG3D_FLAG_CHAIN_OVERFLOW) c->chain_cap *= 2;
-  if (hc.flags & EG3D_FLAG_OBS_OVERFLOW) c->pool_cap *= 2;
+  if (hc.flags & EG3D_FLAG_CHAIN_OVERFLOW) c->learned.chain_cap *= 2;
+  if (hc.flags & EG3D_FLAG_OBS_OVERFLOW) c->learned.pool_cap *= 2;
   H.flags |= hc.flags & 0xffu & ~(uint32_t)(EG3D_FLAG_CHAIN_OVERFLOW | EG3D_FLAG_OBS_OVERFLOW);  // what the chains that keep their results raised
   {
     float t_launch = 0;  // (the launch is over: its counters have been read back)
@@ -722,7 +722,7 @@ int judge_expand(eg3d_ctx* c, HostOut& H, ExpandState& X, Expand* verdict) {
   }
   if (c->tune.trace_arena)
     fprintf(stderr, "eg3d: expand launch of %u chains: %u outgrew their slices (flags %u); relaunching %s with %u points / %u "
-                    "observation slots per chain\n", X.n_launch, n_again, hc.flags & 3u, n_again ? "those" : "the chunk", c->chain_cap, c->pool_cap);
+                    "observation slots per chain\n", X.n_launch, n_again, hc.flags & 3u, n_again ? "those" : "the chunk", c->learned.chain_cap, c->learned.pool_cap);
   if (!n_again) return redo_whole_chunk(c, X, false);  // (the engine form, or nothing listed: the whole chunk again)
   X.redo_n = n_again;
   *verdict = Expand::redo_listed;
@@ -756,8 +756,8 @@ int emit_chunk(eg3d_ctx* c, const BatchState& B, UnitTurn& T, HostOut& H, const 
   BUF_TRY(oc->o_seg.ensure_keep(sizeof(uint32_t) * (O0 + no + 1), sizeof(uint32_t) * O0, st));
   BUF_TRY(oc->o_xy.ensure_keep(sizeof(float) * 2 * (O0 + no + 1), sizeof(float) * 2 * O0, st));
   HIP_TRY(hipEventRecord(c->ea[6], st));
-  c->stage_cap_pts = std::max<uint64_t>(c->stage_cap_pts, (uint64_t)np + np / 16);  // sizing hint of the next launch
-  c->stage_cap_obs = std::max<uint64_t>(c->stage_cap_obs, (uint64_t)no + no / 16);
+  c->learned.stage_cap_pts = std::max<uint64_t>(c->learned.stage_cap_pts, (uint64_t)np + np / 16);  // sizing hint of the next launch
+  c->learned.stage_cap_obs = std::max<uint64_t>(c->learned.stage_cap_obs, (uint64_t)no + no / 16);
   launch_k4(st, c->b_tasks.as<TaskDesc>(), c->b_chains.as<ChainSeed>() + X.c0, X.nc, X.stage,
             c->b_couts.as<ChainOut>(), c->b_cpoff.as<uint32_t>(), c->b_cooff.as<uint32_t>(), P0, O0, key0,
             oc->o_X.as<float>(), oc->o_off.as<eg3d_off_t>(), oc->o_view.as<int32_t>(), oc->o_pl.as<uint32_t>(),
@@ -948,7 +948,7 @@ int run_batch(eg3d_ctx* c, uint32_t b, uint32_t e, UnitTurn& T, HostOut& H) {
   // per seed 12 + k*12 + k*64 + k(k-1)*72 (the vertices touched and the output were
   // added by stage B)
   for (uint32_t sd_i = b; sd_i < e; sd_i++) {
-    const uint64_t k = (*c->h_trk)[sd_i + 1] - (*c->h_trk)[sd_i];
+    const uint64_t k = c->seeds->trk_off[sd_i + 1] - c->seeds->trk_off[sd_i];
     H.bytes_algorithmic += 12 + k * 12 + k * 64 + k * (k - 1) * 72;
   }
   return EG3D_OK;
@@ -960,7 +960,7 @@ int run_batch(eg3d_ctx* c, uint32_t b, uint32_t e, UnitTurn& T, HostOut& H) {
 // `matched` (null: none) is the caller's interval table on the device: samples and hits inside a held interval are left out
 // (k_n1_samples / k_n1_hits <., true>); skip_cnt / drop_cnt (may be null) receive the per-polyline / per-task counts of them.
 int run_sets_stage_a(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
-                     uint32_t set_e, const IvTable* matched, WorkBuf* skip_cnt, WorkBuf* drop_cnt, BatchState& B) {
+                     uint32_t set_e, const IvTable* matched, DevBuf* skip_cnt, DevBuf* drop_cnt, BatchState& B) {
   hipStream_t st = c->stream;
   const uint32_t V = (uint32_t)c->V;
   memset(&B, 0, sizeof(B));
@@ -984,7 +984,7 @@ int run_sets_stage_a(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off
     return EG3D_ERR_CAPACITY;
   }
   BUF_TRY(c->b_start_hits.ensure(sizeof(Obs) * (nt + 1)));  // the samples
-  for (WorkBuf* w : {&c->b_task_seed, &c->b_task_entry, &c->b_task_hit, &c->b_task_k /* first row of the task's set */,
+  for (DevBuf* w : {&c->b_task_seed, &c->b_task_entry, &c->b_task_hit, &c->b_task_k /* first row of the task's set */,
                      &c->b_task_list_off})
     BUF_TRY(w->ensure(sizeof(uint32_t) * (nt + 1)));
   launch_n1_samples(st, true, c->ds, sets, n_rows_total, item_b, n_items, nullptr, c->b_raw_off.as<uint32_t>(),
@@ -1072,41 +1072,20 @@ T* dup_to_malloc(const std::vector<T>& v, size_t extra = 0) {
 // and host thread — and their clouds are concatenated in unit order (CallSink). What that buys on one GPU: the candidate /
 // hypothesis stages and the D2H copy of one unit overlap the expand stage of another, and the thin tail of one expand launch
 // (a few long chains on an otherwise empty GPU) is filled by the next unit's chains.
-// what a lane has learned about the scene's needs serves all of them (capacities only grow)
-static void merge_learned(eg3d_ctx* to, const eg3d_ctx* from) {
-  if (to == from) return;
-  to->chain_cap = std::max(to->chain_cap, from->chain_cap);
-  to->pool_cap = std::max(to->pool_cap, from->pool_cap);
-  to->arena_per_hyp = std::max(to->arena_per_hyp, from->arena_per_hyp);
-  to->hits_per_list = std::max(to->hits_per_list, from->hits_per_list);
-  to->hits_learned = to->hits_learned || from->hits_learned;
-  to->k3b_long_latched = to->k3b_long_latched || from->k3b_long_latched;
-}
+// A lane takes the owner's current seeds and what the owner has learned (run_pipelined gives back what the lanes learned:
+// it serves all of them, capacities only grow). Lane 0 is the owner itself.
 static void lane_share_inputs(eg3d_ctx* owner, eg3d_ctx* l) {
-  if (l == owner) return;
-  l->n_seeds = owner->n_seeds;
-  l->h_trk = owner->h_trk;
-  l->b_toff = owner->b_toff;
-  l->b_tview = owner->b_tview;
-  l->b_txy = owner->b_txy;
-  l->seeds_owner = owner->seeds_owner;
-  merge_learned(l, owner);
+  l->seeds = owner->seeds;
+  l->learned.merge(owner->learned);
 }
 static int ensure_lanes(eg3d_ctx* c, int n) {
   if (c->lanes.empty()) c->lanes.push_back(c);
   while ((int)c->lanes.size() < n) {
+    const StreamPrio prio = !c->tune.lane_priorities ? StreamPrio::plain : c->lanes.size() == 1 ? StreamPrio::middle : StreamPrio::least;
     eg3d_ctx* l = nullptr;
-    BUF_TRY(eg3d_clone(c, &l));
+    BUF_TRY(clone_ctx(c, prio, &l));  // (whole or not at all: nothing below can fail)
     l->is_lane = true;
     l->tune.lanes = 1;
-    if (c->tune.lane_priorities) {
-      int least = 0, greatest = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      (void)hipStreamDestroy(l->stream);
-      l->stream = nullptr;
-      const int mid = (least + greatest) / 2;
-      HIP_TRY(hipStreamCreateWithPriority(&l->stream, hipStreamNonBlocking, c->lanes.size() == 1 ? mid : least));
-    }
     c->lanes.push_back(l);
   }
   return EG3D_OK;
@@ -1181,7 +1160,7 @@ static int run_pipelined(eg3d_ctx* c, CallSink& S, const std::vector<UnitRange>&
   }
   worker(c);
   for (auto& t : th) t.join();
-  for (int l = 0; l < n_lanes; l++) merge_learned(c, c->lanes[(size_t)l]);
+  for (int l = 0; l < n_lanes; l++) c->learned.merge(c->lanes[(size_t)l]->learned);
   if (S.failed) {
     g_err = S.err;
     return S.rc;
@@ -1266,7 +1245,7 @@ static int lanes_for(const eg3d_ctx* c, int device_only) {
   if (device_only) return 1;
   // every lane owns a full slot arena (the residency of the expand kernel x the slice size): on many-view scenes that is
   // 17 GB per lane (C4) for a 3 % gain with the copy and a loss without — such scenes stay on the context alone
-  const size_t arena = chain_layout(c->chain_cap, c->pool_cap, (uint32_t)c->V).total * 8 * (size_t)c->slots_per_xcd;
+  const size_t arena = chain_layout(c->learned.chain_cap, c->learned.pool_cap, (uint32_t)c->V).total * 8 * (size_t)c->slots_per_xcd;
   if (arena > ((size_t)4 << 30)) return 1;
   // ... and a small cloud has no copy worth hiding (C3-real, 0.3 MB: 3.3 ms uncut, 5.1 ms on three lanes)
   return c->host_calls > 0 && c->last_host_cloud_bytes >= ((uint64_t)4 << 20) ? Tunables::kHostCallLanes : 1;
@@ -1278,7 +1257,7 @@ static int lanes_for(const eg3d_ctx* c, int device_only) {
 static std::vector<UnitRange> plan_seed_units(const eg3d_ctx* c, uint32_t b, uint32_t e, int lanes) {
   const uint32_t SEED_BATCH = 16384, MIN_UNIT = 128;
   const uint32_t n = e - b;
-  const std::vector<uint32_t>& trk = *c->h_trk;
+  const std::vector<uint32_t>& trk = c->seeds->trk_off;
   auto cum = [&](uint32_t i) { return (double)trk[i] + 1e-3 * (double)i; };  // (+ a little per seed: seeds without tracks still count)
   if (lanes <= 1 && !c->tune.units) {
     std::vector<UnitRange> out;
@@ -1331,7 +1310,7 @@ static int match_call(eg3d_ctx* c, int device_only, bool keyed_by_sample, const 
 
 extern "C" int eg3d_match_resident(eg3d_ctx* c, uint32_t b, uint32_t e, int device_only, eg3d_edgepoints* out,
                                    eg3d_stage_times* times) {
-  if (!c || !out || b > e || e > c->n_seeds) {
+  if (!c || !out || b > e || e > c->seeds->n_seeds) {
     g_err = "eg3d_match_resident: bad arguments (seeds uploaded?)";
     return EG3D_ERR_ARG;
   }
@@ -1399,13 +1378,13 @@ extern "C" int eg3d_check_polyline_sets(const eg3d_polyline_sets* ps, int32_t n_
   return EG3D_OK;
 }
 
-// The caller's matched_polyline_intervals for the duration of ONE call: host arrays are uploaded into the WorkBufs here
+// The caller's matched_polyline_intervals for the duration of ONE call: host arrays are uploaded into the DevBufs here
 // (released with the call), device arrays are read in place. Everything is checked before anything is indexed with it:
 // what needs no scene on the host for host arrays (their total sizes the upload), then check_interval_row, one lane per
 // row, for both kinds. active: the table holds at least one interval.
 namespace {
 struct MatchedCall {
-  WorkBuf off, sseg, sxy, eseg, exy, bad;
+  DevBuf off, sseg, sxy, eseg, exy, bad;
   IvTable dev{};
   bool active = false;
 };
@@ -1570,7 +1549,7 @@ extern "C" int eg3d_polyline_set_candidates(eg3d_ctx* c, const eg3d_polyline_set
   SetsDev sd;
   BUF_TRY(prepare_sets(c, ps, sd));
   const uint32_t V = (uint32_t)c->V;
-  WorkBuf skip_cnt, drop_cnt;
+  DevBuf skip_cnt, drop_cnt;
   BatchState B;
   BUF_TRY(run_sets_stage_a(c, sd, ps->row_off, ps->n_sets * V, set_b, set_e, matched, &skip_cnt, &drop_cnt, B));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1688,7 +1667,7 @@ extern "C" int eg3d_candidates_run(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_
     }
     o_start_off.push_back((uint32_t)o_start_pl.size());
   }
-  for (uint32_t t = 0; t < nt; t++) o_task_sv[t] = (*c->h_trk)[task_seed[t]] - B.sv_base + task_entry[t];
+  for (uint32_t t = 0; t < nt; t++) o_task_sv[t] = c->seeds->trk_off[task_seed[t]] - B.sv_base + task_entry[t];
   // the tasks' regions of b_hits lie in the order the tasks claimed them: gathered here in (task, list) order, the CSR
   // from the counts
   std::vector<uint32_t> list_off(B.n_lists + 1, 0);

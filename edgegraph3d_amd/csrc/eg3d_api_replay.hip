@@ -82,7 +82,7 @@ extern "C" int eg3d_replay_device(eg3d_ctx* c, const eg3d_device_edgepoints* clo
     HIP_TRY(hipMemsetAsync(g.iv_off, 0, 8 * (NP + 1), st));
   } else {
     // ---- nodes
-    slots = c->replay_table_bits ? std::max<uint64_t>(1ull << c->replay_table_bits, pow2_above(2 * n_pairs))
+    slots = c->tune.replay_table_bits ? std::max<uint64_t>(1ull << c->tune.replay_table_bits, pow2_above(2 * n_pairs))
                                  : pow2_above(std::max<uint64_t>(4 * n_pairs, 63));
     BUF_TRY(c->k8_slot.ensure(4 * slots));
     BUF_TRY(c->k8_last.ensure(4 * slots));

@@ -22,7 +22,7 @@ extern "C" int eg3d_similarity_graph(eg3d_ctx* c, const eg3d_seeds* seeds, uint3
   BUF_TRY(open_seed_range(c, who, seeds, b, e, out, &eg3d_ctx::k10_ctr, &eg3d_ctx::k10_svseed, &r));
   hipStream_t st = c->stream;
   const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_pts = r.n_seeds, sv_base = r.sv_base, n_sv = r.n_sv;
-  const uint64_t budget = c->simgraph_pair_budget ? c->simgraph_pair_budget : EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT;
+  const uint64_t budget = c->tune.simgraph_pair_budget ? c->tune.simgraph_pair_budget : EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT;
   uint32_t n_pair = 0, n_nodes = 0, n_uniq = 0, n_kept = 0, n_chunks = 0;
   uint64_t n_inst = 0;
   float ms_search = 0, ms_graph = 0, ms_weights = 0, ms_copy = 0;
@@ -180,7 +180,7 @@ extern "C" int eg3d_similarity_graph(eg3d_ctx* c, const eg3d_seeds* seeds, uint3
   eg3d_simgraph m;
   memset(&m, 0, sizeof(m));
   const size_t n_adj = 2 * (size_t)n_kept;
-  const auto dev = [&](const WorkBuf& w) { return n_pair ? w.p : nullptr; };  // (an empty range: all-zero arrays of their sizes)
+  const auto dev = [&](const DevBuf& w) { return n_pair ? w.p : nullptr; };  // (an empty range: all-zero arrays of their sizes)
   BUF_TRY(copy_out(st, who,
                    {{&m.node_view, dev(c->k10_nodeview), 4 * (size_t)n_nodes}, {&m.node_pl, dev(c->k10_nodepl), 4 * (size_t)n_nodes},
                     {&m.adj_off, dev(c->k10_adjoff), 4 * ((size_t)n_nodes + 1)}, {&m.adj_node, dev(c->k10_adjnode), 4 * n_adj},
