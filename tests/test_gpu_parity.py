@@ -8,6 +8,7 @@ import pytest
 
 import cbuild
 from edgegraph3d_amd import api, host
+from filter_cloud_cases import _k5_lists
 from parity_util import compare_edgepoints
 
 pytestmark = pytest.mark.gpu
@@ -168,29 +169,6 @@ def test_gn_filter_parity(have_gpu):
     Xr, ir = _oracle(s.scene).gn_filter(Xs, big_off, big_view, big_xy, 2.25, nthreads=8)
     assert np.array_equal(inl, ir) and np.array_equal(Xo.view(np.uint32), Xr.view(np.uint32)) and inl.mean() > 0.5
     ctx.close()
-
-
-def _k5_lists(s, rng, lengths_per_block):
-    """Points of the rig of `s` with the given list lengths, 256 points (one k5_gn_filter block) per entry: views drawn
-    without repetition while the rig has enough, observations = projection + noise of 0.3 .. 2.5 px (a point's own level:
-    both sides of the mse threshold), start = true point + 1.5 per axis."""
-    P = s.scene_np()["cam_P"].reshape(-1, 4, 4)[:, :3, :].astype(np.float64)
-    V = len(P)
-    Xt, _, _, _ = s.points(256 * len(lengths_per_block))
-    Xt = Xt.astype(np.float64)
-    ks = np.concatenate([np.resize(np.asarray(b), 256) for b in lengths_per_block]).astype(np.int64)
-    views = []
-    for k in ks:
-        v = rng.choice(V, min(int(k), V), replace=False)
-        views.append(np.concatenate([v, rng.integers(0, V, int(k) - len(v))]) if k > V else v)
-    off = np.concatenate([[0], np.cumsum(ks)]).astype(np.uint32)
-    view = np.concatenate(views).astype(np.int32)
-    pid = np.repeat(np.arange(len(ks)), ks)
-    h = np.einsum("nij,nj->ni", P[view], np.concatenate([Xt[pid], np.ones((len(pid), 1))], 1))
-    sigma = rng.uniform(0.3, 2.5, len(ks))[pid][:, None]
-    xy = (h[:, :2] / h[:, 2:3] + rng.normal(0, 1, (len(pid), 2)) * sigma).astype(np.float32)
-    X0 = (Xt + rng.normal(0, 1.5, Xt.shape)).astype(np.float32)
-    return X0, off, view, xy
 
 
 @pytest.mark.parametrize("n_views", [256, 257])
