@@ -129,6 +129,21 @@ EG3D_RCCL = {
     "eg3d_concat_edgepoints": (i32, [vp, i32, P(D.DeviceEdgePoints), vp, P(D.DeviceEdgePoints)]),
 }
 
+# include/eg3d_accumulate.h (libeg3d.so, libeg3d_dlt4x4.so): the replay that accumulates over the calls of a run
+EG3D_ACCUMULATE = {
+    "eg3d_replay_accumulate": (i32, [vp, P(D.DeviceEdgePoints), i32, P(D.DeviceGraph3D), P(D.Graph3D), P(D.ReplayStats)]),
+    "eg3d_replay_accumulated": (i32, [vp, u64p, u64p, u64p]),
+}
+
+# include/eg3d_host_accumulate.h (libeg3d_host.so); the eg3d_replay_state handle is a void pointer here
+EG3D_HOST_ACCUMULATE = {
+    "eg3d_host_replay_state_create": (vp, [P(D.Scene)]),
+    "eg3d_host_replay_state_add": (i32, [vp, P(D.EdgePoints)]),
+    "eg3d_host_replay_state_graph": (i32, [vp, P(D.Graph3D)]),
+    "eg3d_host_replay_state_points": (u64, [vp]),
+    "eg3d_host_replay_state_destroy": (None, [vp]),
+}
+
 
 def bind(lib, table):
     """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""

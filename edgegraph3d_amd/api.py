@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D, bind
+from ._cabi import EG3D, EG3D_ACCUMULATE, bind
 
 _LIB = None
 
@@ -34,12 +34,14 @@ def lib():
         if not os.path.exists(path):
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
-        _LIB = bind(C.CDLL(path), EG3D)
+        _LIB = bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE)
     return _LIB
 
 
 # every symbol include/eg3d.h declares (tests/test_abi.py holds the table to the header without a GPU)
 EXPORTED_SYMBOLS = list(EG3D)
+# ... and those of include/eg3d_accumulate.h (tests/test_replay_accumulate.py does the same for that header)
+ACCUMULATE_SYMBOLS = list(EG3D_ACCUMULATE)
 
 
 def _check(rc, what):
@@ -535,6 +537,32 @@ class Context:
             d = D.graph3d_to_dict(g)
             lib().eg3d_free_graph3d(C.byref(g))
         return d, dv, {f[0]: getattr(st, f[0]) for f in D.ReplayStats._fields_}
+
+    # ---- the replay that accumulates over the calls of a run (include/eg3d_accumulate.h) ----
+    def replay_accumulate(self, cloud=None, reset=False, to_host=True, materialise=True):
+        """eg3d_replay_accumulate: add `cloud` (a DeviceEdgePoints; None = the last device output) to this context's
+        accumulator; reset starts a new graph with it. Returns (graph or None, DeviceGraph3D or None, stats dict). The
+        graph is that of all clouds added so far, as host.replay_matches builds it from their concatenation;
+        materialise=False only adds the claims (both None). The DeviceGraph3D views buffers of the accumulator that stay
+        valid until the next replay_accumulate on this context."""
+        g, dv, st = D.Graph3D(), D.DeviceGraph3D(), D.ReplayStats()
+        st.struct_size = C.sizeof(D.ReplayStats)
+        to_host = to_host and materialise
+        _check(lib().eg3d_replay_accumulate(self._h, C.byref(cloud) if cloud is not None else None, 1 if reset else 0,
+                                            C.byref(dv) if materialise else None, C.byref(g) if to_host else None,
+                                            C.byref(st)), "eg3d_replay_accumulate")
+        d = None
+        if to_host:
+            d = D.graph3d_to_dict(g)
+            lib().eg3d_free_graph3d(C.byref(g))
+        return d, (dv if materialise else None), {f[0]: getattr(st, f[0]) for f in D.ReplayStats._fields_}
+
+    def replay_accumulated(self):
+        """eg3d_replay_accumulated: {"n_points", "n_pairs", "state_bytes"} of the accumulator; n_points is the index_base
+        of the next cloud of the run for dedup_device."""
+        n, p, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().eg3d_replay_accumulated(self._h, C.byref(n), C.byref(p), C.byref(b)), "eg3d_replay_accumulated")
+        return {"n_points": int(n.value), "n_pairs": int(p.value), "state_bytes": int(b.value)}
 
     def fetch_device_graph(self, dv):
         """Test/bench plumbing: the graph a DeviceGraph3D views (HBM), copied into the dict graph3d_to_dict gives."""

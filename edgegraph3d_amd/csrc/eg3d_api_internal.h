@@ -17,6 +17,7 @@
 #include "../../include/eg3d.h"
 #include "eg3d_kernels.h"
 #include "eg3d_k8_replay.h"
+#include "eg3d_k8a_accumulate.h"
 #include "eg3d_k9_polymatch.h"
 #include "eg3d_k10_simgraph.h"
 #include "eg3d_k11_louvain.h"
@@ -276,6 +277,34 @@ struct Learned {
     k3b_long_latched = k3b_long_latched || o.k3b_long_latched;
   }
 };
+// The accumulator of eg3d_replay_accumulate (K8a), one per context (a clone starts with an empty one): the running totals,
+// the key the last cloud ended on, and the state on the device — O(nodes + polylines + scene vertices), never the points of
+// the run. The scratch of a call is K8's (eg3d_ctx::k8_*: nothing of it outlives a call of either entry point); the state
+// and the materialised graph are these buffers alone, so eg3d_replay_device and the accumulator do not meet.
+struct ReplayAcc {
+  bool valid = true;      // false: a call failed after it began to change the state; only reset != 0 is accepted
+  bool have_last = false;
+  uint32_t last_key[4] = {0, 0, 0, 0};
+  uint64_t n_points = 0, n_pairs = 0, n_nodes = 0, n_pl = 0, n_iv = 0, slots = 0;
+  bool map_ready = false;  // the claim map is filled with K8_UNCLAIMED (or holds the run's claims)
+  int cur = 0;             // pl_key[cur] holds the sorted keys
+  DevBuf slot, node_X, node_point, pl_start, pl_end, pl_key[2];  // node table; the append-only arrays; sorted polyline keys
+  DevBuf map, r_ss, r_es, r_sxy, r_exy, cnt;                      // claim map, dense records, the interval counter
+  DevBuf node_id, is_new;                                         // per point of the current cloud
+  DevBuf conn_off, conn_pl, iv_off, iv_ss, iv_sxy, iv_es, iv_exy;  // the graph as last materialised
+  void clear() {  // an empty accumulator that keeps its allocations
+    valid = true;
+    have_last = map_ready = false;
+    n_points = n_pairs = n_nodes = n_pl = n_iv = slots = 0;
+    cur = 0;
+  }
+  size_t state_bytes() const {
+    size_t b = 0;
+    for (const DevBuf* d : {&slot, &node_X, &node_point, &pl_start, &pl_end, &pl_key[0], &pl_key[1], &map, &r_ss, &r_es, &r_sxy, &r_exy, &cnt})
+      b += d->cap;
+    return b;
+  }
+};
 EG3D_API_END
 
 // (an internal header: only the eg3d_api*.hip include it, and they are written in these namespaces)
@@ -314,6 +343,7 @@ struct eg3d_ctx : SceneFacts {
   // the scene's segments with its flags and scan. Result (valid until the next replay): the arrays of eg3d_graph3d.
   DevBuf k8_cnt, k8_slot, k8_last, k8_firstof, k8_flag, k8_rank, k8_lastof, k8_plid, k8_key[2], k8_val[2], k8_map, k8_sflag, k8_pos;
   DevBuf g_nodeX, g_nodept, g_pls, g_ple, g_conoff, g_conpl, g_ivoff, g_ivss, g_ivsxy, g_ives, g_ivexy;
+  ReplayAcc ka;  // eg3d_replay_accumulate (K8a): the state of the run and its materialised graph
   // eg3d_match_polylines_closeness (K9). Work: entry -> seed, the per-entry search results, the accept flags and their scan,
   // the match graph over the scene's polylines, the sort buffers, counters + flag word. Result on the device: the accepted
   // ids, row_off, pl_ids (copied to the caller's library-owned arrays at the end of the call).

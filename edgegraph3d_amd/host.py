@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D_HOST, bind
+from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, bind
 
 _LIB = None
 
@@ -16,7 +16,7 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_host.so")
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
-        _LIB = bind(C.CDLL(path), EG3D_HOST)
+        _LIB = bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE)
     return _LIB
 
 
@@ -139,6 +139,48 @@ def replay_matches(scene_ptr, cloud):
     d = D.graph3d_to_dict(g)
     lib().eg3d_host_free_graph3d(C.byref(g))
     return d
+
+
+class ReplayState:
+    """The matches manager as an object that lives through a run (include/eg3d_host_accumulate.h): add(cloud) the clouds
+    of the run in order; graph() is at any time what replay_matches builds from their concatenation. `scene_ptr` is
+    borrowed: keep its owner for as long as the state."""
+
+    def __init__(self, scene_ptr):
+        self._h = lib().eg3d_host_replay_state_create(scene_ptr)
+        if not self._h:
+            raise RuntimeError("eg3d_host_replay_state_create failed")
+
+    def add(self, cloud):
+        """Raises ValueError when the cloud is refused (the state is then as it was)."""
+        ep = D.EdgePointsArrays(cloud)
+        rc = lib().eg3d_host_replay_state_add(self._h, C.byref(ep.c))
+        if rc != 0:
+            raise ValueError("eg3d_host_replay_state_add refused the cloud (%d)" % rc)
+
+    def graph(self):
+        g = D.Graph3D()
+        rc = lib().eg3d_host_replay_state_graph(self._h, C.byref(g))
+        if rc != 0:
+            raise RuntimeError("eg3d_host_replay_state_graph failed (%d)" % rc)
+        d = D.graph3d_to_dict(g)
+        lib().eg3d_host_free_graph3d(C.byref(g))
+        return d
+
+    @property
+    def n_points(self):
+        return int(lib().eg3d_host_replay_state_points(self._h))
+
+    def close(self):
+        if self._h:
+            lib().eg3d_host_replay_state_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def is_matched(scene_ptr, graph, view, pl, seg, xy):

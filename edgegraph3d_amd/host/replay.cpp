@@ -19,10 +19,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <unordered_set>
 #include <vector>
 
 #include "../../include/eg3d_host.h"
+#include "../../include/eg3d_host_accumulate.h"
 
 namespace {
 
@@ -32,12 +34,26 @@ struct NodeTable {
   std::vector<uint32_t> slot;  // node id + 1, 0 = empty
   std::vector<float> key;      // [slots][3] the coordinates the slot was inserted with
   uint64_t mask = 0;
-  explicit NodeTable(uint64_t n_points) {
-    uint64_t cap = 64;
-    while (cap < n_points * 2 + 16) cap <<= 1;
-    slot.assign(cap, 0);
-    key.assign(cap * 3, 0.f);
+  uint64_t used = 0;  // occupied slots
+  // Room for `more` further insertions with at least half the slots free: the table of one cloud of n points (two
+  // insertions per point at the most: a NaN point makes a node per lookup) is what it was when a replay took one cloud;
+  // a state that accumulates grows it by rehashing the stored keys (a NaN key parks at a free slot again).
+  void reserve(uint64_t more) {
+    uint64_t cap = slot.empty() ? 64 : slot.size();
+    while (cap < (used + more) * 2 + 16) cap <<= 1;
+    if (cap == slot.size()) return;
+    std::vector<uint32_t> old_slot(cap, 0);
+    std::vector<float> old_key(cap * 3, 0.f);
+    old_slot.swap(slot);
+    old_key.swap(key);
     mask = cap - 1;
+    for (size_t i = 0; i < old_slot.size(); i++) {
+      if (!old_slot[i]) continue;
+      bool found;
+      const uint64_t j = find(&old_key[i * 3], found);
+      slot[j] = old_slot[i];
+      memcpy(&key[j * 3], &old_key[i * 3], 3 * sizeof(float));
+    }
   }
   static uint32_t canon(float f) {
     uint32_t u;
@@ -86,14 +102,38 @@ bool ordered(float ax, float ay, float bx, float by, float cx, float cy) {
 
 }  // namespace
 
-extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoints* pts, eg3d_graph3d* out) {
-  if (!sc || !pts || !out) return -1;
-  memset(out, 0, sizeof(*out));
-  if (sc->n_views < 1 || !sc->view_pl_off || !sc->pl_vtx_off || !sc->vtx_xy) return -1;
+// The manager itself: everything the replay of one cloud used to keep on its stack lives here, so that the clouds of a
+// run can be added one after the other (include/eg3d_host_accumulate.h). Points are numbered through the run (n_points
+// added so far + the index within the cloud): node_point holds those numbers, and every first-claim rule below sees the
+// earlier clouds' claims standing. eg3d_host_replay_matches is one state that takes one cloud.
+struct eg3d_replay_state {
+  const eg3d_scene* sc = nullptr;
+  NodeTable table;
+  std::vector<float> node_X;
+  std::vector<uint64_t> node_point;
+  std::vector<uint32_t> head, tail, cnt;      // per node: connection list
+  std::vector<uint32_t> link_pl, link_next;   // list cells
+  std::vector<uint32_t> pl_s, pl_e;
+  uint64_t real_nodes = 0;
+  struct Iv {
+    uint32_t gpl, s_seg, e_seg;
+    float sx, sy, ex, ey;
+  };
+  std::vector<Iv> ivs;
+  std::unordered_set<uint64_t> iv_keys;
+  uint64_t n_points = 0;     // points of the clouds added so far
+  uint32_t last_key[4] = {0, 0, 0, 0};  // key of the last point added (a cloud that would continue its chain is refused)
+  bool have_last = false;
+  int add(const eg3d_edgepoints* pts);
+  int graph(eg3d_graph3d* out);
+};
+
+int eg3d_replay_state::add(const eg3d_edgepoints* pts) {
+  if (!pts) return -1;
   const int V = sc->n_views;
   const uint64_t N = pts->n_points;
-  const uint32_t NP = sc->view_pl_off[V];
-  if (N >= 0xfffffff0ull) return -3;  // node / polyline ids are 32-bit here (documented narrowing)
+  const uint64_t base = n_points;
+  if (N >= 0xfffffff0ull || base + N >= 0xfffffff0ull) return -3;  // node / polyline ids are 32-bit here (documented narrowing)
   // the cloud normally comes from eg3d_match_*; one built by the caller is checked before its ids index the scene
   if (N && (!pts->X || !pts->obs_off || !pts->key)) return -1;
   for (uint64_t p = 0; p < N; p++)
@@ -108,13 +148,16 @@ extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoi
     const uint32_t nv = sc->pl_vtx_off[g + 1] - sc->pl_vtx_off[g];
     if (nv < 2 || pts->obs_seg[o] >= nv - 1) return -1;  // a segment index of a polyline that has segments
   }
-  NodeTable table(N);
-  std::vector<float> node_X;
-  std::vector<uint64_t> node_point;
-  std::vector<uint32_t> head, tail, cnt;      // per node: connection list
-  std::vector<uint32_t> link_pl, link_next;   // list cells
-  std::vector<uint32_t> pl_s, pl_e;
-  uint64_t real_nodes = 0;
+  // a cloud is made of whole chains: one whose first point continues the chain the last cloud ended on is refused
+  if (N && have_last && pts->key[0] == last_key[0] && pts->key[1] == last_key[1] && pts->key[2] == last_key[2] &&
+      pts->key[3] == last_key[3] + 1)
+    return -1;
+  // ---- nothing was changed up to here; from here on nothing fails
+  if (!N) return 0;
+  table.reserve(N);
+  n_points = base + N;
+  memcpy(last_key, pts->key + 4 * (N - 1), sizeof(last_key));
+  have_last = true;
 
   auto node_valid = [&](uint32_t id) { return node_X[3 * (size_t)id] != kInvalid && node_X[3 * (size_t)id + 1] != kInvalid; };
   auto new_node = [&](const float* X) {
@@ -143,6 +186,7 @@ extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoi
       return nid;
     }
     const uint32_t id = new_node(X);
+    table.used++;
     table.slot[i] = id + 1;
     table.key[i * 3] = X[0];
     table.key[i * 3 + 1] = X[1];
@@ -183,12 +227,6 @@ extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoi
   };
 
   // matched 2-D intervals
-  struct Iv {
-    uint32_t gpl, s_seg, e_seg;
-    float sx, sy, ex, ey;
-  };
-  std::vector<Iv> ivs;
-  std::unordered_set<uint64_t> iv_keys;
   auto insert_iv = [&](uint32_t gpl, const Plp& a, const Plp& b) {
     if (!iv_keys.insert(((uint64_t)gpl << 32) | a.seg).second) return;  // std::set keyed on start.segment_index
     ivs.push_back({gpl, a.seg, b.seg, a.x, a.y, b.x, b.y});
@@ -218,8 +256,8 @@ extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoi
     const uint32_t na = node_of(pts->X + 3 * (i - 1));
     const uint32_t nb = node_of(pts->X + 3 * i);
     add_connection(na, nb);
-    node_point[na] = i - 1;  // set_observations: last writer wins (first, then second)
-    node_point[nb] = i;
+    node_point[na] = base + i - 1;  // set_observations: last writer wins (first, then second)
+    node_point[nb] = base + i;
     std::fill(slot1.begin(), slot1.end(), -1);
     std::fill(slot2.begin(), slot2.end(), -1);
     for (uint64_t o = pts->obs_off[i - 1]; o < pts->obs_off[i]; o++) slot1[pts->obs_view[o]] = (int64_t)o;
@@ -264,8 +302,14 @@ extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoi
       add_2dsegment(v, pl2, ext, b);
     }
   }
+  return 0;
+}
 
-  // ---- flatten
+// ---- flatten: a snapshot; the state is as it was (the order of `ivs` carries nothing: iv_keys decides the claims)
+int eg3d_replay_state::graph(eg3d_graph3d* out) {
+  if (!out) return -1;
+  memset(out, 0, sizeof(*out));
+  const uint32_t NP = sc->view_pl_off[sc->n_views];
   const uint64_t NN = node_point.size();
   out->n_nodes = NN;
   out->n_real_nodes = real_nodes;
@@ -306,6 +350,28 @@ extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoi
   }
   for (uint32_t p = 0; p < NP; p++) out->iv_off[p + 1] += out->iv_off[p];
   return 0;
+}
+
+extern "C" eg3d_replay_state* eg3d_host_replay_state_create(const eg3d_scene* sc) {
+  if (!sc || sc->n_views < 1 || !sc->view_pl_off || !sc->pl_vtx_off || !sc->vtx_xy) return nullptr;
+  eg3d_replay_state* s = new (std::nothrow) eg3d_replay_state;
+  if (s) s->sc = sc;
+  return s;
+}
+extern "C" int eg3d_host_replay_state_add(eg3d_replay_state* s, const eg3d_edgepoints* pts) { return s ? s->add(pts) : -1; }
+extern "C" int eg3d_host_replay_state_graph(eg3d_replay_state* s, eg3d_graph3d* out) { return s ? s->graph(out) : -1; }
+extern "C" uint64_t eg3d_host_replay_state_points(const eg3d_replay_state* s) { return s ? s->n_points : 0; }
+extern "C" void eg3d_host_replay_state_destroy(eg3d_replay_state* s) { delete s; }
+
+extern "C" int eg3d_host_replay_matches(const eg3d_scene* sc, const eg3d_edgepoints* pts, eg3d_graph3d* out) {
+  if (!sc || !pts || !out) return -1;
+  memset(out, 0, sizeof(*out));
+  eg3d_replay_state* s = eg3d_host_replay_state_create(sc);
+  if (!s) return -1;
+  int rc = s->add(pts);
+  if (rc == 0) rc = s->graph(out);
+  delete s;
+  return rc;
 }
 
 extern "C" void eg3d_host_free_graph3d(eg3d_graph3d* g) {

@@ -422,7 +422,8 @@ int eg3d_dedup_resident(eg3d_ctx* ctx, uint64_t index_base, int reset, int with_
  * survivors of the dedup or the filter, and on the device only the graph has to travel. `cloud`: NULL = this context's last
  * device output (which must be `complete`), or the result of eg3d_compact_device, of the multi-GPU gather or concatenation
  * (include/eg3d_rccl.h), or caller-built device arrays under the alignment contract of the filter stage; offsets are 64-bit
- * without a sentinel. A graph that accumulates over several calls is not offered: concatenate the clouds first.
+ * without a sentinel. This call builds the graph of ONE cloud; a graph that accumulates over the calls of a run is
+ * eg3d_replay_accumulate (include/eg3d_accumulate.h), which does not disturb this call's state or result.
  *
  * The rules, in the order-independent form the kernels use (host/replay.cpp is the sequential statement): a pair is
  * (i - 1, i) with equal key[0..2] and key[3] counting up by one. Two points are one node when the bit patterns of their

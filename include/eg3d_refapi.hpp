@@ -42,6 +42,7 @@
 
 #include "eg3d.h"
 #include "eg3d_host.h" /* eg3d_host_replay_matches (libeg3d_host.so) */
+#include "eg3d_host_accumulate.h" /* eg3d_host_replay_state_* (libeg3d_host.so): PLGMatchesManager::set_accumulate */
 
 namespace eg3d_ref {
 
@@ -114,7 +115,10 @@ using new_3dpoint_plgp_matches = std::tuple<vec3, std::vector<PolyLineGraph2D::p
 class PLGMatchesManager {
  public:
   PLGMatchesManager() { std::memset(&g_, 0, sizeof(g_)); }
-  ~PLGMatchesManager() { eg3d_host_free_graph3d(&g_); }
+  ~PLGMatchesManager() {
+    eg3d_host_free_graph3d(&g_);
+    eg3d_host_replay_state_destroy(state_);
+  }
   PLGMatchesManager(const PLGMatchesManager&) = delete;
   PLGMatchesManager& operator=(const PLGMatchesManager&) = delete;
   const eg3d_graph3d& get_plg3d() const { return g_; }
@@ -166,8 +170,6 @@ class PLGMatchesManager {
   }
   // concatenates the batches of a run (seed order) and replays them
   int replay(const eg3d_scene& sc, const std::vector<eg3d_edgepoints>& parts) {
-    eg3d_host_free_graph3d(&g_);
-    sc_ = sc;
     std::vector<float> X, xy;
     std::vector<uint32_t> pl, seg, key;
     std::vector<uint64_t> off(1, 0);
@@ -193,15 +195,13 @@ class PLGMatchesManager {
     all.obs_seg = seg.data();
     all.obs_xy = xy.data();
     all.key = key.data();
-    return eg3d_host_replay_matches(&sc, &all, &g_);
+    return finish(sc, all);
   }
 
   // the same from chains held as the reference holds them (vector of point tuples per chain; key = seed, index of the
   // chain within the seed): every chain in the order given = the order add_matched_3dpolyline would have seen
   int replay_chains(const eg3d_scene& sc, const std::vector<std::vector<new_3dpoint_plgp_matches>>& chains,
                     const std::vector<std::array<uint32_t, 3>>& chain_key) {
-    eg3d_host_free_graph3d(&g_);
-    sc_ = sc;
     std::vector<float> X, xy;
     std::vector<uint32_t> pl, seg, key;
     std::vector<uint64_t> off(1, 0);
@@ -244,12 +244,43 @@ class PLGMatchesManager {
     all.obs_seg = seg.data();
     all.obs_xy = xy.data();
     all.key = key.data();
-    return eg3d_host_replay_matches(&sc, &all, &g_);
+    return finish(sc, all);
   }
 
+  // The reference's manager is ONE object that grows over every call it is passed to. set_accumulate(true) gives this
+  // one those semantics: replay / replay_chains ADD their cloud to a host state (include/eg3d_host_accumulate.h), and
+  // get_plg3d(), matched_table() and is_matched() answer from the graph of everything added so far. Off (the default) is
+  // what this class always did: a replay replaces. Switching drops the state; the graph last built stays until the next replay.
+  void set_accumulate(bool on) {
+    if (on == accumulate_) return;
+    accumulate_ = on;
+    eg3d_host_replay_state_destroy(state_);
+    state_ = nullptr;
+  }
+  bool accumulates() const { return accumulate_; }
+
  private:
+  // what replay and replay_chains end with: the cloud replaces the graph, or is added to the state
+  int finish(const eg3d_scene& sc, const eg3d_edgepoints& all) {
+    if (!accumulate_) {
+      eg3d_host_free_graph3d(&g_);
+      sc_ = sc;
+      return eg3d_host_replay_matches(&sc, &all, &g_);
+    }
+    if (!state_) {
+      sc_ = sc;
+      state_ = eg3d_host_replay_state_create(&sc_);  // (the state borrows sc_: this object's copy, whose arrays are the edge manager's)
+      if (!state_) return -1;
+    }
+    const int rc = eg3d_host_replay_state_add(state_, &all);
+    if (rc != 0) return rc;  // refused: the state and the graph are as they were
+    eg3d_host_free_graph3d(&g_);
+    return eg3d_host_replay_state_graph(state_, &g_);
+  }
   eg3d_graph3d g_;
   eg3d_scene sc_{};  // the scene of the last replay (the edge manager's: its arrays outlive the run)
+  bool accumulate_ = false;
+  eg3d_replay_state* state_ = nullptr;
 };
 
 // EdgeManager (edge_manager.hpp:54-73): the abstract base the path's entry points take (`const EdgeManager* em`, which
