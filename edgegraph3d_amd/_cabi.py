@@ -1,6 +1,9 @@
 """The C ABI as ctypes sees it: one table per library, function name -> (restype, argtypes), covering every function
 of include/eg3d.h, include/eg3d_host.h and include/eg3d_rccl.h, and bind(), which applies a table to a CDLL. Written by
-hand; tests/test_abi.py reads the headers and holds every row (and every struct mirror of _cdefs.py) to them."""
+hand; tests/test_abi.py reads the headers and holds every row (and every struct mirror of _cdefs.py) to them. Those three
+tables are frozen; the entry points of later headers have tables of their own below (eg3d_accumulate.h,
+eg3d_host_accumulate.h: tests/test_replay_accumulate.py; eg3d_dedup_phases.h, eg3d_host_dedup_phases.h,
+eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py)."""
 import ctypes as C
 
 from . import _cdefs as D
@@ -142,6 +145,29 @@ EG3D_HOST_ACCUMULATE = {
     "eg3d_host_replay_state_graph": (i32, [vp, P(D.Graph3D)]),
     "eg3d_host_replay_state_points": (u64, [vp]),
     "eg3d_host_replay_state_destroy": (None, [vp]),
+}
+
+# include/eg3d_dedup_phases.h (libeg3d.so, libeg3d_dlt4x4.so): the 3 px dedup as claim / keep / the map / the merge of maps
+EG3D_DEDUP_PHASES = {
+    "eg3d_dedup_claim": (i32, [vp, P(D.DeviceEdgePoints), u64, i32]),
+    "eg3d_dedup_keep": (i32, [vp, P(D.DeviceEdgePoints), u64, vp, u64p]),
+    "eg3d_dedup_claims": (i32, [vp, P(vp), u64p]),
+    "eg3d_dedup_merge_claims": (i32, [vp, vp, u64, u64p]),
+    "eg3d_dedup_phase_ms": (i32, [vp, f32p]),
+}
+
+# include/eg3d_host_dedup_phases.h (libeg3d_host.so): their sequential definition on host clouds
+EG3D_HOST_DEDUP_PHASES = {
+    "eg3d_host_dedup_n_cells": (u64, [i32, i32, i32]),
+    "eg3d_host_dedup_claim": (i32, [i32, i32, i32, P(D.EdgePoints), u64, u32p]),
+    "eg3d_host_dedup_keep": (i32, [i32, i32, i32, P(D.EdgePoints), u64, u32p, u8p, u64p]),
+    "eg3d_host_dedup_merge": (i32, [u32p, u32p, u64]),
+}
+
+# include/eg3d_rccl_claims.h (libeg3d_rccl.so): the minimum all-reduce of the claim maps and the scan of the point counts
+EG3D_RCCL_CLAIMS = {
+    "eg3d_allreduce_claims": (i32, [vp, i32, i32, vp, vp, u64, i32, u64]),
+    "eg3d_exscan_points": (i32, [vp, i32, i32, vp, u64, u64p, u64p]),
 }
 
 

@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D, EG3D_ACCUMULATE, bind
+from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, bind
 
 _LIB = None
 
@@ -34,7 +34,7 @@ def lib():
         if not os.path.exists(path):
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
-        _LIB = bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE)
+        _LIB = bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES)
     return _LIB
 
 
@@ -42,6 +42,8 @@ def lib():
 EXPORTED_SYMBOLS = list(EG3D)
 # ... and those of include/eg3d_accumulate.h (tests/test_replay_accumulate.py does the same for that header)
 ACCUMULATE_SYMBOLS = list(EG3D_ACCUMULATE)
+# ... and of include/eg3d_dedup_phases.h (tests/test_abi_dedup_phases.py)
+DEDUP_PHASES_SYMBOLS = list(EG3D_DEDUP_PHASES)
 
 
 def _check(rc, what):
@@ -521,6 +523,58 @@ class Context:
             d = D.edgepoints_to_dict(e)
             lib().eg3d_free_edgepoints(C.byref(e))
         return d, dv, {f[0]: getattr(st, f[0]) for f in D.DedupStats._fields_}
+
+    # ---- the dedup in phases (include/eg3d_dedup_phases.h): claim in any order, merge claim maps, then keep ----
+    def dedup_claim(self, cloud, index_base=0, reset=False):
+        """eg3d_dedup_claim: the claim pass alone on `cloud` (a DeviceEdgePoints), its points counting from index_base within
+        the run. Clouds may be claimed in any order and on any context; reset empties this context's map first. A cloud
+        whose offsets do not ascend is refused and leaves the map as it was."""
+        _check(lib().eg3d_dedup_claim(self._h, C.byref(cloud), int(index_base), 1 if reset else 0), "eg3d_dedup_claim")
+
+    def dedup_keep(self, cloud, index_base=0, keep=None):
+        """eg3d_dedup_keep: the keep pass alone, against this context's map as it stands (its own claims and whatever was
+        merged or reduced into it). keep: DeviceArray or device address of n_points bytes, allocated when not given.
+        Returns (keep, n_kept). Refused while the context holds no valid map."""
+        n = int(cloud.n_points)
+        keep = keep if keep is not None else DeviceArray(n, self.device)
+        n_kept = C.c_uint64(0)
+        _check(lib().eg3d_dedup_keep(self._h, C.byref(cloud), int(index_base), _dev_ptr(keep), C.byref(n_kept)),
+               "eg3d_dedup_keep")
+        return keep, int(n_kept.value)
+
+    def dedup_claims(self):
+        """eg3d_dedup_claims: (device address, n_cells) of this context's claim map, created empty (0xFFFFFFFF) when there
+        is no valid one. Borrowed: valid until the context is closed or a dedup call on it fails. A caller may lower
+        entries in place (a min all-reduce does); the map then holds those claims too."""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        _check(lib().eg3d_dedup_claims(self._h, C.byref(p), C.byref(n)), "eg3d_dedup_claims")
+        return int(p.value), int(n.value)
+
+    def fetch_dedup_claims(self):
+        """Test/bench plumbing: a host copy of the claim map (uint32[n_cells])."""
+        p, n = self.dedup_claims()
+        a = np.empty(n, np.uint32)
+        if n and _hip().hipMemcpy(a.ctypes.data, C.c_void_p(p), a.nbytes, 2) != 0:
+            raise Eg3dError("hipMemcpy from the device failed")
+        return a
+
+    def dedup_merge_claims(self, other, n_cells=None):
+        """eg3d_dedup_merge_claims: this context's map becomes the element-wise minimum of itself and `other` — another
+        Context (its map), or (DeviceArray or device address, n_cells) of any device-readable uint32 array, 4-byte aligned.
+        Returns the number of entries that got smaller."""
+        if isinstance(other, Context):
+            other, n_cells = other.dedup_claims()
+        if n_cells is None:
+            raise ValueError("n_cells is needed with a device address")
+        n_low = C.c_uint64(0)
+        _check(lib().eg3d_dedup_merge_claims(self._h, _dev_ptr(other), int(n_cells), C.byref(n_low)), "eg3d_dedup_merge_claims")
+        return int(n_low.value)
+
+    def dedup_phase_ms(self):
+        """eg3d_dedup_phase_ms: device time of the last dedup_claim / dedup_keep / dedup_merge_claims of this context."""
+        ms = C.c_float(0)
+        _check(lib().eg3d_dedup_phase_ms(self._h, C.byref(ms)), "eg3d_dedup_phase_ms")
+        return ms.value
 
     # ---- the PLGMatchesManager replay on a device-resident cloud (include/eg3d.h) ----
     def replay_device(self, cloud=None, to_host=True):

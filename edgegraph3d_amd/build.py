@@ -166,12 +166,14 @@ RCCL_LIB = os.path.join(PKG, "libeg3d_rccl.so")
 def build_rccl(force=False):
     """The RCCL all-gather of the edge-point cloud for C/C++ hosts (include/eg3d_rccl.h): its own
     library so that libeg3d.so carries no communication dependency."""
-    src = os.path.join(PKG, "rccl", "eg3d_rccl.hip")
-    deps = [src] + _all_sources(INC_DIR, (".h",)) + _all_sources(os.path.join(PKG, "rccl"), (".h",))
+    # eg3d_rccl.hip: the gather (include/eg3d_rccl.h); eg3d_rccl_claims.hip: the exchanges of the phased dedup
+    # (include/eg3d_rccl_claims.h)
+    srcs = [os.path.join(PKG, "rccl", f) for f in ("eg3d_rccl.hip", "eg3d_rccl_claims.hip")]
+    deps = srcs + _all_sources(INC_DIR, (".h",)) + _all_sources(os.path.join(PKG, "rccl"), (".h",)) + [os.path.abspath(__file__)]
     if force or _newer(RCCL_LIB, deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        _run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", INC_DIR, src,
-              "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib", "-o", RCCL_LIB])
+        _run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", INC_DIR] + srcs +
+             ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib", "-o", RCCL_LIB])
     return RCCL_LIB
 
 
@@ -203,6 +205,10 @@ RESOURCE_BOUNDS = {
     # the 3 px dedup (eg3d_dedup_device): 64 staged 64-bit offsets per wave / one count per wave; no spills, no scratch
     "k7_dedup_claim": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},
     "k7_dedup_keep": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 16},
+    # the dedup in phases (eg3d_dedup_merge_claims, eg3d_dedup_claim): the minimum of two claim maps, both store forms — one
+    # count per wave in LDS — and the offsets check; no spills, no scratch
+    "k7_claims_min": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 16},
+    "k7_offsets_check": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # the replay (eg3d_replay_device): small kernels, no LDS; no spills, no scratch (a substring: all of them)
     "k8_": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # the accumulating replay (eg3d_replay_accumulate): as K8 — small kernels, no LDS, no spills, no scratch (all of them)

@@ -1,5 +1,5 @@
-"""Host-side helpers on cloud dicts (numpy): order-preserving compaction, the 3 px dedup as the first-claim rule and
-bit-exact comparison — what the tests, tools/bench_filter_resident.py and tools/bench_dedup_resident.py compare the
+"""Host-side helpers on cloud dicts (numpy): order-preserving compaction, the 3 px dedup as the first-claim rule (whole:
+np_dedup; in its phases: np_claim, np_keep) and bit-exact comparison — what the tests, tools/bench_filter_resident.py and tools/bench_dedup_resident.py compare the
 device-resident filter and dedup stages with."""
 import numpy as np
 
@@ -32,16 +32,11 @@ def dedup_claims(n_views, width, height):
     return np.full((int(n_views), h, w), UNCLAIMED, np.uint32)
 
 
-def np_dedup(c, n_views, width, height, claims=None, index_base=0):
-    """The 3 px dedup (eg3d_host_filter_close_2d, eg3d_dedup_device) of a host cloud dict as the first-claim rule: the first
-    point that touches a cell is always kept, so keep[i] = some observation of i lies in a valid cell whose smallest
-    touching point index is i. Two order-independent passes: a minimum per cell, one test per point. claims: a map from
-    dedup_claims that is updated in place (None: a fresh one); with the map of cloud A and index_base = |A| the mask of
-    cloud B is the second half of the mask of A || B. Returns the uint8 mask."""
+def _cells_and_owners(c, claims, index_base):
+    """(cell per valid observation, run-wide point index per valid observation, n_points) of a host cloud dict on the
+    grid of `claims`: the cell rule of eg3d_host_filter_close_2d."""
     off = np.asarray(c["obs_off"]).astype(np.int64)
     n = len(off) - 1
-    if claims is None:
-        claims = dedup_claims(n_views, width, height)
     V, h, w = claims.shape
     if index_base + n >= UNCLAIMED:
         raise ValueError("index_base + n_points must stay below 2^32 - 1")
@@ -54,13 +49,37 @@ def np_dedup(c, n_views, width, height, claims=None, index_base=0):
         cx, cy = np.trunc(np.where(ok, fx, 0)).astype(np.int64), np.trunc(np.where(ok, fy, 0)).astype(np.int64)
     ok &= (cx >= 0) & (cy >= 0) & (cx < w) & (cy < h)     # (-1, 0) truncates to cell 0
     owner = np.repeat(np.arange(n, dtype=np.int64), np.diff(off)) + int(index_base)
-    cell = ((view * h + cy) * w + cx)[ok]
-    flat = claims.reshape(-1)
-    np.minimum.at(flat, cell, owner[ok].astype(np.uint32))
+    return ((view * h + cy) * w + cx)[ok], owner[ok], n
+
+
+def np_claim(c, claims, index_base=0):
+    """The claim pass alone (eg3d_dedup_claim, eg3d_host_dedup_claim): claims[cell] = min(claims[cell], index_base + i)
+    over the observations of every point i, in place. Clouds may be claimed in any order; maps are joined with
+    np.minimum(a, b, out=a). Returns claims."""
+    cell, owner, _ = _cells_and_owners(c, claims, index_base)
+    np.minimum.at(claims.reshape(-1), cell, owner.astype(np.uint32))
+    return claims
+
+
+def np_keep(c, claims, index_base=0):
+    """The keep pass alone (eg3d_dedup_keep, eg3d_host_dedup_keep) against the map as it stands: the uint8 mask with
+    keep[i] = some observation of i lies in a cell that holds index_base + i."""
+    cell, owner, n = _cells_and_owners(c, claims, index_base)
     keep = np.zeros(n, np.uint8)
-    mine = flat[cell] == owner[ok]
-    keep[owner[ok][mine] - int(index_base)] = 1
+    mine = claims.reshape(-1)[cell] == owner
+    keep[owner[mine] - int(index_base)] = 1
     return keep
+
+
+def np_dedup(c, n_views, width, height, claims=None, index_base=0):
+    """The 3 px dedup (eg3d_host_filter_close_2d, eg3d_dedup_device) of a host cloud dict as the first-claim rule: the first
+    point that touches a cell is always kept, so keep[i] = some observation of i lies in a valid cell whose smallest
+    touching point index is i. Two order-independent passes: a minimum per cell, one test per point. claims: a map from
+    dedup_claims that is updated in place (None: a fresh one); with the map of cloud A and index_base = |A| the mask of
+    cloud B is the second half of the mask of A || B. Returns the uint8 mask."""
+    if claims is None:
+        claims = dedup_claims(n_views, width, height)
+    return np_keep(c, np_claim(c, claims, index_base), index_base)
 
 
 def same_cloud(a, b):

@@ -224,42 +224,27 @@ extern "C" int eg3d_filter_resident(eg3d_ctx* c, float gn_max_mse, int legacy_ab
 }
 
 // ---- the 3 px de-duplication on a device-resident cloud ------------------------------------------------------------------
-#define EG3D_DEDUP_MAX_INDEX 0xFFFFFFFFull /* K7_UNCLAIMED: index_base + n_points stays below it */
-static int dedup_index_check(const char* who, uint64_t index_base, uint64_t n_points) {
-  if (index_base >= EG3D_DEDUP_MAX_INDEX || n_points >= EG3D_DEDUP_MAX_INDEX - index_base) {
-    g_err = std::string(who) + ": index_base + n_points must stay below 2^32 - 1 (the claim map holds 32-bit point indices)";
-    return EG3D_ERR_ARG;
-  }
-  return EG3D_OK;
-}
+// The combined call, in the steps the phased calls are made of (eg3d_api_dedup_phases.hip): the map filled when `reset` or
+// not valid, claim, keep, one read-back of the kept count and the flags.
 static int dedup_device_impl(eg3d_ctx* c, const eg3d_device_edgepoints* d, uint64_t index_base, int reset, uint8_t* keep_dev,
                              uint64_t* n_kept, float* ms) {
   hipStream_t st = c->stream;
-  const int w = (int)std::ceil((float)c->W / 3), h = (int)std::ceil((float)c->H / 3);  // as host/post_steps.cpp
-  const size_t map_bytes = 4 * (size_t)c->V * (size_t)w * (size_t)h;
-  if (!c->d_first.p) c->dedup_valid = false;
-  BUF_TRY(c->d_first.ensure_exact(map_bytes));  // (it never grows, and a many-view rig's map is hundreds of MB)
-  const bool fill = reset || !c->dedup_valid;
-  c->dedup_valid = false;  // until this call is known to have completed: a failure below leaves the map to be refilled
-  if (fill) HIP_TRY(hipMemsetAsync(c->d_first.p, 0xFF, map_bytes, st));
-  BUF_TRY(c->d_cnt.ensure(16));
-  HIP_TRY(hipMemsetAsync(c->d_cnt.p, 0, 16, st));
-  unsigned long long* cnt = c->d_cnt.as<unsigned long long>();
-  const K7Map m{c->d_first.as<uint32_t>(), c->V, w, h};
+  K7Map m;
+  BUF_TRY(dedup_map_open(c, reset != 0, &m));  // (dedup_valid is false from here until the call is known to have completed)
+  unsigned long long* cnt = nullptr;
+  BUF_TRY(dedup_counters_zero(c, &cnt));
   const CloudView in = cloud_view(d);
   HIP_TRY(hipEventRecord(c->ea[0], st));
   launch_dedup_claim(st, in, m, (uint32_t)index_base);
   launch_dedup_keep(st, in, m, (uint32_t)index_base, keep_dev, cnt, (uint32_t*)(cnt + 1));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->eb[0], st));
-  uint64_t back[2];  // kept points, flags
-  HIP_TRY(hipMemcpyAsync(back, cnt, sizeof(back), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ea[0], c->eb[0]));
+  uint64_t kept = 0;
   // (claims made through bad offsets are discarded: dedup_valid stays false, the next call starts from an empty map)
-  if ((uint32_t)back[1]) return device_flags_error("eg3d_dedup_device", (uint32_t)back[1]);
+  BUF_TRY(dedup_counters_read(c, "eg3d_dedup_device", &kept));
+  if (ms) HIP_TRY(hipEventElapsedTime(ms, c->ea[0], c->eb[0]));
   c->dedup_valid = true;
-  if (n_kept) *n_kept = back[0];
+  if (n_kept) *n_kept = kept;
   return EG3D_OK;
 }
 

@@ -157,6 +157,8 @@ struct Tunables {
   uint32_t slots_per_xcd = 0;  // 0 = sized from the occupancy query
   bool use_lpt = true;
   bool compact_nt = false;  // EG3D_COMPACT_NT=1: non-temporal loads of the compaction's source
+  bool merge_write_all = false;  // EG3D_MERGE_WRITE_ALL=1 (A-B): eg3d_dedup_merge_claims writes every word back, not
+                                     // only the words it lowered (tools/bench_dedup_phases.py measures one against the other)
   int replay_table_bits = 0;  // EG3D_REPLAY_TABLE_BITS (tests): a node table of 2^bits slots, raised to the smallest power of
                               // two above the number of lookups; 0 = the default, about twice that
   uint64_t simgraph_pair_budget = 0;  // EG3D_SIMGRAPH_PAIR_BUDGET (tests): edge keys one chunk of the clique expansion may
@@ -191,6 +193,7 @@ struct Tunables {
     if (const char* e = getenv("EG3D_UNIT_RAMP")) t.unit_ramp = std::min(16.0, std::max(1.0 / 16.0, atof(e)));
     if (const char* e = getenv("EG3D_PIPELINE_UNITS")) t.units = std::min(4096, std::max(0, atoi(e)));
     if (const char* e = getenv("EG3D_COMPACT_NT")) t.compact_nt = e[0] == '1';
+    if (const char* e = getenv("EG3D_MERGE_WRITE_ALL")) t.merge_write_all = e[0] == '1';
     if (const char* e = getenv("EG3D_REPLAY_TABLE_BITS")) t.replay_table_bits = std::min(40, std::max(0, atoi(e)));
     if (const char* e = getenv("EG3D_SIMGRAPH_PAIR_BUDGET")) t.simgraph_pair_budget = std::min(1ull << 31, strtoull(e, nullptr, 10));
     if (const char* e = getenv("EG3D_LOUVAIN_TABLE_SLOTS")) {
@@ -449,6 +452,21 @@ int ensure_grid10(eg3d_ctx* c, K9Grid* out, float* ms);
 CloudView cloud_view(const eg3d_device_edgepoints* d);
 int check_cloud(const eg3d_device_edgepoints* d, const char* who, bool all_arrays);
 int device_flags_error(const char* who, uint32_t flags);
+
+// ---- the steps of the 3 px dedup (eg3d_api_dedup_phases.hip) --------------------------------------------------------------
+// eg3d_dedup_device / eg3d_dedup_resident (eg3d_api_filter.hip) and the phased calls of include/eg3d_dedup_phases.h are
+// written in these and nothing else, so that the combined and the phased forms cannot drift apart.
+// index_base + n_points must stay below 2^32 - 1 (K7_UNCLAIMED); sets g_err under `who`
+int dedup_index_check(const char* who, uint64_t index_base, uint64_t n_points);
+uint64_t dedup_n_cells(const eg3d_ctx* c, int* w = nullptr, int* h = nullptr);  // n_views x ceil(W / 3) x ceil(H / 3), as the host step
+// The context's map, allocated on first use and filled with K7_UNCLAIMED when `reset` or when it holds no valid claims.
+// Leaves dedup_valid FALSE: the caller sets it once its call is known to have completed, so that a failure in between
+// leaves a map that the next call refills.
+int dedup_map_open(eg3d_ctx* c, bool reset, K7Map* m);
+// the kept count and the flag word (d_cnt: 2 x 8 bytes), zeroed on the stream
+int dedup_counters_zero(eg3d_ctx* c, unsigned long long** cnt);
+// the read-back that ends a pass: [0] a count, [1] the flag word; synchronises the stream. Flags -> EG3D_ERR_ARG under `who`
+int dedup_counters_read(eg3d_ctx* c, const char* who, uint64_t* count);
 
 // ---- one copy of each idiom of the post stages ---------------------------------------------------------------------------
 // The two-call form of a rocPRIM primitive (eg3d_k8_replay.h .. eg3d_k11_louvain.h): ask for the scratch size, make room

@@ -237,4 +237,15 @@ void launch_dedup_claim(hipStream_t st, CloudView in, K7Map m, uint32_t index_ba
 void launch_dedup_keep(hipStream_t st, CloudView in, K7Map m, uint32_t index_base, uint8_t* keep, unsigned long long* n_kept,
                        uint32_t* flags);
 
+// ---- eg3d_k7b_claims.hip: what the dedup in phases adds (include/eg3d_dedup_phases.h) ----
+#define K7B_BLOCK 256
+#define K7B_MAX_BLOCKS 2048 /* of k7_claims_min: maps of more than 2 097 152 cells go round by grid stride */
+// first[c] = min(first[c], other[c]) for c < n; *n_lowered += the entries that got smaller. `first` must be 16-byte aligned
+// (a context's map is); `other` needs 4-byte alignment only and is never written; write_all: the form that writes every word back (measured against the default, which
+// writes only the words it lowered)
+void launch_claims_min(hipStream_t st, uint32_t* first, const uint32_t* other, uint64_t n, unsigned long long* n_lowered,
+                       bool write_all);
+// one lane per point: K5_FLAG_BAD_OFFSETS into *flags for offsets that do not ascend within [0, n_obs]
+void launch_offsets_check(hipStream_t st, CloudView in, uint32_t* flags);
+
 }  // namespace eg3d

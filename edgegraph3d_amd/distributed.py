@@ -84,8 +84,9 @@ def gather_lib():
     if _GATHER_LIB is None:
         import ctypes as C
         import os
-        from ._cabi import EG3D_RCCL, bind
-        _GATHER_LIB = bind(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_rccl.so")), EG3D_RCCL)
+        from ._cabi import EG3D_RCCL, EG3D_RCCL_CLAIMS, bind
+        _GATHER_LIB = bind(bind(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_rccl.so")), EG3D_RCCL),
+                           EG3D_RCCL_CLAIMS)
     return _GATHER_LIB
 
 
@@ -247,6 +248,27 @@ class RcclCloudGather:
             self.abandon_comm()
         return out, rc
 
+    # ---- the exchanges of the dedup in phases (include/eg3d_rccl_claims.h) ----
+    def exscan_points(self, n_points):
+        """eg3d_exscan_points: (points of the lower ranks, points of all ranks, rc); the same rc on every rank."""
+        C = self.C
+        base, total = C.c_uint64(0), C.c_uint64(0)
+        rc = self.G.eg3d_exscan_points(self.comm, self.world, self.rank, self.stream, int(n_points), C.byref(base), C.byref(total))
+        if rc == -6:
+            self.abandon_comm()
+        return int(base.value), int(total.value), rc
+
+    def allreduce_claims(self, ctx, chunk_bytes=0):
+        """eg3d_allreduce_claims on the claim map of `ctx` (a Context), in place: afterwards every rank's map holds the
+        claims of all ranks. ctx = None: this rank has no usable map (its claim failed); it still takes part, and every
+        rank returns EG3D_GATHER_ERR_INCOMPLETE (-4) before any payload moves. Returns rc, the same on every rank."""
+        ptr, n_cells = ctx.dedup_claims() if ctx is not None else (None, 0)
+        rc = self.G.eg3d_allreduce_claims(self.comm, self.world, self.rank, self.stream, ptr, n_cells, 1 if ctx is not None else 0,
+                                          int(chunk_bytes))
+        if rc == -6:
+            self.abandon_comm()
+        return rc
+
     def close(self):
         if getattr(self, "g", None):
             self.G.eg3d_gather_destroy(self.g)
@@ -339,6 +361,94 @@ class HostCloudGather:
         return out, 0
 
 
+    # ---- the exchanges of the dedup in phases, as RcclCloudGather has them ----
+    def exscan_points(self, n_points):
+        """(points of the lower ranks, points of all ranks, rc): one all-gather of the counts."""
+        allc = torch.empty(self.world, dtype=torch.int64)
+        self.dist.all_gather_into_tensor(allc, torch.tensor([int(n_points)], dtype=torch.int64))
+        counts = [int(x) for x in allc.tolist()]
+        if sum(counts) >= 0xFFFFFFFF:
+            return 0, sum(counts), -1
+        return sum(counts[:self.rank]), sum(counts), 0
+
+    def allreduce_claims(self, first_np):
+        """first_np (a contiguous uint32 claim map, e.g. HostShard.dedup_claims()) becomes the minimum over the ranks, in
+        place. None: this rank has no usable map. First the agreement round of eg3d_allreduce_claims — any rank without a
+        map: -4 on every rank; ranks whose maps differ in size: -1 on every rank — then the reduction. gloo has no uint32,
+        and 0xFFFFFFFF read as int32 is -1, which a minimum would prefer to every claim: the map is reduced as an int64
+        copy and written back."""
+        import numpy as np
+        mine = -1 if first_np is None else int(first_np.size)
+        allc = torch.empty(self.world, dtype=torch.int64)
+        self.dist.all_gather_into_tensor(allc, torch.tensor([mine], dtype=torch.int64))
+        sizes = allc.tolist()
+        if any(x < 0 for x in sizes):
+            return -4
+        if any(x != sizes[0] for x in sizes):
+            return -1
+        if first_np.dtype != np.uint32 or not first_np.flags["C_CONTIGUOUS"]:
+            raise ValueError("a contiguous uint32 map is needed")
+        t = torch.from_numpy(first_np.astype(np.int64).reshape(-1))
+        if self.world > 1 and t.numel():
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.MIN)
+        first_np.reshape(-1)[:] = t.numpy().astype(np.uint32)
+        return 0
+
+
+class HostShard:
+    """A rank's shard on host arrays with the calls of api.Context that dedup_filter_then_gather makes, on the host
+    statements: eg3d_host_dedup_claim / _keep (include/eg3d_host_dedup_phases.h) and cloudnp.np_compact. The
+    Gauss-Newton verdict comes from the caller: gn_filter(cloud dict, gn_max_mse, legacy_abs) -> (X_new [n, 3] float32,
+    inlier [n] uint8) — the product has no host form of that filter; the tests pass the CPU oracle's. A run on
+    HostCloudGather (gloo) is then the same sequence as a run on the device and RcclCloudGather."""
+
+    def __init__(self, cloud, n_views, width, height, gn_filter):
+        import types
+        self.n_views, self.width, self.height, self.gn_filter = int(n_views), int(width), int(height), gn_filter
+        self.view = types.SimpleNamespace(n_points=int(cloud["n_points"]), n_obs=int(cloud["n_obs"]), complete=1, arrays=cloud)
+        self.first = None
+
+    def last_device_output(self):
+        return self.view
+
+    def dedup_claims(self):
+        from . import host
+        if self.first is None:
+            self.first = host.dedup_empty_claims(self.n_views, self.width, self.height)
+        return self.first
+
+    def dedup_claim(self, view, index_base=0, reset=False):
+        from . import host
+        if reset:
+            self.first = None
+        host.dedup_claim(view.arrays, self.n_views, self.width, self.height, self.dedup_claims(), index_base)
+
+    def dedup_keep(self, view, index_base=0):
+        from . import host
+        if self.first is None:
+            raise ValueError("nothing was claimed")
+        return host.dedup_keep(view.arrays, self.n_views, self.width, self.height, self.first, index_base)
+
+    def gn_filter_device(self, view, keep=None, gn_max_mse=2.25, legacy_abs=False):
+        import numpy as np
+        from .cloudnp import np_compact
+        c, n = view.arrays, view.n_points
+        sel = np.ones(n, bool) if keep is None else np.asarray(keep).astype(bool)
+        X_out, inlier = np.array(c["X"], np.float32).reshape(-1, 3).copy(), np.zeros(n, np.uint8)
+        if sel.any():   # a masked-out point is no inlier and keeps its X, as on the device
+            Xs, inl = self.gn_filter(np_compact(c, sel), gn_max_mse, legacy_abs)
+            X_out[sel], inlier[sel] = Xs, inl
+        k = np.diff(np.asarray(c["obs_off"]).astype(np.int64))[inlier.astype(bool)]
+        hist = np.bincount(k[k <= self.n_views], minlength=self.n_views + 1).astype(np.int64)
+        return X_out, inlier, hist, int(inlier.sum()), 0.0
+
+    def compact_device(self, view, keep=None, X_new=None, min_obs=-1):
+        import numpy as np
+        from .cloudnp import np_compact
+        out = np_compact(view.arrays, np.ones(view.n_points, np.uint8) if keep is None else keep, X_new, min_obs)
+        return out
+
+
 # ---- the filter stage over ranks: each rank filters the shard it already holds in HBM, only the survivors travel ----
 def observation_threshold(hist, n_views, forced_min_filter=-1, count=None):
     """The rule of eg3d_host_observation_filter (host/post_steps.cpp) on a histogram by list length: hist[k] = points with
@@ -384,9 +494,9 @@ def global_observation_threshold(dist, local_hist, n_views, forced_min_filter=-1
 
 def filter_then_gather(ctx, gather, dist, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, keep=None):
     """The end of a multi-GPU run without a gathered intermediate: (1) Context.gn_filter_device on this rank's
-    device-only cloud (keep: optional device mask of the shard, e.g. its dedup mask — Context.dedup_device now produces
-    it on the device, for a shard on its own or for a gathered / concatenated cloud; the dedup of a SHARDED cloud against
-    the other ranks' shards before the gather would need the claim maps exchanged and is not built), (2) the global threshold,
+    device-only cloud (keep: optional device mask of the shard — Context.dedup_device gives the dedup mask of a shard on
+    its own or of a gathered / concatenated cloud; the dedup of a SHARDED cloud against the other ranks' shards, which
+    exchanges the claim maps, is dedup_filter_then_gather below), (2) the global threshold,
     (3) Context.compact_device of the inliers above it, new X in place, (4) gather.allgather of the compacted shard.
     Returns (DeviceEdgePoints of all ranks' survivors, rc of the gather, threshold). Every rank must call it."""
     cloud = ctx.last_device_output()
@@ -399,4 +509,46 @@ def filter_then_gather(ctx, gather, dist, gn_max_mse=2.25, legacy_abs=False, for
     out, rc = gather.allgather(shard)
     X_out.free()
     inlier.free()
+    return out, rc, thr
+
+
+def dedup_filter_then_gather(ctx, gather, dist, run_base=0, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1,
+                             base_hist=None, reset=None):
+    """The reference-exact end of a sharded step, the raw cloud never travelling: the reference dedups BEFORE it filters,
+    and a shard can only be deduplicated against the claims of all ranks. On this rank's device-only cloud:
+      (1) gather.exscan_points: the shard's index base = the points of the lower ranks (rank order = seed order);
+      (2) ctx.dedup_claim with run_base + that base (run_base: the points of the earlier steps of the run; reset, default
+          run_base == 0, empties the map first — without it the claims of the earlier steps, already reduced, stand);
+      (3) gather.allreduce_claims: the element-wise minimum of the ranks' claim maps, in place;
+      (4) ctx.dedup_keep: the shard's part of the mask of the whole cloud;
+      (5) ctx.gn_filter_device with that mask; (6) global_observation_threshold; (7) ctx.compact_device;
+      (8) gather.allgather of the survivors.
+    Every rank ends with eg3d_dedup_resident(with_filter) of the concatenation of the shards. ctx / gather: an api.Context
+    with an RcclCloudGather, or a HostShard with a HostCloudGather. Returns (cloud of all ranks' survivors, rc, threshold);
+    a rank whose claim fails still takes part in (3), every rank then gets (None, -4, None) and none blocks; ranks that
+    disagree on the rig get (None, -1, None). Every rank must call it."""
+    cloud = ctx.last_device_output()
+    if not cloud.complete:
+        raise RuntimeError("the device view does not hold the whole cloud of the last call")
+    base, total, rc = gather.exscan_points(int(cloud.n_points))
+    if rc != 0:
+        return None, rc, None
+    index_base, claimed = int(run_base) + base, True
+    try:
+        ctx.dedup_claim(cloud, index_base, reset=(int(run_base) == 0) if reset is None else bool(reset))
+    except Exception:   # this rank's verdict travels in the agreement round: the peers must not wait for its payload
+        claimed = False
+    mine = None if not claimed else (ctx if isinstance(gather, RcclCloudGather) else ctx.dedup_claims())
+    rc = gather.allreduce_claims(mine)
+    if rc != 0:
+        return None, rc, None
+    keep, _ = ctx.dedup_keep(cloud, index_base)
+    # (inliers with more observations than views sit in no bin: n_inl counts them too)
+    X_out, inlier, hist, n_inl, _ = ctx.gn_filter_device(cloud, keep, gn_max_mse, legacy_abs)
+    thr = global_observation_threshold(dist, hist, ctx.n_views, forced_min_filter, base_hist, local_count=n_inl)
+    shard = ctx.compact_device(cloud, inlier, X_out, thr)
+    out, rc = gather.allgather(shard)
+    for a in (keep, X_out, inlier):
+        if hasattr(a, "free"):
+            a.free()
     return out, rc, thr

@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, bind
+from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_DEDUP_PHASES, bind
 
 _LIB = None
 
@@ -16,7 +16,7 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_host.so")
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
-        _LIB = bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE)
+        _LIB = bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES)
     return _LIB
 
 
@@ -181,6 +181,48 @@ class ReplayState:
             self.close()
         except Exception:
             pass
+
+
+# ---- the 3 px dedup in phases on host clouds (include/eg3d_host_dedup_phases.h) ----
+def dedup_empty_claims(n_views, width, height):
+    """An empty claim map: uint32[eg3d_host_dedup_n_cells] of 0xFFFFFFFF."""
+    return np.full(int(lib().eg3d_host_dedup_n_cells(n_views, width, height)), 0xFFFFFFFF, np.uint32)
+
+
+def dedup_claim(cloud, n_views, width, height, first, index_base=0):
+    """eg3d_host_dedup_claim of a cloud dict into the map `first` (contiguous uint32, lowered in place). Raises ValueError
+    when the cloud is refused (the map is then as it was)."""
+    ep = D.EdgePointsArrays(cloud)
+    if first.dtype != np.uint32 or not first.flags["C_CONTIGUOUS"] or first.size != lib().eg3d_host_dedup_n_cells(n_views, width, height):
+        raise ValueError("first must be a contiguous uint32 map of this rig")
+    rc = lib().eg3d_host_dedup_claim(n_views, width, height, C.byref(ep.c), int(index_base), D.np_ptr(first, C.c_uint32))
+    if rc != 0:
+        raise ValueError("eg3d_host_dedup_claim refused the cloud (%d)" % rc)
+    return first
+
+
+def dedup_keep(cloud, n_views, width, height, first, index_base=0):
+    """eg3d_host_dedup_keep: (uint8 mask of the cloud against the map as it stands, n_kept)."""
+    ep = D.EdgePointsArrays(cloud)
+    if first.dtype != np.uint32 or not first.flags["C_CONTIGUOUS"] or first.size != lib().eg3d_host_dedup_n_cells(n_views, width, height):
+        raise ValueError("first must be a contiguous uint32 map of this rig")
+    n = int(cloud["n_points"])
+    keep, n_kept = np.zeros(max(n, 1), np.uint8), C.c_uint64(0)
+    rc = lib().eg3d_host_dedup_keep(n_views, width, height, C.byref(ep.c), int(index_base), D.np_ptr(first, C.c_uint32),
+                                    D.np_ptr(keep, C.c_uint8), C.byref(n_kept))
+    if rc != 0:
+        raise ValueError("eg3d_host_dedup_keep refused the cloud (%d)" % rc)
+    return keep[:n], int(n_kept.value)
+
+
+def dedup_merge(first, other):
+    """eg3d_host_dedup_merge: first = min(first, other), in place. Returns first."""
+    if first.dtype != np.uint32 or other.dtype != np.uint32 or first.shape != other.shape:
+        raise ValueError("two uint32 maps of one shape are needed")
+    other = np.ascontiguousarray(other)
+    if lib().eg3d_host_dedup_merge(D.np_ptr(first, C.c_uint32), D.np_ptr(other, C.c_uint32), first.size) != 0:
+        raise ValueError("eg3d_host_dedup_merge failed")
+    return first
 
 
 def is_matched(scene_ptr, graph, view, pl, seg, xy):
