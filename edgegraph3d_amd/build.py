@@ -153,7 +153,7 @@ def build_probe(force=False):
     """TEST-ONLY: device primitives of the product's headers behind a tiny C interface
     (tests/probe/eg3d_probe.h) for the bit-for-bit arithmetic checks; never linked into libeg3d.so."""
     src = os.path.join(ROOT, "tests", "probe", "eg3d_probe.hip")
-    deps = [src] + _all_sources(CSRC_DIR, (".h", ".hpp")) + [os.path.abspath(__file__)]
+    deps = [src] + _all_sources(os.path.dirname(src), (".h",)) + _all_sources(CSRC_DIR, (".h", ".hpp")) + [os.path.abspath(__file__)]
     if force or _newer(PROBE_LIB, deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         _run([hipcc] + HIP_FLAGS + ["-I", INC_DIR, "-I", CSRC_DIR, "-I", os.path.dirname(src), "-o", PROBE_LIB, src])

@@ -185,7 +185,8 @@ EG3D_HD LineDir line_dir(float la, float lb) {
 }
 // seg_line_cos(...) > thr, decided on the squares when that is unambiguous (relative margin 1e-4
 // >> the few-ulp error of either form); the division and square root are evaluated only in the
-// knife-edge band and for degenerate magnitudes — same decisions as the plain expression.
+// knife-edge band and for degenerate magnitudes — same decisions as the plain expression
+// (tests/test_gpu_geom_primitives.py holds it to that on the GPU, cosines on and within a few ulps of the threshold included).
 EG3D_HD bool seg_line_cos_gt(float x1, float y1, float x2, float y2, const LineDir& ld, float thr) {
   float ax = x2 - x1, ay = y2 - y1;
   float d = dotf(ax, ay, ld.bx, ld.by);
@@ -712,6 +713,8 @@ EG3D_HD float polyline_closest_pruned(const PlRef& pl, float px, float py, uint3
 }
 
 // ---------------------------------------------------------------- grid cells ---
+// (the device's builtins and the host's libm must round alike: tests/test_gpu_geom_primitives.py compares cell_of and
+// cell_window with the oracle ulp by ulp around every cell boundary and across the 0.001 threshold of cell_round)
 #if defined(__HIP_DEVICE_COMPILE__)
 #define EG3D_CEILF(x) __builtin_ceilf(x)
 #define EG3D_FLOORF(x) __builtin_floorf(x)

@@ -68,6 +68,23 @@ def lib():
         L.orc_next_by_line.argtypes = [D.f32p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                                        C.c_uint32, D.f32p, C.c_int, C.c_float, C.c_float, D.u32p, D.f32p,
                                        C.POINTER(C.c_int)]
+        # batched probes (tests/test_glm_pin.py, tests/test_geom_cases.py)
+        L.orc_batch_mindist.argtypes = [C.c_uint64, D.f32p, D.f32p]
+        L.orc_batch_mindist.restype = None
+        L.orc_batch_anglecos.argtypes = [C.c_uint64, D.f32p, D.f32p]
+        L.orc_batch_anglecos.restype = None
+        L.orc_batch_next_by_distance.argtypes = [D.f32p, D.u32p, D.u32p, D.u32p, C.c_uint64, D.u32p, D.u32p, D.u32p, D.f32p,
+                                                 D.u32p, D.u32p, D.f32p]
+        L.orc_batch_next_by_distance.restype = None
+        L.orc_batch_next_by_line.argtypes = [D.f32p, D.u32p, D.u32p, D.u32p, C.c_uint64, D.u32p, D.u32p, D.u32p, D.f32p,
+                                             D.f32p, D.u8p, D.f32p, D.u32p, D.u32p, D.f32p]
+        L.orc_batch_next_by_line.restype = None
+        L.orc_batch_segment_line.argtypes = [C.c_uint64, D.f32p, D.u8p, D.f32p, D.u8p, D.f32p, D.u8p, D.f32p]
+        L.orc_batch_segment_line.restype = None
+        L.orc_batch_cell_from_coords.argtypes = [C.c_uint64, D.f32p, D.i32p]
+        L.orc_batch_cell_from_coords.restype = None
+        L.orc_batch_epiline.argtypes = [C.c_uint64, D.f64p, D.u8p, D.f32p, D.i32p, D.f32p]
+        L.orc_batch_epiline.restype = None
         # the checker follows the DLT form the product library was built with (include/eg3d.h eg3d_dlt_rows)
         rows = os.environ.get("EG3D_ORACLE_DLT_ROWS")
         if rows is None:

@@ -794,6 +794,104 @@ extern "C" int orc_next_by_line(const float* vtx, int n, uint32_t start, uint32_
   *flags = (fqp ? 1 : 0) | (reached ? 2 : 0) | (bdv ? 4 : 0);
   return found;
 }
+// batched forms of the walk / segment / cell / epipolar-line probes above, for the case tables of tests/geom_cases.py (tens of
+// thousands of rows each). Polylines are slices pl_off[p] .. pl_off[p + 1] of vtx; a row names its polyline. Outputs that the
+// reference leaves unset are LEFT AS THE CALLER FILLED THEM (a sentinel), so "untouched" is visible in the result.
+// status: 1 found, 2 extreme reached, 4 quasi-parallel stop, 8 bound violated (the WALK_* bits of eg3d_dev_geom.h).
+extern "C" void orc_batch_next_by_distance(const float* vtx, const uint32_t* pl_off, const uint32_t* pl_start,
+                                           const uint32_t* pl_end, uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg,
+                                           const uint32_t* row_dir, const float* row_xy_dist /*[n][3]*/, uint32_t* status,
+                                           uint32_t* out_seg, float* out_xy) {
+  uint32_t cur = 0xffffffffu;
+  polyline pl;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t p = row_pl[i];
+    if (p != cur) {
+      pl = make_pl(vtx + 2 * (size_t)pl_off[p], (int)(pl_off[p + 1] - pl_off[p]), pl_start[p], pl_end[p]);
+      cur = p;
+    }
+    bool reached;
+    const float* q = row_xy_dist + 3 * i;
+    pl_point r = pl.next_pl_point_by_distance(pl_point(row_seg[i], vec2(q[0], q[1])), row_dir[i], q[2], reached);
+    status[i] = reached ? 2u : 1u;
+    out_seg[i] = (uint32_t)r.segment_index;
+    out_xy[2 * i] = r.coords.x;
+    out_xy[2 * i + 1] = r.coords.y;
+  }
+}
+extern "C" void orc_batch_next_by_line(const float* vtx, const uint32_t* pl_off, const uint32_t* pl_start, const uint32_t* pl_end,
+                                       uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg, const uint32_t* row_dir,
+                                       const float* row_xy /*[n][2]*/, const float* row_line /*[n][3]*/, const uint8_t* row_bounded,
+                                       const float* row_minmax /*[n][2]*/, uint32_t* status, uint32_t* out_seg, float* out_xy) {
+  uint32_t cur = 0xffffffffu;
+  polyline pl;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t p = row_pl[i];
+    if (p != cur) {
+      pl = make_pl(vtx + 2 * (size_t)pl_off[p], (int)(pl_off[p + 1] - pl_off[p]), pl_start[p], pl_end[p]);
+      cur = p;
+    }
+    pl_point next, nbq;
+    bool fqp, reached, bdv, found;
+    pl.next_pl_point_by_line_intersection_impl(pl_point(row_seg[i], vec2(row_xy[2 * i], row_xy[2 * i + 1])), row_dir[i],
+                                               row_line + 3 * i, row_bounded[i] != 0, row_minmax[2 * i], row_minmax[2 * i + 1],
+                                               next, fqp, nbq, reached, bdv, found);
+    status[i] = (found ? 1u : 0u) | (reached ? 2u : 0u) | (fqp ? 4u : 0u) | (bdv ? 8u : 0u);
+    if (found || bdv) {  // (`next` is assigned exactly then)
+      out_seg[i] = (uint32_t)next.segment_index;
+      out_xy[2 * i] = next.coords.x;
+      out_xy[2 * i + 1] = next.coords.y;
+    }
+  }
+}
+// rows [n][7] = x1 y1 x2 y2 a b c. found / inter: intersect_segment_line; found_nqp / inter_nqp / qp / distance:
+// intersect_segment_line_no_quasiparallel (distance stays -1 where the reference does not assign it)
+extern "C" void orc_batch_segment_line(uint64_t n, const float* seg_line, uint8_t* found, float* inter, uint8_t* found_nqp,
+                                       float* inter_nqp, uint8_t* qp, float* distance) {
+  for (uint64_t i = 0; i < n; i++) {
+    const float* q = seg_line + 7 * i;
+    bool p, o, f, qq, v;
+    vec2 h;
+    intersect_segment_line(q[0], q[1], q[2], q[3], q + 4, p, o, f, h);
+    found[i] = f;
+    if (f) {
+      inter[2 * i] = h.x;
+      inter[2 * i + 1] = h.y;
+    }
+    float d = -1;
+    vec2 g;
+    intersect_segment_line_no_quasiparallel(q[0], q[1], q[2], q[3], q + 4, QP_COS, QP_DIST, p, o, f, qq, v, d, g);
+    found_nqp[i] = f;
+    if (f) {
+      inter_nqp[2 * i] = g.x;
+      inter_nqp[2 * i + 1] = g.y;
+    }
+    qp[i] = qq;
+    distance[i] = d;
+  }
+}
+extern "C" void orc_batch_cell_from_coords(uint64_t n, const float* cell_xy /*[n][3]*/, int32_t* out /*[n][4]: col row b_row b_col*/) {
+  for (uint64_t i = 0; i < n; i++) {
+    bool br, bc;
+    auto c = get_2dmap_cell_from_coords(cell_xy[3 * i], vec2(cell_xy[3 * i + 1], cell_xy[3 * i + 2]), br, bc);
+    out[4 * i] = (int)c.first;
+    out[4 * i + 1] = (int)c.second;
+    out[4 * i + 2] = br;
+    out[4 * i + 3] = bc;
+  }
+}
+// one matrix and one validity byte per row (the "pair" of the row); line is left as filled for an invalid pair
+extern "C" void orc_batch_epiline(uint64_t n, const double* F /*[n][9]*/, const uint8_t* valid, const float* xy, int32_t* ok,
+                                  float* line /*[n][3]*/) {
+  for (uint64_t i = 0; i < n; i++) {
+    Cameras cm;
+    cm.n_views = 1;
+    cm.F = F + 9 * i;
+    cm.F_valid = valid + i;
+    cm.P = nullptr;
+    ok[i] = computeCorrespondEpilineSinglePoint(cm, 0, 0, vec2(xy[2 * i], xy[2 * i + 1]), line + 3 * i) ? 1 : 0;
+  }
+}
 
 // ---------------------------------------------------------------------------- N4 ----
 // get_point_sets_on_images (edge_graph_3d_utilities.cpp:369-380), find_points_on_both_images (:345-352),

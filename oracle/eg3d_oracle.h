@@ -103,6 +103,22 @@ int orc_next_by_distance(const float* vtx, int n, uint32_t start, uint32_t end, 
 int orc_next_by_line(const float* vtx, int n, uint32_t start, uint32_t end, uint32_t seg, float x, float y,
                      uint32_t direction, const float* line, int bounded, float mind, float maxd, uint32_t* out_seg,
                      float* out_xy, int* flags /*1 qp,2 extreme,4 bound*/);
+/* batched forms of the probes above for the case tables of tests/geom_cases.py: polyline p = vertices pl_off[p] ..
+ * pl_off[p + 1] - 1 of vtx, a row names its polyline. status: 1 found, 2 extreme, 4 quasi-parallel stop, 8 bound violated.
+ * Whatever the reference leaves unset (the point of a walk that found nothing, the hit of a segment without one, the line of
+ * an invalid pair) is left as the caller filled it. */
+void orc_batch_next_by_distance(const float* vtx, const uint32_t* pl_off, const uint32_t* pl_start, const uint32_t* pl_end,
+                                uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg, const uint32_t* row_dir,
+                                const float* row_xy_dist /*[n][3]*/, uint32_t* status, uint32_t* out_seg, float* out_xy);
+void orc_batch_next_by_line(const float* vtx, const uint32_t* pl_off, const uint32_t* pl_start, const uint32_t* pl_end,
+                            uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg, const uint32_t* row_dir,
+                            const float* row_xy /*[n][2]*/, const float* row_line /*[n][3]*/, const uint8_t* row_bounded,
+                            const float* row_minmax /*[n][2]*/, uint32_t* status, uint32_t* out_seg, float* out_xy);
+void orc_batch_segment_line(uint64_t n, const float* seg_line /*[n][7]*/, uint8_t* found, float* inter, uint8_t* found_nqp,
+                            float* inter_nqp, uint8_t* qp, float* distance /* -1 where the reference assigns none */);
+void orc_batch_cell_from_coords(uint64_t n, const float* cell_xy /*[n][3]*/, int32_t* out /*[n][4]: col row b_row b_col*/);
+void orc_batch_epiline(uint64_t n, const double* F /*[n][9]*/, const uint8_t* valid, const float* xy, int32_t* ok,
+                       float* line /*[n][3]*/);
 
 #ifdef __cplusplus
 }

@@ -498,3 +498,76 @@ extern "C" int hostsim_gn_filter(const float* cam_P, const float* X, const uint3
   }
   return 0;
 }
+
+// ---- the tables of tests/geom_cases.py through the HOST compilation of eg3d_dev_geom.h / epiline: the same items, the same
+// arguments and the same return codes as the probe library's eg3d_probe_walk / _seg / _cells / _closest / _epiline
+// (tests/probe/eg3d_probe.h), which run them on the GPU. -1: the table breaks the input contract, nothing was run.
+#include "../probe/eg3d_geom_items.h"
+namespace gi = eg3d_items;
+
+extern "C" int hostsim_geom_walk(int form, const float* vtx, uint64_t nv, const uint32_t* pl_off, const uint32_t* pl_start,
+                                 const uint32_t* pl_end, uint32_t npl, uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg,
+                                 const uint32_t* row_dir, const float* row_f, const uint8_t* row_bnd, uint32_t* status,
+                                 uint32_t* seg, float* xy) {
+  if (form < 0 || form >= gi::WALK_N_FORMS || form == gi::WALK_F_LINE_LDS) return -1;  // (no address_space(3) on the host)
+  if (!gi::polylines_ok(vtx, nv, pl_off, npl) || !gi::walk_rows_ok(pl_off, npl, n, row_pl, row_seg)) return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    PlRef pl;
+    pl.v = reinterpret_cast<const f2*>(vtx) + pl_off[row_pl[i]];
+    pl.n = pl_off[row_pl[i] + 1] - pl_off[row_pl[i]];
+    pl.start = pl_start[row_pl[i]];
+    pl.end = pl_end[row_pl[i]];
+    PlPt o;
+    o.seg = seg[i];
+    o.x = xy[2 * i];
+    o.y = xy[2 * i + 1];
+    status[i] = gi::walk_item(form, pl, row_seg[i], row_dir[i], row_f + 8 * i, row_bnd[i] != 0, o);
+    seg[i] = o.seg;
+    xy[2 * i] = o.x;
+    xy[2 * i + 1] = o.y;
+  }
+  return 0;
+}
+extern "C" int hostsim_geom_seg(int mode, uint64_t n, const float* in, uint32_t* r, float* o) {
+  if (mode < 0 || mode >= gi::SEG_N_MODES) return -1;
+  for (uint64_t i = 0; i < 8 * n; i++)
+    if (!gi::finite_f(in[i])) return -1;
+  for (uint64_t i = 0; i < n; i++) gi::seg_item(mode, in + 8 * i, r[i], o + 2 * i);
+  return 0;
+}
+extern "C" int hostsim_geom_cells(int mode, uint64_t n, const float* in, const int32_t* dims, int32_t* out) {
+  if (mode < 0 || mode >= gi::CELL_N_MODES) return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    if (!gi::finite_f(in[3 * i]) || !gi::finite_f(in[3 * i + 1]) || !gi::finite_f(in[3 * i + 2]) || !(in[3 * i] > 0.0f)) return -1;
+    if (mode == gi::CELL_M_WINDOW && (dims[4 * i] < 1 || dims[4 * i + 1] < 1 || dims[4 * i + 2] < 1 || dims[4 * i + 3] < 1)) return -1;
+  }
+  for (uint64_t i = 0; i < n; i++) gi::cell_item(mode, in + 3 * i, dims + 4 * i, out + 4 * i);
+  return 0;
+}
+extern "C" int hostsim_geom_closest(int mode, const float* vtx, uint64_t nv, const uint32_t* pl_off, uint32_t npl, const float* bb,
+                                    uint64_t nbb, const uint32_t* bb_off, uint64_t n, const uint32_t* row_pl, const uint32_t* row_s0,
+                                    const uint32_t* row_s1, const float* q, float* d, uint32_t* seg, float* xy) {
+  if (mode < 0 || mode >= gi::CLOSEST_N_MODES) return -1;
+  if (!gi::polylines_ok(vtx, nv, pl_off, npl) || !gi::closest_rows_ok(pl_off, npl, bb_off, nbb, n, row_pl, row_s0, row_s1)) return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    PlRef pl;
+    pl.v = reinterpret_cast<const f2*>(vtx) + pl_off[row_pl[i]];
+    pl.n = pl_off[row_pl[i] + 1] - pl_off[row_pl[i]];
+    pl.start = 0;
+    pl.end = 1;
+    pl.bb = mode == gi::CLOSEST_M_PRUNED ? bb + 4 * (size_t)bb_off[row_pl[i]] : nullptr;
+    PlPt o;
+    o.seg = seg[i];
+    o.x = xy[2 * i];
+    o.y = xy[2 * i + 1];
+    d[i] = gi::closest_item(mode, pl, q[2 * i], q[2 * i + 1], row_s0[i], row_s1[i], o);
+    seg[i] = o.seg;
+    xy[2 * i] = o.x;
+    xy[2 * i + 1] = o.y;
+  }
+  return 0;
+}
+extern "C" int hostsim_geom_epiline(uint64_t n, const double* F, const uint8_t* valid, const float* xy, int32_t* ok, float* line) {
+  for (uint64_t i = 0; i < n; i++) ok[i] = gi::epiline_item(F + 9 * i, valid + i, xy[2 * i], xy[2 * i + 1], line + 3 * i);
+  return 0;
+}

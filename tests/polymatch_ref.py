@@ -90,23 +90,36 @@ def compute_distancesq(vtx, x, y):
     return F32(best)
 
 
-def search(scene, view, grid, x, y):
-    """find_polylines_within_search_dist_with_reprojections at (x, y) of `view`: [(polyline id, distance as float)]."""
-    ncols, nrows, off, ids = grid
+def window_rule(width, height, ncols, nrows, x, y, cc):
+    """The cells find_polylines_within_search_dist_with_reprojections visits around (x, y) (polyLine_2d_map_search.cpp:46-77):
+    cc = cell_from_coords(cell, x, y) = (col, row, on_boundary_row, on_boundary_col). None for a point on or outside the
+    image border, else (col0, col1, row0, row1), inclusive. (The one statement of the rule: search() below and the
+    cell_window rows of tests/test_geom_cases.py both use it.)"""
     x, y = F32(x), F32(y)
-    if x <= 0 or x >= scene["width"] or y <= 0 or y >= scene["height"]:
-        return []
-    col, row, b_row, b_col = cell_from_coords(FIND_WITHIN_DIST, x, y)
+    if x <= 0 or x >= width or y <= 0 or y >= height:
+        return None
+    col, row, b_row, b_col = cc() if callable(cc) else cc   # (a callable is evaluated for points inside the image only)
     col = ncols - 1 if (col < 0 or col >= ncols) else col   # (the reference compares as unsigned)
     row = nrows - 1 if (row < 0 or row >= nrows) else row
     i0 = -1 if row > 0 else 0
     i1 = 0 if b_row else (1 if row < nrows - 1 else 0)
     j0 = -1 if col > 0 else 0
     j1 = 0 if b_col else (1 if col < ncols - 1 else 0)
+    return col + j0, col + j1, row + i0, row + i1
+
+
+def search(scene, view, grid, x, y):
+    """find_polylines_within_search_dist_with_reprojections at (x, y) of `view`: [(polyline id, distance as float)]."""
+    ncols, nrows, off, ids = grid
+    x, y = F32(x), F32(y)
+    w = window_rule(scene["width"], scene["height"], ncols, nrows, x, y, lambda: cell_from_coords(FIND_WITHIN_DIST, x, y))
+    if w is None:
+        return []
+    c0, c1, r0, r1 = w
     cand = set()
-    for i in range(i0, i1 + 1):
-        for j in range(j0, j1 + 1):
-            c = (row + i) * ncols + (col + j)
+    for r in range(r0, r1 + 1):
+        for cl in range(c0, c1 + 1):
+            c = r * ncols + cl
             cand.update(int(p) for p in ids[off[c]:off[c + 1]])
     res = []
     g0 = int(scene["view_pl_off"][view])

@@ -1,7 +1,11 @@
 /*
  * eg3d_probe.h — TEST-ONLY entry points of tests/probe/libeg3d_probe.so: single device primitives of
  * the product's headers run on the GPU, for the bit-for-bit arithmetic checks of
- * tests/test_gpu_arith.py. Not part of the product and not linked into libeg3d.so.
+ * tests/test_gpu_arith.py, the lane-group solver checks of tests/test_gpu_coop_gn.py, the glm pin of tests/test_glm_pin.py
+ * and the item-by-item checks of the geometry and walk primitives of tests/test_gpu_geom_primitives.py (the walks in all
+ * their forms, the segment / line tests, the grid-cell rounding, the closest-point scans, the epipolar line; tables from
+ * tests/geom_cases.py, reference rows from the oracle, tests/test_geom_cases.py). Not part of the product and not linked
+ * into libeg3d.so.
  */
 #ifndef EG3D_PROBE_H_
 #define EG3D_PROBE_H_
@@ -44,6 +48,41 @@ int eg3d_probe_coop_gn_variants(void); /* number of variants */
 /* 2-D geometry primitives on the GPU (tests/test_glm_pin.py): mode 0 project_f32 (in [n][19] = P16 + X -> [n][2]),
  * 1 seg_line_cos (in [n][7] = segment + line -> [n]), 2 seg_closest (in [n][6] = p, v, w -> [n][3] = d2, closest point) */
 int eg3d_probe_geom(uint64_t n, int mode, const float* in, float* out);
+
+/* ---- the geometry and walk primitives of eg3d_dev_geom.h and epiline (eg3d_dev_tri.h), item by item
+ * (tests/test_gpu_geom_primitives.py): one row per lane, one primitive call per row, through the items of eg3d_geom_items.h
+ * that tests/hostsim runs through the HOST compilation of the same headers (hostsim_geom_*: same arguments). The outputs are
+ * read and written in place: the caller fills them with a sentinel, and what a primitive leaves untouched comes back as the
+ * sentinel. All return 0, -1 when a table breaks the input contract (nothing is launched then: a polyline of fewer than 2
+ * vertices, offsets not ascending or outside the vertex array, seg > n - 2, s0 / s1 > n - 1, a vertex or segment row that is
+ * not finite, the wrong number of boxes), the positive code of hipGetLastError() when the launch itself fails, -2 on any other
+ * HIP error.
+ * Polylines: vtx = [nv + 1][2], ONE SPARE VERTEX behind the nv used ones; polyline p = vertices pl_off[p] .. pl_off[p + 1] - 1.
+ *
+ * eg3d_probe_walk: one walk step per row. form 0 walk_by_distance, 1 walk_by_distance_pf, 2 walk_by_line (global pointer),
+ * 3 walk_by_line on PlRefT<const address_space(3) f2*> (one polyline per block, staged in LDS first; rows must be grouped by
+ * polyline, ascending, and no polyline may exceed eg3d_probe_walk_lds_capacity() vertices), 4 walk_by_line_pf, 5..8
+ * walk_by_line_head<1..4> followed in the same lane by walk_seg_test over k < left and walk_resolve. row_f = [n][8]: x, y of the
+ * start point, la, lb, lc, distance, min_d, max_d; row_dir = the node id walked towards; row_bnd = bounded walk. */
+int eg3d_probe_walk(int form, const float* vtx, uint64_t nv, const uint32_t* pl_off, const uint32_t* pl_start,
+                    const uint32_t* pl_end, uint32_t npl, uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg,
+                    const uint32_t* row_dir, const float* row_f, const uint8_t* row_bnd, uint32_t* status, uint32_t* seg,
+                    float* xy);
+int eg3d_probe_walk_lds_capacity(void);
+/* in = [n][8]: x1 y1 x2 y2 la lb lc thr. mode 0 seg_line_hit (r = found, o = the hit), 1 seg_line_hit_guarded (r = its bits,
+ * o = the hit), 2 point_line_dist of (x1, y1) (o[0]), 3 r = bit 0 seg_line_cos_gt(..., thr), bit 1 seg_line_cos(...) > thr
+ * evaluated in the same kernel, o[0] = seg_line_cos */
+int eg3d_probe_seg(int mode, uint64_t n, const float* in, uint32_t* r, float* o2);
+/* in = [n][3]: cell x y; dims = [n][4]: img_w img_h map_w map_h (mode 1). mode 0 cell_of -> col row bx by, 1 cell_window ->
+ * c0 c1 r0 r1 */
+int eg3d_probe_cells(int mode, uint64_t n, const float* in, const int32_t* dims, int32_t* out4);
+/* mode 0 polyline_closest, 1 polyline_closest_range [s0, s1), 2 polyline_closest_pruned with the boxes bb = [nbb][4] (blocks
+ * of EG3D_BB_SEGS segments; polyline p's boxes start at bb_off[p]). q = [n][2] query points (NaN / infinite allowed). */
+int eg3d_probe_closest(int mode, const float* vtx, uint64_t nv, const uint32_t* pl_off, uint32_t npl, const float* bb,
+                       uint64_t nbb, const uint32_t* bb_off, uint64_t n, const uint32_t* row_pl, const uint32_t* row_s0,
+                       const uint32_t* row_s1, const float* q, float* d, uint32_t* seg, float* xy);
+/* epiline with one matrix F = [n][9] and one validity byte per row */
+int eg3d_probe_epiline(uint64_t n, const double* F, const uint8_t* valid, const float* xy, int32_t* ok, float* line3);
 #ifdef __cplusplus
 }
 #endif

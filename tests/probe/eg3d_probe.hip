@@ -10,6 +10,7 @@
 #include "eg3d_probe.h"
 #include "eg3d_dev_pipeline.h"
 #include "eg3d_dev_coopgn.h"
+#include "eg3d_geom_items.h"
 
 using namespace eg3d;
 
@@ -520,5 +521,282 @@ extern "C" int eg3d_probe_geom(uint64_t n, int mode, const float* in, float* out
   PT(hipMemcpy(out, dout, n * rout * 4, hipMemcpyDeviceToHost));
   (void)hipFree(di);
   (void)hipFree(dout);
+  return 0;
+}
+
+// ---- the geometry and walk primitives of eg3d_dev_geom.h (and epiline) ITEM BY ITEM (tests/test_gpu_geom_primitives.py): one
+// row of a table of tests/geom_cases.py per lane, one primitive call per row (eg3d_geom_items.h: the same items the host
+// simulation runs through the host compilation of the header). Every loop on the device is one of the header's own, bounded by
+// the polyline's length; the host side refuses a table that breaks the input contract (-1) before anything is launched, and
+// every vertex array carries one spare vertex behind its last one.
+namespace gi = eg3d_items;
+
+// the launch's own error goes back as its (positive) HIP code
+#define PT_LAUNCH()                        \
+  do {                                     \
+    const hipError_t e_ = hipGetLastError(); \
+    if (e_ != hipSuccess) return (int)e_;  \
+  } while (0)
+
+// device memory that frees itself, so that a refused table or a failed copy leaks nothing
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+  hipError_t up(const void* src, size_t bytes) {
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e != hipSuccess || !bytes) return e;
+    return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+  }
+  hipError_t down(void* dst, size_t bytes) const { return bytes ? hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+};
+
+struct WalkTab {
+  const f2* vtx;
+  const uint32_t *pl_off, *pl_start, *pl_end;
+  const uint32_t *row_pl, *row_seg, *row_dir;
+  const float* row_f;
+  const uint8_t* row_bnd;
+  uint32_t *status, *seg;
+  float* xy;
+};
+
+__global__ void __launch_bounds__(256) k_probe_walk(int form, uint64_t n, WalkTab t) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = t.row_pl[i];
+  PlRef pl;
+  pl.v = t.vtx + t.pl_off[p];
+  pl.n = t.pl_off[p + 1] - t.pl_off[p];
+  pl.start = t.pl_start[p];
+  pl.end = t.pl_end[p];
+  PlPt o;
+  o.seg = t.seg[i];
+  o.x = t.xy[2 * i];
+  o.y = t.xy[2 * i + 1];
+  t.status[i] = gi::walk_item(form, pl, t.row_seg[i], t.row_dir[i], t.row_f + 8 * i, t.row_bnd[i] != 0, o);
+  t.seg[i] = o.seg;
+  t.xy[2 * i] = o.x;
+  t.xy[2 * i + 1] = o.y;
+}
+
+// walk_by_line on an address_space(3) pointer, as the expand kernel's side walks instantiate it (PlRefT<lds_f2p>,
+// eg3d_k3b_expand.h): block b stages the polyline blk[b][0] in LDS and its lanes take the rows blk[b][1] .. blk[b][2] - 1
+// (at most one per lane), all of that polyline. A polyline of more than EG3D_PROBE_LDS_VTX vertices gets no block.
+#define EG3D_PROBE_LDS_VTX 512
+__global__ void __launch_bounds__(256) k_probe_walk_lds(const uint32_t* blk, WalkTab t) {
+  typedef const __attribute__((address_space(3))) f2* lds_f2p;
+  __shared__ f2 sv[EG3D_PROBE_LDS_VTX + 1];
+  const uint32_t p = blk[3 * blockIdx.x];
+  const uint32_t v0 = t.pl_off[p], nvert = t.pl_off[p + 1] - v0;
+  for (uint32_t k = threadIdx.x; k < nvert + 1 && k < EG3D_PROBE_LDS_VTX + 1; k += blockDim.x) sv[k] = t.vtx[v0 + k];  // + the spare one
+  __syncthreads();
+  const uint64_t i = (uint64_t)blk[3 * blockIdx.x + 1] + threadIdx.x;
+  if (i >= blk[3 * blockIdx.x + 2]) return;
+  PlRefT<lds_f2p> pl;
+  pl.v = (lds_f2p)&sv[0];
+  pl.n = nvert;
+  pl.start = t.pl_start[p];
+  pl.end = t.pl_end[p];
+  const float* f = t.row_f + 8 * i;
+  PlPt q, o;
+  q.seg = t.row_seg[i];
+  q.x = f[0];
+  q.y = f[1];
+  o.seg = t.seg[i];
+  o.x = t.xy[2 * i];
+  o.y = t.xy[2 * i + 1];
+  t.status[i] = walk_by_line(pl, q, t.row_dir[i], f[2], f[3], f[4], t.row_bnd[i] != 0, f[6], f[7], o);
+  t.seg[i] = o.seg;
+  t.xy[2 * i] = o.x;
+  t.xy[2 * i + 1] = o.y;
+}
+
+extern "C" int eg3d_probe_walk_lds_capacity(void) { return EG3D_PROBE_LDS_VTX; }
+
+extern "C" int eg3d_probe_walk(int form, const float* vtx, uint64_t nv, const uint32_t* pl_off, const uint32_t* pl_start,
+                               const uint32_t* pl_end, uint32_t npl, uint64_t n, const uint32_t* row_pl, const uint32_t* row_seg,
+                               const uint32_t* row_dir, const float* row_f, const uint8_t* row_bnd, uint32_t* status, uint32_t* seg,
+                               float* xy) {
+  if (form < 0 || form >= gi::WALK_N_FORMS || !n || n > 0x7fffffffull || nv > 0x7fffffffull) return -1;
+  if (!pl_start || !pl_end || !row_pl || !row_seg || !row_dir || !row_f || !row_bnd || !status || !seg || !xy) return -1;
+  if (!gi::polylines_ok(vtx, nv, pl_off, npl) || !gi::walk_rows_ok(pl_off, npl, n, row_pl, row_seg)) return -1;
+  std::vector<uint32_t> blk;
+  if (form == gi::WALK_F_LINE_LDS) {  // rows grouped by polyline (ascending), chunks of one block each
+    for (uint64_t i = 0; i < n;) {
+      const uint32_t p = row_pl[i];
+      if (i && p < row_pl[i - 1]) return -1;
+      if (pl_off[p + 1] - pl_off[p] > EG3D_PROBE_LDS_VTX) return -1;  // (the caller leaves such polylines out)
+      uint64_t e = i;
+      while (e < n && row_pl[e] == p && e - i < 256) e++;
+      blk.insert(blk.end(), {p, (uint32_t)i, (uint32_t)e});
+      i = e;
+    }
+  }
+  DevBuf dv, dpo, dps, dpe, drp, drs, drd, drf, drb, dst, dsg, dxy, dblk;
+  PT(dv.up(vtx, (nv + 1) * 8));
+  PT(dpo.up(pl_off, ((size_t)npl + 1) * 4));
+  PT(dps.up(pl_start, (size_t)npl * 4));
+  PT(dpe.up(pl_end, (size_t)npl * 4));
+  PT(drp.up(row_pl, n * 4));
+  PT(drs.up(row_seg, n * 4));
+  PT(drd.up(row_dir, n * 4));
+  PT(drf.up(row_f, n * 32));
+  PT(drb.up(row_bnd, n));
+  PT(dst.up(status, n * 4));  // (the outputs go up too: the sentinel the caller filled them with)
+  PT(dsg.up(seg, n * 4));
+  PT(dxy.up(xy, n * 8));
+  WalkTab t = {dv.as<f2>(),       dpo.as<uint32_t>(), dps.as<uint32_t>(), dpe.as<uint32_t>(), drp.as<uint32_t>(), drs.as<uint32_t>(),
+               drd.as<uint32_t>(), drf.as<float>(),    drb.as<uint8_t>(),  dst.as<uint32_t>(), dsg.as<uint32_t>(), dxy.as<float>()};
+  if (form == gi::WALK_F_LINE_LDS) {
+    PT(dblk.up(blk.data(), blk.size() * 4));
+    hipLaunchKernelGGL(k_probe_walk_lds, dim3((unsigned)(blk.size() / 3)), dim3(256), 0, 0, dblk.as<uint32_t>(), t);
+  } else {
+    hipLaunchKernelGGL(k_probe_walk, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, form, n, t);
+  }
+  PT_LAUNCH();
+  PT(hipDeviceSynchronize());
+  PT(dst.down(status, n * 4));
+  PT(dsg.down(seg, n * 4));
+  PT(dxy.down(xy, n * 8));
+  return 0;
+}
+
+__global__ void __launch_bounds__(256) k_probe_seg(int mode, uint64_t n, const float* in, uint32_t* r, float* o) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t ri = r[i];
+  float oi[2] = {o[2 * i], o[2 * i + 1]};
+  gi::seg_item(mode, in + 8 * i, ri, oi);
+  r[i] = ri;
+  o[2 * i] = oi[0];
+  o[2 * i + 1] = oi[1];
+}
+extern "C" int eg3d_probe_seg(int mode, uint64_t n, const float* in, uint32_t* r, float* o) {
+  if (mode < 0 || mode >= gi::SEG_N_MODES || !n || n > 0x7fffffffull || !in || !r || !o) return -1;
+  for (uint64_t i = 0; i < 8 * n; i++)
+    if (!gi::finite_f(in[i])) return -1;
+  DevBuf di, dr, dout;
+  PT(di.up(in, n * 32));
+  PT(dr.up(r, n * 4));
+  PT(dout.up(o, n * 8));
+  hipLaunchKernelGGL(k_probe_seg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, mode, n, di.as<float>(), dr.as<uint32_t>(),
+                     dout.as<float>());
+  PT_LAUNCH();
+  PT(hipDeviceSynchronize());
+  PT(dr.down(r, n * 4));
+  PT(dout.down(o, n * 8));
+  return 0;
+}
+
+__global__ void __launch_bounds__(256) k_probe_cells(int mode, uint64_t n, const float* in, const int32_t* dims, int32_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int32_t o[4] = {out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+  gi::cell_item(mode, in + 3 * i, dims + 4 * i, o);
+  for (int k = 0; k < 4; k++) out[4 * i + k] = o[k];
+}
+extern "C" int eg3d_probe_cells(int mode, uint64_t n, const float* in, const int32_t* dims, int32_t* out) {
+  if (mode < 0 || mode >= gi::CELL_N_MODES || !n || n > 0x7fffffffull || !in || !dims || !out) return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    if (!gi::finite_f(in[3 * i]) || !gi::finite_f(in[3 * i + 1]) || !gi::finite_f(in[3 * i + 2]) || !(in[3 * i] > 0.0f)) return -1;
+    if (mode == gi::CELL_M_WINDOW && (dims[4 * i] < 1 || dims[4 * i + 1] < 1 || dims[4 * i + 2] < 1 || dims[4 * i + 3] < 1)) return -1;
+  }
+  DevBuf di, dd, dout;
+  PT(di.up(in, n * 12));
+  PT(dd.up(dims, n * 16));
+  PT(dout.up(out, n * 16));
+  hipLaunchKernelGGL(k_probe_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, mode, n, di.as<float>(), dd.as<int32_t>(),
+                     dout.as<int32_t>());
+  PT_LAUNCH();
+  PT(hipDeviceSynchronize());
+  PT(dout.down(out, n * 16));
+  return 0;
+}
+
+struct ClosestTab {
+  const f2* vtx;
+  const uint32_t* pl_off;
+  const float* bb;
+  const uint32_t* bb_off;
+  const uint32_t *row_pl, *row_s0, *row_s1;
+  const float* q;
+  float* d;
+  uint32_t* seg;
+  float* xy;
+};
+__global__ void __launch_bounds__(256) k_probe_closest(int mode, uint64_t n, ClosestTab t) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = t.row_pl[i];
+  PlRef pl;
+  pl.v = t.vtx + t.pl_off[p];
+  pl.n = t.pl_off[p + 1] - t.pl_off[p];
+  pl.start = 0;
+  pl.end = 1;
+  pl.bb = mode == gi::CLOSEST_M_PRUNED ? t.bb + 4 * (size_t)t.bb_off[p] : nullptr;
+  PlPt o;
+  o.seg = t.seg[i];
+  o.x = t.xy[2 * i];
+  o.y = t.xy[2 * i + 1];
+  t.d[i] = gi::closest_item(mode, pl, t.q[2 * i], t.q[2 * i + 1], t.row_s0[i], t.row_s1[i], o);
+  t.seg[i] = o.seg;
+  t.xy[2 * i] = o.x;
+  t.xy[2 * i + 1] = o.y;
+}
+extern "C" int eg3d_probe_closest(int mode, const float* vtx, uint64_t nv, const uint32_t* pl_off, uint32_t npl, const float* bb,
+                                  uint64_t nbb, const uint32_t* bb_off, uint64_t n, const uint32_t* row_pl, const uint32_t* row_s0,
+                                  const uint32_t* row_s1, const float* q, float* d, uint32_t* seg, float* xy) {
+  if (mode < 0 || mode >= gi::CLOSEST_N_MODES || !n || n > 0x7fffffffull || nv > 0x7fffffffull) return -1;
+  if (!bb || !bb_off || !row_pl || !row_s0 || !row_s1 || !q || !d || !seg || !xy) return -1;
+  if (!gi::polylines_ok(vtx, nv, pl_off, npl) || !gi::closest_rows_ok(pl_off, npl, bb_off, nbb, n, row_pl, row_s0, row_s1)) return -1;
+  DevBuf dv, dpo, dbb, dbo, drp, d0, d1, dq, dd, dsg, dxy;
+  PT(dv.up(vtx, (nv + 1) * 8));
+  PT(dpo.up(pl_off, ((size_t)npl + 1) * 4));
+  PT(dbb.up(bb, nbb * 16));
+  PT(dbo.up(bb_off, ((size_t)npl + 1) * 4));
+  PT(drp.up(row_pl, n * 4));
+  PT(d0.up(row_s0, n * 4));
+  PT(d1.up(row_s1, n * 4));
+  PT(dq.up(q, n * 8));
+  PT(dd.up(d, n * 4));
+  PT(dsg.up(seg, n * 4));
+  PT(dxy.up(xy, n * 8));
+  ClosestTab t = {dv.as<f2>(),        dpo.as<uint32_t>(), dbb.as<float>(), dbo.as<uint32_t>(), drp.as<uint32_t>(), d0.as<uint32_t>(),
+                  d1.as<uint32_t>(), dq.as<float>(),     dd.as<float>(),  dsg.as<uint32_t>(), dxy.as<float>()};
+  hipLaunchKernelGGL(k_probe_closest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, mode, n, t);
+  PT_LAUNCH();
+  PT(hipDeviceSynchronize());
+  PT(dd.down(d, n * 4));
+  PT(dsg.down(seg, n * 4));
+  PT(dxy.down(xy, n * 8));
+  return 0;
+}
+
+__global__ void __launch_bounds__(256) k_probe_epiline(uint64_t n, const double* F, const uint8_t* valid, const float* xy, int32_t* ok,
+                                                       float* line) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float l[3] = {line[3 * i], line[3 * i + 1], line[3 * i + 2]};
+  ok[i] = gi::epiline_item(F + 9 * i, valid + i, xy[2 * i], xy[2 * i + 1], l);
+  for (int k = 0; k < 3; k++) line[3 * i + k] = l[k];
+}
+extern "C" int eg3d_probe_epiline(uint64_t n, const double* F, const uint8_t* valid, const float* xy, int32_t* ok, float* line) {
+  if (!n || n > 0x7fffffffull || !F || !valid || !xy || !ok || !line) return -1;
+  DevBuf dF, dval, dxy, dok, dl;
+  PT(dF.up(F, n * 72));
+  PT(dval.up(valid, n));
+  PT(dxy.up(xy, n * 8));
+  PT(dok.up(ok, n * 4));
+  PT(dl.up(line, n * 12));
+  hipLaunchKernelGGL(k_probe_epiline, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, dF.as<double>(), dval.as<uint8_t>(),
+                     dxy.as<float>(), dok.as<int32_t>(), dl.as<float>());
+  PT_LAUNCH();
+  PT(hipDeviceSynchronize());
+  PT(dok.down(ok, n * 4));
+  PT(dl.down(line, n * 12));
   return 0;
 }
