@@ -3,7 +3,8 @@ of include/eg3d.h, include/eg3d_host.h and include/eg3d_rccl.h, and bind(), whic
 hand; tests/test_abi.py reads the headers and holds every row (and every struct mirror of _cdefs.py) to them. Those three
 tables are frozen; the entry points of later headers have tables of their own below (eg3d_accumulate.h,
 eg3d_host_accumulate.h: tests/test_replay_accumulate.py; eg3d_dedup_phases.h, eg3d_host_dedup_phases.h,
-eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py)."""
+eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py; eg3d_replay_merge.h, eg3d_host_replay_merge.h:
+tests/test_replay_merge.py)."""
 import ctypes as C
 
 from . import _cdefs as D
@@ -168,6 +169,16 @@ EG3D_HOST_DEDUP_PHASES = {
 EG3D_RCCL_CLAIMS = {
     "eg3d_allreduce_claims": (i32, [vp, i32, i32, vp, vp, u64, i32, u64]),
     "eg3d_exscan_points": (i32, [vp, i32, i32, vp, u64, u64p, u64p]),
+}
+
+# include/eg3d_replay_merge.h (libeg3d.so, libeg3d_dlt4x4.so): the accumulator takes the graph of the run that follows
+EG3D_REPLAY_MERGE = {
+    "eg3d_replay_merge_graph": (i32, [vp, P(D.DeviceGraph3D), u64, u64, i32, P(D.DeviceGraph3D), P(D.Graph3D), P(D.ReplayStats)]),
+}
+
+# include/eg3d_host_replay_merge.h (libeg3d_host.so): its sequential definition on a host state
+EG3D_HOST_REPLAY_MERGE = {
+    "eg3d_host_replay_state_merge_graph": (i32, [vp, P(D.Graph3D), u64]),
 }
 
 

@@ -309,6 +309,39 @@ def graph3d_to_dict(g):
     }
 
 
+GRAPH3D_ARRAYS = (("node_X", np.float32), ("node_point", np.uint64), ("pl_start", np.uint32), ("pl_end", np.uint32),
+                  ("conn_off", np.uint64), ("conn_pl", np.uint32), ("iv_off", np.uint64), ("iv_start_seg", np.uint32),
+                  ("iv_start_xy", np.float32), ("iv_end_seg", np.uint32), ("iv_end_xy", np.float32))
+
+
+def graph3d_lengths_check(g, a):
+    """The C struct carries no array lengths: a graph dict whose arrays (`a`: flattened) are shorter or longer than its
+    counts and its interval offsets say is refused here, with ValueError, before a pointer to them is handed on. conn_* are
+    not held to it (the merge does not read them)."""
+    nn, npl = int(g["n_nodes"]), int(g["n_polylines"])
+    ni = int(a["iv_off"][-1]) if a["iv_off"].size else -1
+    want = {"node_X": 3 * nn, "node_point": nn, "pl_start": npl, "pl_end": npl, "iv_start_seg": ni, "iv_end_seg": ni,
+            "iv_start_xy": 2 * ni, "iv_end_xy": 2 * ni}
+    for k, n in want.items():
+        if a[k].size != n:
+            raise ValueError("graph: %s holds %d values where its counts say %d" % (k, a[k].size, n))
+
+
+class Graph3DArrays:
+    """Owns numpy copies of a graph (a dict as returned by graph3d_to_dict) and exposes a Graph3D struct over them, for
+    the steps that consume a graph (host.ReplayState.merge). n_scene_polylines is what iv_off says."""
+
+    def __init__(self, g):
+        self.a = {k: np.ascontiguousarray(g[k], t).reshape(-1) for k, t in GRAPH3D_ARRAYS}
+        a = self.a
+        graph3d_lengths_check(g, a)
+        self.c = Graph3D()
+        self.c.n_nodes, self.c.n_real_nodes, self.c.n_polylines = int(g["n_nodes"]), int(g["n_real_nodes"]), int(g["n_polylines"])
+        self.c.n_scene_polylines = int(g.get("n_scene_polylines", len(a["iv_off"]) - 1))
+        for k, t in GRAPH3D_ARRAYS:
+            setattr(self.c, k, np_ptr(a[k], np.ctypeslib.as_ctypes_type(t)) if a[k].size else None)
+
+
 class EdgePointsArrays:
     """Owns numpy copies of an edge-point cloud (a dict as returned by edgepoints_to_dict) and
     exposes an EdgePoints struct over them, for the host steps that consume a cloud."""

@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, bind
+from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, bind
 
 _LIB = None
 
@@ -34,7 +34,7 @@ def lib():
         if not os.path.exists(path):
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
-        _LIB = bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES)
+        _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE)
     return _LIB
 
 
@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = list(EG3D)
 ACCUMULATE_SYMBOLS = list(EG3D_ACCUMULATE)
 # ... and of include/eg3d_dedup_phases.h (tests/test_abi_dedup_phases.py)
 DEDUP_PHASES_SYMBOLS = list(EG3D_DEDUP_PHASES)
+# ... and of include/eg3d_replay_merge.h (tests/test_replay_merge.py)
+REPLAY_MERGE_SYMBOLS = list(EG3D_REPLAY_MERGE)
 
 
 def _check(rc, what):
@@ -617,6 +619,42 @@ class Context:
         n, p, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().eg3d_replay_accumulated(self._h, C.byref(n), C.byref(p), C.byref(b)), "eg3d_replay_accumulated")
         return {"n_points": int(n.value), "n_pairs": int(p.value), "state_bytes": int(b.value)}
+
+    # ---- the accumulator takes the graph of the run that follows (include/eg3d_replay_merge.h) ----
+    def upload_graph(self, graph):
+        """A graph dict (as replay_device or host.replay_matches return it) as caller-built device arrays:
+        (DeviceGraph3D, the DeviceArrays that own the memory — keep them for as long as the view is used)."""
+        dv, held = D.DeviceGraph3D(), {}
+        dv.n_nodes, dv.n_real_nodes, dv.n_polylines = int(graph["n_nodes"]), int(graph["n_real_nodes"]), int(graph["n_polylines"])
+        dv.n_scene_polylines = int(graph.get("n_scene_polylines", len(graph["iv_off"]) - 1))
+        flat = {k: np.ascontiguousarray(graph[k], t).reshape(-1) for k, t in D.GRAPH3D_ARRAYS}
+        D.graph3d_lengths_check(graph, flat)
+        for k, t in D.GRAPH3D_ARRAYS:
+            a = flat[k]
+            held[k] = self.upload(a if a.size else np.zeros(1, t))
+            setattr(dv, k, held[k].ptr)
+        return dv, held
+
+    def replay_merge(self, later, n_points, n_pairs=0, reset=False, to_host=True, materialise=True):
+        """eg3d_replay_merge_graph: this context's accumulator takes, in place of the cloud of the run that follows
+        directly, the graph a replay of it built elsewhere. `later`: a DeviceGraph3D of ANOTHER context on this device
+        (replay_device / replay_accumulate / replay_merge), or a graph dict, which is uploaded. n_points: the points of
+        later's cloud; n_pairs: its pairs, only added to the totals. Returns what replay_accumulate returns."""
+        held = None
+        if not isinstance(later, D.DeviceGraph3D):
+            later, held = self.upload_graph(later)
+        g, dv, st = D.Graph3D(), D.DeviceGraph3D(), D.ReplayStats()
+        st.struct_size = C.sizeof(D.ReplayStats)
+        to_host = to_host and materialise
+        _check(lib().eg3d_replay_merge_graph(self._h, C.byref(later), int(n_points), int(n_pairs), 1 if reset else 0,
+                                             C.byref(dv) if materialise else None, C.byref(g) if to_host else None,
+                                             C.byref(st)), "eg3d_replay_merge_graph")
+        del held
+        d = None
+        if to_host:
+            d = D.graph3d_to_dict(g)
+            lib().eg3d_free_graph3d(C.byref(g))
+        return d, (dv if materialise else None), {f[0]: getattr(st, f[0]) for f in D.ReplayStats._fields_}
 
     def fetch_device_graph(self, dv):
         """Test/bench plumbing: the graph a DeviceGraph3D views (HBM), copied into the dict graph3d_to_dict gives."""

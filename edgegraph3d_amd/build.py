@@ -213,6 +213,9 @@ RESOURCE_BOUNDS = {
     "k8_": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # the accumulating replay (eg3d_replay_accumulate): as K8 — small kernels, no LDS, no spills, no scratch (all of them)
     "k8a_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    # the merge of a later shard's graph into the accumulator (eg3d_replay_merge_graph): one lane per node, polyline or
+    # interval — no LDS, no spills, no scratch (all of them)
+    "k8m_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # the polyline matcher (eg3d_match_polylines_closeness): no spills, no scratch (a substring: all of them); LDS only in the
     # search, one 64-bit slot per lane as in k1_seed_candidates
     "k9_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 2048},

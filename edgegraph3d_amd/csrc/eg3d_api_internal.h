@@ -289,6 +289,8 @@ struct ReplayAcc {
   bool have_last = false;
   uint32_t last_key[4] = {0, 0, 0, 0};
   uint64_t n_points = 0, n_pairs = 0, n_nodes = 0, n_pl = 0, n_iv = 0, slots = 0;
+  uint64_t tab_pairs = 0;  // what the node table is sized for: the pairs of the clouds + the nodes of the merged graphs
+                           // (eg3d_replay_merge_graph: a graph's pair count is the caller's word, its nodes are counted)
   bool map_ready = false;  // the claim map is filled with K8_UNCLAIMED (or holds the run's claims)
   int cur = 0;             // pl_key[cur] holds the sorted keys
   DevBuf slot, node_X, node_point, pl_start, pl_end, pl_key[2];  // node table; the append-only arrays; sorted polyline keys
@@ -298,7 +300,7 @@ struct ReplayAcc {
   void clear() {  // an empty accumulator that keeps its allocations
     valid = true;
     have_last = map_ready = false;
-    n_points = n_pairs = n_nodes = n_pl = n_iv = slots = 0;
+    n_points = n_pairs = n_nodes = n_pl = n_iv = slots = tab_pairs = 0;
     cur = 0;
   }
   size_t state_bytes() const {

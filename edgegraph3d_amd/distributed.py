@@ -552,3 +552,26 @@ def dedup_filter_then_gather(ctx, gather, dist, run_base=0, gn_max_mse=2.25, leg
         if hasattr(a, "free"):
             a.free()
     return out, rc, thr
+
+
+def replay_merge_ranks(target, dist, graph, n_points, n_pairs=0, reset=True):
+    """The matches manager of a sharded run, the raw cloud never travelling: every rank replays its own shard (rank order =
+    seed order; a shard is made of whole chains, as a seed range is) and contributes the GRAPH — `graph`: the dict that
+    Context.replay_device, Context.replay_accumulate or host.replay_matches return — with the shard's point count and,
+    for the totals, its pairs. The graphs are gathered (plain arrays: 12 + 8 bytes per node, 8 per polyline, at most one
+    interval per scene vertex; dist.all_gather_object, no RCCL code of this library) and every rank folds them in rank order
+    into `target` — an api.Context (its accumulator, eg3d_replay_merge_graph; reset starts a new graph with rank 0's) or a
+    host.ReplayState (eg3d_host_replay_state_merge_graph; an existing state is continued). Every rank ends with the same
+    graph, byte for byte what the replay of the concatenation of all shards' clouds builds, and returns it as a dict. A
+    refused graph raises on every rank alike (all fold the same graphs). Every rank must call it."""
+    world = dist.get_world_size()
+    mine = {k: (v if hasattr(v, "dtype") else int(v)) for k, v in graph.items()}
+    parts = [None] * world
+    dist.all_gather_object(parts, (mine, int(n_points), int(n_pairs)))
+    out = None
+    for r, (g, n, pairs) in enumerate(parts):
+        if hasattr(target, "replay_merge"):
+            out = target.replay_merge(g, n, pairs, reset=bool(reset) and r == 0, materialise=(r == world - 1))[0]
+        else:
+            target.merge(g, n)
+    return out if out is not None else target.graph()

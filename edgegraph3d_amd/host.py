@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_DEDUP_PHASES, bind
+from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE, bind
 
 _LIB = None
 
@@ -16,7 +16,7 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_host.so")
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
-        _LIB = bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES)
+        _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES), EG3D_HOST_REPLAY_MERGE)
     return _LIB
 
 
@@ -157,6 +157,17 @@ class ReplayState:
         rc = lib().eg3d_host_replay_state_add(self._h, C.byref(ep.c))
         if rc != 0:
             raise ValueError("eg3d_host_replay_state_add refused the cloud (%d)" % rc)
+
+    def merge(self, graph, n_points):
+        """eg3d_host_replay_state_merge_graph (include/eg3d_host_replay_merge.h): in place of the cloud of the run that
+        follows directly, the graph a replay of it built elsewhere (a dict as graph() returns it) and the number of its
+        points. Raises ValueError when the graph is refused (the state is then as it was); .code holds the C code."""
+        ga = D.Graph3DArrays(graph)
+        rc = lib().eg3d_host_replay_state_merge_graph(self._h, C.byref(ga.c), int(n_points))
+        if rc != 0:
+            err = ValueError("eg3d_host_replay_state_merge_graph refused the graph (%d)" % rc)
+            err.code = rc
+            raise err
 
     def graph(self):
         g = D.Graph3D()

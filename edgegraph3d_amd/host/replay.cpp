@@ -25,6 +25,7 @@
 
 #include "../../include/eg3d_host.h"
 #include "../../include/eg3d_host_accumulate.h"
+#include "../../include/eg3d_host_replay_merge.h"
 
 namespace {
 
@@ -125,6 +126,7 @@ struct eg3d_replay_state {
   uint32_t last_key[4] = {0, 0, 0, 0};  // key of the last point added (a cloud that would continue its chain is refused)
   bool have_last = false;
   int add(const eg3d_edgepoints* pts);
+  int merge(const eg3d_graph3d* later, uint64_t later_points);
   int graph(eg3d_graph3d* out);
 };
 
@@ -305,6 +307,119 @@ int eg3d_replay_state::add(const eg3d_edgepoints* pts) {
   return 0;
 }
 
+// ---- the graph of the run that follows directly, in place of its cloud (include/eg3d_host_replay_merge.h states the rule)
+int eg3d_replay_state::merge(const eg3d_graph3d* B, uint64_t nB) {
+  if (!B) return -1;
+  const uint64_t nA = n_points;
+  if (nB >= 0xfffffff0ull || nA + nB >= 0xfffffff0ull) return -3;
+  const uint32_t NP = sc->view_pl_off[sc->n_views];
+  const uint64_t NN = B->n_nodes, NL = B->n_polylines;
+  if (B->n_scene_polylines != NP || !B->iv_off) return -1;
+  if (NN > nB || NL > nB) return -1;  // every node has a point of its own, every polyline a pair of its own
+  if ((NN && (!B->node_X || !B->node_point)) || (NL && (!B->pl_start || !B->pl_end))) return -1;
+  auto segments = [&](uint32_t g) {
+    const uint32_t nv = sc->pl_vtx_off[g + 1] - sc->pl_vtx_off[g];
+    return nv < 2 ? 0u : nv - 1;
+  };
+  // ---- the checks: nothing of B is used as an index before it is known to be one, and nothing of the state changes
+  for (uint64_t n = 0; n < NN; n++)
+    if (B->node_point[n] >= nB) return -1;
+  for (uint64_t j = 0; j < NL; j++)
+    if (B->pl_start[j] >= NN || B->pl_end[j] >= NN) return -1;
+  if (B->iv_off[0] != 0) return -1;
+  for (uint32_t g = 0; g < NP; g++)
+    if (B->iv_off[g] > B->iv_off[g + 1] || B->iv_off[g + 1] - B->iv_off[g] > segments(g)) return -1;
+  const uint64_t NI = B->iv_off[NP];
+  if (NI && (!B->iv_start_seg || !B->iv_end_seg || !B->iv_start_xy || !B->iv_end_xy)) return -1;
+  for (uint32_t g = 0; g < NP; g++)
+    for (uint64_t k = B->iv_off[g]; k < B->iv_off[g + 1]; k++) {
+      if (B->iv_start_seg[k] >= segments(g) || B->iv_end_seg[k] >= segments(g)) return -1;
+      if (k > B->iv_off[g] && B->iv_start_seg[k - 1] >= B->iv_start_seg[k]) return -1;
+    }
+  {
+    std::unordered_set<uint64_t> pairs;
+    for (uint64_t j = 0; j < NL; j++) {
+      const uint32_t a = B->pl_start[j], b = B->pl_end[j];
+      if (!pairs.insert(((uint64_t)(a < b ? a : b) << 32) | (a < b ? b : a)).second) return -1;
+    }
+    NodeTable own;  // B's nodes among themselves, by the bit patterns (a NaN is refused below, after every -1)
+    own.reserve(NN);
+    for (uint64_t n = 0; n < NN; n++) {
+      uint64_t i = NodeTable::hash(B->node_X + 3 * n) & own.mask;
+      for (; own.slot[i]; i = (i + 1) & own.mask) {
+        const float* k = B->node_X + 3 * (size_t)(own.slot[i] - 1);
+        if (NodeTable::canon(k[0]) == NodeTable::canon(B->node_X[3 * n]) && NodeTable::canon(k[1]) == NodeTable::canon(B->node_X[3 * n + 1]) &&
+            NodeTable::canon(k[2]) == NodeTable::canon(B->node_X[3 * n + 2]))
+          return -1;
+      }
+      own.slot[i] = (uint32_t)n + 1;
+    }
+  }
+  auto plain = [](const float* X) { return X[0] == X[0] && X[1] == X[1] && X[2] == X[2] && X[0] != kInvalid && X[1] != kInvalid; };
+  if (B->n_real_nodes != NN || real_nodes != node_point.size()) return -5;
+  for (uint64_t n = 0; n < NN; n++)
+    if (!plain(B->node_X + 3 * n)) return -5;
+  for (size_t n = 0; n < node_point.size(); n++)
+    if (!plain(&node_X[3 * n])) return -5;
+  // ---- nothing was changed up to here; from here on nothing fails
+  n_points = nA + nB;
+  if (nB) have_last = false;  // a graph does not carry the key its cloud ended on: the next cloud is not checked against it
+  table.reserve(NN);
+  std::vector<uint32_t> id_of((size_t)NN);
+  for (uint64_t n = 0; n < NN; n++) {
+    const float* X = B->node_X + 3 * n;
+    bool found;
+    const uint64_t i = table.find(X, found);
+    if (found)
+      id_of[n] = table.slot[i] - 1;  // A's node: its node_X stands
+    else {
+      id_of[n] = (uint32_t)node_point.size();
+      node_X.insert(node_X.end(), X, X + 3);
+      node_point.push_back(~0ull);
+      head.push_back(~0u);
+      tail.push_back(~0u);
+      cnt.push_back(0);
+      real_nodes++;
+      table.used++;
+      table.slot[i] = id_of[n] + 1;
+      memcpy(&table.key[i * 3], X, 3 * sizeof(float));
+    }
+    node_point[id_of[n]] = nA + B->node_point[n];  // B's points all come after A's: last writer
+  }
+  auto connect = [&](uint32_t node, uint32_t pl) {
+    const uint32_t cell = (uint32_t)link_pl.size();
+    link_pl.push_back(pl);
+    link_next.push_back(~0u);
+    if (tail[node] == ~0u)
+      head[node] = cell;
+    else
+      link_next[tail[node]] = cell;
+    tail[node] = cell;
+    cnt[node]++;
+  };
+  for (uint64_t j = 0; j < NL; j++) {
+    const uint32_t a = id_of[B->pl_start[j]], b = id_of[B->pl_end[j]];
+    bool held = false;
+    for (uint32_t c = head[cnt[a] < cnt[b] ? a : b]; c != ~0u && !held; c = link_next[c]) {
+      const uint32_t p = link_pl[c];
+      held = (pl_s[p] == a && pl_e[p] == b) || (pl_s[p] == b && pl_e[p] == a);
+    }
+    if (held) continue;  // A's polyline: id and orientation stand
+    const uint32_t id = (uint32_t)pl_s.size();
+    pl_s.push_back(a);
+    pl_e.push_back(b);
+    connect(a, id);
+    if (a != b) connect(b, id);
+  }
+  for (uint32_t g = 0; g < NP; g++)
+    for (uint64_t k = B->iv_off[g]; k < B->iv_off[g + 1]; k++) {
+      if (!iv_keys.insert(((uint64_t)g << 32) | B->iv_start_seg[k]).second) continue;  // A's record stands
+      ivs.push_back({g, B->iv_start_seg[k], B->iv_end_seg[k], B->iv_start_xy[2 * k], B->iv_start_xy[2 * k + 1], B->iv_end_xy[2 * k],
+                     B->iv_end_xy[2 * k + 1]});
+    }
+  return 0;
+}
+
 // ---- flatten: a snapshot; the state is as it was (the order of `ivs` carries nothing: iv_keys decides the claims)
 int eg3d_replay_state::graph(eg3d_graph3d* out) {
   if (!out) return -1;
@@ -359,6 +474,9 @@ extern "C" eg3d_replay_state* eg3d_host_replay_state_create(const eg3d_scene* sc
   return s;
 }
 extern "C" int eg3d_host_replay_state_add(eg3d_replay_state* s, const eg3d_edgepoints* pts) { return s ? s->add(pts) : -1; }
+extern "C" int eg3d_host_replay_state_merge_graph(eg3d_replay_state* s, const eg3d_graph3d* later, uint64_t later_points) {
+  return s ? s->merge(later, later_points) : -1;
+}
 extern "C" int eg3d_host_replay_state_graph(eg3d_replay_state* s, eg3d_graph3d* out) { return s ? s->graph(out) : -1; }
 extern "C" uint64_t eg3d_host_replay_state_points(const eg3d_replay_state* s) { return s ? s->n_points : 0; }
 extern "C" void eg3d_host_replay_state_destroy(eg3d_replay_state* s) { delete s; }
