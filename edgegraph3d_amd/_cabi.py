@@ -4,7 +4,7 @@ hand; tests/test_abi.py reads the headers and holds every row (and every struct 
 tables are frozen; the entry points of later headers have tables of their own below (eg3d_accumulate.h,
 eg3d_host_accumulate.h: tests/test_replay_accumulate.py; eg3d_dedup_phases.h, eg3d_host_dedup_phases.h,
 eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py; eg3d_replay_merge.h, eg3d_host_replay_merge.h:
-tests/test_replay_merge.py)."""
+tests/test_replay_merge.py; eg3d_sets_device.h: tests/test_abi_sets_device.py)."""
 import ctypes as C
 
 from . import _cdefs as D
@@ -179,6 +179,18 @@ EG3D_REPLAY_MERGE = {
 # include/eg3d_host_replay_merge.h (libeg3d_host.so): its sequential definition on a host state
 EG3D_HOST_REPLAY_MERGE = {
     "eg3d_host_replay_state_merge_graph": (i32, [vp, P(D.Graph3D), u64]),
+}
+
+# include/eg3d_sets_device.h (libeg3d.so, libeg3d_dlt4x4.so): polyline sets resident on the device, the extractor on item
+# ranges (tests/test_abi_sets_device.py)
+EG3D_SETS_DEVICE = {
+    "eg3d_upload_polyline_sets": (i32, [vp, P(D.PolylineSets), P(D.DevicePolylineSets)]),
+    "eg3d_polyline_matches_device": (i32, [vp, P(D.DevicePolylineSets)]),
+    "eg3d_sets_from_communities_device": (i32, [vp, i64p, u64, P(D.DevicePolylineSets), P(D.SetsDeviceStats)]),
+    "eg3d_polyline_item_samples": (i32, [vp, P(D.DevicePolylineSets), u32, u32, P(D.MatchedIntervals), u32p]),
+    "eg3d_match_polyline_items": (i32, [vp, P(D.DevicePolylineSets), P(D.ItemsCall), P(D.MatchedIntervals), i32, P(D.EdgePoints),
+                                        P(D.StageTimes)]),
+    "eg3d_polyline_items_units": (i32, [vp, u32p, u32p]),
 }
 
 

@@ -26,6 +26,23 @@ class PolylineSets(C.Structure):
     _fields_ = [("n_sets", C.c_uint32), ("row_off", u32p), ("pl_ids", u32p)]
 
 
+class DevicePolylineSets(C.Structure):
+    """eg3d_device_polyline_sets (include/eg3d_sets_device.h): a view into buffers of the context that produced it."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_sets", C.c_uint32), ("n_views", C.c_int32), ("device", C.c_int32),
+                ("n_ids", C.c_uint64), ("row_off", C.c_void_p), ("pl_ids", C.c_void_p)]
+
+
+class ItemsCall(C.Structure):
+    """eg3d_items_call: the item range of one eg3d_match_polyline_items call and the samples before it."""
+    _fields_ = [("struct_size", C.c_uint32), ("item_begin", C.c_uint32), ("item_end", C.c_uint32), ("sample_base", C.c_uint32)]
+
+
+class SetsDeviceStats(C.Structure):
+    """eg3d_sets_device_stats: struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_nodes", C.c_uint32), ("n_named", C.c_uint32), ("n_sets", C.c_uint32),
+                ("n_ids", C.c_uint64), ("ms_device", C.c_float), ("ms_upload", C.c_float)]
+
+
 class EdgePoints(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("n_obs", C.c_uint64), ("X", f32p), ("obs_off", u64p),
                 ("obs_view", i32p), ("obs_pl", u32p), ("obs_seg", u32p), ("obs_xy", f32p), ("key", u32p),

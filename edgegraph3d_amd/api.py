@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, bind
+from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, bind
 
 _LIB = None
 
@@ -34,7 +34,7 @@ def lib():
         if not os.path.exists(path):
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
-        _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE)
+        _LIB = bind(bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE), EG3D_SETS_DEVICE)
     return _LIB
 
 
@@ -46,6 +46,8 @@ ACCUMULATE_SYMBOLS = list(EG3D_ACCUMULATE)
 DEDUP_PHASES_SYMBOLS = list(EG3D_DEDUP_PHASES)
 # ... and of include/eg3d_replay_merge.h (tests/test_replay_merge.py)
 REPLAY_MERGE_SYMBOLS = list(EG3D_REPLAY_MERGE)
+# ... and of include/eg3d_sets_device.h (tests/test_abi_sets_device.py)
+SETS_DEVICE_SYMBOLS = list(EG3D_SETS_DEVICE)
 
 
 def _check(rc, what):
@@ -340,6 +342,92 @@ class Context:
         d = {"ids": D.as_np(m.ids, int(m.n_nodes), np.int64), "n_communities": int(m.n_communities),
              "stats": {f[0]: getattr(st, f[0]) for f in D.LouvainStats._fields_}}
         lib().eg3d_free_communities(C.byref(m))
+        return d
+
+    # ---- include/eg3d_sets_device.h: polyline sets resident on the device, the extractor on item ranges ----
+    def upload_polyline_sets(self, n_sets, row_off, pl_ids):
+        """eg3d_upload_polyline_sets: a caller's sets made resident and checked on the device. Returns the view
+        (DevicePolylineSets), current until the next upload on this context."""
+        row_off = np.ascontiguousarray(row_off, np.uint32)
+        pl_ids = np.ascontiguousarray(pl_ids if len(pl_ids) else [0], np.uint32)
+        ps = D.PolylineSets(n_sets, D.np_ptr(row_off, C.c_uint32), D.np_ptr(pl_ids, C.c_uint32))
+        v = D.DevicePolylineSets()
+        _check(lib().eg3d_upload_polyline_sets(self._h, C.byref(ps), C.byref(v)), "eg3d_upload_polyline_sets")
+        return v
+
+    def polyline_matches_device(self):
+        """eg3d_polyline_matches_device: the rows of the last match_polylines_closeness call on this context, in place."""
+        v = D.DevicePolylineSets()
+        _check(lib().eg3d_polyline_matches_device(self._h, C.byref(v)), "eg3d_polyline_matches_device")
+        return v
+
+    def sets_from_communities_device(self, ids=None, n=None, with_stats=False):
+        """eg3d_sets_from_communities_device (K13): the sets of a community assignment over the nodes of the last
+        similarity_graph call on this context. ids: int64 per node, or None for the ids the last communities call left on
+        the device (`n`, the node count, is then required). Returns the view, or (view, stats dict)."""
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int64)
+            n = len(ids) if n is None else n
+            keep = ids if len(ids) else np.zeros(1, np.int64)
+            p = D.np_ptr(keep, C.c_int64)
+        else:
+            if n is None:
+                raise Eg3dError("sets_from_communities_device: `n` is required with the ids on the device")
+            p = None
+        v, st = D.DevicePolylineSets(), D.SetsDeviceStats()
+        st.struct_size = C.sizeof(D.SetsDeviceStats)
+        _check(lib().eg3d_sets_from_communities_device(self._h, p, int(n), C.byref(v), C.byref(st)),
+               "eg3d_sets_from_communities_device")
+        return (v, {f[0]: getattr(st, f[0]) for f in D.SetsDeviceStats._fields_}) if with_stats else v
+
+    def fetch_polyline_sets(self, view):
+        """Test plumbing: (n_sets, row_off, pl_ids) of a device sets view as numpy copies."""
+        n_rows = int(view.n_sets) * int(view.n_views)
+        a = np.empty(n_rows + 1, np.uint32)
+        b = np.empty(int(view.n_ids), np.uint32)
+        for dst, src in ((a, view.row_off), (b, view.pl_ids)):
+            if dst.nbytes and _hip().hipMemcpy(dst.ctypes.data, C.c_void_p(src), dst.nbytes, 2) != 0:
+                raise Eg3dError("hipMemcpy of the device sets failed")
+        return int(view.n_sets), a, b
+
+    def polyline_item_samples(self, view, item_begin=0, item_end=None, matched=None):
+        """eg3d_polyline_item_samples: the 20 px samples of every item (entry of pl_ids) of [item_begin, item_end), uint32;
+        with `matched` (as in match_polyline_sets) the samples left under those intervals."""
+        if item_end is None:
+            item_end = int(view.n_ids)
+        counts = np.zeros(max(item_end - item_begin, 0), np.uint32)
+        m = None
+        if matched is not None:
+            m = matched if isinstance(matched, D.MatchedIntervalsArrays) else D.MatchedIntervalsArrays(matched)
+        keep = counts if len(counts) else np.zeros(1, np.uint32)
+        _check(lib().eg3d_polyline_item_samples(self._h, C.byref(view), item_begin, item_end, C.byref(m.c) if m else None,
+                                                D.np_ptr(keep, C.c_uint32)), "eg3d_polyline_item_samples")
+        return counts
+
+    def match_polyline_items(self, view, item_begin=0, item_end=None, sample_base=0, device_only=False, matched=None):
+        """eg3d_match_polyline_items: the extractor on items [item_begin, item_end) of a device sets view; key[0] = the
+        sample's index within the range + sample_base. Returns what match_polyline_sets returns, plus "n_units" and "n_redone"
+        (units the call cut in two and redid because a 32-bit total wrapped)."""
+        if item_end is None:
+            item_end = int(view.n_ids)
+        call = D.ItemsCall(C.sizeof(D.ItemsCall), item_begin, item_end, sample_base)
+        m = None
+        if matched is not None:
+            m = matched if isinstance(matched, D.MatchedIntervalsArrays) else D.MatchedIntervalsArrays(matched)
+        e, tm = D.EdgePoints(), D.StageTimes()
+        rc = lib().eg3d_match_polyline_items(self._h, C.byref(view), C.byref(call), C.byref(m.c) if m else None,
+                                             1 if device_only else 0, C.byref(e), C.byref(tm))
+        _check(rc, "eg3d_match_polyline_items")
+        if device_only:
+            d = {"n_points": int(e.n_points), "n_obs": int(e.n_obs), "n_tasks": int(e.n_tasks),
+                 "n_hypotheses": int(e.n_hypotheses), "n_chains": int(e.n_chains), "flags": int(e.flags)}
+        else:
+            d = D.edgepoints_to_dict(e)
+        lib().eg3d_free_edgepoints(C.byref(e))
+        d["times"] = {f[0]: getattr(tm, f[0]) for f in D.StageTimes._fields_}
+        nu, nr = C.c_uint32(), C.c_uint32()
+        _check(lib().eg3d_polyline_items_units(self._h, C.byref(nu), C.byref(nr)), "eg3d_polyline_items_units")
+        d["n_units"], d["n_redone"] = int(nu.value), int(nr.value)
         return d
 
     def last_device_output(self):

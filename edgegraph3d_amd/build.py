@@ -234,6 +234,9 @@ RESOURCE_BOUNDS = {
     # ... and the fit kernel, one wavefront per SIMD with both 9 x 9 matrices of the Jacobi in registers: what does not fit
     # the 256 VGPRs is parked in AGPRs, which this figure counts (the build reports 90; a margin of a few registers)
     "k12_fit": {"vgpr_spill_count": 96},
+    # the resident polyline sets (eg3d_sets_from_communities_device, eg3d_upload_polyline_sets): one lane per node, row or
+    # id — no LDS, no spills, no scratch (a substring: all of them)
+    "k13_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},
@@ -318,7 +321,7 @@ def device_source_fingerprint(defines=()):
     moving a kernel to another file does (file names are hashed, each in front of its text). The kernels live in the
     per-stage eg3d_k*.hip / eg3d_n1_sets.hip files and the headers they include. Of the eg3d_api* files
     (eg3d_api.hip, eg3d_api_match.hip, the per-stage eg3d_api_filter / _replay / _polymatch / _simgraph / _louvain /
-    _fundamental.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
+    _fundamental / _sets.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
     the preprocessor lines count — the macros that choose the kernel build, its default form and the slot-pool sizing;
     EG3D_EXTRA_HIPFLAGS and the `defines` of the build are part of the switches."""
     import hashlib

@@ -129,6 +129,9 @@ struct DevBuf {
 //                          nothing can hide, is the smallest); EG3D_LANE_PRIORITIES=0|1: lane 0's stream high priority, lane
 //                          1 normal, the others low (default 1: the earlier units finish — and cross PCIe — first)
 //   EG3D_TEST_FAIL_UNIT=k  tests: the k-th unit (1-based) of every pipelined call fails when its turn to place comes
+//   EG3D_ITEM_UNIT_SAMPLES=n  eg3d_match_polyline_items: 20 px samples per unit at most (default 262 144; 32 768 from 64 views)
+//   EG3D_TEST_ITEM_WRAP=n  tests: eg3d_match_polyline_items treats a unit with more than n samples x views, hits or
+//                          hypotheses as one whose 32-bit totals wrap (the cut-in-two-and-redo path)
 struct Tunables {
   bool grid_on_host = false;  // EG3D_GRID_ON_HOST=1 (diagnostic / A-B): build the uniform grids with the host builder on threads
                               // (rounds 1-5, and round 6 before K0) instead of on the device
@@ -165,6 +168,10 @@ struct Tunables {
                                       // write; 0 = EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT
   uint32_t louvain_log2_slots = 0;  // EG3D_LOUVAIN_TABLE_SLOTS (tests): slots of the sweep's per-wave LDS table, raised to a
                                     // power of two in 16 .. 1024; 0 = K11_DEFAULT_SLOTS
+  uint32_t item_unit_samples = 0;  // EG3D_ITEM_UNIT_SAMPLES: 20 px samples a unit of eg3d_match_polyline_items holds at most (a
+                                   // single polyline with more is a unit of its own); 0 = the default of match_items_call
+  uint32_t test_item_wrap = 0;  // EG3D_TEST_ITEM_WRAP (tests): a unit of eg3d_match_polyline_items whose samples x views, hits or
+                                // hypotheses exceed it is treated as one whose 32-bit totals wrap (cut in two and redone)
   static Tunables from_env() {
     Tunables t;
     if (const char* e = getenv("EG3D_K3A_ENGINE_WAVES")) t.k3a_engine_waves = atoi(e);
@@ -200,6 +207,8 @@ struct Tunables {
       const unsigned long long want = std::min<unsigned long long>(K11_MAX_SLOTS, std::max<unsigned long long>(K11_MIN_SLOTS, strtoull(e, nullptr, 10)));
       while ((1ull << t.louvain_log2_slots) < want) t.louvain_log2_slots++;
     }
+    if (const char* e = getenv("EG3D_TEST_ITEM_WRAP")) t.test_item_wrap = (uint32_t)std::min(0xffffffffull, strtoull(e, nullptr, 10));
+    if (const char* e = getenv("EG3D_ITEM_UNIT_SAMPLES")) t.item_unit_samples = (uint32_t)std::min(1ull << 30, std::max(1ull, strtoull(e, nullptr, 10)));
     return t;
   }
 };
@@ -365,6 +374,20 @@ struct eg3d_ctx : SceneFacts {
   // renumbering, the overflow rows, two (key, value) sort buffers, the ids, the counters (K11Buf names them).
   DevBuf k11[K11B_COUNT];
   DevBuf b_sets_off, b_sets_ids;  // polyline sets of the current eg3d_match_polyline_sets call
+  // include/eg3d_sets_device.h: polyline sets that stay on the device. u_*: the caller's sets of eg3d_upload_polyline_sets
+  // and the flag word of their check. k13_*: eg3d_sets_from_communities_device (K13) — the caller's ids, the "named" flags
+  // and their scan, two key buffers, counters ([0] max id + 1, [1] flag word, [2] distinct keys), and the result. What the
+  // last call of each producer left (ResidentSets; K9's rows are k9_rowoff / k9_plids), and what K10 / K11 left for K13.
+  DevBuf u_sets_off, u_sets_ids, u_bad;
+  DevBuf k13_ids, k13_flag, k13_pos, k13_key[2], k13_ctr, k13_rowoff, k13_plids;
+  struct ResidentSets {
+    bool valid = false;
+    uint32_t n_sets = 0;
+    uint64_t n_ids = 0;
+  } rs_upload, rs_k9, rs_k13;
+  bool k10_valid = false, k11_valid = false;  // the last eg3d_similarity_graph / eg3d_detect_communities call succeeded ...
+  uint32_t k10_nodes = 0, k11_nodes = 0;      // ... on that many nodes (k10_nodeview / k10_nodepl, k11[K11B_IDS])
+  uint32_t items_units = 0, items_redone = 0;  // units of the last eg3d_match_polyline_items call; units it cut in two and redid
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
   // and the staging area finished chains are packed into (sized from the previous launches; grow-only)
@@ -532,4 +555,16 @@ struct HostCopy {
   HostCopy(T** d, const void* s, size_t b) : dst((void**)d), src(s), bytes(b) {}
 };
 int copy_out(hipStream_t st, const char* who, std::initializer_list<HostCopy> items);
+
+// ---- the extractor on item ranges (eg3d_api_match.hip; the entry points are in eg3d_api_sets.hip) ------------------------
+// An item is one entry of pl_ids. `sets` is resident and checked, n_rows = n_sets * V, [item_b, item_e) lies inside it.
+// count_item_samples: the count pass of k_n1_samples alone over the range, as ONE launch on the context's stream — under
+// the intervals of `m` when given. counts_host (may be null) receives the n counts, prefix (may be null) their n + 1
+// exclusive prefix sums.
+int count_item_samples(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t item_e,
+                       const eg3d_matched_intervals* m, uint32_t* counts_host, std::vector<uint32_t>* prefix);
+// match_items_call: the cloud of the items' samples, key[0] = sample index within the range + sample_base. Units are item
+// ranges cut by the sample counts; c->items_units tells how many, c->items_redone how many of them were cut in two and redone.
+int match_items_call(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t item_e, uint32_t sample_base,
+                     const eg3d_matched_intervals* m, int device_only, eg3d_edgepoints* out, eg3d_stage_times* times);
 EG3D_API_END

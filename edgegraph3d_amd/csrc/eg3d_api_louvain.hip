@@ -62,6 +62,7 @@ extern "C" int eg3d_detect_communities(eg3d_ctx* c, const eg3d_simgraph* g, cons
     g_err = "eg3d_detect_communities: a threshold is negative or not a number";
     return EG3D_ERR_ARG;
   }
+  c->k11_valid = false;
   const uint32_t log2_slots = c->tune.louvain_log2_slots ? c->tune.louvain_log2_slots : (uint32_t)__builtin_ctz(K11_DEFAULT_SLOTS);
   const auto now = [] { return std::chrono::steady_clock::now(); };
   const auto ms_since = [](std::chrono::steady_clock::time_point t) {
@@ -242,6 +243,8 @@ extern "C" int eg3d_detect_communities(eg3d_ctx* c, const eg3d_simgraph* g, cons
   out->n_nodes = n_nodes;
   out->ids = ids;
   out->n_communities = n_comm;
+  c->k11_valid = true;  // (K11B_IDS holds the ids of n_nodes nodes: eg3d_sets_from_communities_device reads them there)
+  c->k11_nodes = n_nodes;
   if (stats) {
     stats->struct_size = (uint32_t)sizeof(eg3d_louvain_stats);
     stats->n_phases = n_phases;

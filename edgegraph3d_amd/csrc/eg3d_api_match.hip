@@ -8,6 +8,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
+#include <functional>
 #include <shared_mutex>
 #include <thread>
 
@@ -310,6 +311,8 @@ struct UnitTurn {
   uint32_t u;
   double weight;       // the unit's share of the call (sum of track lengths / polylines)
   bool held = false, passed = false;
+  bool more_parts = false;  // the unit is run as several parts (eg3d_match_polyline_items: a unit cut in two and redone) and
+                            // the part in progress is not its last: its tasks are counted, the turn stays with the unit
   bool take() {
     if (held) return true;
     if (passed) return false;
@@ -335,7 +338,7 @@ struct UnitTurn {
   bool finish(uint32_t n_tasks) {
     if (!take()) return false;
     S.unit_tasks(n_tasks);
-    pass();
+    if (!more_parts) pass();
     return true;
   }
 };
@@ -909,9 +912,14 @@ int stage_times_and_counts(eg3d_ctx* c, const BatchState& B, HostOut& H, const E
   return EG3D_OK;
 }
 
+// (the steps behind count_hypotheses: a caller that judges the unit's totals first — run_items_part — enters here)
+int run_stage_b_counted(eg3d_ctx* c, BatchState& B, UnitTurn& T, HostOut& H);
 int run_stage_b(eg3d_ctx* c, BatchState& B, UnitTurn& T, HostOut& H) {
-  const bool device_only = T.S.device_only != 0;
   BUF_TRY(count_hypotheses(c, B));
+  return run_stage_b_counted(c, B, T, H);
+}
+int run_stage_b_counted(eg3d_ctx* c, BatchState& B, UnitTurn& T, HostOut& H) {
+  const bool device_only = T.S.device_only != 0;
   BUF_TRY(follow_and_select(c, B, H));
   // ---- K3b + K4. One launch takes all the chains of the batch: their working slices are slots of a fixed arena
   // (8 XCDs x slots_per_xcd), so nothing grows with the number of chains but the staging area the finished chains
@@ -959,13 +967,13 @@ int run_batch(eg3d_ctx* c, uint32_t b, uint32_t e, UnitTurn& T, HostOut& H) {
 // device; h_row_off is its host copy of the row offsets.
 // `matched` (null: none) is the caller's interval table on the device: samples and hits inside a held interval are left out
 // (k_n1_samples / k_n1_hits <., true>); skip_cnt / drop_cnt (may be null) receive the per-polyline / per-task counts of them.
-int run_sets_stage_a(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
-                     uint32_t set_e, const IvTable* matched, DevBuf* skip_cnt, DevBuf* drop_cnt, BatchState& B) {
+// (the kernels work on items — entries [item_b, item_e) of pl_ids; a run of whole sets is the items of its rows)
+int run_items_stage_a(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows_total, uint32_t item_b, uint32_t item_e,
+                      const IvTable* matched, DevBuf* skip_cnt, DevBuf* drop_cnt, BatchState& B) {
   hipStream_t st = c->stream;
   const uint32_t V = (uint32_t)c->V;
   memset(&B, 0, sizeof(B));
   B.key0_base = 0;  // (key[0] = sample index of the CALL: the sink adds the samples of the units before this one)
-  const uint32_t item_b = h_row_off[(size_t)set_b * V], item_e = h_row_off[(size_t)set_e * V];
   const uint32_t n_items = item_e - item_b;
   BUF_TRY(c->b_ctr.ensure(sizeof(Counters)));
   HIP_TRY(hipMemsetAsync(c->b_ctr.p, 0, sizeof(Counters), st));
@@ -1025,12 +1033,32 @@ int run_sets_stage_a(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off
   return EG3D_OK;
 }
 
-int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
-                   uint32_t set_e, const IvTable* matched, UnitTurn& T, HostOut& H) {
+int run_sets_stage_a(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
+                     uint32_t set_e, const IvTable* matched, DevBuf* skip_cnt, DevBuf* drop_cnt, BatchState& B) {
+  const uint32_t V = (uint32_t)c->V;
+  return run_items_stage_a(c, sets, n_rows_total, h_row_off[(size_t)set_b * V], h_row_off[(size_t)set_e * V], matched, skip_cnt,
+                           drop_cnt, B);
+}
+
+// One unit of a polyline-set call, items [item_b, item_e): stage A above, then the common stage B.
+// `wrapped` (null: the unit runs or the call fails, as eg3d_match_polyline_sets does): the caller can cut the unit. The
+// unit's 32-bit totals — samples x views, epipolar hits, hypotheses — are all known before the first chain is followed;
+// where one does not fit (or exceeds wrap_limit, EG3D_TEST_ITEM_WRAP; 0 = no such limit), *wrapped is set and EG3D_OK
+// returned with nothing placed, nothing counted into H and the turn untouched.
+int run_items_batch(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows_total, uint32_t item_b, uint32_t item_e,
+                    const IvTable* matched, UnitTurn& T, HostOut& H, uint32_t wrap_limit = 0, bool* wrapped = nullptr) {
   hipStream_t st = c->stream;
   const uint32_t V = (uint32_t)c->V;
   BatchState B;
-  BUF_TRY(run_sets_stage_a(c, sets, h_row_off, n_rows_total, set_b, set_e, matched, nullptr, nullptr, B));
+  {
+    const int rc = run_items_stage_a(c, sets, n_rows_total, item_b, item_e, matched, nullptr, nullptr, B);
+    if (wrapped) {
+      *wrapped = rc == EG3D_ERR_CAPACITY ||
+                 (rc == EG3D_OK && wrap_limit && ((uint64_t)B.n_tasks * V > wrap_limit || B.n_hits > wrap_limit));
+      if (*wrapped) return EG3D_OK;
+    }
+    BUF_TRY(rc);
+  }
   const uint32_t nt = B.n_tasks;
   // every sample of the unit lies inside a held interval: nothing to launch, the unit only takes its turn
   if (matched && !nt) return T.finish(0) ? EG3D_OK : EG3D_ERR_HIP;
@@ -1049,11 +1077,25 @@ int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, 
   }
   fill_stage_a_view(c, B);  // (no tracks, seed_begin = sv_base = 0: B was zeroed)
   B.a.dense_k = V;
-  BUF_TRY(run_stage_b(c, B, T, H));
+  if (wrapped) {
+    const int rc = count_hypotheses(c, B);
+    *wrapped = rc == EG3D_ERR_CAPACITY || (rc == EG3D_OK && wrap_limit && B.n_hyp > wrap_limit);
+    if (*wrapped) return EG3D_OK;
+    BUF_TRY(rc);
+    BUF_TRY(run_stage_b_counted(c, B, T, H));
+  } else {
+    BUF_TRY(run_stage_b(c, B, T, H));
+  }
   // per sample: its coordinates, V camera matrices, V-1 fundamental matrices (the scanned vertices
   // and the output were added by the kernels)
   H.bytes_algorithmic += (uint64_t)nt * (8 + (uint64_t)V * 64 + (uint64_t)(V - 1) * 72);
   return EG3D_OK;
+}
+
+int run_sets_batch(eg3d_ctx* c, const SetsDev& sets, const uint32_t* h_row_off, uint32_t n_rows_total, uint32_t set_b,
+                   uint32_t set_e, const IvTable* matched, UnitTurn& T, HostOut& H) {
+  const uint32_t V = (uint32_t)c->V;
+  return run_items_batch(c, sets, n_rows_total, h_row_off[(size_t)set_b * V], h_row_off[(size_t)set_e * V], matched, T, H);
 }
 
 template <typename T>
@@ -1285,14 +1327,16 @@ static std::vector<UnitRange> plan_seed_units(const eg3d_ctx* c, uint32_t b, uin
 
 // What eg3d_match_resident and eg3d_match_polyline_sets do with their units: the call's sink, the units on the lanes
 // (run(lane, unit index, turn, stats) -> status computes one), the call's time, the result. keyed_by_sample: key[0] of a
-// point is the sample index of the CALL (polyline sets), not a seed id.
+// point is the sample index of the CALL (polyline sets), not a seed id; key0_start is then the index of the call's first
+// sample (eg3d_match_polyline_items: the samples of the item ranges before this one).
 template <typename Run>
 static int match_call(eg3d_ctx* c, int device_only, bool keyed_by_sample, const std::vector<UnitRange>& units, int lanes,
-                      eg3d_edgepoints* out, eg3d_stage_times* times, Run run) {
+                      eg3d_edgepoints* out, eg3d_stage_times* times, Run run, uint32_t key0_start = 0) {
   CallSink S;
   S.owner = c;
   S.device_only = device_only;
   S.keyed_by_sample = keyed_by_sample;
+  S.key0_next = key0_start;
   c->last_np = c->last_no = 0;
   c->last_chunks = 0;
   const auto t0 = std::chrono::steady_clock::now();
@@ -1493,6 +1537,110 @@ extern "C" int eg3d_match_polyline_sets_matched(eg3d_ctx* c, const eg3d_polyline
                                                 const eg3d_matched_intervals* m, int device_only, eg3d_edgepoints* out,
                                                 eg3d_stage_times* times) {
   return match_sets_call(c, ps, set_b, set_e, m, device_only, out, times);
+}
+
+// ---- the extractor on item ranges (include/eg3d_sets_device.h; the entry points are in eg3d_api_sets.hip) -----------------
+// The count pass of k_n1_samples over items [item_b, item_b + n_items) on the context's stream: the counts in b_raw_cnt,
+// their exclusive scan in b_raw_off (n_items + 1 words), the total on the host.
+static int count_items(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t n_items, const IvTable* matched,
+                       uint32_t& total) {
+  hipStream_t st = c->stream;
+  BUF_TRY(c->b_ctr.ensure(sizeof(Counters)));
+  HIP_TRY(hipMemsetAsync(c->b_ctr.p, 0, sizeof(Counters), st));
+  BUF_TRY(c->b_raw_cnt.ensure(sizeof(uint32_t) * ((size_t)n_items + 1)));
+  BUF_TRY(c->b_raw_off.ensure(sizeof(uint32_t) * ((size_t)n_items + 1)));
+  HIP_TRY(hipMemsetAsync(c->b_raw_cnt.as<uint32_t>() + n_items, 0, sizeof(uint32_t), st));
+  launch_n1_samples(st, false, c->ds, sets, n_rows, item_b, n_items, c->b_raw_cnt.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, nullptr, c->b_ctr.as<Counters>(), matched, nullptr);
+  BUF_TRY(scan_total_u32(c, c->b_raw_cnt.as<uint32_t>(), c->b_raw_off.as<uint32_t>(), (size_t)n_items + 1, total, "samples"));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (matched) {
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpy(&flags, &c->b_ctr.as<Counters>()->flags, sizeof(flags), hipMemcpyDeviceToHost));
+    if (flags & CTR_N1_NO_PROGRESS) return bad_matched("the walk does not advance past a matched interval: the intervals do not belong to this scene");
+  }
+  return EG3D_OK;
+}
+
+int eg3d::api::count_item_samples(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t item_e,
+                                  const eg3d_matched_intervals* m, uint32_t* counts_host, std::vector<uint32_t>* prefix) {
+  HIP_TRY(hipSetDevice(c->device));
+  MatchedCall M;
+  BUF_TRY(prepare_matched(c, m, M));
+  const uint32_t n_items = item_e - item_b;
+  uint32_t total = 0;
+  BUF_TRY(count_items(c, sets, n_rows, item_b, n_items, M.active ? &M.dev : nullptr, total));
+  if (counts_host && n_items) HIP_TRY(hipMemcpy(counts_host, c->b_raw_cnt.p, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost));
+  if (prefix) {
+    prefix->resize((size_t)n_items + 1);
+    HIP_TRY(hipMemcpy(prefix->data(), c->b_raw_off.p, sizeof(uint32_t) * ((size_t)n_items + 1), hipMemcpyDeviceToHost));
+  }
+  return EG3D_OK;
+}
+
+int eg3d::api::match_items_call(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t item_e,
+                                uint32_t sample_base, const eg3d_matched_intervals* m, int device_only, eg3d_edgepoints* out,
+                                eg3d_stage_times* times) {
+  HIP_TRY(hipSetDevice(c->device));
+  MatchedCall M;
+  BUF_TRY(prepare_matched(c, m, M));  // (before `out` is touched)
+  const IvTable* matched = M.active ? &M.dev : nullptr;
+  memset(out, 0, sizeof(*out));
+  c->items_units = 0;
+  const uint32_t V = (uint32_t)c->V, n_items = item_e - item_b;
+  // one count pass for the range; its prefix sums, read back, are what the units are cut by
+  uint32_t total = 0;
+  std::vector<uint32_t> pre((size_t)n_items + 1, 0);
+  BUF_TRY(count_items(c, sets, n_rows, item_b, n_items, matched, total));
+  HIP_TRY(hipMemcpy(pre.data(), c->b_raw_off.p, sizeof(uint32_t) * ((size_t)n_items + 1), hipMemcpyDeviceToHost));
+  if ((uint64_t)sample_base + total > 0xffffffffull) {
+    g_err = "eg3d_match_polyline_items: sample_base + the samples of the range does not fit key[0]";
+    return EG3D_ERR_CAPACITY;
+  }
+  const int lanes = lanes_for(c, device_only);
+  // units = item ranges of at most unit_samples samples (every sample owns V lists); with several lanes at least one unit
+  // per lane, balanced by the samples. A set larger than a unit is cut inside; only a single polyline stays whole.
+  const uint32_t unit_samples = c->tune.item_unit_samples ? c->tune.item_unit_samples : (V >= 64 ? 1u << 15 : 1u << 18);
+  std::vector<UnitRange> units;
+  {
+    auto cum = [&](uint32_t i) { return (double)pre[i - item_b] + 1e-3 * (double)i; };  // (+ a little per item: empty ones count)
+    const uint32_t want = c->tune.units ? (uint32_t)c->tune.units : (uint32_t)lanes;
+    for (const UnitRange& r : cut_by_weight(item_b, item_e, want, cum))
+      for (uint32_t i0 = r.b; i0 < r.e;) {
+        uint32_t i1 = i0 + 1;
+        while (i1 < r.e && pre[i1 + 1 - item_b] - pre[i0 - item_b] <= unit_samples) i1++;
+        units.push_back({i0, i1, cum(i1) - cum(i0)});
+        i0 = i1;
+      }
+  }
+  c->items_units = (uint32_t)units.size();
+  // A unit whose 32-bit totals wrap is cut in two by its samples and redone, down to one item: the parts run one after the
+  // other on the unit's lane and under the unit's turn (UnitTurn::more_parts), so the cloud's bytes do not depend on it.
+  std::atomic<uint32_t> redone{0};
+  const uint32_t wrap_limit = c->tune.test_item_wrap;
+  std::function<int(eg3d_ctx*, uint32_t, uint32_t, bool, UnitTurn&, HostOut&)> part = [&](eg3d_ctx* lane, uint32_t b, uint32_t e,
+                                                                                           bool last, UnitTurn& T, HostOut& H) -> int {
+    T.more_parts = !last;
+    bool wrapped = false;
+    BUF_TRY(run_items_batch(lane, sets, n_rows, b, e, matched, T, H, wrap_limit, &wrapped));
+    if (!wrapped) return EG3D_OK;
+    if (e - b <= 1) {
+      g_err = "eg3d_match_polyline_items: the samples x views, epipolar hits or hypotheses of a single polyline exceed 2^32-1";
+      return EG3D_ERR_CAPACITY;
+    }
+    redone.fetch_add(1);
+    const uint32_t half = pre[b - item_b] + (pre[e - item_b] - pre[b - item_b]) / 2;
+    uint32_t mid = b + 1;
+    while (mid < e - 1 && pre[mid - item_b] < half) mid++;
+    BUF_TRY(part(lane, b, mid, false, T, H));
+    return part(lane, mid, e, last, T, H);
+  };
+  const int rc = match_call(
+      c, device_only, true, units, lanes, out, times,
+      [&](eg3d_ctx* lane, uint32_t u, UnitTurn& T, HostOut& H) { return part(lane, units[u].b, units[u].e, true, T, H); },
+      sample_base);
+  c->items_redone = redone.load();
+  return rc;
 }
 
 namespace {

@@ -23,6 +23,7 @@ static int polymatch_impl(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint
   BUF_TRY(open_seed_range(c, who, seeds, b, e, out, &eg3d_ctx::k9_ctr, &eg3d_ctx::k9_svseed, &r));  // k9_ctr: [0] flags, [1] nodes, [2] sets
   hipStream_t st = c->stream;
   const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_seeds = r.n_seeds, sv_base = r.sv_base, n_sv = r.n_sv;
+  c->rs_k9.valid = false;  // (k9_rowoff / k9_plids are rewritten: eg3d_polyline_matches_device views them once this call is through)
   uint32_t n_acc = 0, n_nodes = 0, n_sets = 0;
   float ms_search = 0, ms_comp = 0, ms_copy = 0;
   if (r.active) {
@@ -110,6 +111,9 @@ static int polymatch_impl(eg3d_ctx* c, const eg3d_seeds* seeds, uint32_t b, uint
   m.n_sets = n_sets;
   ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = m;
+  c->rs_k9.valid = true;
+  c->rs_k9.n_sets = n_sets;
+  c->rs_k9.n_ids = n_nodes;
   if (stats) {
     stats->struct_size = (uint32_t)sizeof(eg3d_polymatch_stats);
     stats->n_entries = n_sv;

@@ -21,6 +21,7 @@ extern "C" int eg3d_similarity_graph(eg3d_ctx* c, const eg3d_seeds* seeds, uint3
   SeedRange r;  // k10_ctr: [0] flags, [1] nodes, [2] distinct edges, [3] kept edges
   BUF_TRY(open_seed_range(c, who, seeds, b, e, out, &eg3d_ctx::k10_ctr, &eg3d_ctx::k10_svseed, &r));
   hipStream_t st = c->stream;
+  c->k10_valid = false;
   const uint32_t V = (uint32_t)c->V, NP = c->n_pl, n_pts = r.n_seeds, sv_base = r.sv_base, n_sv = r.n_sv;
   const uint64_t budget = c->tune.simgraph_pair_budget ? c->tune.simgraph_pair_budget : EG3D_SIMGRAPH_PAIR_BUDGET_DEFAULT;
   uint32_t n_pair = 0, n_nodes = 0, n_uniq = 0, n_kept = 0, n_chunks = 0;
@@ -194,6 +195,8 @@ extern "C" int eg3d_similarity_graph(eg3d_ctx* c, const eg3d_seeds* seeds, uint3
   m.n_polylines = NP;
   ms_copy = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = m;
+  c->k10_valid = true;  // (k10_nodeview / k10_nodepl hold the n_nodes nodes: eg3d_sets_from_communities_device reads them there)
+  c->k10_nodes = n_nodes;
   if (stats) {
     stats->struct_size = (uint32_t)sizeof(eg3d_simgraph_stats);
     stats->n_entries = n_sv;

@@ -74,6 +74,50 @@ class StepPlan:
         return (self.n_total + self.batch - 1) // self.batch
 
 
+class SetsPlan:
+    """Which ITEMS of resident polyline sets a rank takes (include/eg3d_sets_device.h), in the shape of StepPlan: pure
+    arithmetic on the per-item sample counts that Context.polyline_item_samples returns. The items [0, n) are split into
+    `world` contiguous ranges balanced by the samples; rank order = item order, and sample_base(rank) — the samples of the
+    ranks before — is what the rank passes to Context.match_polyline_items, so that the concatenation of the ranks' clouds
+    is the cloud of one call over all items. Rank k's range ends at the first item boundary at which the samples so far
+    reach k + 1 shares of the total, so no share exceeds the ideal (total / world) by as much as its largest item. Items
+    without samples travel with the range they fall into; with no samples at all the items are split evenly."""
+
+    def __init__(self, counts, world, rank=0):
+        import numpy as np
+        self.world, self.rank = int(world), int(rank)
+        if self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError("SetsPlan: need world >= 1 and 0 <= rank < world")
+        c = np.asarray(counts, np.int64).reshape(-1)
+        if (c < 0).any():
+            raise ValueError("SetsPlan: a sample count is negative")
+        self.n_items = len(c)
+        self.prefix = np.concatenate([[0], np.cumsum(c)]).astype(np.int64)
+        self.total = int(self.prefix[-1])
+        k = np.arange(1, self.world, dtype=np.int64)
+        if self.total:
+            # first boundary whose prefix reaches k shares (k * total / world, compared exactly in integers)
+            inner = np.searchsorted(self.prefix * self.world, k * self.total, side="left")
+        else:
+            inner = (k * self.n_items) // self.world
+        self.cuts = np.concatenate([[0], inner, [self.n_items]]).astype(np.int64)
+
+    def item_range(self, rank=None):
+        r = self.rank if rank is None else int(rank)
+        return int(self.cuts[r]), int(self.cuts[r + 1])
+
+    def sample_base(self, rank=None):
+        return int(self.prefix[self.item_range(rank)[0]])
+
+    def n_samples(self, rank=None):
+        b, e = self.item_range(rank)
+        return int(self.prefix[e] - self.prefix[b])
+
+    def ranges(self):
+        """[(item_begin, item_end, sample_base)] of every rank, in rank order."""
+        return [self.item_range(r) + (self.sample_base(r),) for r in range(self.world)]
+
+
 _GATHER_LIB = None
 
 

@@ -33,6 +33,9 @@
 //   edge_matcher_refpoints <dir>/input.json <dir>/plgs.bin <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs]
 //                          [--sets1 <polyline matches of pipeline 1>] [--sets2 <... of pipeline 2> | --match2]
 //                          [--refpoints-first]   (pipeline 3 first; pipelines 1-2 skip what it already matched)
+//                          [--resident-sets]     (--match2 / --louvain / --communities: the matches stay on the device —
+//                                                 eg3d_polyline_matches_device, eg3d_sets_from_communities_device — and the
+//                                                 extractor takes them there, eg3d_match_polyline_items; same output)
 //        a match file is text: "eg3d-polyline-sets 1", then "<n_sets> <n_views>", then one line per (set, view):
 //        "<count> <polyline id> ..." with view-local ids (the reference's vector<set<ulong>> per match)
 //        (--make-synthetic also writes <dir>/sets1.txt and <dir>/sets2.txt: the polylines of 3-D curves 0-2 / 3-5)
@@ -49,6 +52,7 @@
 
 #include "eg3d.h"
 #include "eg3d_host.h"
+#include "eg3d_sets_device.h"
 
 static int fail(const char* what) {
   std::fprintf(stderr, "edge_matcher_refpoints: %s (%s)\n", what, eg3d_last_error());
@@ -202,7 +206,7 @@ int main(int argc, char** argv) {
   if (argc >= 4 && std::strcmp(argv[1], "--make-synthetic") == 0) return make_synthetic(std::atoi(argv[2]), argv[3]);
   if (argc >= 4 && std::strcmp(argv[1], "--make-plgs") == 0) return make_plgs(argv[2], argc - 3, argv + 3);
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup] [--refpoints-first]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup] [--refpoints-first] [--resident-sets]\n", argv[0]);
     return 2;
   }
   bool do_filter = false, estimate_F = false, all_pairs = false, estimate_F_device = false;
@@ -251,6 +255,10 @@ int main(int argc, char** argv) {
       if (a + 1 < argc && std::strncmp(argv[a + 1], "--", 2) != 0) louvain_out = argv[++a];
     }
   }
+  // --resident-sets: the polyline matches of --match2 and of --louvain / --communities are not rebuilt as host rows and
+  // uploaded again: the extractor reads them where K9 / K13 leave them (include/eg3d_sets_device.h)
+  bool resident_sets = false;
+  for (int a = 4; a < argc; a++) resident_sets |= std::strcmp(argv[a], "--resident-sets") == 0;
   if ((communities_path || louvain) && sets_path[0]) {
     std::fprintf(stderr, "--communities / --louvain and --sets1 exclude each other\n");
     return 2;
@@ -401,6 +409,8 @@ int main(int argc, char** argv) {
     const bool match1 = stage == 0 && (graph_path || communities_path || louvain);
     if (!sets_path[stage] && !(stage == 1 && match2) && !match1) continue;
     MatchSets ms;
+    eg3d_device_polyline_sets dsets;
+    bool on_device = false;
     if (match1) {  // pipelines.cpp:219 -> polyline_matcher.cpp:222-336; the community detection: --louvain, or the caller's
       eg3d_seeds rp;
       eg3d_sfm_seeds(sfm, &rp);
@@ -433,16 +443,24 @@ int main(int argc, char** argv) {
         return fail("reading the communities");
       }
       eg3d_polyline_sets cs;
-      const int rc = eg3d_host_sets_from_communities(&sg, ids, n_ids, V, &cs);
+      std::memset(&cs, 0, sizeof(cs));
+      // (--resident-sets: K13 on the graph's nodes where the graph call left them; --louvain's ids are on the device too)
+      const int rc = resident_sets ? eg3d_sets_from_communities_device(ctx, louvain ? nullptr : ids, n_ids, &dsets, nullptr)
+                                   : eg3d_host_sets_from_communities(&sg, ids, n_ids, V, &cs);
       if (louvain) eg3d_free_communities(&cm);
       else eg3d_host_free(ids);
       eg3d_free_simgraph(&sg);
       if (rc != EG3D_OK) return fail("the communities do not fit the graph (one id per node)");
-      ms.n_sets = cs.n_sets;
-      ms.row_off.assign(cs.row_off, cs.row_off + (size_t)cs.n_sets * V + 1);
-      ms.ids.assign(cs.pl_ids, cs.pl_ids + ms.row_off.back());
-      if (ms.ids.empty()) ms.ids.push_back(0);
-      eg3d_host_free_polyline_sets(&cs);
+      if (resident_sets) {
+        on_device = true;
+        ms.n_sets = dsets.n_sets;
+      } else {
+        ms.n_sets = cs.n_sets;
+        ms.row_off.assign(cs.row_off, cs.row_off + (size_t)cs.n_sets * V + 1);
+        ms.ids.assign(cs.pl_ids, cs.pl_ids + ms.row_off.back());
+        if (ms.ids.empty()) ms.ids.push_back(0);
+        eg3d_host_free_polyline_sets(&cs);
+      }
     } else if (stage == 1 && match2) {  // pipelines.cpp:118
       eg3d_seeds rp;
       eg3d_sfm_seeds(sfm, &rp);
@@ -455,14 +473,22 @@ int main(int argc, char** argv) {
       if (ms.ids.empty()) ms.ids.push_back(0);
       std::printf("pipeline 2: %u reference points accepted by the polyline matcher\n", pm.n_refpoints);
       eg3d_free_polyline_matches(&pm);
+      if (resident_sets) {
+        if (eg3d_polyline_matches_device(ctx, &dsets) != EG3D_OK) return fail("eg3d_polyline_matches_device");
+        on_device = true;
+      }
     } else if (!read_match_sets(sets_path[stage], V, ms)) return fail("reading a polyline match file");
     eg3d_polyline_sets ps;
     ps.n_sets = ms.n_sets;
     ps.row_off = ms.row_off.data();
     ps.pl_ids = ms.ids.data();
     eg3d_edgepoints e;
-    if (eg3d_match_polyline_sets_matched(ctx, &ps, 0, ms.n_sets, refpoints_first ? &held : nullptr, resident_dedup ? 1 : 0, &e,
-                                         &tm) != EG3D_OK)
+    if (on_device) {  // every item of the resident sets, as one range
+      const eg3d_items_call all = {(uint32_t)sizeof(eg3d_items_call), 0u, (uint32_t)dsets.n_ids, 0u};
+      if (eg3d_match_polyline_items(ctx, &dsets, &all, refpoints_first ? &held : nullptr, resident_dedup ? 1 : 0, &e, &tm) != EG3D_OK)
+        return fail("eg3d_match_polyline_items");
+    } else if (eg3d_match_polyline_sets_matched(ctx, &ps, 0, ms.n_sets, refpoints_first ? &held : nullptr, resident_dedup ? 1 : 0,
+                                                &e, &tm) != EG3D_OK)
       return fail("eg3d_match_polyline_sets");
     std::printf("pipeline %d: %u polyline matches -> %llu edge-points (%llu observations) in %.2f ms on the GPU\n", stage + 1,
                 ms.n_sets, (unsigned long long)e.n_points, (unsigned long long)e.n_obs, tm.ms_total);
