@@ -4,7 +4,8 @@ hand; tests/test_abi.py reads the headers and holds every row (and every struct 
 tables are frozen; the entry points of later headers have tables of their own below (eg3d_accumulate.h,
 eg3d_host_accumulate.h: tests/test_replay_accumulate.py; eg3d_dedup_phases.h, eg3d_host_dedup_phases.h,
 eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py; eg3d_replay_merge.h, eg3d_host_replay_merge.h:
-tests/test_replay_merge.py; eg3d_sets_device.h: tests/test_abi_sets_device.py)."""
+tests/test_replay_merge.py; eg3d_sets_device.h: tests/test_abi_sets_device.py; eg3d_triangulate.h,
+eg3d_host_triangulate.h: tests/test_abi_triangulate.py)."""
 import ctypes as C
 
 from . import _cdefs as D
@@ -191,6 +192,18 @@ EG3D_SETS_DEVICE = {
     "eg3d_match_polyline_items": (i32, [vp, P(D.DevicePolylineSets), P(D.ItemsCall), P(D.MatchedIntervals), i32, P(D.EdgePoints),
                                         P(D.StageTimes)]),
     "eg3d_polyline_items_units": (i32, [vp, u32p, u32p]),
+}
+
+# include/eg3d_triangulate.h (libeg3d.so, libeg3d_dlt4x4.so): FP64 triangulation of caller-supplied tracks, K14
+# (tests/test_abi_triangulate.py)
+EG3D_TRIANGULATE = {
+    "eg3d_triangulate": (i32, [vp, i32, u64, u32p, i32p, f32p, f32p, f32p, u8p, u8p, P(D.TriStats)]),
+    "eg3d_triangulate_device": (i32, [vp, i32, P(D.DeviceEdgePoints), vp, vp, vp, P(D.TriStats)]),
+}
+
+# include/eg3d_host_triangulate.h (libeg3d_host.so): its sequential statement, both DLT forms
+EG3D_HOST_TRIANGULATE = {
+    "eg3d_host_triangulate": (i32, [i32, f32p, i32, i32, u64, u32p, i32p, f32p, f32p, i32, f32p, u8p, u8p]),
 }
 
 

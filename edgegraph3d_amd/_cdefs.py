@@ -43,6 +43,13 @@ class SetsDeviceStats(C.Structure):
                 ("n_ids", C.c_uint64), ("ms_device", C.c_float), ("ms_upload", C.c_float)]
 
 
+class TriStats(C.Structure):
+    """eg3d_tri_stats (include/eg3d_triangulate.h): struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_batches", C.c_uint32), ("n_tracks", C.c_uint64), ("n_valid", C.c_uint64),
+                ("n_short", C.c_uint64), ("n_degenerate", C.c_uint64), ("ms_kernel", C.c_float), ("ms_stage", C.c_float),
+                ("ms_copy", C.c_float)]
+
+
 class EdgePoints(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("n_obs", C.c_uint64), ("X", f32p), ("obs_off", u64p),
                 ("obs_view", i32p), ("obs_pl", u32p), ("obs_seg", u32p), ("obs_xy", f32p), ("key", u32p),

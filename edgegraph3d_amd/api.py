@@ -13,13 +13,18 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, bind
+from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, EG3D_TRIANGULATE, bind
 
 _LIB = None
 
 
 class Eg3dError(RuntimeError):
     pass
+
+
+# include/eg3d_triangulate.h
+TRI_FROM_SCRATCH, TRI_REFINE = 0, 1
+TRI_FLAG_SHORT, TRI_FLAG_DEGENERATE = 1, 2
 
 
 def lib_path():
@@ -35,6 +40,7 @@ def lib():
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
         _LIB = bind(bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE), EG3D_SETS_DEVICE)
+        bind(_LIB, EG3D_TRIANGULATE)
     return _LIB
 
 
@@ -48,6 +54,8 @@ DEDUP_PHASES_SYMBOLS = list(EG3D_DEDUP_PHASES)
 REPLAY_MERGE_SYMBOLS = list(EG3D_REPLAY_MERGE)
 # ... and of include/eg3d_sets_device.h (tests/test_abi_sets_device.py)
 SETS_DEVICE_SYMBOLS = list(EG3D_SETS_DEVICE)
+# ... and of include/eg3d_triangulate.h (tests/test_abi_triangulate.py)
+TRIANGULATE_SYMBOLS = list(EG3D_TRIANGULATE)
 
 
 def _check(rc, what):
@@ -560,6 +568,45 @@ class Context:
         _check(lib().eg3d_compact_device(self._h, C.byref(cloud), _dev_ptr(keep), _dev_ptr(X_new), int(min_obs),
                                          C.byref(out)), "eg3d_compact_device")
         return out
+
+    # ---- FP64 triangulation of caller-supplied tracks, K14 (include/eg3d_triangulate.h) ----
+    @staticmethod
+    def _tri_stats(st):
+        return {f[0]: getattr(st, f[0]) for f in D.TriStats._fields_ if f[0] != "struct_size"}
+
+    def triangulate(self, obs_off, obs_view, obs_xy, X0=None, mode=None, with_flags=True):
+        """eg3d_triangulate on host arrays (obs_off [n + 1] uint32, obs_view, obs_xy [m, 2]). mode: TRI_FROM_SCRATCH
+        (compute_3d_point_coords: DLT, then Gauss-Newton) or TRI_REFINE (Gauss-Newton from X0 [n, 3]); by default REFINE when
+        X0 is given. Returns (X [n, 3] float32, valid [n] uint8, flags [n] uint8 or None, stats dict)."""
+        if mode is None:
+            mode = TRI_FROM_SCRATCH if X0 is None else TRI_REFINE
+        obs_off = np.ascontiguousarray(obs_off, np.uint32)
+        obs_view = np.ascontiguousarray(obs_view, np.int32)
+        obs_xy = np.ascontiguousarray(obs_xy, np.float32)
+        n = len(obs_off) - 1
+        x0 = None if X0 is None else np.ascontiguousarray(X0, np.float32)
+        X, valid = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+        flags = np.zeros(n, np.uint8) if with_flags else None
+        st = D.TriStats(struct_size=C.sizeof(D.TriStats))
+        _check(lib().eg3d_triangulate(self._h, int(mode), n, D.np_ptr(obs_off, C.c_uint32), D.np_ptr(obs_view, C.c_int32),
+                                      D.np_ptr(obs_xy, C.c_float), None if x0 is None else D.np_ptr(x0, C.c_float),
+                                      D.np_ptr(X, C.c_float), D.np_ptr(valid, C.c_uint8),
+                                      None if flags is None else D.np_ptr(flags, C.c_uint8), C.byref(st)), "eg3d_triangulate")
+        return X, valid, flags, self._tri_stats(st)
+
+    def triangulate_device(self, cloud=None, mode=1, X_out=None, valid=None, flags=None, with_flags=True):
+        """eg3d_triangulate_device on `cloud` (a DeviceEdgePoints; None = this context's last device output). X_out / valid /
+        flags: DeviceArray or device address, allocated when not given (flags only with with_flags); X_out may be the
+        cloud's own X. Returns (X_out, valid, flags or None, stats dict); X_out and valid plug into compact_device."""
+        n = int((cloud if cloud is not None else self.last_device_output()).n_points)
+        X_out = X_out if X_out is not None else DeviceArray(12 * n, self.device)
+        valid = valid if valid is not None else DeviceArray(n, self.device)
+        if flags is None and with_flags:
+            flags = DeviceArray(n, self.device)
+        st = D.TriStats(struct_size=C.sizeof(D.TriStats))
+        _check(lib().eg3d_triangulate_device(self._h, int(mode), C.byref(cloud) if cloud is not None else None, _dev_ptr(X_out),
+                                             _dev_ptr(valid), _dev_ptr(flags), C.byref(st)), "eg3d_triangulate_device")
+        return X_out, valid, flags, self._tri_stats(st)
 
     def filter_resident(self, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, to_host=True):
         """eg3d_filter_resident on the last device output. Returns (cloud dict or None, DeviceEdgePoints, stats dict)."""

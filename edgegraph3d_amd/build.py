@@ -237,6 +237,16 @@ RESOURCE_BOUNDS = {
     # the resident polyline sets (eg3d_sets_from_communities_device, eg3d_upload_polyline_sets): one lane per node, row or
     # id — no LDS, no spills, no scratch (a substring: all of them)
     "k13_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    # the triangulation of caller-supplied tracks (eg3d_triangulate, eg3d_triangulate_device): no spilled register in any of
+    # them (a substring: check, cut, stage, solve). The build reports for the solve kernel 122 VGPRs, 32 B of scratch (the
+    # start point's three doubles) and 9 664 B of LDS (CoopLds); the bounds are 128 VGPRs and 8 LDS allocation units of
+    # 1 280 B — the limits of four single-wave workgroups per SIMD, 6 registers and 576 B above the figures — and 64 B of
+    # scratch. The other three report 6 - 10 VGPRs, no scratch, no LDS.
+    "k14_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 64, "group_segment_fixed_size": 10240},
+    "k14_solve": {"vgpr_count": 128},
+    "k14_check": {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k14_cut": {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k14_stage": {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},

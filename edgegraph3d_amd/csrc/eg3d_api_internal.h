@@ -21,6 +21,7 @@
 #include "eg3d_k9_polymatch.h"
 #include "eg3d_k10_simgraph.h"
 #include "eg3d_k11_louvain.h"
+#include "eg3d_k14_triangulate.h"
 
 // (hidden: what the drivers share is not part of the library's dynamic symbol table)
 #define EG3D_API_BEGIN namespace eg3d { namespace api __attribute__((visibility("hidden"))) {
@@ -94,7 +95,8 @@ struct DevBuf {
 };
 
 // Test / tuning knobs, ALL of them, read from the environment ONCE when a context is created (eg3d_create calls from_env; a
-// clone copies the struct) — nothing else in the library calls getenv:
+// clone copies the struct) — nothing else in the library calls getenv, but for EG3D_TRI_STAGE_OBS, which eg3d_triangulate and
+// eg3d_triangulate_device read at every call (include/eg3d_triangulate.h):
 //   EG3D_K3A_ENGINE_WAVES=n  wavefronts per SIMD the K3a engine launches (default 2 = what its 256-VGPR build allows)
 //   EG3D_K3A_ENGINE_LANES=n  lanes of a K3a wavefront that take work (default: 64, fewer for small batches)
 #ifndef EG3D_K3B_ENGINE_DEFAULT
@@ -388,6 +390,10 @@ struct eg3d_ctx : SceneFacts {
   bool k10_valid = false, k11_valid = false;  // the last eg3d_similarity_graph / eg3d_detect_communities call succeeded ...
   uint32_t k10_nodes = 0, k11_nodes = 0;      // ... on that many nodes (k10_nodeview / k10_nodepl, k11[K11B_IDS])
   uint32_t items_units = 0, items_redone = 0;  // units of the last eg3d_match_polyline_items call; units it cut in two and redid
+  // include/eg3d_triangulate.h (K14). k14_rec: the Obs records of the current batch (at most the staging budget, or one
+  // track); k14_ctr: the flag word and the three counts; k14_cuts: the batches of the call. k14_off .. k14_flags: the
+  // caller's arrays and the results of eg3d_triangulate (the device entry point works in the caller's own arrays).
+  DevBuf k14_rec, k14_ctr, k14_cuts, k14_off, k14_view, k14_xy, k14_X0, k14_Xo, k14_valid, k14_flags;
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
   // and the staging area finished chains are packed into (sized from the previous launches; grow-only)

@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE, bind
+from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE, EG3D_HOST_TRIANGULATE, bind
 
 _LIB = None
 
@@ -17,6 +17,7 @@ def lib():
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
         _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES), EG3D_HOST_REPLAY_MERGE)
+        bind(_LIB, EG3D_HOST_TRIANGULATE)
     return _LIB
 
 
@@ -234,6 +235,29 @@ def dedup_merge(first, other):
     if lib().eg3d_host_dedup_merge(D.np_ptr(first, C.c_uint32), D.np_ptr(other, C.c_uint32), first.size) != 0:
         raise ValueError("eg3d_host_dedup_merge failed")
     return first
+
+
+def triangulate(cam_P, obs_off, obs_view, obs_xy, X0=None, mode=None, dlt_rows=3, n_threads=1):
+    """eg3d_host_triangulate (include/eg3d_host_triangulate.h): the host statement of Context.triangulate, without a GPU.
+    cam_P [V, 16]; dlt_rows 3 = the 6x4 DLT system (libeg3d.so), 2 = the 4x4 one (libeg3d_dlt4x4.so); mode 0 = DLT then
+    Gauss-Newton, 1 = Gauss-Newton from X0 (the default when X0 is given). Returns (X [n, 3] float32, valid [n] uint8,
+    flags [n] uint8: 1 short, 2 degenerate DLT pair). Raises ValueError when the arguments are refused."""
+    if mode is None:
+        mode = 0 if X0 is None else 1
+    P = np.ascontiguousarray(np.asarray(cam_P, np.float32).reshape(-1, 16))
+    obs_off = np.ascontiguousarray(obs_off, np.uint32)
+    obs_view = np.ascontiguousarray(obs_view, np.int32)
+    obs_xy = np.ascontiguousarray(obs_xy, np.float32)
+    n = len(obs_off) - 1
+    x0 = None if X0 is None else np.ascontiguousarray(X0, np.float32)
+    X, valid, flags = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    rc = lib().eg3d_host_triangulate(int(dlt_rows), D.np_ptr(P, C.c_float), len(P), int(mode), n, D.np_ptr(obs_off, C.c_uint32),
+                                     D.np_ptr(obs_view, C.c_int32), D.np_ptr(obs_xy, C.c_float),
+                                     None if x0 is None else D.np_ptr(x0, C.c_float), int(n_threads), D.np_ptr(X, C.c_float),
+                                     D.np_ptr(valid, C.c_uint8), D.np_ptr(flags, C.c_uint8))
+    if rc != 0:
+        raise ValueError("eg3d_host_triangulate refused its arguments (rc=%d)" % rc)
+    return X, valid, flags
 
 
 def is_matched(scene_ptr, graph, view, pl, seg, xy):

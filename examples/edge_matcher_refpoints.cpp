@@ -36,6 +36,9 @@
 //                          [--resident-sets]     (--match2 / --louvain / --communities: the matches stay on the device —
 //                                                 eg3d_polyline_matches_device, eg3d_sets_from_communities_device — and the
 //                                                 extractor takes them there, eg3d_match_polyline_items; same output)
+//                          [--triangulate-refpoints]   (before matching: the input's own reference-point tracks through
+//                                                 eg3d_triangulate, EG3D_TRI_FROM_SCRATCH — how many of them triangulate under
+//                                                 these cameras, how many are too short or start from a degenerate pair)
 //        a match file is text: "eg3d-polyline-sets 1", then "<n_sets> <n_views>", then one line per (set, view):
 //        "<count> <polyline id> ..." with view-local ids (the reference's vector<set<ulong>> per match)
 //        (--make-synthetic also writes <dir>/sets1.txt and <dir>/sets2.txt: the polylines of 3-D curves 0-2 / 3-5)
@@ -53,6 +56,7 @@
 #include "eg3d.h"
 #include "eg3d_host.h"
 #include "eg3d_sets_device.h"
+#include "eg3d_triangulate.h"
 
 static int fail(const char* what) {
   std::fprintf(stderr, "edge_matcher_refpoints: %s (%s)\n", what, eg3d_last_error());
@@ -206,7 +210,7 @@ int main(int argc, char** argv) {
   if (argc >= 4 && std::strcmp(argv[1], "--make-synthetic") == 0) return make_synthetic(std::atoi(argv[2]), argv[3]);
   if (argc >= 4 && std::strcmp(argv[1], "--make-plgs") == 0) return make_plgs(argv[2], argc - 3, argv + 3);
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup] [--refpoints-first] [--resident-sets]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <input.json> <plgs.bin> <out.json> [--filter] [--estimate-F [--estimate-F-device]] [--all-pairs] [--resident-dedup] [--refpoints-first] [--resident-sets] [--triangulate-refpoints]\n", argv[0]);
     return 2;
   }
   bool do_filter = false, estimate_F = false, all_pairs = false, estimate_F_device = false;
@@ -353,6 +357,23 @@ int main(int argc, char** argv) {
   // ---- pipeline 3 on the GPU (pipelines.cpp:160-176, :227); with --refpoints-first it also leaves the matched intervals
   eg3d_seeds seeds;
   eg3d_sfm_seeds(sfm, &seeds);
+  // --triangulate-refpoints (off by default): the reference points' own tracks through compute_3d_point_coords on the
+  // device. Cameras and tracks that disagree show here, before any edge is matched.
+  bool triangulate_refpoints = false;
+  for (int a = 4; a < argc; a++) triangulate_refpoints |= std::strcmp(argv[a], "--triangulate-refpoints") == 0;
+  if (triangulate_refpoints && seeds.n_seeds) {
+    std::vector<float> Xt(3 * (size_t)seeds.n_seeds);
+    std::vector<uint8_t> ok(seeds.n_seeds);
+    eg3d_tri_stats ts;
+    ts.struct_size = (uint32_t)sizeof(ts);
+    if (eg3d_triangulate(ctx, EG3D_TRI_FROM_SCRATCH, seeds.n_seeds, seeds.trk_off, seeds.trk_view, seeds.trk_xy, nullptr, Xt.data(),
+                         ok.data(), nullptr, &ts) != EG3D_OK)
+      return fail("eg3d_triangulate");
+    std::printf("reference-point tracks: %llu of %llu triangulate from their own observations (%llu short, %llu with a degenerate "
+                "DLT pair; kernels %.3f ms)\n", (unsigned long long)ts.n_valid, (unsigned long long)ts.n_tracks,
+                (unsigned long long)ts.n_short, (unsigned long long)ts.n_degenerate, ts.ms_kernel);
+    lap("triangulation of the reference-point tracks");
+  }
   eg3d_graph3d held_host;
   std::memset(&held_host, 0, sizeof(held_host));
   eg3d_matched_intervals held;

@@ -43,6 +43,7 @@
 #include "eg3d.h"
 #include "eg3d_host.h" /* eg3d_host_replay_matches (libeg3d_host.so) */
 #include "eg3d_host_accumulate.h" /* eg3d_host_replay_state_* (libeg3d_host.so): PLGMatchesManager::set_accumulate */
+#include "eg3d_triangulate.h" /* eg3d_triangulate (K14): compute_3d_point_coords */
 
 namespace eg3d_ref {
 
@@ -997,6 +998,63 @@ inline void gaussNewtonFiltering(SfMData& sfm_data_, std::vector<bool>& inliers,
     throw;
   }
   d = saved;
+}
+
+// compute_3d_point_coords(const SfMData&, const vector<glm::vec2>&, const vector<int>&, glm::vec3&, bool&) —
+// triangulation.hpp:48 (triangulation.cpp:468-481): fewer than two observations are not valid; otherwise the 2-view DLT on
+// (the first entry with the minimal view id, the last entry) and FP64 Gauss-Newton over all of them, on the GPU
+// (eg3d_triangulate, EG3D_TRI_FROM_SCRATCH). new_point_data is assigned only when valid. The GPU context is the registered
+// edge manager's or a private one, as for gaussNewtonFiltering; one call per point pays a launch and two copies — many
+// points go through the batched overload below. Throws Eg3dError on a failure of the GPU path (a view id outside the rig).
+//
+// Batched: track i is (coords[i], ids[i]); points / valid get one entry per track (a point that is not valid is (0, 0, 0));
+// flags, optional, the EG3D_TRI_FLAG_* of every track.
+inline void compute_3d_point_coords(const SfMData& sfmd, const std::vector<std::vector<vec2>>& coords,
+                                    const std::vector<std::vector<int>>& ids, std::vector<vec3>& points, std::vector<bool>& valid,
+                                    std::vector<uint8_t>* flags = nullptr) {
+  const size_t n = coords.size();
+  if (ids.size() != n) throw Eg3dError(EG3D_ERR_ARG, "compute_3d_point_coords: coords and ids differ in length");
+  points.assign(n, vec3{0.f, 0.f, 0.f});
+  valid.assign(n, false);
+  if (flags) flags->assign(n, 0);
+  if (!n) return;
+  std::vector<uint32_t> off(1, 0);
+  std::vector<int32_t> view;
+  std::vector<float> xy;
+  for (size_t i = 0; i < n; i++) {
+    if (coords[i].size() != ids[i].size()) throw Eg3dError(EG3D_ERR_ARG, "compute_3d_point_coords: a track's coords and ids differ in length");
+    for (size_t j = 0; j < ids[i].size(); j++) {
+      view.push_back(ids[i][j]);
+      xy.push_back(coords[i][j].x);
+      xy.push_back(coords[i][j].y);
+    }
+    if (view.size() > 0xffffffffull) throw Eg3dError(EG3D_ERR_ARG, "compute_3d_point_coords: more than 2^32 - 1 observations");
+    off.push_back((uint32_t)view.size());
+  }
+  if (view.empty()) {
+    view.push_back(0);
+    xy.assign(2, 0.f);
+  }
+  std::vector<float> X(3 * n);
+  std::vector<uint8_t> ok(n), fl(n);
+  detail::FilterContext fc(sfmd);
+  const int rc = eg3d_triangulate(fc.ctx, EG3D_TRI_FROM_SCRATCH, n, off.data(), view.data(), xy.data(), nullptr, X.data(), ok.data(),
+                                  fl.data(), nullptr);
+  if (rc != EG3D_OK) throw Eg3dError(rc, std::string("eg3d_triangulate: ") + eg3d_last_error());
+  for (size_t i = 0; i < n; i++) {
+    points[i] = vec3{X[3 * i], X[3 * i + 1], X[3 * i + 2]};
+    valid[i] = ok[i] != 0;
+    if (flags) (*flags)[i] = fl[i];
+  }
+}
+inline void compute_3d_point_coords(const SfMData& sfmd, const std::vector<vec2>& selected_2d_reprojections_coords,
+                                    const std::vector<int>& selected_2d_reprojections_ids, vec3& new_point_data, bool& valid) {
+  std::vector<vec3> p;
+  std::vector<bool> v;
+  compute_3d_point_coords(sfmd, std::vector<std::vector<vec2>>(1, selected_2d_reprojections_coords),
+                          std::vector<std::vector<int>>(1, selected_2d_reprojections_ids), p, v);
+  valid = v[0];
+  if (valid) new_point_data = p[0];
 }
 
 #define EG3D_REF_GN_MAX_MSE 2.25f           /* GN_MAX_MSE, gauss_newton.hpp:18 */
