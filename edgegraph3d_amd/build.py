@@ -369,6 +369,16 @@ def build_oracle(force=False):
     return os.path.join(d, "liboracle.so")
 
 
+def build_hostsim(force=False):
+    """TEST-ONLY: the host compilation of the kernels' per-lane bodies (tests/hostsim), one library per DLT form. The
+    tests build it on first use as well (tests/hostsim_binding.py); built here it costs a GPU test nothing."""
+    d = os.path.join(ROOT, "tests", "hostsim")
+    if force:
+        _run(["make", "-C", d, "clean"])
+    _run(["make", "-s", "-j2", "-C", d])
+    return os.path.join(d, "libhostsim.so")
+
+
 def build_all(force=False):
     build_host(force)
     build_hip(force)
@@ -377,6 +387,7 @@ def build_all(force=False):
     build_probe(force)
     build_rccl(force)
     build_oracle(force)
+    build_hostsim(force)
 
 
 if __name__ == "__main__":

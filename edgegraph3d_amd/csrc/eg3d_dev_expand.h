@@ -15,6 +15,14 @@
 #pragma once
 #include "eg3d_dev_follow.h"
 
+#ifndef EG3D_REACH
+// Reach counters of the host simulation (tests/hostsim: which capacity boundary of the expand kernel a scene reaches,
+// counted in the sequential statement of the stage); nothing on the device. what = 0: lines consumed by one side walk,
+// 1: rows of one solve (the extra row of an ADD request included), 2 / 3: length of the list an N-view step's first /
+// later starting observation is walked from.
+#define EG3D_REACH(what, value)
+#endif
+
 namespace eg3d {
 
 // A chain point: its observations are a CONTIGUOUS block pool[off .. off+nobs) of the chain's
@@ -145,6 +153,7 @@ EG3D_HD bool add_observation_solve(const DevScene& s, const Chain& c, const Chai
   double X0[3] = {(double)p.X[0], (double)p.X[1], (double)p.X[2]};
   const int n = (int)p.nobs;
   const Obs* a = c.pool + p.off;
+  EG3D_REACH(1, n + 1);
   if (n + 1 <= EG3D_LOCAL_OBS) {
     // gather the block once (independent loads); the solver then streams from lane-private arrays
     LocalCursor lc;
@@ -237,6 +246,7 @@ struct TeamSeq {
   EG3D_HD int side_walk(const DevScene& s, Chain& c, int view, const PlRef& pl, const Obs& from, uint32_t direction, int lo,
                         int ci, int hi, bool towards_start, Pending* out) const;
   EG3D_HD bool gn_array(const DevScene& s, const Obs* a, int n, const double X0[3], float Xout[3]) const {
+    EG3D_REACH(1, n);
     ArrayCursor cur;
     cur.a = a;
     cur.n = n;
@@ -246,6 +256,7 @@ struct TeamSeq {
   }
   // one ADD solve of a plain observation array (the greedy phase of the 3-subset fallback): rows a[0..n) + extra, from X0
   EG3D_HD bool add_array(const DevScene& s, const Obs* a, int n, const Obs& extra, const float X0[3], float Xout[3]) const {
+    EG3D_REACH(1, n + 1);
     ArrayCursor cur;
     cur.a = a;
     cur.n = n;
@@ -284,6 +295,7 @@ struct TeamSeqSlots : TeamSeq {
 template <class Team>
 EG3D_HD_FLAT int stepn_walks(const Team& tm, const DevScene& s, const Obs* co_all, int n, int st, const uint32_t* dirs,
                         Obs* sel, int sel_cap, uint32_t& flags) {
+  EG3D_REACH(st == 0 ? 2 : 3, n);
   const Obs so = co_all[st];
   PlRef ps = polyline_of(s, so.view, so.pl);
   PlPt p, q;
@@ -586,6 +598,7 @@ EG3D_HD int walk_side_candidates_core(const DevScene& s, Chain& c, const PlT& pl
     else
       i++;
   }
+  EG3D_REACH(0, t);
   return cnt;
 }
 EG3D_HD int TeamSeq::side_walk(const DevScene& s, Chain& c, int view, const PlRef& pl, const Obs& from, uint32_t direction,

@@ -11,8 +11,26 @@
 
 #include "../../include/eg3d.h"
 #include "../../include/eg3d_host.h"
-static unsigned long long g_stat[8], g_hist[2][16], g_hsum[2][16];
+// (per thread: the plain expand stage below runs its chains in parallel; everything that reads g_stat runs on the calling thread)
+static thread_local unsigned long long g_stat[8];
+static unsigned long long g_hist[2][16], g_hsum[2][16];
 #define EG3D_STAT(i) (g_stat[i]++)
+// Reach counters (eg3d_dev_expand.h, EG3D_REACH): histograms of the last hostsim_match — [0] lines consumed by one side walk,
+// [1] rows of one solve of the expand stage, [2] / [3] list length of an N-view step's first / later starting observation.
+// Values beyond the last bin are counted in it. Read with hostsim_reach (tests/expand_boundary_cases.py).
+#define HOSTSIM_REACH_KINDS 4
+#define HOSTSIM_REACH_BINS 4096
+static unsigned long long g_reach[HOSTSIM_REACH_KINDS][HOSTSIM_REACH_BINS];
+static thread_local unsigned long long t_reach[HOSTSIM_REACH_KINDS][HOSTSIM_REACH_BINS];  // a thread's share, until reach_merge()
+static inline void hostsim_reach_note(int what, long long v) {
+  t_reach[what][v < 0 ? 0 : v >= HOSTSIM_REACH_BINS ? HOSTSIM_REACH_BINS - 1 : v]++;
+}
+static void reach_merge() {  // by every thread that ran chains, one at a time
+  for (int k = 0; k < HOSTSIM_REACH_KINDS; k++)
+    for (int b = 0; b < HOSTSIM_REACH_BINS; b++) g_reach[k][b] += t_reach[k][b];
+  memset(t_reach, 0, sizeof(t_reach));
+}
+#define EG3D_REACH(what, value) hostsim_reach_note((what), (long long)(value))
 #include "eg3d_dev_pipeline.h"
 #include "eg3d_chain_sm.h"
 
@@ -200,6 +218,8 @@ extern "C" int hostsim_match(const eg3d_scene* sc, const eg3d_seeds* seeds, uint
   }
   const uint32_t n_hyp = hyp_off[nt];
   for (int i = 0; i < 8; i++) g_stat[i] = 0;
+  memset(g_reach, 0, sizeof(g_reach));
+  memset(t_reach, 0, sizeof(t_reach));
   for (int i = 0; i < 16; i++) g_sm[i] = 0;
   for (int i = 0; i < 8; i++) g_smreq[i] = g_smrows[i] = 0;
   // K3a
@@ -281,7 +301,20 @@ extern "C" int hostsim_match(const eg3d_scene* sc, const eg3d_seeds* seeds, uint
   std::vector<ChainOut> couts(chains.size() ? chains.size() : 1);
   uint64_t np = 0, no = 0;
   const unsigned long long sm_walks0 = g_stat[5], sm_segs0 = g_stat[6];
-  for (size_t j = 0; j < chains.size(); j++) {
+  if (slot_step == 0) {  // the plain stage: chains are independent (own slice, own result), so they run side by side
+#pragma omp parallel
+    {
+#pragma omp for schedule(dynamic, 1)
+      for (size_t j = 0; j < chains.size(); j++) {
+        const ChainSeed& cs = chains[j];
+        expand_chain(TeamSeq(), ds, a, tasks[cs.task], cs, hyp_off[cs.task], res.data(), arena.data(), map_view.data(),
+                     map_entry.data(), map_n.data(), L, scratch.data() + L.total * j, couts[j]);
+      }
+#pragma omp critical
+      reach_merge();
+    }
+  }
+  for (size_t j = 0; j < chains.size() && slot_step != 0; j++) {
     const ChainSeed& cs = chains[j];
     if (slot_step == 3)  // the machine with the streaming forms of its lane-private loops (what the engine kernel runs)
       run_chain_machine<SmEnvStream>(ds, a, tasks[cs.task], cs, hyp_off[cs.task], res.data(), arena.data(), map_view.data(),
@@ -289,12 +322,11 @@ extern "C" int hostsim_match(const eg3d_scene* sc, const eg3d_seeds* seeds, uint
     else if (slot_step == 2)
       run_chain_machine<SmEnvSeq>(ds, a, tasks[cs.task], cs, hyp_off[cs.task], res.data(), arena.data(), map_view.data(),
                         map_entry.data(), map_n.data(), L, scratch.data() + L.total * j, couts[j]);
-    else if (slot_step)
+    else
       expand_chain(TeamSeqSlots(), ds, a, tasks[cs.task], cs, hyp_off[cs.task], res.data(), arena.data(),
                    map_view.data(), map_entry.data(), map_n.data(), L, scratch.data() + L.total * j, couts[j]);
-    else
-      expand_chain(TeamSeq(), ds, a, tasks[cs.task], cs, hyp_off[cs.task], res.data(), arena.data(), map_view.data(),
-                   map_entry.data(), map_n.data(), L, scratch.data() + L.total * j, couts[j]);
+  }
+  for (size_t j = 0; j < chains.size(); j++) {
     flags |= couts[j].flags;
     np += couts[j].n_points;
     no += couts[j].n_obs;
@@ -318,6 +350,7 @@ extern "C" int hostsim_match(const eg3d_scene* sc, const eg3d_seeds* seeds, uint
       if (g_smreq[k]) fprintf(stderr, " %s %.1f (%.1f)", kn[k], g_smreq[k] / nc, (double)g_smrows[k] / (double)g_smreq[k]);
     fprintf(stderr, "\n");
   }
+  reach_merge();  // (the forms that ran on this thread alone)
   // K4
   out->n_points = np;
   out->n_obs = no;
@@ -341,6 +374,13 @@ extern "C" int hostsim_match(const eg3d_scene* sc, const eg3d_seeds* seeds, uint
   out->n_chains = chains.size();
   out->flags = flags;
   return 0;
+}
+
+// histogram `what` of the last hostsim_match (see g_reach): hist[v] = events with the value v, v < n_bins; the number of kinds
+extern "C" int hostsim_reach(int what, unsigned long long* hist, int n_bins) {
+  if (what < 0 || what >= HOSTSIM_REACH_KINDS || n_bins != HOSTSIM_REACH_BINS) return -1;
+  memcpy(hist, g_reach[what], sizeof(g_reach[what]));
+  return HOSTSIM_REACH_KINDS;
 }
 
 extern "C" void hostsim_free_edgepoints(eg3d_edgepoints* e) {
