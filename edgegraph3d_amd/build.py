@@ -330,7 +330,8 @@ def device_source_fingerprint(defines=()):
     it is then reported as such, not as this run's traffic). Editing a comment does not change it; renaming a source or
     moving a kernel to another file does (file names are hashed, each in front of its text). The kernels live in the
     per-stage eg3d_k*.hip / eg3d_n1_sets.hip files and the headers they include. Of the eg3d_api* files
-    (eg3d_api.hip, eg3d_api_match.hip, the per-stage eg3d_api_filter / _replay / _polymatch / _simgraph / _louvain /
+    (eg3d_api.hip, the match path's eg3d_api_match.hip / _match_stage_b / _match_sets / _candidates.hip and
+    eg3d_api_match_internal.h, the per-stage eg3d_api_filter / _replay / _polymatch / _simgraph / _louvain /
     _fundamental / _sets.hip and eg3d_api_internal.h — host orchestration: no kernel lives there) only
     the preprocessor lines count — the macros that choose the kernel build, its default form and the slot-pool sizing;
     EG3D_EXTRA_HIPFLAGS and the `defines` of the build are part of the switches."""

@@ -1,6 +1,7 @@
 // eg3d_api_internal.h — what the host drivers of the C ABI (eg3d_api*.hip) share: the error string, the device buffer
 // type, the knobs, the context and what it shares (Scene, Seeds) or has learned, the small read-backs and one copy of each
-// idiom the stages repeat. Host only; no kernel lives here.
+// idiom the stages repeat. Host only; no kernel lives here. (What only the files of the match path share — a batch's state,
+// a call's sink and turnstile — is in eg3d_api_match_internal.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -561,16 +562,4 @@ struct HostCopy {
   HostCopy(T** d, const void* s, size_t b) : dst((void**)d), src(s), bytes(b) {}
 };
 int copy_out(hipStream_t st, const char* who, std::initializer_list<HostCopy> items);
-
-// ---- the extractor on item ranges (eg3d_api_match.hip; the entry points are in eg3d_api_sets.hip) ------------------------
-// An item is one entry of pl_ids. `sets` is resident and checked, n_rows = n_sets * V, [item_b, item_e) lies inside it.
-// count_item_samples: the count pass of k_n1_samples alone over the range, as ONE launch on the context's stream — under
-// the intervals of `m` when given. counts_host (may be null) receives the n counts, prefix (may be null) their n + 1
-// exclusive prefix sums.
-int count_item_samples(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t item_e,
-                       const eg3d_matched_intervals* m, uint32_t* counts_host, std::vector<uint32_t>* prefix);
-// match_items_call: the cloud of the items' samples, key[0] = sample index within the range + sample_base. Units are item
-// ranges cut by the sample counts; c->items_units tells how many, c->items_redone how many of them were cut in two and redone.
-int match_items_call(eg3d_ctx* c, const SetsDev& sets, uint32_t n_rows, uint32_t item_b, uint32_t item_e, uint32_t sample_base,
-                     const eg3d_matched_intervals* m, int device_only, eg3d_edgepoints* out, eg3d_stage_times* times);
 EG3D_API_END

@@ -1,9 +1,9 @@
 // eg3d_api_sets.hip — polyline sets that stay on the device (include/eg3d_sets_device.h): the three producers of a device
 // view (upload + device checks, K9's rows in place, K13), and the entry points of the extractor on item ranges, whose
-// cutting and units live with the other match calls in eg3d_api_match.hip. Host orchestration only: the kernels are in
-// eg3d_k13_sets.hip.
+// cutting and units live with the other calls on polyline sets in eg3d_api_match_sets.hip. Host orchestration only: the
+// kernels are in eg3d_k13_sets.hip.
 #include "../../include/eg3d_sets_device.h"
-#include "eg3d_api_internal.h"
+#include "eg3d_api_match_internal.h"
 #include "eg3d_k13_sets.h"
 
 namespace {

@@ -1,5 +1,5 @@
 """Scenes that stand on either side of the capacities the three builds of the expand kernel (k3b_expand: small, many
-views, general — launch_expand in edgegraph3d_amd/csrc/eg3d_api_match.hip) are cut at, and, per scene, the REACH TABLE:
+views, general — launch_expand in edgegraph3d_amd/csrc/eg3d_api_match_stage_b.hip) are cut at, and, per scene, the REACH TABLE:
 what the reference run of the scene reaches, computed on the CPU. Shared by the CPU half
 (tests/test_expand_boundary_cases.py: the reach conditions, and the host compilation of the stage against the oracle)
 and the GPU half (tests/test_gpu_expand_boundaries.py: the three builds against the oracle, the expected verdicts

@@ -102,7 +102,7 @@ def test_scene_class_builds_of_the_expand_kernel_agree_with_the_general_one(have
 def test_solve_longer_than_a_packed_round_is_redone_by_the_general_build(have_gpu, monkeypatch):
     """A few-views build of the expand stage (k3b_expand small scenes / the engine without the solver's long-request
     path) that meets a solve of more than 32 rows must not fail the call: it raises CTR_LONG_REFUSED, the host latches
-    the general build for the context and redoes the chunk (eg3d_api_match.hip judge_expand). Forced here with
+    the general build for the context and redoes the chunk (eg3d_api_match_stage_b.hip judge_expand). Forced here with
     EG3D_K3B_ASSUME_SHORT=1 on a 40-view scene whose points carry up to 40 observations; cloud == oracle, twice (the
     second call runs the latched general build from the start)."""
     cfg = host.default_config(1)

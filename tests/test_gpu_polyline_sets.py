@@ -218,3 +218,24 @@ def test_rows_must_be_strictly_ascending(have_gpu, eg3d_form):
             ctx.match_polyline_sets(n, row_off, bad, n - 1, n)
         _same(good, ctx.match_polyline_sets(n, row_off, ids, 0, 3), what)
     ctx.close()
+
+
+def test_null_pl_ids_is_refused_before_an_id_is_read(have_gpu, eg3d_form):
+    """A CSR whose row_off names ids while the pl_ids pointer is null is refused by the argument checks of both entry
+    points on host sets — EG3D_ERR_ARG, "pl_ids is null", no id read, no kernel launched — and the context stays usable."""
+    from edgegraph3d_amd import _cdefs as D
+    c = cases.overlap()
+    n, row_off, ids = c.csr()
+    assert row_off[-1] > 0
+    sa = c.scene_arrays()
+    ctx = api.Context(C.byref(sa.c))
+    good = ctx.match_polyline_sets(n, row_off, ids, 0, 3)
+    L = api.lib()
+    ps = D.PolylineSets(n, D.np_ptr(row_off, C.c_uint32), None)
+    e, tm, sc = D.EdgePoints(), D.StageTimes(), D.SetCandidates()
+    assert L.eg3d_match_polyline_sets(ctx._h, C.byref(ps), 0, n, 0, C.byref(e), C.byref(tm)) == -1  # EG3D_ERR_ARG
+    assert b"pl_ids is null" in L.eg3d_last_error()
+    assert L.eg3d_polyline_set_candidates(ctx._h, C.byref(ps), 0, n, None, C.byref(sc)) == -1
+    assert b"pl_ids is null" in L.eg3d_last_error()
+    _same(good, ctx.match_polyline_sets(n, row_off, ids, 0, 3), "after the refusals")
+    ctx.close()

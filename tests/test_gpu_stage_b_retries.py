@@ -1,4 +1,4 @@
-"""-m gpu: the retries of stage B (eg3d_api_match.hip run_stage_b), alone and all in one call. A launch of the expand
+"""-m gpu: the retries of stage B (eg3d_api_match_stage_b.hip run_stage_b), alone and all in one call. A launch of the expand
 stage can be answered in five ways: K2's hit buffer was too small (EG3D_HITS_CAP0), the hypothesis arena overflowed
 (EG3D_ARENA_CAP0), chains outgrew their working slices (EG3D_CHAIN_CAP0 / EG3D_POOL_CAP0), a few-views build refused a
 solve (EG3D_K3B_ASSUME_SHORT: test_gpu_parity.py), and the staging area the finished chains are packed into was too small
