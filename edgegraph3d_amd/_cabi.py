@@ -5,7 +5,7 @@ tables are frozen; the entry points of later headers have tables of their own be
 eg3d_host_accumulate.h: tests/test_replay_accumulate.py; eg3d_dedup_phases.h, eg3d_host_dedup_phases.h,
 eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py; eg3d_replay_merge.h, eg3d_host_replay_merge.h:
 tests/test_replay_merge.py; eg3d_sets_device.h: tests/test_abi_sets_device.py; eg3d_triangulate.h,
-eg3d_host_triangulate.h: tests/test_abi_triangulate.py)."""
+eg3d_host_triangulate.h: tests/test_abi_triangulate.py; eg3d_colour.h, eg3d_host_colour.h: tests/test_abi_colour.py)."""
 import ctypes as C
 
 from . import _cdefs as D
@@ -204,6 +204,24 @@ EG3D_TRIANGULATE = {
 # include/eg3d_host_triangulate.h (libeg3d_host.so): its sequential statement, both DLT forms
 EG3D_HOST_TRIANGULATE = {
     "eg3d_host_triangulate": (i32, [i32, f32p, i32, i32, u64, u32p, i32p, f32p, f32p, i32, f32p, u8p, u8p]),
+}
+
+# include/eg3d_colour.h (libeg3d.so, libeg3d_dlt4x4.so): the colours of a cloud from the source images, K15
+# (tests/test_abi_colour.py)
+EG3D_COLOUR = {
+    "eg3d_upload_images": (i32, [vp, i32, i32p, i32p, P(u8p)]),
+    "eg3d_release_images": (i32, [vp]),
+    "eg3d_colour_device": (i32, [vp, P(D.DeviceEdgePoints), vp, vp, vp, P(D.ColourStats)]),
+    "eg3d_colour_points": (i32, [vp, u64, u32p, i32p, f32p, u8p, u8p, u8p, P(D.ColourStats)]),
+}
+
+# include/eg3d_host_colour.h (libeg3d_host.so): its sequential statement, the PLY writer, the RGB PNG reader
+EG3D_HOST_COLOUR = {
+    "eg3d_host_colour_points": (i32, [i32, i32p, i32p, P(u8p), u64, u32p, i32p, f32p, u8p, i32, u8p, u8p, u64p]),
+    "eg3d_host_reflect101_loop": (i32, [i32, i32]),
+    "eg3d_host_reflect101_closed": (i32, [i32, i32]),
+    "eg3d_host_write_ply": (i32, [cstr, u64, f32p, u8p, u8p]),
+    "eg3d_host_png_read_rgb": (i32, [cstr, intp, intp, P(u8p)]),
 }
 
 

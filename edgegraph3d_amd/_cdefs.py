@@ -50,6 +50,37 @@ class TriStats(C.Structure):
                 ("ms_copy", C.c_float)]
 
 
+class ColourStats(C.Structure):
+    """eg3d_colour_stats (include/eg3d_colour.h): struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_images", C.c_uint32), ("n_points", C.c_uint64), ("n_coloured", C.c_uint64),
+                ("n_empty", C.c_uint64), ("n_obs_sampled", C.c_uint64), ("ms_sample", C.c_float), ("ms_mix", C.c_float),
+                ("ms_copy", C.c_float)]
+
+
+class ImageArgs:
+    """Owns what eg3d_upload_images / eg3d_host_colour_points take for `images`: a sequence with one entry per view, an
+    [H, W, 3] uint8 array (RGB) or None for a view without an image."""
+
+    def __init__(self, images):
+        self.arrays = []
+        for im in images:
+            if im is not None:
+                im = np.ascontiguousarray(im, np.uint8)
+                if im.ndim != 3 or im.shape[2] != 3:
+                    raise ValueError("an image is an [H, W, 3] uint8 array")
+            self.arrays.append(im)
+        self.n = len(self.arrays)
+        self.width = np.array([0 if a is None else a.shape[1] for a in self.arrays] or [0], np.int32)
+        self.height = np.array([0 if a is None else a.shape[0] for a in self.arrays] or [0], np.int32)
+        self.rgb = (u8p * max(self.n, 1))()
+        for v, a in enumerate(self.arrays):
+            if a is not None:
+                self.rgb[v] = a.ctypes.data_as(u8p)
+
+    def args(self):
+        return self.n, np_ptr(self.width, C.c_int32), np_ptr(self.height, C.c_int32), self.rgb
+
+
 class EdgePoints(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("n_obs", C.c_uint64), ("X", f32p), ("obs_off", u64p),
                 ("obs_view", i32p), ("obs_pl", u32p), ("obs_seg", u32p), ("obs_xy", f32p), ("key", u32p),

@@ -13,7 +13,8 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D, EG3D_ACCUMULATE, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, EG3D_TRIANGULATE, bind
+from ._cabi import (EG3D, EG3D_ACCUMULATE, EG3D_COLOUR, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, EG3D_TRIANGULATE,
+                    bind)
 
 _LIB = None
 
@@ -25,6 +26,8 @@ class Eg3dError(RuntimeError):
 # include/eg3d_triangulate.h
 TRI_FROM_SCRATCH, TRI_REFINE = 0, 1
 TRI_FLAG_SHORT, TRI_FLAG_DEGENERATE = 1, 2
+# include/eg3d_colour.h
+COLOUR_FLAG_EMPTY = 1
 
 
 def lib_path():
@@ -40,7 +43,7 @@ def lib():
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
         _LIB = bind(bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE), EG3D_SETS_DEVICE)
-        bind(_LIB, EG3D_TRIANGULATE)
+        bind(bind(_LIB, EG3D_TRIANGULATE), EG3D_COLOUR)
     return _LIB
 
 
@@ -56,6 +59,8 @@ REPLAY_MERGE_SYMBOLS = list(EG3D_REPLAY_MERGE)
 SETS_DEVICE_SYMBOLS = list(EG3D_SETS_DEVICE)
 # ... and of include/eg3d_triangulate.h (tests/test_abi_triangulate.py)
 TRIANGULATE_SYMBOLS = list(EG3D_TRIANGULATE)
+# ... and of include/eg3d_colour.h (tests/test_abi_colour.py)
+COLOUR_SYMBOLS = list(EG3D_COLOUR)
 
 
 def _check(rc, what):
@@ -607,6 +612,49 @@ class Context:
         _check(lib().eg3d_triangulate_device(self._h, int(mode), C.byref(cloud) if cloud is not None else None, _dev_ptr(X_out),
                                              _dev_ptr(valid), _dev_ptr(flags), C.byref(st)), "eg3d_triangulate_device")
         return X_out, valid, flags, self._tri_stats(st)
+
+    # ---- the colours of a cloud from the source images, K15 (include/eg3d_colour.h) ----
+    @staticmethod
+    def _colour_stats(st):
+        return {f[0]: getattr(st, f[0]) for f in D.ColourStats._fields_ if f[0] != "struct_size"}
+
+    def upload_images(self, images):
+        """eg3d_upload_images: `images` has one entry per view of the rig, an [H, W, 3] uint8 RGB array (each view its own
+        size) or None for a view without an image. They stay on this context's device until release_images, the next
+        upload or close; a clone does not inherit them."""
+        a = D.ImageArgs(images)
+        _check(lib().eg3d_upload_images(self._h, *a.args()), "eg3d_upload_images")
+
+    def release_images(self):
+        _check(lib().eg3d_release_images(self._h), "eg3d_release_images")
+
+    def colour_device(self, cloud=None, keep=None, rgb=None, flags=None, with_flags=True):
+        """eg3d_colour_device on `cloud` (a DeviceEdgePoints; None = this context's last device output). keep / rgb / flags:
+        DeviceArray or device address; rgb [n, 3] and flags [n] are allocated when not given (flags only with with_flags).
+        Returns (rgb, flags or None, stats dict)."""
+        n = int((cloud if cloud is not None else self.last_device_output()).n_points)
+        rgb = rgb if rgb is not None else DeviceArray(3 * n, self.device)
+        if flags is None and with_flags:
+            flags = DeviceArray(n, self.device)
+        st = D.ColourStats(struct_size=C.sizeof(D.ColourStats))
+        _check(lib().eg3d_colour_device(self._h, C.byref(cloud) if cloud is not None else None, _dev_ptr(keep), _dev_ptr(rgb),
+                                        _dev_ptr(flags), C.byref(st)), "eg3d_colour_device")
+        return rgb, flags, self._colour_stats(st)
+
+    def colour_points(self, obs_off, obs_view, obs_xy, keep=None):
+        """eg3d_colour_points on host arrays (obs_off [n + 1] uint32, obs_view, obs_xy [m, 2], keep [n] uint8 or None).
+        Returns (rgb [n, 3] uint8, flags [n] uint8: COLOUR_FLAG_EMPTY, stats dict)."""
+        obs_off = np.ascontiguousarray(obs_off, np.uint32)
+        obs_view = np.ascontiguousarray(obs_view, np.int32)
+        obs_xy = np.ascontiguousarray(obs_xy, np.float32)
+        n = len(obs_off) - 1
+        k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        rgb, flags = np.zeros((n, 3), np.uint8), np.zeros(n, np.uint8)
+        st = D.ColourStats(struct_size=C.sizeof(D.ColourStats))
+        _check(lib().eg3d_colour_points(self._h, n, D.np_ptr(obs_off, C.c_uint32), D.np_ptr(obs_view, C.c_int32),
+                                        D.np_ptr(obs_xy, C.c_float), None if k is None else D.np_ptr(k, C.c_uint8),
+                                        D.np_ptr(rgb, C.c_uint8), D.np_ptr(flags, C.c_uint8), C.byref(st)), "eg3d_colour_points")
+        return rgb, flags, self._colour_stats(st)
 
     def filter_resident(self, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, to_host=True):
         """eg3d_filter_resident on the last device output. Returns (cloud dict or None, DeviceEdgePoints, stats dict)."""

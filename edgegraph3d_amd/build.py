@@ -247,6 +247,11 @@ RESOURCE_BOUNDS = {
     "k14_check": {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     "k14_cut": {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     "k14_stage": {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    # the colours of a cloud (eg3d_colour_device, eg3d_colour_points): two kernels that hold a dozen values — no spilled
+    # register, no scratch, no LDS; the VGPR bounds are the counts the build reports (sample 23, mix 14), in both DLT forms
+    "k15_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    "k15_sample": {"vgpr_count": 23},
+    "k15_mix": {"vgpr_count": 14},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},

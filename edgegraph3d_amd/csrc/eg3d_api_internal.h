@@ -23,6 +23,7 @@
 #include "eg3d_k10_simgraph.h"
 #include "eg3d_k11_louvain.h"
 #include "eg3d_k14_triangulate.h"
+#include "eg3d_k15_colour.h"
 
 // (hidden: what the drivers share is not part of the library's dynamic symbol table)
 #define EG3D_API_BEGIN namespace eg3d { namespace api __attribute__((visibility("hidden"))) {
@@ -395,6 +396,13 @@ struct eg3d_ctx : SceneFacts {
   // track); k14_ctr: the flag word and the three counts; k14_cuts: the batches of the call. k14_off .. k14_flags: the
   // caller's arrays and the results of eg3d_triangulate (the device entry point works in the caller's own arrays).
   DevBuf k14_rec, k14_ctr, k14_cuts, k14_off, k14_view, k14_xy, k14_X0, k14_Xo, k14_valid, k14_flags;
+  // include/eg3d_colour.h (K15). k15_img: the uploaded images, one after the other; k15_tab: the K15Image of every view
+  // (both this context's alone: a clone starts without); k15_words: one word per observation of the current call;
+  // k15_ctr: the flag word and the three counts. k15_off .. k15_flags: the caller's arrays and the results of
+  // eg3d_colour_points (the device entry point works in the caller's own arrays).
+  DevBuf k15_img, k15_tab, k15_words, k15_ctr, k15_off, k15_view, k15_xy, k15_keep, k15_rgb, k15_flags;
+  bool k15_have_images = false;
+  uint32_t k15_n_images = 0;
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
   // and the staging area finished chains are packed into (sized from the previous launches; grow-only)

@@ -5,7 +5,8 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE, EG3D_HOST_TRIANGULATE, bind
+from ._cabi import (EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_COLOUR, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE,
+                    EG3D_HOST_TRIANGULATE, bind)
 
 _LIB = None
 
@@ -17,7 +18,7 @@ def lib():
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
         _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES), EG3D_HOST_REPLAY_MERGE)
-        bind(_LIB, EG3D_HOST_TRIANGULATE)
+        bind(bind(_LIB, EG3D_HOST_TRIANGULATE), EG3D_HOST_COLOUR)
     return _LIB
 
 
@@ -258,6 +259,53 @@ def triangulate(cam_P, obs_off, obs_view, obs_xy, X0=None, mode=None, dlt_rows=3
     if rc != 0:
         raise ValueError("eg3d_host_triangulate refused its arguments (rc=%d)" % rc)
     return X, valid, flags
+
+
+def colour_points(images, obs_off, obs_view, obs_xy, keep=None, n_threads=1):
+    """eg3d_host_colour_points (include/eg3d_host_colour.h): the host statement of Context.colour_points / colour_device,
+    without a GPU. images: one [H, W, 3] uint8 RGB array or None per view. Returns (rgb [n, 3] uint8, flags [n] uint8,
+    counts dict: n_coloured, n_empty, n_obs_sampled). Raises ValueError when the arguments are refused."""
+    a = D.ImageArgs(images)
+    obs_off = np.ascontiguousarray(obs_off, np.uint32)
+    obs_view = np.ascontiguousarray(obs_view, np.int32)
+    obs_xy = np.ascontiguousarray(obs_xy, np.float32)
+    n = len(obs_off) - 1
+    k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    rgb, flags, counts = np.zeros((n, 3), np.uint8), np.zeros(n, np.uint8), np.zeros(3, np.uint64)
+    rc = lib().eg3d_host_colour_points(*a.args(), n, D.np_ptr(obs_off, C.c_uint32), D.np_ptr(obs_view, C.c_int32),
+                                       D.np_ptr(obs_xy, C.c_float), None if k is None else D.np_ptr(k, C.c_uint8), int(n_threads),
+                                       D.np_ptr(rgb, C.c_uint8), D.np_ptr(flags, C.c_uint8), D.np_ptr(counts, C.c_uint64))
+    if rc != 0:
+        raise ValueError("eg3d_host_colour_points refused its arguments (rc=%d)" % rc)
+    return rgb, flags, {"n_coloured": int(counts[0]), "n_empty": int(counts[1]), "n_obs_sampled": int(counts[2])}
+
+
+def write_ply(path, X, rgb=None, keep=None):
+    """eg3d_host_write_ply: the reference's ASCII PLY point cloud of X [n, 3]; rgb [n, 3] uint8 or None (white); keep [n]
+    or None (all) — the `inliers` forms."""
+    X = np.ascontiguousarray(X, np.float32).reshape(-1, 3)
+    n = len(X)
+    c = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
+    if (c is not None and len(c) != n) or (k is not None and len(k) != n):
+        raise ValueError("write_ply: X, rgb and keep differ in length")
+    rc = lib().eg3d_host_write_ply(os.fsencode(path), n, D.np_ptr(X, C.c_float) if n else None,
+                                   D.np_ptr(c, C.c_uint8) if c is not None and n else None,
+                                   D.np_ptr(k, C.c_uint8) if k is not None and n else None)
+    if rc != 0:
+        raise OSError("eg3d_host_write_ply failed (rc=%d): %s" % (rc, path))
+
+
+def read_png_rgb(path):
+    """eg3d_host_png_read_rgb: a non-interlaced PNG of any colour type and bit depth as an [H, W, 3] uint8 RGB array."""
+    w, h, p = C.c_int(0), C.c_int(0), D.u8p()
+    rc = lib().eg3d_host_png_read_rgb(os.fsencode(path), C.byref(w), C.byref(h), C.byref(p))
+    if rc != 0:
+        raise ValueError("eg3d_host_png_read_rgb failed (rc=%d): %s" % (rc, path))
+    try:
+        return D.as_np(p, w.value * h.value * 3, np.uint8).reshape(h.value, w.value, 3)
+    finally:
+        lib().eg3d_host_free(p)
 
 
 def is_matched(scene_ptr, graph, view, pl, seg, xy):

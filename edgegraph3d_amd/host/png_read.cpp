@@ -5,7 +5,8 @@
 // decoder of what the format needs: all colour types and bit depths, the five scanline filters,
 // zlib streams split over any number of IDAT chunks (inflate from the system's libz); no
 // interlacing (the dtu006 edge maps are 1-bit greyscale, non-interlaced). Output: one byte per pixel,
-// 1 where an 8-bit BGR load of the image would be pure white.
+// 1 where an 8-bit BGR load of the image would be pure white — or, for the source images the point cloud is coloured
+// from (eg3d_host_png_read_rgb, include/eg3d_host_colour.h), the three bytes of that load as R, G, B.
 #include <zlib.h>
 
 #include <climits>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/eg3d_host.h"
+#include "../../include/eg3d_host_colour.h"
 
 namespace {
 uint32_t be32(const unsigned char* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -29,7 +31,8 @@ int paeth(int a, int b, int c) {
 static const size_t kMaxFileBytes = (size_t)1 << 30;     // 1 GiB of PNG
 static const size_t kMaxDecodedBytes = (size_t)1 << 30;  // 1 GiB of decoded scanlines (e.g. 16384 x 16384 RGBA 8-bit)
 
-static int png_read_edge_mask_impl(const char* path, int* width, int* height, uint8_t** mask_out) {
+// as_rgb = false: the edge mask, one byte per pixel; true: RGB8 interleaved, three bytes per pixel (eg3d_host_png_read_rgb)
+static int png_read_impl(const char* path, int* width, int* height, uint8_t** mask_out, bool as_rgb) {
   if (!path || !width || !height || !mask_out) return -1;
   *mask_out = nullptr;
   FILE* f = fopen(path, "rb");
@@ -134,7 +137,7 @@ static int png_read_edge_mask_impl(const char* path, int* width, int* height, ui
       line[x] = (unsigned char)(line[x] + p);
     }
   }
-  uint8_t* mask = (uint8_t*)malloc((size_t)w * h);
+  uint8_t* mask = (uint8_t*)malloc((size_t)w * h * (as_rgb ? 3 : 1));
   if (!mask) return -6;
   const int maxv = depth >= 8 ? 255 : (1 << depth) - 1;
   for (uint32_t r = 0; r < h; r++) {
@@ -151,6 +154,25 @@ static int png_read_edge_mask_impl(const char* path, int* width, int* height, ui
           const size_t bit = k * depth;
           s[ch] = (line[bit >> 3] >> (8 - depth - (bit & 7))) & maxv;
         }
+      }
+      if (as_rgb) {
+        // what an 8-bit colour load of the image holds, as R, G, B: the palette expanded (an index past its end: black),
+        // grey scaled to 0 .. 255 and replicated, alpha dropped, 16-bit samples by their high byte (taken above)
+        uint8_t* px = mask + ((size_t)r * w + x) * 3;
+        if (ctype == 3) {
+          const size_t e = (size_t)s[0] * 3;
+          const bool in = e + 2 < plte.size();
+          px[0] = in ? plte[e] : 0;
+          px[1] = in ? plte[e + 1] : 0;
+          px[2] = in ? plte[e + 2] : 0;
+        } else if (ctype == 0 || ctype == 4) {
+          px[0] = px[1] = px[2] = (uint8_t)(s[0] * 255 / maxv);
+        } else {
+          px[0] = (uint8_t)s[0];
+          px[1] = (uint8_t)s[1];
+          px[2] = (uint8_t)s[2];
+        }
+        continue;
       }
       bool white;
       if (ctype == 3) {
@@ -172,11 +194,23 @@ static int png_read_edge_mask_impl(const char* path, int* width, int* height, ui
 
 extern "C" int eg3d_png_read_edge_mask(const char* path, int* width, int* height, uint8_t** mask_out) {
   try {
-    return png_read_edge_mask_impl(path, width, height, mask_out);
+    return png_read_impl(path, width, height, mask_out, false);
   } catch (...) {  // std::bad_alloc and friends: an error code, never std::terminate through the C ABI
     if (mask_out && *mask_out) {
       free(*mask_out);
       *mask_out = nullptr;
+    }
+    return -6;
+  }
+}
+
+extern "C" int eg3d_host_png_read_rgb(const char* path, int* width, int* height, uint8_t** rgb_out) {
+  try {
+    return png_read_impl(path, width, height, rgb_out, true);
+  } catch (...) {
+    if (rgb_out && *rgb_out) {
+      free(*rgb_out);
+      *rgb_out = nullptr;
     }
     return -6;
   }

@@ -39,6 +39,11 @@
 //                          [--triangulate-refpoints]   (before matching: the input's own reference-point tracks through
 //                                                 eg3d_triangulate, EG3D_TRI_FROM_SCRATCH — how many of them triangulate under
 //                                                 these cameras, how many are too short or start from a degenerate pair)
+//                          [--ply FILE [--ply-images DIR/]]   (after the JSON: the final cloud as the reference's json_to_ply
+//                                                 writes it, eg3d_host_write_ply — white, or with --ply-images coloured on the
+//                                                 device from DIR/ + the base name of every view's path, PNG only. The final
+//                                                 cloud of this tool is the SfM data on the host, so the colours come through
+//                                                 eg3d_colour_points; a cloud that stays resident takes eg3d_colour_device)
 //        a match file is text: "eg3d-polyline-sets 1", then "<n_sets> <n_views>", then one line per (set, view):
 //        "<count> <polyline id> ..." with view-local ids (the reference's vector<set<ulong>> per match)
 //        (--make-synthetic also writes <dir>/sets1.txt and <dir>/sets2.txt: the polylines of 3-D curves 0-2 / 3-5)
@@ -57,6 +62,8 @@
 #include "eg3d_host.h"
 #include "eg3d_sets_device.h"
 #include "eg3d_triangulate.h"
+#include "eg3d_colour.h"
+#include "eg3d_host_colour.h"
 
 static int fail(const char* what) {
   std::fprintf(stderr, "edge_matcher_refpoints: %s (%s)\n", what, eg3d_last_error());
@@ -562,6 +569,47 @@ int main(int argc, char** argv) {
   if (eg3d_sfm_write_json(sfm, argv[1], argv[3]) != 0) return fail("writing the output");
   lap("write the OpenMVG JSON");
   std::printf("wrote %s (%llu points)\n", argv[3], (unsigned long long)eg3d_sfm_n_points(sfm));
+
+  // ---- json_to_ply (src/utils/json_to_ply.cpp) on the final cloud
+  const char* ply_path = nullptr;
+  const char* ply_images = nullptr;
+  for (int a = 4; a + 1 < argc; a++) {
+    if (std::strcmp(argv[a], "--ply") == 0) ply_path = argv[a + 1];
+    if (std::strcmp(argv[a], "--ply-images") == 0) ply_images = argv[a + 1];
+  }
+  if (ply_path) {
+    eg3d_seeds all;
+    eg3d_sfm_seeds(sfm, &all);
+    const uint64_t n = all.n_seeds;
+    std::vector<uint8_t> rgb;
+    if (ply_images) {
+      std::vector<int32_t> iw((size_t)V), ih((size_t)V);
+      std::vector<uint8_t*> img((size_t)V, nullptr);
+      bool ok = true;
+      for (int v = 0; v < V && ok; v++) {
+        const std::string name = eg3d_sfm_image_path(sfm, v);
+        const std::string path = std::string(ply_images) + name.substr(name.find_last_of("/\\") + 1);
+        int w = 0, h = 0;
+        ok = eg3d_host_png_read_rgb(path.c_str(), &w, &h, &img[(size_t)v]) == 0;
+        if (!ok) std::fprintf(stderr, "edge_matcher_refpoints: cannot read %s as a PNG image\n", path.c_str());
+        iw[(size_t)v] = w;
+        ih[(size_t)v] = h;
+      }
+      rgb.resize(3 * n + 1);
+      eg3d_colour_stats cs;
+      cs.struct_size = (uint32_t)sizeof(cs);
+      ok = ok && eg3d_upload_images(ctx, V, iw.data(), ih.data(), img.data()) == EG3D_OK &&
+           eg3d_colour_points(ctx, n, all.trk_off, all.trk_view, all.trk_xy, nullptr, rgb.data(), nullptr, &cs) == EG3D_OK;
+      for (uint8_t* p : img) eg3d_host_free(p);
+      if (!ok) return fail("colouring the final cloud");
+      std::printf("coloured %llu points from %llu observations on the GPU (%llu without observations)\n",
+                  (unsigned long long)cs.n_coloured, (unsigned long long)cs.n_obs_sampled, (unsigned long long)cs.n_empty);
+      lap("colours of the final cloud (eg3d_colour_points)");
+    }
+    if (eg3d_host_write_ply(ply_path, n, eg3d_sfm_points(sfm), ply_images ? rgb.data() : nullptr, nullptr) != 0)
+      return fail("writing the PLY file");
+    std::printf("wrote %s (%llu points%s)\n", ply_path, (unsigned long long)n, ply_images ? ", coloured" : "");
+  }
   if (print_times)
     std::fprintf(stderr, "[time] %-44s %9.2f ms\n", "whole run", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
   eg3d_destroy(ctx);
