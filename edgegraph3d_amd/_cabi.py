@@ -224,6 +224,28 @@ EG3D_HOST_COLOUR = {
     "eg3d_host_png_read_rgb": (i32, [cstr, intp, intp, P(u8p)]),
 }
 
+# include/eg3d_transform.h (libeg3d.so, libeg3d_dlt4x4.so): a 4 x 4 transform applied to a cloud's points, K16
+# (tests/test_abi_transform.py)
+EG3D_TRANSFORM = {
+    "eg3d_transform_device": (i32, [vp, P(D.DeviceEdgePoints), f64p, vp, vp, P(D.TransformStats)]),
+    "eg3d_transform_points": (i32, [vp, f64p, f32p, u64, f32p, P(D.TransformStats)]),
+}
+
+# include/eg3d_host_transform.h (libeg3d_host.so): the similarity fit to known camera centres, its sequential application
+# to points and cameras, the position error, and the same on a loaded SfM object
+EG3D_HOST_TRANSFORM = {
+    "eg3d_host_read_camera_poses": (i32, [cstr, i32, f64p]),
+    "eg3d_host_null_cameras": (i32, [i32, f32p, f32p, u8p]),
+    "eg3d_host_similarity_fit": (i32, [i32, f64p, f64p, u8p, f64p, P(D.SimilarityStats)]),
+    "eg3d_host_transform_points": (i32, [f64p, f32p, u64, f32p]),
+    "eg3d_host_transform_cameras": (i32, [f64p, i32, f32p, f32p, f32p, f32p, f32p]),
+    "eg3d_host_glm_inverse4": (i32, [f32p, f32p]),
+    "eg3d_host_glm_mul4": (i32, [f32p, f32p, f32p]),
+    "eg3d_host_camera_errors": (i32, [i32, f32p, u8p, f64p, f32p]),
+    "eg3d_sfm_camera_centres": (i32, [vp, f64p, u8p]),
+    "eg3d_sfm_apply_transform": (i32, [vp, f64p, i32]),
+}
+
 
 def bind(lib, table):
     """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""

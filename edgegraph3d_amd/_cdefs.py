@@ -57,6 +57,18 @@ class ColourStats(C.Structure):
                 ("ms_copy", C.c_float)]
 
 
+class TransformStats(C.Structure):
+    """eg3d_transform_stats (include/eg3d_transform.h): struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_points", C.c_uint64), ("n_transformed", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("ms_kernel", C.c_float), ("ms_copy", C.c_float)]
+
+
+class SimilarityStats(C.Structure):
+    """eg3d_similarity_stats (include/eg3d_host_transform.h): struct_size is set to the size of this mirror by its user."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_used", C.c_uint32), ("scale", C.c_double), ("singular", C.c_double * 3),
+                ("src_var", C.c_double), ("reflection", C.c_uint32), ("rank_deficient", C.c_uint32)]
+
+
 class ImageArgs:
     """Owns what eg3d_upload_images / eg3d_host_colour_points take for `images`: a sequence with one entry per view, an
     [H, W, 3] uint8 array (RGB) or None for a view without an image."""

@@ -13,8 +13,8 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import (EG3D, EG3D_ACCUMULATE, EG3D_COLOUR, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, EG3D_TRIANGULATE,
-                    bind)
+from ._cabi import (EG3D, EG3D_ACCUMULATE, EG3D_COLOUR, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, EG3D_TRANSFORM,
+                    EG3D_TRIANGULATE, bind)
 
 _LIB = None
 
@@ -43,7 +43,7 @@ def lib():
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
         _LIB = bind(bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE), EG3D_SETS_DEVICE)
-        bind(bind(_LIB, EG3D_TRIANGULATE), EG3D_COLOUR)
+        bind(bind(bind(_LIB, EG3D_TRIANGULATE), EG3D_COLOUR), EG3D_TRANSFORM)
     return _LIB
 
 
@@ -61,6 +61,9 @@ SETS_DEVICE_SYMBOLS = list(EG3D_SETS_DEVICE)
 TRIANGULATE_SYMBOLS = list(EG3D_TRIANGULATE)
 # ... and of include/eg3d_colour.h (tests/test_abi_colour.py)
 COLOUR_SYMBOLS = list(EG3D_COLOUR)
+# ... and of include/eg3d_transform.h (tests/test_abi_transform.py)
+TRANSFORM_SYMBOLS = list(EG3D_TRANSFORM)
+ERR_TRANSFORM_NONFINITE, ERR_TRANSFORM_OVERLAP = -16, -17
 
 
 def _check(rc, what):
@@ -655,6 +658,44 @@ class Context:
                                         D.np_ptr(obs_xy, C.c_float), None if k is None else D.np_ptr(k, C.c_uint8),
                                         D.np_ptr(rgb, C.c_uint8), D.np_ptr(flags, C.c_uint8), C.byref(st)), "eg3d_colour_points")
         return rgb, flags, self._colour_stats(st)
+
+    # ---- a 4 x 4 transform applied to a cloud's points, K16 (include/eg3d_transform.h) ----
+    @staticmethod
+    def _transform_stats(st):
+        return {f[0]: getattr(st, f[0]) for f in D.TransformStats._fields_ if f[0] not in ("struct_size", "reserved")}
+
+    @staticmethod
+    def _T16(T):
+        T = np.ascontiguousarray(T, np.float64).reshape(-1)
+        if T.size != 16:
+            raise ValueError("T must hold 16 values (a row-major 4 x 4)")
+        return T
+
+    def transform_device(self, T, keep=None, out=None, cloud=None):
+        """eg3d_transform_device: the points of `cloud` (a DeviceEdgePoints; None = this context's last device output)
+        through T (row-major 4 x 4, float64; host.similarity_fit). keep: DeviceArray or device address of [n] uint8, None =
+        every point; out: where the [n, 3] result goes, None = in place. A DeviceArray whose size is not the cloud's
+        (n bytes for keep, 12 n for out) is refused here with ValueError. Returns the stats dict."""
+        n = int((cloud if cloud is not None else self.last_device_output()).n_points)
+        if isinstance(keep, DeviceArray) and keep.nbytes != n:
+            raise ValueError("transform_device: keep holds %d bytes, the cloud %d points" % (keep.nbytes, n))
+        if isinstance(out, DeviceArray) and out.nbytes != 12 * n:
+            raise ValueError("transform_device: out holds %d bytes, the cloud needs %d" % (out.nbytes, 12 * n))
+        T = self._T16(T)
+        st = D.TransformStats(struct_size=C.sizeof(D.TransformStats))
+        _check(lib().eg3d_transform_device(self._h, C.byref(cloud) if cloud is not None else None, D.np_ptr(T, C.c_double),
+                                           _dev_ptr(keep), _dev_ptr(out), C.byref(st)), "eg3d_transform_device")
+        return self._transform_stats(st)
+
+    def transform_points(self, T, X):
+        """eg3d_transform_points on a host array X [n, 3] float32. Returns (X' [n, 3] float32, stats dict)."""
+        T = self._T16(T)
+        X = np.ascontiguousarray(X, np.float32).reshape(-1, 3)
+        out = np.empty_like(X)
+        st = D.TransformStats(struct_size=C.sizeof(D.TransformStats))
+        _check(lib().eg3d_transform_points(self._h, D.np_ptr(T, C.c_double), D.np_ptr(X, C.c_float), len(X),
+                                           D.np_ptr(out, C.c_float), C.byref(st)), "eg3d_transform_points")
+        return out, self._transform_stats(st)
 
     def filter_resident(self, gn_max_mse=2.25, legacy_abs=False, forced_min_filter=-1, base_hist=None, to_host=True):
         """eg3d_filter_resident on the last device output. Returns (cloud dict or None, DeviceEdgePoints, stats dict)."""

@@ -252,6 +252,9 @@ RESOURCE_BOUNDS = {
     "k15_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     "k15_sample": {"vgpr_count": 23},
     "k15_mix": {"vgpr_count": 14},
+    # the transform of a cloud's points (eg3d_transform_device, eg3d_transform_points): one kernel, the matrix in scalar
+    # registers, the lanes' exchange through cross-lane reads — no spilled register, no scratch, no LDS
+    "k16_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},

@@ -24,6 +24,7 @@
 #include "eg3d_k11_louvain.h"
 #include "eg3d_k14_triangulate.h"
 #include "eg3d_k15_colour.h"
+#include "eg3d_k16_transform.h"
 
 // (hidden: what the drivers share is not part of the library's dynamic symbol table)
 #define EG3D_API_BEGIN namespace eg3d { namespace api __attribute__((visibility("hidden"))) {
@@ -403,6 +404,9 @@ struct eg3d_ctx : SceneFacts {
   DevBuf k15_img, k15_tab, k15_words, k15_ctr, k15_off, k15_view, k15_xy, k15_keep, k15_rgb, k15_flags;
   bool k15_have_images = false;
   uint32_t k15_n_images = 0;
+  // include/eg3d_transform.h (K16). k16_ctr: the two counts; k16_X: the caller's points of eg3d_transform_points, transformed
+  // in place (the device entry point works in the caller's own arrays).
+  DevBuf k16_ctr, k16_X;
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
   // and the staging area finished chains are packed into (sized from the previous launches; grow-only)

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _cdefs as D
 from ._cabi import (EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_COLOUR, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE,
-                    EG3D_HOST_TRIANGULATE, bind)
+                    EG3D_HOST_TRANSFORM, EG3D_HOST_TRIANGULATE, bind)
 
 _LIB = None
 
@@ -18,7 +18,7 @@ def lib():
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
         _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES), EG3D_HOST_REPLAY_MERGE)
-        bind(bind(_LIB, EG3D_HOST_TRIANGULATE), EG3D_HOST_COLOUR)
+        bind(bind(bind(_LIB, EG3D_HOST_TRIANGULATE), EG3D_HOST_COLOUR), EG3D_HOST_TRANSFORM)
     return _LIB
 
 
@@ -278,6 +278,128 @@ def colour_points(images, obs_off, obs_view, obs_xy, keep=None, n_threads=1):
     if rc != 0:
         raise ValueError("eg3d_host_colour_points refused its arguments (rc=%d)" % rc)
     return rgb, flags, {"n_coloured": int(counts[0]), "n_empty": int(counts[1]), "n_obs_sampled": int(counts[2])}
+
+
+# ---- include/eg3d_host_transform.h: the similarity fit to known camera centres and its application ----
+class TransformError(ValueError):
+    """A refusal of include/eg3d_host_transform.h; `rc` is its EG3D_TRANSFORM_ERR_* code."""
+
+    def __init__(self, what, rc):
+        ValueError.__init__(self, "%s refused its arguments (rc=%d)" % (what, rc))
+        self.rc = rc
+
+
+TRANSFORM_ERR_ARG, TRANSFORM_ERR_FEW, TRANSFORM_ERR_DEGENERATE = -1, -2, -3
+TRANSFORM_ERR_NONFINITE, TRANSFORM_ERR_FILE, TRANSFORM_ERR_SHORT = -4, -5, -6
+
+
+def _T16(T):
+    T = np.ascontiguousarray(T, np.float64).reshape(-1)
+    if T.size != 16:
+        raise ValueError("T must hold 16 values (a row-major 4 x 4)")
+    return T
+
+
+def read_camera_poses(path, n_cameras):
+    """eg3d_host_read_camera_poses: [n_cameras, 3] float64; TransformError (rc -5 unreadable, -6 short) otherwise."""
+    out = np.zeros((int(n_cameras), 3), np.float64)
+    rc = lib().eg3d_host_read_camera_poses(os.fsencode(path), int(n_cameras), D.np_ptr(out, C.c_double))
+    if rc != 0:
+        raise TransformError("eg3d_host_read_camera_poses", rc)
+    return out
+
+
+def null_cameras(R, C3):
+    """eg3d_host_null_cameras: uint8 [n], 1 where the centre and the whole rotation are exactly 0."""
+    R = np.ascontiguousarray(R, np.float32).reshape(-1, 9)
+    C3 = np.ascontiguousarray(C3, np.float32).reshape(-1, 3)
+    mask = np.zeros(len(R), np.uint8)
+    if len(R) != len(C3) or lib().eg3d_host_null_cameras(len(R), D.np_ptr(R, C.c_float), D.np_ptr(C3, C.c_float),
+                                                         D.np_ptr(mask, C.c_uint8)) != 0:
+        raise ValueError("null_cameras: R and C differ in length")
+    return mask
+
+
+def similarity_fit(src, dst, null_mask=None):
+    """eg3d_host_similarity_fit: (T [4, 4] float64, stats dict: n_used, scale, singular [3], src_var, reflection,
+    rank_deficient). TransformError with rc -2 (fewer than 3 cameras), -3 (all source centres equal), -4 (a NaN / inf)."""
+    src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+    dst = np.ascontiguousarray(dst, np.float64).reshape(-1, 3)
+    m = None if null_mask is None else np.ascontiguousarray(null_mask, np.uint8).reshape(-1)
+    if len(src) != len(dst) or (m is not None and len(m) != len(src)):
+        raise ValueError("similarity_fit: src, dst and null_mask differ in length")
+    T = np.zeros(16, np.float64)
+    st = D.SimilarityStats(struct_size=C.sizeof(D.SimilarityStats))
+    rc = lib().eg3d_host_similarity_fit(len(src), D.np_ptr(src, C.c_double), D.np_ptr(dst, C.c_double),
+                                        None if m is None else D.np_ptr(m, C.c_uint8), D.np_ptr(T, C.c_double), C.byref(st))
+    if rc != 0:
+        raise TransformError("eg3d_host_similarity_fit", rc)
+    return T.reshape(4, 4), {"n_used": st.n_used, "scale": st.scale, "singular": np.array(st.singular[:]), "src_var": st.src_var,
+                             "reflection": bool(st.reflection), "rank_deficient": bool(st.rank_deficient)}
+
+
+def transform_points(T, X, out=None):
+    """eg3d_host_transform_points: X [n, 3] float32 through T (row-major 4 x 4, float64) — the sequential statement of
+    Context.transform_device / transform_points. out may be X itself (in place)."""
+    T = _T16(T)
+    X = np.ascontiguousarray(X, np.float32).reshape(-1, 3)
+    if out is None:
+        out = np.empty_like(X)
+    if out.dtype != np.float32 or out.shape != X.shape or not out.flags.c_contiguous:
+        raise ValueError("transform_points: out must be a contiguous float32 array shaped like X")
+    rc = lib().eg3d_host_transform_points(D.np_ptr(T, C.c_double), D.np_ptr(X, C.c_float), len(X), D.np_ptr(out, C.c_float))
+    if rc != 0:
+        raise TransformError("eg3d_host_transform_points", rc)
+    return out
+
+
+def transform_cameras(T, fpp, R, C3, t):
+    """eg3d_host_transform_cameras on copies: fpp [n, 3] (focal, ppx, ppy), R [n, 9], C [n, 3], t [n, 3] ->
+    (R', C', t', P [n, 16]); the rows of a null camera come back unchanged and its P as zeros."""
+    T = _T16(T)
+    fpp = np.ascontiguousarray(fpp, np.float32).reshape(-1, 3)
+    R = np.array(R, np.float32).reshape(-1, 9)
+    C3 = np.array(C3, np.float32).reshape(-1, 3)
+    t = np.array(t, np.float32).reshape(-1, 3)
+    n = len(fpp)
+    if not (len(R) == len(C3) == len(t) == n):
+        raise ValueError("transform_cameras: the arrays differ in length")
+    P = np.zeros((n, 16), np.float32)
+    rc = lib().eg3d_host_transform_cameras(D.np_ptr(T, C.c_double), n, D.np_ptr(fpp, C.c_float), D.np_ptr(R, C.c_float),
+                                           D.np_ptr(C3, C.c_float), D.np_ptr(t, C.c_float), D.np_ptr(P, C.c_float))
+    if rc != 0:
+        raise TransformError("eg3d_host_transform_cameras", rc)
+    return R, C3, t, P
+
+
+def glm_inverse4(m):
+    m = np.ascontiguousarray(m, np.float32).reshape(16)
+    out = np.zeros(16, np.float32)
+    lib().eg3d_host_glm_inverse4(D.np_ptr(m, C.c_float), D.np_ptr(out, C.c_float))
+    return out.reshape(4, 4)
+
+
+def glm_mul4(a, b):
+    a, b = np.ascontiguousarray(a, np.float32).reshape(16), np.ascontiguousarray(b, np.float32).reshape(16)
+    out = np.zeros(16, np.float32)
+    lib().eg3d_host_glm_mul4(D.np_ptr(a, C.c_float), D.np_ptr(b, C.c_float), D.np_ptr(out, C.c_float))
+    return out.reshape(4, 4)
+
+
+def camera_errors(C3, target, null_mask=None):
+    """eg3d_host_camera_errors: the reference's mean camera position error as a float — the sum runs over the non-null
+    cameras, the division is by ALL cameras."""
+    C3 = np.ascontiguousarray(C3, np.float32).reshape(-1, 3)
+    target = np.ascontiguousarray(target, np.float64).reshape(-1, 3)
+    m = None if null_mask is None else np.ascontiguousarray(null_mask, np.uint8).reshape(-1)
+    if len(C3) != len(target) or (m is not None and len(m) != len(C3)):
+        raise ValueError("camera_errors: the arrays differ in length")
+    out = C.c_float(0)
+    rc = lib().eg3d_host_camera_errors(len(C3), D.np_ptr(C3, C.c_float), None if m is None else D.np_ptr(m, C.c_uint8),
+                                       D.np_ptr(target, C.c_double), C.byref(out))
+    if rc != 0:
+        raise TransformError("eg3d_host_camera_errors", rc)
+    return np.float32(out.value)
 
 
 def write_ply(path, X, rgb=None, keep=None):

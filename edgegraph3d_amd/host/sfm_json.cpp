@@ -27,6 +27,7 @@
 #endif
 
 #include "../../include/eg3d_host.h"
+#include "../../include/eg3d_host_transform.h"
 #include "camera_model.hpp"
 #include "json_text.hpp"
 
@@ -425,6 +426,32 @@ extern "C" int eg3d_sfm_remove_outliers(eg3d_sfm* s, const uint8_t* inlier) {
 extern "C" int eg3d_sfm_set_point_coords(eg3d_sfm* s, const float* X) {
   if (!s || !X) return -1;
   memcpy(s->X.data(), X, sizeof(float) * s->X.size());
+  return 0;
+}
+
+// include/eg3d_host_transform.h: the fit's inputs and update_sfmd_transform on this object
+extern "C" int eg3d_sfm_camera_centres(const eg3d_sfm* s, double* centres_f64, uint8_t* null_mask) {
+  if (!s) return -1;
+  for (size_t i = 0; i < s->cams.size(); i++) {
+    const Cam& c = s->cams[i];
+    if (centres_f64)
+      for (int k = 0; k < 3; k++) centres_f64[3 * i + k] = (double)c.C[k];
+    if (null_mask) eg3d_host_null_cameras(1, c.R, c.C, null_mask + i);
+  }
+  return 0;
+}
+
+extern "C" int eg3d_sfm_apply_transform(eg3d_sfm* s, const double* T_f64, int what) {
+  if (!s || !T_f64 || !(what & (EG3D_SFM_TRANSFORM_CAMERAS | EG3D_SFM_TRANSFORM_POINTS))) return -1;
+  if (what & EG3D_SFM_TRANSFORM_CAMERAS) {
+    for (Cam& c : s->cams) {
+      const float fpp[3] = {c.focal, c.ppx, c.ppy};
+      const int rc = eg3d_host_transform_cameras(T_f64, 1, fpp, c.R, c.C, c.t, c.P);
+      if (rc) return rc;  // (T is checked before the first camera is touched)
+    }
+    s->refresh_P();
+  }
+  if (what & EG3D_SFM_TRANSFORM_POINTS) return eg3d_host_transform_points(T_f64, s->X.data(), s->X.size() / 3, s->X.data());
   return 0;
 }
 

@@ -39,6 +39,10 @@
 //                          [--triangulate-refpoints]   (before matching: the input's own reference-point tracks through
 //                                                 eg3d_triangulate, EG3D_TRI_FROM_SCRATCH — how many of them triangulate under
 //                                                 these cameras, how many are too short or start from a degenerate pair)
+//                          [--align camera_poses.txt]   (after the JSON, before --ply: the reference's coordinate_system_transform
+//                                                 on the final cloud — a similarity fitted to the target camera centres, one
+//                                                 "x y z" per camera; the cameras on the host, the points through
+//                                                 eg3d_transform_points. The PLY file is then in the target frame)
 //                          [--ply FILE [--ply-images DIR/]]   (after the JSON: the final cloud as the reference's json_to_ply
 //                                                 writes it, eg3d_host_write_ply — white, or with --ply-images coloured on the
 //                                                 device from DIR/ + the base name of every view's path, PNG only. The final
@@ -64,6 +68,8 @@
 #include "eg3d_triangulate.h"
 #include "eg3d_colour.h"
 #include "eg3d_host_colour.h"
+#include "eg3d_host_transform.h"
+#include "eg3d_transform.h"
 
 static int fail(const char* what) {
   std::fprintf(stderr, "edge_matcher_refpoints: %s (%s)\n", what, eg3d_last_error());
@@ -569,6 +575,44 @@ int main(int argc, char** argv) {
   if (eg3d_sfm_write_json(sfm, argv[1], argv[3]) != 0) return fail("writing the output");
   lap("write the OpenMVG JSON");
   std::printf("wrote %s (%llu points)\n", argv[3], (unsigned long long)eg3d_sfm_n_points(sfm));
+
+  // ---- coordinate_system_transform (src/coordinate_system_transform/) on the final cloud: the fit on the host, the
+  // cameras on the host, the points through K16 on the run's context (eg3d_transform_points: the final cloud of this tool
+  // is the SfM data on the host; a cloud that stays resident takes eg3d_transform_device). The JSON above is written in
+  // the reconstruction's own frame; what follows — the PLY file — is in the target frame.
+  const char* align_path = nullptr;
+  for (int a = 4; a + 1 < argc; a++)
+    if (std::strcmp(argv[a], "--align") == 0) align_path = argv[a + 1];
+  if (align_path) {
+    std::vector<double> target((size_t)V * 3), centres((size_t)V * 3), T(16);
+    std::vector<uint8_t> null_mask((size_t)V);
+    if (eg3d_host_read_camera_poses(align_path, V, target.data()) != 0) return fail("reading the target camera centres (--align)");
+    eg3d_sfm_camera_centres(sfm, centres.data(), null_mask.data());
+    eg3d_similarity_stats fit;
+    fit.struct_size = sizeof(fit);
+    if (eg3d_host_similarity_fit(V, centres.data(), target.data(), null_mask.data(), T.data(), &fit) != 0)
+      return fail("fitting the similarity to the target camera centres (--align)");
+    auto error = [&]() {
+      std::vector<double> c64((size_t)V * 3);
+      eg3d_sfm_camera_centres(sfm, c64.data(), nullptr);
+      std::vector<float> c32(c64.begin(), c64.end());
+      float e = 0;
+      eg3d_host_camera_errors(V, c32.data(), null_mask.data(), target.data(), &e);
+      return e;
+    };
+    const float before = error();
+    const uint64_t n = eg3d_sfm_n_points(sfm);
+    std::vector<float> Xa(3 * (size_t)n);
+    eg3d_transform_stats ts;
+    ts.struct_size = sizeof(ts);
+    if (eg3d_transform_points(ctx, T.data(), eg3d_sfm_points(sfm), n, Xa.data(), &ts) != EG3D_OK) return fail("eg3d_transform_points");
+    if (eg3d_sfm_apply_transform(sfm, T.data(), EG3D_SFM_TRANSFORM_CAMERAS) != 0) return fail("transforming the cameras (--align)");
+    if (n) eg3d_sfm_set_point_coords(sfm, Xa.data());
+    std::printf("align: %u cameras, scale %g%s; camera position errors before: %g, after: %g; %llu points, %llu not finite\n", fit.n_used,
+                fit.scale, fit.reflection ? " (mirrored target)" : "", before, error(), (unsigned long long)ts.n_transformed,
+                (unsigned long long)ts.n_nonfinite);
+    lap("align to the target camera centres (fit on the host, points on the GPU)");
+  }
 
   // ---- json_to_ply (src/utils/json_to_ply.cpp) on the final cloud
   const char* ply_path = nullptr;
