@@ -1,11 +1,8 @@
-"""The C ABI as ctypes sees it: one table per library, function name -> (restype, argtypes), covering every function
-of include/eg3d.h, include/eg3d_host.h and include/eg3d_rccl.h, and bind(), which applies a table to a CDLL. Written by
-hand; tests/test_abi.py reads the headers and holds every row (and every struct mirror of _cdefs.py) to them. Those three
-tables are frozen; the entry points of later headers have tables of their own below (eg3d_accumulate.h,
-eg3d_host_accumulate.h: tests/test_replay_accumulate.py; eg3d_dedup_phases.h, eg3d_host_dedup_phases.h,
-eg3d_rccl_claims.h: tests/test_abi_dedup_phases.py; eg3d_replay_merge.h, eg3d_host_replay_merge.h:
-tests/test_replay_merge.py; eg3d_sets_device.h: tests/test_abi_sets_device.py; eg3d_triangulate.h,
-eg3d_host_triangulate.h: tests/test_abi_triangulate.py; eg3d_colour.h, eg3d_host_colour.h: tests/test_abi_colour.py)."""
+"""The C ABI as ctypes sees it: one hand-written table per public header, function name -> (restype, argtypes), and HEADERS,
+which says which library carries each table; bind_library() declares all of a library's tables on a CDLL. tests/test_abi.py
+reads every header of include/ and holds every row, every struct mirror (_cdefs.MIRRORS) and every built library to them.
+The next header: write it, add its table and one HEADERS row here and the mirrors of its structs to _cdefs.MIRRORS.
+eg3d.h, eg3d_host.h and eg3d_rccl.h are frozen: a new entry point gets a header of its own."""
 import ctypes as C
 
 from . import _cdefs as D
@@ -183,7 +180,7 @@ EG3D_HOST_REPLAY_MERGE = {
 }
 
 # include/eg3d_sets_device.h (libeg3d.so, libeg3d_dlt4x4.so): polyline sets resident on the device, the extractor on item
-# ranges (tests/test_abi_sets_device.py)
+# ranges
 EG3D_SETS_DEVICE = {
     "eg3d_upload_polyline_sets": (i32, [vp, P(D.PolylineSets), P(D.DevicePolylineSets)]),
     "eg3d_polyline_matches_device": (i32, [vp, P(D.DevicePolylineSets)]),
@@ -195,7 +192,6 @@ EG3D_SETS_DEVICE = {
 }
 
 # include/eg3d_triangulate.h (libeg3d.so, libeg3d_dlt4x4.so): FP64 triangulation of caller-supplied tracks, K14
-# (tests/test_abi_triangulate.py)
 EG3D_TRIANGULATE = {
     "eg3d_triangulate": (i32, [vp, i32, u64, u32p, i32p, f32p, f32p, f32p, u8p, u8p, P(D.TriStats)]),
     "eg3d_triangulate_device": (i32, [vp, i32, P(D.DeviceEdgePoints), vp, vp, vp, P(D.TriStats)]),
@@ -207,7 +203,6 @@ EG3D_HOST_TRIANGULATE = {
 }
 
 # include/eg3d_colour.h (libeg3d.so, libeg3d_dlt4x4.so): the colours of a cloud from the source images, K15
-# (tests/test_abi_colour.py)
 EG3D_COLOUR = {
     "eg3d_upload_images": (i32, [vp, i32, i32p, i32p, P(u8p)]),
     "eg3d_release_images": (i32, [vp]),
@@ -225,7 +220,6 @@ EG3D_HOST_COLOUR = {
 }
 
 # include/eg3d_transform.h (libeg3d.so, libeg3d_dlt4x4.so): a 4 x 4 transform applied to a cloud's points, K16
-# (tests/test_abi_transform.py)
 EG3D_TRANSFORM = {
     "eg3d_transform_device": (i32, [vp, P(D.DeviceEdgePoints), f64p, vp, vp, P(D.TransformStats)]),
     "eg3d_transform_points": (i32, [vp, f64p, f32p, u64, f32p, P(D.TransformStats)]),
@@ -246,10 +240,40 @@ EG3D_HOST_TRANSFORM = {
     "eg3d_sfm_apply_transform": (i32, [vp, f64p, i32]),
 }
 
+# header -> (library, table), in the order the headers were added; "eg3d" is both product libraries
+HEADERS = {
+    "eg3d.h": ("eg3d", EG3D),
+    "eg3d_host.h": ("host", EG3D_HOST),
+    "eg3d_rccl.h": ("rccl", EG3D_RCCL),
+    "eg3d_accumulate.h": ("eg3d", EG3D_ACCUMULATE),
+    "eg3d_host_accumulate.h": ("host", EG3D_HOST_ACCUMULATE),
+    "eg3d_dedup_phases.h": ("eg3d", EG3D_DEDUP_PHASES),
+    "eg3d_host_dedup_phases.h": ("host", EG3D_HOST_DEDUP_PHASES),
+    "eg3d_rccl_claims.h": ("rccl", EG3D_RCCL_CLAIMS),
+    "eg3d_replay_merge.h": ("eg3d", EG3D_REPLAY_MERGE),
+    "eg3d_host_replay_merge.h": ("host", EG3D_HOST_REPLAY_MERGE),
+    "eg3d_sets_device.h": ("eg3d", EG3D_SETS_DEVICE),
+    "eg3d_triangulate.h": ("eg3d", EG3D_TRIANGULATE),
+    "eg3d_host_triangulate.h": ("host", EG3D_HOST_TRIANGULATE),
+    "eg3d_colour.h": ("eg3d", EG3D_COLOUR),
+    "eg3d_host_colour.h": ("host", EG3D_HOST_COLOUR),
+    "eg3d_transform.h": ("eg3d", EG3D_TRANSFORM),
+    "eg3d_host_transform.h": ("host", EG3D_HOST_TRANSFORM),
+}
+FROZEN_HEADERS = ("eg3d.h", "eg3d_host.h", "eg3d_rccl.h")
+
 
 def bind(lib, table):
     """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""
     for name, (restype, argtypes) in table.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+def bind_library(lib, library):
+    """Declare on the CDLL `lib` every table HEADERS gives to `library` ("eg3d", "host" or "rccl"). Returns `lib`."""
+    for owner, table in HEADERS.values():
+        if owner == library:
+            bind(lib, table)
     return lib

@@ -1,4 +1,4 @@
-"""ctypes mirrors of the POD structs in include/eg3d.h and include/eg3d_host.h (plumbing only)."""
+"""ctypes mirrors of the POD structs the headers of include/ define, listed in MIRRORS (plumbing only)."""
 import ctypes as C
 
 import numpy as np
@@ -464,3 +464,24 @@ def candidates_to_dict(c):
         "hit_pl": as_np(c.hit_pl, nh, np.uint32), "hit_seg": as_np(c.hit_seg, nh, np.uint32),
         "hit_xy": as_np(c.hit_xy, 2 * nh, np.float32).reshape(nh, 2),
     }
+
+
+# header of include/ -> {C struct: its mirror above}; tests/test_abi.py holds each to gcc's layout of the struct
+MIRRORS = {
+    "eg3d.h": {
+        "eg3d_scene": Scene, "eg3d_seeds": Seeds, "eg3d_edgepoints": EdgePoints, "eg3d_candidates": Candidates,
+        "eg3d_stage_times": StageTimes, "eg3d_polyline_sets": PolylineSets, "eg3d_matched_intervals": MatchedIntervals,
+        "eg3d_set_candidates": SetCandidates, "eg3d_device_edgepoints": DeviceEdgePoints, "eg3d_filter_stats": FilterStats,
+        "eg3d_dedup_stats": DedupStats, "eg3d_device_graph3d": DeviceGraph3D, "eg3d_replay_stats": ReplayStats,
+        "eg3d_polyline_matches": PolylineMatches, "eg3d_polymatch_stats": PolymatchStats, "eg3d_simgraph": Simgraph,
+        "eg3d_simgraph_stats": SimgraphStats, "eg3d_louvain_params": LouvainParams, "eg3d_communities": Communities,
+        "eg3d_louvain_stats": LouvainStats, "eg3d_fund_params": FundParams, "eg3d_fund_stats": FundStats,
+    },
+    "eg3d_host.h": {"eg3d_synth_config": SynthConfig, "eg3d_plg_view": PlgView, "eg3d_graph3d": Graph3D},
+    "eg3d_sets_device.h": {"eg3d_device_polyline_sets": DevicePolylineSets, "eg3d_items_call": ItemsCall,
+                           "eg3d_sets_device_stats": SetsDeviceStats},
+    "eg3d_triangulate.h": {"eg3d_tri_stats": TriStats},
+    "eg3d_colour.h": {"eg3d_colour_stats": ColourStats},
+    "eg3d_transform.h": {"eg3d_transform_stats": TransformStats},
+    "eg3d_host_transform.h": {"eg3d_similarity_stats": SimilarityStats},
+}

@@ -13,8 +13,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import (EG3D, EG3D_ACCUMULATE, EG3D_COLOUR, EG3D_DEDUP_PHASES, EG3D_REPLAY_MERGE, EG3D_SETS_DEVICE, EG3D_TRANSFORM,
-                    EG3D_TRIANGULATE, bind)
+from ._cabi import EG3D, bind_library
 
 _LIB = None
 
@@ -42,27 +41,12 @@ def lib():
         if not os.path.exists(path):
             raise Eg3dError("libeg3d.so (HIP extension) is missing: run `python -m edgegraph3d_amd.build`. "
                             "There is no CPU fallback.")
-        _LIB = bind(bind(bind(bind(bind(C.CDLL(path), EG3D), EG3D_ACCUMULATE), EG3D_DEDUP_PHASES), EG3D_REPLAY_MERGE), EG3D_SETS_DEVICE)
-        bind(bind(bind(_LIB, EG3D_TRIANGULATE), EG3D_COLOUR), EG3D_TRANSFORM)
+        _LIB = bind_library(C.CDLL(path), "eg3d")
     return _LIB
 
 
-# every symbol include/eg3d.h declares (tests/test_abi.py holds the table to the header without a GPU)
+# every symbol include/eg3d.h declares (the later headers' functions are in their tables in _cabi.py)
 EXPORTED_SYMBOLS = list(EG3D)
-# ... and those of include/eg3d_accumulate.h (tests/test_replay_accumulate.py does the same for that header)
-ACCUMULATE_SYMBOLS = list(EG3D_ACCUMULATE)
-# ... and of include/eg3d_dedup_phases.h (tests/test_abi_dedup_phases.py)
-DEDUP_PHASES_SYMBOLS = list(EG3D_DEDUP_PHASES)
-# ... and of include/eg3d_replay_merge.h (tests/test_replay_merge.py)
-REPLAY_MERGE_SYMBOLS = list(EG3D_REPLAY_MERGE)
-# ... and of include/eg3d_sets_device.h (tests/test_abi_sets_device.py)
-SETS_DEVICE_SYMBOLS = list(EG3D_SETS_DEVICE)
-# ... and of include/eg3d_triangulate.h (tests/test_abi_triangulate.py)
-TRIANGULATE_SYMBOLS = list(EG3D_TRIANGULATE)
-# ... and of include/eg3d_colour.h (tests/test_abi_colour.py)
-COLOUR_SYMBOLS = list(EG3D_COLOUR)
-# ... and of include/eg3d_transform.h (tests/test_abi_transform.py)
-TRANSFORM_SYMBOLS = list(EG3D_TRANSFORM)
 ERR_TRANSFORM_NONFINITE, ERR_TRANSFORM_OVERLAP = -16, -17
 
 
@@ -457,15 +441,10 @@ class Context:
         d = self.last_device_output()
         if not d.complete:
             raise RuntimeError("the device view does not hold the whole cloud of the last call")
-        try:
-            hip = C.CDLL("libamdhip64.so.7")      # by SONAME: the copy libeg3d.so (or torch) already loaded
-        except OSError:
-            hip = C.CDLL("/opt/rocm/lib/libamdhip64.so")
-        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
 
         def fetch(ptr, n, dtype):
             a = np.empty(n, dtype)
-            if n and hip.hipMemcpy(a.ctypes.data, C.cast(ptr, C.c_void_p), a.nbytes, 2) != 0:
+            if n and _hip().hipMemcpy(a.ctypes.data, C.cast(ptr, C.c_void_p), a.nbytes, 2) != 0:
                 raise RuntimeError("hipMemcpy of the device cloud failed")
             return a
         n, m = int(d.n_points), int(d.n_obs)
@@ -479,16 +458,11 @@ class Context:
         """Test plumbing: points [p0, p1) of a device-resident cloud `dev` (a DeviceEdgePoints: this context's last
         output, or the result of a gather / concat) as numpy arrays, observation offsets rebased to the slice.
         For clouds too large to copy whole (BASELINE config 4 in one call: 82 GB)."""
-        try:
-            hip = C.CDLL("libamdhip64.so.7")
-        except OSError:
-            hip = C.CDLL("/opt/rocm/lib/libamdhip64.so")
-        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
 
         def fetch(ptr, first, n, dtype):
             a = np.empty(n, dtype)
             src = C.cast(ptr, C.c_void_p).value + first * a.itemsize if n else 0
-            if n and hip.hipMemcpy(a.ctypes.data, C.c_void_p(src), a.nbytes, 2) != 0:
+            if n and _hip().hipMemcpy(a.ctypes.data, C.c_void_p(src), a.nbytes, 2) != 0:
                 raise RuntimeError("hipMemcpy of the device cloud failed")
             return a
         n_all, m_all = int(dev.n_points), int(dev.n_obs)

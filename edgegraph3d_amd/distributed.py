@@ -128,9 +128,8 @@ def gather_lib():
     if _GATHER_LIB is None:
         import ctypes as C
         import os
-        from ._cabi import EG3D_RCCL, EG3D_RCCL_CLAIMS, bind
-        _GATHER_LIB = bind(bind(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_rccl.so")), EG3D_RCCL),
-                           EG3D_RCCL_CLAIMS)
+        from ._cabi import bind_library
+        _GATHER_LIB = bind_library(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_rccl.so")), "rccl")
     return _GATHER_LIB
 
 

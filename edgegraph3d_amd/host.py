@@ -5,8 +5,7 @@ import os
 import numpy as np
 
 from . import _cdefs as D
-from ._cabi import (EG3D_HOST, EG3D_HOST_ACCUMULATE, EG3D_HOST_COLOUR, EG3D_HOST_DEDUP_PHASES, EG3D_HOST_REPLAY_MERGE,
-                    EG3D_HOST_TRANSFORM, EG3D_HOST_TRIANGULATE, bind)
+from ._cabi import bind_library
 
 _LIB = None
 
@@ -17,8 +16,7 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeg3d_host.so")
         if not os.path.exists(path):
             raise RuntimeError("libeg3d_host.so is not built: run `python -m edgegraph3d_amd.build`")
-        _LIB = bind(bind(bind(bind(C.CDLL(path), EG3D_HOST), EG3D_HOST_ACCUMULATE), EG3D_HOST_DEDUP_PHASES), EG3D_HOST_REPLAY_MERGE)
-        bind(bind(bind(_LIB, EG3D_HOST_TRIANGULATE), EG3D_HOST_COLOUR), EG3D_HOST_TRANSFORM)
+        _LIB = bind_library(C.CDLL(path), "host")
     return _LIB
 
 

@@ -1,7 +1,9 @@
-"""The whole C ABI against its Python description, without a GPU: every struct of include/eg3d.h and include/eg3d_host.h
-against its ctypes mirror (edgegraph3d_amd/_cdefs.py) and against the frozen layout of tests/golden/abi_layout.json, every
-function the three public headers declare against its row in edgegraph3d_amd/_cabi.py, and the symbols the built libraries
-export. A public struct is changed by editing abi_layout.json on purpose; a function is added by adding its row."""
+"""The whole C ABI against its Python description, without a GPU, driven by the registry of edgegraph3d_amd/_cabi.py: every
+header of include/ has a row in _cabi.HEADERS; every function a header declares is held to its row in that header's table,
+every struct to its ctypes mirror (_cdefs.MIRRORS) and to the frozen layouts of tests/golden/abi_layout.json (eg3d.h,
+eg3d_host.h) and abi_layout_later.json (the later headers); and every built library is held to the tables HEADERS gives it,
+as nm lists it and as api.lib() / host.lib() load it. A public struct is changed by editing its layout file on purpose; a
+function is added by adding its row; a header by adding its table, its HEADERS row and its count below."""
 import ctypes as C
 import json
 import os
@@ -18,18 +20,29 @@ from edgegraph3d_amd import api, build, host
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_layout.json")
-TABLES = {"eg3d.h": _cabi.EG3D, "eg3d_host.h": _cabi.EG3D_HOST, "eg3d_rccl.h": _cabi.EG3D_RCCL}
-MIRRORS = {
-    "eg3d_scene": D.Scene, "eg3d_seeds": D.Seeds, "eg3d_edgepoints": D.EdgePoints, "eg3d_candidates": D.Candidates,
-    "eg3d_stage_times": D.StageTimes, "eg3d_polyline_sets": D.PolylineSets, "eg3d_matched_intervals": D.MatchedIntervals,
-    "eg3d_set_candidates": D.SetCandidates, "eg3d_device_edgepoints": D.DeviceEdgePoints, "eg3d_filter_stats": D.FilterStats,
-    "eg3d_dedup_stats": D.DedupStats, "eg3d_device_graph3d": D.DeviceGraph3D, "eg3d_replay_stats": D.ReplayStats,
-    "eg3d_polyline_matches": D.PolylineMatches, "eg3d_polymatch_stats": D.PolymatchStats, "eg3d_simgraph": D.Simgraph,
-    "eg3d_simgraph_stats": D.SimgraphStats, "eg3d_louvain_params": D.LouvainParams, "eg3d_communities": D.Communities,
-    "eg3d_louvain_stats": D.LouvainStats, "eg3d_fund_params": D.FundParams, "eg3d_fund_stats": D.FundStats,
-    "eg3d_synth_config": D.SynthConfig, "eg3d_plg_view": D.PlgView, "eg3d_graph3d": D.Graph3D,
-}
+GOLDEN_LATER = os.path.join(ROOT, "tests", "golden", "abi_layout_later.json")
+HEADERS, FROZEN_HEADERS = _cabi.HEADERS, _cabi.FROZEN_HEADERS
+LATER_HEADERS = [h for h in HEADERS if h not in FROZEN_HEADERS]
+MIRRORS = {cname: mirror for per_header in D.MIRRORS.values() for cname, mirror in per_header.items()}
+# functions per header: a table grows or shrinks only together with its figure here
+COUNTS = {"eg3d.h": 36, "eg3d_host.h": 59, "eg3d_rccl.h": 10, "eg3d_accumulate.h": 2, "eg3d_host_accumulate.h": 5,
+          "eg3d_dedup_phases.h": 5, "eg3d_host_dedup_phases.h": 4, "eg3d_rccl_claims.h": 2, "eg3d_replay_merge.h": 1,
+          "eg3d_host_replay_merge.h": 1, "eg3d_sets_device.h": 6, "eg3d_triangulate.h": 2, "eg3d_host_triangulate.h": 1,
+          "eg3d_colour.h": 4, "eg3d_host_colour.h": 5, "eg3d_transform.h": 2, "eg3d_host_transform.h": 10}
+# the structs of the later headers: each carries its own size, first
+LATER_STRUCTS = ("eg3d_device_polyline_sets", "eg3d_items_call", "eg3d_sets_device_stats", "eg3d_tri_stats",
+                 "eg3d_colour_stats", "eg3d_transform_stats", "eg3d_similarity_stats")
 STRUCT = re.compile(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", re.S)
+MEMBER = re.compile(r"(\w+)\s*(\[\d+\])?\s*$")
+
+
+def tables(library):
+    """The tables of one library ("eg3d", "host" or "rccl") in HEADERS' order."""
+    return [table for owner, table in HEADERS.values() if owner == library]
+
+
+def names(library):
+    return {fn for table in tables(library) for fn in table}
 
 
 def header_text(name):
@@ -38,13 +51,13 @@ def header_text(name):
     return re.sub(r"^\s*#.*$", "", re.sub(r"/\*.*?\*/|//[^\n]*", " ", t, flags=re.S), flags=re.M)
 
 
-def header_structs():
-    """{struct name: [member names]} of the two headers that define structs, as the C text states them."""
+def header_structs(headers=tuple(HEADERS)):
+    """{struct name: [member names]} of the given headers (default: all of HEADERS), as the C text states them."""
     out = {}
-    for h in ("eg3d.h", "eg3d_host.h"):
+    for h in headers:
         for body, name in STRUCT.findall(header_text(h)):
             decls = [d for d in (x.strip() for x in body.split(";")) if d]
-            out[name] = [re.search(r"(\w+)\s*$", piece).group(1) for d in decls for piece in d.split(",")]
+            out[name] = [MEMBER.search(piece).group(1) for d in decls for piece in d.split(",")]
     return out
 
 
@@ -52,9 +65,9 @@ def header_structs():
 @pytest.fixture(scope="session")
 def c_layout(tmp_path_factory):
     """{struct: {"size": sizeof, "fields": [[member, offsetof, sizeof], ...]}} as gcc lays the headers' structs out: one C99
-    program over every struct and every member the headers name, compiled and run once."""
+    program over every header of HEADERS, every struct and every member they name, compiled and run once."""
     d = tmp_path_factory.mktemp("abi")
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "eg3d.h"', '#include "eg3d_host.h"', "int main(void) {"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>'] + ['#include "%s"' % h for h in HEADERS] + ["int main(void) {"]
     for s, members in header_structs().items():
         lines.append('  printf("S %s %%zu\\n", sizeof(%s));' % (s, s))
         lines += ['  printf("F %s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (s, m, s, m, s, m) for m in members]
@@ -70,9 +83,18 @@ def c_layout(tmp_path_factory):
     return out
 
 
+def test_every_header_of_the_include_directory_has_its_row():
+    assert set(HEADERS) == {f for f in os.listdir(INC) if f.endswith(".h")}
+    assert list(HEADERS)[:3] == list(FROZEN_HEADERS) and len(HEADERS) == 17
+    assert {owner for owner, _ in HEADERS.values()} == {"eg3d", "host", "rccl"}
+
+
 def test_every_struct_of_the_headers_has_a_mirror():
-    assert set(header_structs()) == set(MIRRORS), set(header_structs()) ^ set(MIRRORS)
-    assert len(MIRRORS) == 25
+    for h in HEADERS:   # (a header without a row in _cdefs.MIRRORS defines no struct)
+        assert set(header_structs((h,))) == set(D.MIRRORS.get(h, {})), h
+    assert set(D.MIRRORS) <= set(HEADERS)
+    assert len(MIRRORS) == 32 and len(MIRRORS) == sum(len(per_header) for per_header in D.MIRRORS.values())
+    assert set(header_structs(LATER_HEADERS)) == set(LATER_STRUCTS)
 
 
 @pytest.mark.parametrize("cname", sorted(MIRRORS))
@@ -81,7 +103,7 @@ def test_mirror_has_the_layout_of_the_c_struct(c_layout, cname):
     assert got["size"] == C.sizeof(mirror)
     assert got["fields"] == [[f[0], getattr(mirror, f[0]).offset, getattr(mirror, f[0]).size] for f in mirror._fields_]
     # a struct that carries its own size carries it first: the library reads it before anything else
-    if any(f[0] == "struct_size" for f in got["fields"]):
+    if any(f[0] == "struct_size" for f in got["fields"]) or cname in LATER_STRUCTS:
         assert got["fields"][0] == ["struct_size", 0, 4]
 
 
@@ -91,7 +113,15 @@ def test_layout_is_the_frozen_one(c_layout):
     frozen = json.load(open(GOLDEN))
     assert list(frozen)[0] == "generated_from"
     assert len(frozen["structs"]) == 25
-    assert c_layout == frozen["structs"]
+    assert {s: c_layout[s] for s in header_structs(FROZEN_HEADERS)} == frozen["structs"]
+
+
+def test_layout_of_the_later_structs_is_the_frozen_one(c_layout):
+    """The same for the structs of the later headers, in tests/golden/abi_layout_later.json."""
+    frozen = json.load(open(GOLDEN_LATER))
+    assert list(frozen)[0] == "generated_from"
+    assert sorted(frozen["structs"]) == sorted(LATER_STRUCTS)
+    assert {s: c_layout[s] for s in header_structs(LATER_HEADERS)} == frozen["structs"]
 
 
 def test_stats_structs_keep_their_named_fields():
@@ -140,10 +170,11 @@ def header_functions(name):
     return out
 
 
-@pytest.mark.parametrize("header", sorted(TABLES))
+@pytest.mark.parametrize("header", list(HEADERS))
 def test_table_states_what_the_header_declares(header):
-    declared, table = header_functions(header), TABLES[header]
+    declared, table = header_functions(header), HEADERS[header][1]
     assert set(declared) == set(table), set(declared) ^ set(table)
+    assert len(table) == COUNTS[header]
     bad = []
     for fn, (ret, params) in declared.items():
         restype, argtypes = table[fn]
@@ -151,13 +182,20 @@ def test_table_states_what_the_header_declares(header):
         if got != (ret, params):
             bad.append((fn, "header", (ret, params), "table", got))
     assert not bad, bad
+    assert not [n for n in table if "probe" in n or "internal" in n]
 
 
-def test_tables_cover_105_functions_and_api_lists_its_own():
-    assert [len(TABLES[h]) for h in sorted(TABLES)] == [36, 59, 10]   # (ten: gather create / destroy / set_mode /
-    #                                  set_chunk_bytes, allgather, concat, comm unique_id / init / query / destroy)
-    assert len(_cabi.EG3D_HOST) > 24
-    assert sorted(api.EXPORTED_SYMBOLS) == sorted(_cabi.EG3D)
+def test_every_name_has_one_table_and_the_frozen_headers_hold_nothing_of_the_later_ones():
+    assert set(COUNTS) == set(HEADERS) and sum(COUNTS.values()) == 155
+    every = [fn for _, table in HEADERS.values() for fn in table]
+    assert len(every) == len(set(every)), sorted(fn for fn in set(every) if every.count(fn) > 1)
+    frozen_text = header_text("eg3d.h") + header_text("eg3d_host.h")
+    for name in [fn for h in LATER_HEADERS for fn in HEADERS[h][1]] + list(LATER_STRUCTS):
+        assert name not in frozen_text, name
+
+
+def test_frozen_tables_keep_their_named_functions_and_api_lists_its_own():
+    assert api.EXPORTED_SYMBOLS == list(_cabi.EG3D)
     for name in ("eg3d_dedup_device", "eg3d_dedup_resident", "eg3d_gn_filter_device", "eg3d_compact_device",
                  "eg3d_filter_resident", "eg3d_detect_communities", "eg3d_free_communities", "eg3d_similarity_graph",
                  "eg3d_free_simgraph", "eg3d_estimate_fundamental"):
@@ -176,22 +214,31 @@ def test_product_library_exports_the_table_and_no_test_hook(rows):
     if not os.path.exists(path):
         (build.build_hip if rows == 3 else build.build_hip_dlt4x4)()
     syms = exported(path)
-    assert not set(_cabi.EG3D) - syms, set(_cabi.EG3D) - syms
+    assert not names("eg3d") - syms, names("eg3d") - syms
     # no test hooks in the product library: the probes live in tests/probe/libeg3d_probe.so
     assert not [n for n in syms if "probe" in n or "internal" in n], syms
-    assert "eg3d_host_estimate_fundamental" not in syms  # (libeg3d.so does not carry the host statement)
+    # the host statements live in libeg3d_host.so alone; the grid builder is the one host function the product library shares
+    host_only = names("host") - {"eg3d_host_build_grid"}
+    assert not host_only & syms, host_only & syms
 
 
 def test_host_and_gather_libraries_export_their_tables():
-    assert not set(_cabi.EG3D_HOST) - exported(build.HOST_LIB)
+    assert not names("host") - exported(build.HOST_LIB)
     # the RCCL gather library: symbol table only — loading it would pull /opt/rocm's librccl into a process that may already
     # hold the torch wheel's ROCm runtime (distributed.gather_lib() is lazy for the same reason)
-    assert not set(_cabi.EG3D_RCCL) - exported(build.RCCL_LIB)
-    for name in _cabi.EG3D_HOST:
-        assert hasattr(host.lib(), name), name
+    assert not names("rccl") - exported(build.RCCL_LIB)
 
 
 def test_loaded_library_carries_the_replay_entry_points():
     """The C-ABI library loads without a GPU, every function of the table declared on it."""
     assert hasattr(api.lib(), "eg3d_replay_device") and hasattr(api.lib(), "eg3d_free_graph3d")
     assert _cabi.EG3D["eg3d_replay_device"][1] == api.lib().eg3d_replay_device.argtypes
+
+
+@pytest.mark.parametrize("library,loaded", [("eg3d", api.lib), ("host", host.lib)], ids=("eg3d", "host"))
+def test_loaded_library_declares_every_function_as_its_table_states(library, loaded):
+    """The C-ABI library and the host library load without a GPU, every function of every table declared on them."""
+    for table in tables(library):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(loaded(), name)
+            assert fn.argtypes == argtypes and fn.restype == restype, name

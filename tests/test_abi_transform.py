@@ -1,12 +1,11 @@
-"""What tests/test_abi.py does for the frozen headers, for include/eg3d_transform.h and include/eg3d_host_transform.h: every
-function they declare against its row in _cabi.EG3D_TRANSFORM / EG3D_HOST_TRANSFORM, both stats structs against their
-ctypes mirrors as gcc lays them out, the tables against the symbols the product libraries and the host library export, the
-null-argument refusals of the host entry points, and the build guard's bound on K16. No GPU."""
+"""What include/eg3d_transform.h and include/eg3d_host_transform.h promise beyond their signatures and layouts: the codes and
+the phrases, the named fields, the callable wrappers, the null-argument refusals of the entry points, and the build
+guard's bound on K16. The signatures, layouts, exports and loaded functions of every header are held by tests/test_abi.py;
+the tests here that bear those names call it for these two headers and add only what is said above. No GPU."""
 import ctypes as C
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,33 +14,14 @@ import forms
 import test_abi
 from edgegraph3d_amd import _cabi, api, build, host
 from edgegraph3d_amd import _cdefs as D
+from test_abi import c_layout  # noqa: F401  (the one generated layout program, as a fixture of this module too)
 
 HEADER, HOST_HEADER = "eg3d_transform.h", "eg3d_host_transform.h"
-MIRRORS = {"eg3d_transform_stats": D.TransformStats, "eg3d_similarity_stats": D.SimilarityStats}
-FROZEN = (_cabi.EG3D, _cabi.EG3D_HOST, _cabi.EG3D_RCCL)
-OTHERS = (_cabi.EG3D_ACCUMULATE, _cabi.EG3D_HOST_ACCUMULATE, _cabi.EG3D_DEDUP_PHASES, _cabi.EG3D_HOST_DEDUP_PHASES,
-          _cabi.EG3D_RCCL_CLAIMS, _cabi.EG3D_REPLAY_MERGE, _cabi.EG3D_HOST_REPLAY_MERGE, _cabi.EG3D_SETS_DEVICE,
-          _cabi.EG3D_TRIANGULATE, _cabi.EG3D_HOST_TRIANGULATE, _cabi.EG3D_COLOUR, _cabi.EG3D_HOST_COLOUR)
-NEW = (_cabi.EG3D_TRANSFORM, _cabi.EG3D_HOST_TRANSFORM)
 
 
-def _structs(header):
-    out = {}
-    for body, name in test_abi.STRUCT.findall(test_abi.header_text(header)):
-        decls = [d for d in (x.strip() for x in body.split(";")) if d]
-        out[name] = [re.search(r"(\w+)\s*(\[\d+\])?\s*$", piece).group(1) for d in decls for piece in d.split(",")]
-    return out
-
-
-@pytest.mark.parametrize("header,table,count", [(HEADER, _cabi.EG3D_TRANSFORM, 2), (HOST_HEADER, _cabi.EG3D_HOST_TRANSFORM, 10)],
-                         ids=("device", "host"))
-def test_table_states_what_the_header_declares(header, table, count):
-    declared = test_abi.header_functions(header)
-    assert set(declared) == set(table), set(declared) ^ set(table)
-    assert len(table) == count
-    for fn, (ret, params) in declared.items():
-        restype, argtypes = table[fn]
-        assert (test_abi.ctypes_kind(restype), [test_abi.ctypes_kind(a) for a in argtypes]) == (ret, params), fn
+@pytest.mark.parametrize("header", (HEADER, HOST_HEADER), ids=("device", "host"))
+def test_table_states_what_the_header_declares(header):
+    test_abi.test_table_states_what_the_header_declares(header)
 
 
 def test_the_headers_state_the_codes_and_what_is_pinned():
@@ -60,36 +40,15 @@ def test_the_headers_state_the_codes_and_what_is_pinned():
 
 
 def test_the_frozen_tables_are_untouched_and_the_new_ones_disjoint():
-    assert [len(t) for t in FROZEN] == [36, 59, 10]
-    names = [n for t in FROZEN + OTHERS + NEW for n in t]
-    assert len(names) == len(set(names))
-    assert sorted(api.TRANSFORM_SYMBOLS) == sorted(_cabi.EG3D_TRANSFORM)
-    assert not set(api.TRANSFORM_SYMBOLS) & set(api.EXPORTED_SYMBOLS)
-    frozen_text = test_abi.header_text("eg3d.h") + test_abi.header_text("eg3d_host.h")
-    for name in list(MIRRORS) + [n for t in NEW for n in t]:   # the frozen headers hold nothing of the new ones
-        assert name not in frozen_text, name
+    test_abi.test_every_name_has_one_table_and_the_frozen_headers_hold_nothing_of_the_later_ones()
+    assert not set(_cabi.EG3D_TRANSFORM) & set(api.EXPORTED_SYMBOLS)
 
 
-def test_mirrors_have_the_layout_gcc_gives_the_structs(tmp_path):
-    structs = dict(_structs(HEADER), **_structs(HOST_HEADER))
-    assert set(structs) == set(MIRRORS), set(structs) ^ set(MIRRORS)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, '#include "%s"' % HOST_HEADER, "int main(void) {"]
-    for s, members in structs.items():
-        lines.append('  printf("S %s %%zu\\n", sizeof(%s));' % (s, s))
-        lines += ['  printf("F %s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (s, m, s, m, s, m) for m in members]
-    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", test_abi.INC, str(tmp_path / "layout.c"), "-o", exe])
-    got = {}
-    for w in (l.split() for l in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()):
-        if w[0] == "S":
-            got[w[1]] = {"size": int(w[2]), "fields": []}
-        else:
-            got[w[1]]["fields"].append([w[2], int(w[3]), int(w[4])])
-    for cname, mirror in MIRRORS.items():
-        assert got[cname]["size"] == C.sizeof(mirror), cname
-        assert got[cname]["fields"] == [[f[0], getattr(mirror, f[0]).offset, getattr(mirror, f[0]).size] for f in mirror._fields_], cname
-        assert got[cname]["fields"][0] == ["struct_size", 0, 4], cname   # new structs carry their size first
+def test_mirrors_have_the_layout_gcc_gives_the_structs(c_layout):  # noqa: F811
+    structs = test_abi.header_structs((HEADER, HOST_HEADER))
+    assert set(structs) == {"eg3d_transform_stats", "eg3d_similarity_stats"}
+    for cname in structs:
+        test_abi.test_mirror_has_the_layout_of_the_c_struct(c_layout, cname)
     for f in ("n_points", "n_transformed", "n_nonfinite", "ms_kernel", "ms_copy"):
         assert f in structs["eg3d_transform_stats"], f
     for f in ("scale", "singular", "reflection", "rank_deficient"):
@@ -98,27 +57,18 @@ def test_mirrors_have_the_layout_gcc_gives_the_structs(tmp_path):
 
 @pytest.mark.parametrize("rows", list(forms.FORMS), ids=[forms.IDS[r] for r in forms.FORMS])
 def test_product_library_exports_the_table(rows):
-    path = forms.lib_path(rows)
-    if not os.path.exists(path):
-        (build.build_hip if rows == 3 else build.build_hip_dlt4x4)()
-    syms = test_abi.exported(path)
-    assert not set(_cabi.EG3D_TRANSFORM) - syms, set(_cabi.EG3D_TRANSFORM) - syms
-    assert not set(_cabi.EG3D_HOST_TRANSFORM) & syms   # (the product library does not carry the host statement)
+    test_abi.test_product_library_exports_the_table_and_no_test_hook(rows)
 
 
 def test_host_library_exports_the_table():
-    syms = test_abi.exported(build.build_host())
-    assert not set(_cabi.EG3D_HOST_TRANSFORM) - syms
-    for name in _cabi.EG3D_HOST_TRANSFORM:
-        assert _cabi.EG3D_HOST_TRANSFORM[name][1] == getattr(host.lib(), name).argtypes
+    test_abi.test_host_and_gather_libraries_export_their_tables()
+    test_abi.test_loaded_library_declares_every_function_as_its_table_states("host", host.lib)
     for f in ("similarity_fit", "transform_points", "transform_cameras", "camera_errors", "read_camera_poses", "null_cameras"):
         assert callable(getattr(host, f)), f
 
 
 def test_loaded_library_carries_the_entry_points():
-    for name in _cabi.EG3D_TRANSFORM:   # (the C-ABI library loads without a GPU)
-        assert hasattr(api.lib(), name), name
-        assert _cabi.EG3D_TRANSFORM[name][1] == getattr(api.lib(), name).argtypes
+    test_abi.test_loaded_library_declares_every_function_as_its_table_states("eg3d", api.lib)
     for m in ("transform_device", "transform_points"):
         assert callable(getattr(api.Context, m)), m
 

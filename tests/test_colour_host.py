@@ -2,7 +2,12 @@
   * eg3d_host_colour_points on every row of tests/colour_cases.py: colours, flags, counts and refusals;
   * the closed form of the border rule the kernel uses (the host compilation of csrc/eg3d_dev_colour.h) against the loop,
     in C and in Python, for every p in [-4 len - 3, 4 len + 3], len 1 .. 9;
-  * eg3d_host_write_ply byte for byte; eg3d_host_png_read_rgb on PNG files written here with zlib."""
+  * eg3d_host_write_ply byte for byte; eg3d_host_png_read_rgb on PNG files written here with zlib;
+  * what the two colour headers promise beyond their signatures (those are held by tests/test_abi.py): the flag, the stated
+    deviations, the named fields, the build guard's bound on K15."""
+import json
+import os
+import re
 import struct
 import zlib
 
@@ -11,7 +16,8 @@ import pytest
 
 import colour_cases as cc
 import colour_ref as cr
-from edgegraph3d_amd import host
+import test_abi
+from edgegraph3d_amd import api, build, host
 
 V = 16
 _REF = {}
@@ -168,3 +174,44 @@ def test_png_read_rgb(tmp_path):
     assert (host.read_png_rgb(_png(tmp_path / "rgb16.png", W, H, 16, 2, rows16)) == rgb).all()
     with pytest.raises(ValueError):
         host.read_png_rgb(str(tmp_path / "missing.png"))
+
+
+# ---- what the two headers promise beyond their signatures ------------------------------------------------------------------------
+HEADER, HOST_HEADER = "eg3d_colour.h", "eg3d_host_colour.h"
+
+
+def test_the_header_states_the_flag_and_the_deviations():
+    text = open(os.path.join(test_abi.INC, HEADER)).read()   # (header_text drops the preprocessor lines)
+    assert re.search(r"#define\s+EG3D_COLOUR_FLAG_EMPTY\s+1u\b", text)
+    assert api.COLOUR_FLAG_EMPTY == 1
+    for phrase in ("A clone (eg3d_clone) does NOT inherit them", "n == 0 is undefined behaviour in the reference", "JPEG is not read",
+                   "the integer division"):
+        assert phrase in text, phrase
+    assert "JPEG is not read" in open(os.path.join(test_abi.INC, HOST_HEADER)).read()
+
+
+def test_the_stats_keep_their_named_fields_and_the_wrappers_are_there():
+    fields = test_abi.header_structs((HEADER,))["eg3d_colour_stats"]
+    for f in ("n_points", "n_coloured", "n_empty", "n_obs_sampled", "ms_sample", "ms_mix", "ms_copy"):
+        assert f in fields, f
+    for f in ("colour_points", "write_ply", "read_png_rgb"):
+        assert callable(getattr(host, f)), f
+    for m in ("upload_images", "release_images", "colour_device", "colour_points"):
+        assert callable(getattr(api.Context, m)), m
+
+
+def test_the_build_guard_holds_k15():
+    """No spilled register, no scratch and no LDS in either K15 kernel; the VGPR bounds are the build's counts."""
+    b = build.RESOURCE_BOUNDS["k15_"]
+    assert b["vgpr_spill_count"] == 0 and b["sgpr_spill_count"] == 0
+    assert b["private_segment_fixed_size"] == 0 and b["group_segment_fixed_size"] == 0
+    for k in ("k15_sample", "k15_mix"):
+        assert 0 < build.RESOURCE_BOUNDS[k]["vgpr_count"] <= 64, k
+    for lib in ("libeg3d", "libeg3d_dlt4x4"):
+        rec = json.load(open(os.path.join(build.ROOT, "profiles", "kernel_resources_%s.json" % lib)))
+        k15 = {n: r for n, r in rec.items() if "k15_" in n}
+        assert len(k15) == 2, sorted(k15)
+        for n, r in k15.items():
+            key = "k15_sample" if "k15_sample" in n else "k15_mix"
+            assert r["vgpr_count"] <= build.RESOURCE_BOUNDS[key]["vgpr_count"], n
+            assert r["vgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0 and r["group_segment_fixed_size"] == 0, n

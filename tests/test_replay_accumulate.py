@@ -1,7 +1,7 @@
 """The matches manager that accumulates over calls, host form (include/eg3d_host_accumulate.h), without a GPU: a state fed
 the parts of a cloud must hold, after every add, the graph host.replay_matches and the oracle's replay_matches build from the
 concatenation of the parts so far. Every comparison is exact (replay_gpu_cases.same_graph). Also here: the reference-API
-shim's set_accumulate, and the two new headers against their tables in edgegraph3d_amd/_cabi.py."""
+shim's set_accumulate. (The two headers against their tables: tests/test_abi.py.)"""
 import ctypes as C
 import itertools
 import os
@@ -13,8 +13,7 @@ import pytest
 import cbuild
 import forms
 import replay_gpu_cases as rc
-import test_abi
-from edgegraph3d_amd import _cabi, api, build, host
+from edgegraph3d_amd import host
 from oracle import binding as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -240,34 +239,3 @@ def test_shim_manager_accumulates_when_asked(tmp_path):
     exe = cbuild.build_caller("tests/refapi/accumulate_check.cpp", tmp_path, lib=cbuild.DEFAULT_LIB)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "accumulate_check 0" in r.stdout, (r.stdout, r.stderr)
-
-
-# ---- 5. the new headers against their tables -----------------------------------------------------------------------------------
-NEW_TABLES = {"eg3d_accumulate.h": _cabi.EG3D_ACCUMULATE, "eg3d_host_accumulate.h": _cabi.EG3D_HOST_ACCUMULATE}
-
-
-@pytest.mark.parametrize("header", sorted(NEW_TABLES))
-def test_new_table_states_what_the_new_header_declares(header):
-    declared, table = test_abi.header_functions(header), NEW_TABLES[header]
-    assert set(declared) == set(table), set(declared) ^ set(table)
-    for fn, (ret, params) in declared.items():
-        restype, argtypes = table[fn]
-        assert (test_abi.ctypes_kind(restype), [test_abi.ctypes_kind(a) for a in argtypes]) == (ret, params), fn
-    assert not [n for n in table if "probe" in n or "internal" in n]
-
-
-def test_libraries_export_the_new_symbols_and_the_frozen_tables_keep_their_length():
-    assert [len(_cabi.EG3D), len(_cabi.EG3D_HOST), len(_cabi.EG3D_RCCL)] == [36, 59, 10]
-    assert not set(_cabi.EG3D_ACCUMULATE) & set(_cabi.EG3D) and not set(_cabi.EG3D_HOST_ACCUMULATE) & set(_cabi.EG3D_HOST)
-    assert not set(_cabi.EG3D_HOST_ACCUMULATE) - test_abi.exported(build.HOST_LIB)
-    for rows in forms.FORMS:
-        path = forms.lib_path(rows)
-        if not os.path.exists(path):
-            (build.build_hip if rows == 3 else build.build_hip_dlt4x4)()
-        assert not set(_cabi.EG3D_ACCUMULATE) - test_abi.exported(path), rows
-    assert sorted(api.ACCUMULATE_SYMBOLS) == sorted(_cabi.EG3D_ACCUMULATE)
-    assert not set(api.ACCUMULATE_SYMBOLS) & set(api.EXPORTED_SYMBOLS)
-    for name in _cabi.EG3D_ACCUMULATE:
-        assert hasattr(api.lib(), name), name
-    for name in _cabi.EG3D_HOST_ACCUMULATE:
-        assert hasattr(host.lib(), name), name

@@ -2,7 +2,7 @@
 state that takes, in place of the clouds of a run, the graphs that separate replays of them built must hold after every
 merge the graph the oracle's replay_matches builds from the concatenation of those clouds — as a left fold and as a pairwise
 tree. The reference is never the merge itself. Every comparison is exact (replay_gpu_cases.same_graph). Also here: every
-refusal, and the two new headers against their tables in edgegraph3d_amd/_cabi.py."""
+refusal. (The two headers against their tables: tests/test_abi.py.)"""
 import ctypes as C
 import itertools
 import os
@@ -14,8 +14,7 @@ import pytest
 import forms
 import replay_gpu_cases as rc
 import replay_merge_cases as mc
-import test_abi
-from edgegraph3d_amd import _cabi, _cdefs as D, api, build, host
+from edgegraph3d_amd import _cdefs as D, build, host
 from oracle import binding as ob
 from test_replay_accumulate import chain_starts, concat, parts_at, slice_cloud, _ranges
 
@@ -234,41 +233,3 @@ def test_the_stand_alone_fold_through_the_c_entry_points(tmp_path):
                            "-Wl,-rpath," + pkg, "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "replay_merge_check 0" in r.stdout, (r.stdout, r.stderr)
-
-
-# ---- 5. the new headers against their tables -----------------------------------------------------------------------------------------
-NEW_TABLES = {"eg3d_replay_merge.h": _cabi.EG3D_REPLAY_MERGE, "eg3d_host_replay_merge.h": _cabi.EG3D_HOST_REPLAY_MERGE}
-
-
-@pytest.mark.parametrize("header", sorted(NEW_TABLES))
-def test_new_table_states_what_the_new_header_declares(header):
-    declared, table = test_abi.header_functions(header), NEW_TABLES[header]
-    assert set(declared) == set(table), set(declared) ^ set(table)
-    for fn, (ret, params) in declared.items():
-        restype, argtypes = table[fn]
-        assert (test_abi.ctypes_kind(restype), [test_abi.ctypes_kind(a) for a in argtypes]) == (ret, params), fn
-    assert not [n for n in table if "probe" in n or "internal" in n]
-
-
-def test_libraries_export_the_new_symbols_and_the_earlier_tables_are_unchanged():
-    assert [len(_cabi.EG3D), len(_cabi.EG3D_HOST), len(_cabi.EG3D_RCCL), len(_cabi.EG3D_ACCUMULATE),
-            len(_cabi.EG3D_HOST_ACCUMULATE)] == [36, 59, 10, 2, 5]
-    assert [len(_cabi.EG3D_DEDUP_PHASES), len(_cabi.EG3D_HOST_DEDUP_PHASES), len(_cabi.EG3D_RCCL_CLAIMS)] == [5, 4, 2]
-    earlier = (_cabi.EG3D, _cabi.EG3D_HOST, _cabi.EG3D_RCCL, _cabi.EG3D_ACCUMULATE, _cabi.EG3D_HOST_ACCUMULATE,
-               _cabi.EG3D_DEDUP_PHASES, _cabi.EG3D_HOST_DEDUP_PHASES, _cabi.EG3D_RCCL_CLAIMS)
-    for t in earlier:
-        assert not (set(_cabi.EG3D_REPLAY_MERGE) | set(_cabi.EG3D_HOST_REPLAY_MERGE)) & set(t)
-    for header in ("eg3d.h", "eg3d_host.h", "eg3d_rccl.h"):      # the frozen headers gained no declaration
-        assert not [f for f in test_abi.header_functions(header) if "merge_graph" in f]
-    assert not set(_cabi.EG3D_HOST_REPLAY_MERGE) - test_abi.exported(build.HOST_LIB)
-    for rows in forms.FORMS:
-        path = forms.lib_path(rows)
-        if not os.path.exists(path):
-            (build.build_hip if rows == 3 else build.build_hip_dlt4x4)()
-        assert not set(_cabi.EG3D_REPLAY_MERGE) - test_abi.exported(path), rows
-    assert sorted(api.REPLAY_MERGE_SYMBOLS) == sorted(_cabi.EG3D_REPLAY_MERGE)
-    assert not set(api.REPLAY_MERGE_SYMBOLS) & set(api.EXPORTED_SYMBOLS)
-    for name in _cabi.EG3D_REPLAY_MERGE:
-        assert hasattr(api.lib(), name), name
-    for name in _cabi.EG3D_HOST_REPLAY_MERGE:
-        assert hasattr(host.lib(), name), name

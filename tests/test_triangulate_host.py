@@ -2,15 +2,20 @@
 for both forms of the DLT system, on the tables of tests/triangulate_cases.py: the three rigs of coop_gn_cases.rigs(), every
 row count of coop_gn_cases.ROWS, 4096 rows once, lengths 0 and 1, every kind in EG3D_TRI_REFINE, and in
 EG3D_TRI_FROM_SCRATCH the kinds near / wild / singular / nan_obs plus the three cases of the DLT's choice of entries. A
-track that is not valid keeps X0 (REFINE) or gets +0.0 (FROM_SCRATCH). Thread counts 1 and 4 give the same bytes. No GPU."""
+track that is not valid keeps X0 (REFINE) or gets +0.0 (FROM_SCRATCH). Thread counts 1 and 4 give the same bytes. Then what
+include/eg3d_triangulate.h promises beyond its signatures (those are held by tests/test_abi.py): the modes and flags, the
+wrappers, the build guard's bound on K14. No GPU."""
 import functools
+import os
+import re
 
 import numpy as np
 import pytest
 
 import forms
+import test_abi
 import triangulate_cases as tc
-from edgegraph3d_amd import host
+from edgegraph3d_amd import api, build, host
 
 RIGS = ("c5", "wide", "tiny")
 
@@ -85,3 +90,26 @@ def test_refusals_and_empty_input():
         host.triangulate(rig.P, long_off, np.zeros(32768, np.int32), np.zeros((32768, 2), np.float32), mode=0)
     n = 32767  # the longest list that passes
     host.triangulate(rig.P, np.array([0, n], np.uint32), np.arange(n, dtype=np.int32) % rig.V, np.ones((n, 2), np.float32), mode=0)
+
+
+# ---- what the header promises beyond its signatures ------------------------------------------------------------------------------
+def test_the_header_states_the_modes_and_flags_and_the_wrappers_are_there():
+    text = open(os.path.join(test_abi.INC, "eg3d_triangulate.h")).read()   # (header_text drops the preprocessor lines)
+    for name, value in (("EG3D_TRI_FROM_SCRATCH", "0"), ("EG3D_TRI_REFINE", "1"), ("EG3D_TRI_FLAG_SHORT", "1u"),
+                        ("EG3D_TRI_FLAG_DEGENERATE", "2u")):
+        assert re.search(r"#define\s+%s\s+%s\b" % (name, value), text), name
+    assert (api.TRI_FROM_SCRATCH, api.TRI_REFINE, api.TRI_FLAG_SHORT, api.TRI_FLAG_DEGENERATE) == (0, 1, 1, 2)
+    assert callable(host.triangulate)
+    for m in ("triangulate", "triangulate_device"):
+        assert callable(getattr(api.Context, m)), m
+
+
+def test_the_build_guard_holds_k14():
+    """No spilled register in any K14 kernel; the solve kernel within four single-wave workgroups per SIMD (128 VGPRs, 8 LDS
+    allocation units); no scratch and no LDS in the other three."""
+    b = build.RESOURCE_BOUNDS["k14_"]
+    assert b["vgpr_spill_count"] == 0 and b["sgpr_spill_count"] == 0
+    assert b["private_segment_fixed_size"] <= 64 and b["group_segment_fixed_size"] <= 10240
+    assert build.RESOURCE_BOUNDS["k14_solve"]["vgpr_count"] <= 128
+    for k in ("k14_check", "k14_cut", "k14_stage"):
+        assert build.RESOURCE_BOUNDS[k] == {"private_segment_fixed_size": 0, "group_segment_fixed_size": 0}
