@@ -262,6 +262,27 @@ HEADERS = {
 }
 FROZEN_HEADERS = ("eg3d.h", "eg3d_host.h", "eg3d_rccl.h")
 
+# include/eg3d/edges.h (libeg3d.so, libeg3d_dlt4x4.so): the 3-D edge model of a graph3d traced and simplified on the device, K17
+EDGES = {
+    "eg3d_edge_chains_device": (i32, [vp, P(D.DeviceGraph3D), f32, i32, P(D.DeviceEdgeChains), P(D.EdgeChains), P(D.EdgesStats)]),
+    "eg3d_edge_chains": (i32, [vp, P(D.Graph3D), f32, i32, P(D.DeviceEdgeChains), P(D.EdgeChains), P(D.EdgesStats)]),
+    "eg3d_free_edge_chains": (None, [P(D.EdgeChains)]),
+}
+
+# include/eg3d/host_edges.h (libeg3d_host.so): its sequential statement and the PLY line model
+HOST_EDGES = {
+    "eg3d_host_edge_chains": (i32, [P(D.Graph3D), f32, i32, P(D.EdgeChains), P(D.EdgesStats)]),
+    "eg3d_host_free_edge_chains": (None, [P(D.EdgeChains)]),
+    "eg3d_host_write_ply_edges": (i32, [cstr, P(D.EdgeChains), f32p]),
+}
+
+# The headers that live in subdirectories of include/, as HEADERS: header -> (library, table). bind_library declares these
+# as well; tests/test_abi_edges.py holds them to their headers, mirrors (_cdefs.MIRRORS_EXT) and exports.
+EXT_HEADERS = {
+    "eg3d/edges.h": ("eg3d", EDGES),
+    "eg3d/host_edges.h": ("host", HOST_EDGES),
+}
+
 
 def bind(lib, table):
     """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""
@@ -272,8 +293,8 @@ def bind(lib, table):
 
 
 def bind_library(lib, library):
-    """Declare on the CDLL `lib` every table HEADERS gives to `library` ("eg3d", "host" or "rccl"). Returns `lib`."""
-    for owner, table in HEADERS.values():
+    """Declare on the CDLL `lib` every table HEADERS and EXT_HEADERS give to `library` ("eg3d", "host" or "rccl"). Returns `lib`."""
+    for owner, table in list(HEADERS.values()) + list(EXT_HEADERS.values()):
         if owner == library:
             bind(lib, table)
     return lib

@@ -69,6 +69,86 @@ class SimilarityStats(C.Structure):
                 ("src_var", C.c_double), ("reflection", C.c_uint32), ("rank_deficient", C.c_uint32)]
 
 
+class EdgeChains(C.Structure):
+    """eg3d_edge_chain_set (include/eg3d/host_edges.h): the traced and simplified chains, library-owned host arrays."""
+    _fields_ = [("n_chains", C.c_uint64), ("n_vertices", C.c_uint64), ("n_kept", C.c_uint64), ("chain_off", u64p),
+                ("chain_node", u32p), ("chain_flags", u32p), ("s_off", u64p), ("s_node", u32p), ("length", f32p)]
+
+
+class DeviceEdgeChains(C.Structure):
+    """eg3d_device_edge_chains (include/eg3d/edges.h): the same, the pointers into HBM."""
+    _fields_ = [("n_chains", C.c_uint64), ("n_vertices", C.c_uint64), ("n_kept", C.c_uint64), ("chain_off", C.c_void_p),
+                ("chain_node", C.c_void_p), ("chain_flags", C.c_void_p), ("s_off", C.c_void_p), ("s_node", C.c_void_p),
+                ("length", C.c_void_p)]
+
+
+class EdgesStats(C.Structure):
+    """eg3d_edges_stats (include/eg3d/host_edges.h): struct_size is set to the size of this mirror by its user before the call."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_chains", C.c_uint64), ("n_rings", C.c_uint64),
+                ("n_loops_dropped", C.c_uint64), ("n_vertices_in", C.c_uint64), ("n_vertices_kept", C.c_uint64),
+                ("longest_chain", C.c_uint64), ("ms_trace", C.c_float), ("ms_simplify", C.c_float), ("ms_copy", C.c_float),
+                ("reserved2", C.c_float)]
+
+
+def edge_chains_to_dict(c, stats=None):
+    """The arrays of an EdgeChains as numpy copies: chain_off, chain_node, flags, s_off, s_node, length (+ stats)."""
+    n = int(c.n_chains)
+    d = {"chain_off": as_np(c.chain_off, n + 1, np.uint64), "chain_node": as_np(c.chain_node, int(c.n_vertices), np.uint32),
+         "flags": as_np(c.chain_flags, n, np.uint32), "s_off": as_np(c.s_off, n + 1, np.uint64),
+         "s_node": as_np(c.s_node, int(c.n_kept), np.uint32), "length": as_np(c.length, n, np.float32)}
+    if stats is not None:
+        d["stats"] = {f[0]: getattr(stats, f[0]) for f in EdgesStats._fields_ if not f[0].startswith("reserved")}
+    return d
+
+
+class EdgeChainsArrays:
+    """Owns numpy copies of a chains dict (as edge_chains_to_dict gives it) and exposes an EdgeChains struct over them."""
+
+    def __init__(self, d):
+        self.a = {"chain_off": np.ascontiguousarray(d["chain_off"], np.uint64), "chain_node": np.ascontiguousarray(d["chain_node"], np.uint32),
+                  "flags": np.ascontiguousarray(d["flags"], np.uint32), "s_off": np.ascontiguousarray(d["s_off"], np.uint64),
+                  "s_node": np.ascontiguousarray(d["s_node"], np.uint32), "length": np.ascontiguousarray(d["length"], np.float32)}
+        a = self.a
+        n = len(a["flags"])
+        if len(a["chain_off"]) != n + 1 or len(a["s_off"]) != n + 1 or len(a["length"]) != n:
+            raise ValueError("chains: the arrays do not agree on the number of chains")
+        if int(a["chain_off"][-1]) != len(a["chain_node"]) or int(a["s_off"][-1]) != len(a["s_node"]):
+            raise ValueError("chains: the offsets do not end at the length of their array")
+        if np.any(np.diff(a["s_off"].astype(np.int64)) < 0):
+            raise ValueError("chains: s_off does not ascend")
+        self.c = EdgeChains(n, len(a["chain_node"]), len(a["s_node"]), np_ptr(a["chain_off"], C.c_uint64),
+                            np_ptr(a["chain_node"], C.c_uint32), np_ptr(a["flags"], C.c_uint32), np_ptr(a["s_off"], C.c_uint64),
+                            np_ptr(a["s_node"], C.c_uint32), np_ptr(a["length"], C.c_float))
+
+
+class EdgesGraphArrays:
+    """Owns numpy copies of the geometric half of a graph dict (n_nodes, n_polylines, node_X, pl_start, pl_end, conn_off,
+    conn_pl) and exposes a Graph3D struct over them for the edge-chain entry points. The C struct carries no array lengths:
+    node_X, pl_start, pl_end and conn_off are held to the counts here (ValueError); conn_pl is padded with the invalid id
+    0xFFFFFFFF up to 2 * n_polylines entries, so that whatever offsets the C side accepts, it reads inside the array."""
+
+    def __init__(self, g):
+        nn, npl = int(g["n_nodes"]), int(g["n_polylines"])
+        X = np.ascontiguousarray(g["node_X"], np.float32).reshape(-1)
+        ps, pe = np.ascontiguousarray(g["pl_start"], np.uint32).reshape(-1), np.ascontiguousarray(g["pl_end"], np.uint32).reshape(-1)
+        off = np.ascontiguousarray(g["conn_off"], np.uint64).reshape(-1)
+        cpl = np.ascontiguousarray(g["conn_pl"], np.uint32).reshape(-1)
+        for name, a, n in (("node_X", X, 3 * nn), ("pl_start", ps, npl), ("pl_end", pe, npl), ("conn_off", off, nn + 1)):
+            if a.size != n:
+                raise ValueError("graph: %s holds %d values where its counts say %d" % (name, a.size, n))
+        if cpl.size < 2 * npl:
+            cpl = np.concatenate([cpl, np.full(2 * npl - cpl.size, 0xFFFFFFFF, np.uint32)])
+        self.a = (X, ps, pe, off, cpl)
+        self.c = Graph3D()
+        self.c.n_nodes = self.c.n_real_nodes = nn
+        self.c.n_polylines = npl
+        self.c.node_X = np_ptr(X, C.c_float) if X.size else None
+        self.c.pl_start = np_ptr(ps, C.c_uint32) if npl else None
+        self.c.pl_end = np_ptr(pe, C.c_uint32) if npl else None
+        self.c.conn_off = np_ptr(off, C.c_uint64)
+        self.c.conn_pl = np_ptr(cpl, C.c_uint32) if cpl.size else None
+
+
 class ImageArgs:
     """Owns what eg3d_upload_images / eg3d_host_colour_points take for `images`: a sequence with one entry per view, an
     [H, W, 3] uint8 array (RGB) or None for a view without an image."""
@@ -484,4 +564,9 @@ MIRRORS = {
     "eg3d_colour.h": {"eg3d_colour_stats": ColourStats},
     "eg3d_transform.h": {"eg3d_transform_stats": TransformStats},
     "eg3d_host_transform.h": {"eg3d_similarity_stats": SimilarityStats},
+}
+# the same for the headers in subdirectories of include/ (_cabi.EXT_HEADERS); tests/test_abi_edges.py holds these
+MIRRORS_EXT = {
+    "eg3d/edges.h": {"eg3d_device_edge_chains": DeviceEdgeChains},
+    "eg3d/host_edges.h": {"eg3d_edge_chain_set": EdgeChains, "eg3d_edges_stats": EdgesStats},
 }

@@ -854,6 +854,35 @@ class Context:
             lib().eg3d_free_graph3d(C.byref(g))
         return d, (dv if materialise else None), {f[0]: getattr(st, f[0]) for f in D.ReplayStats._fields_}
 
+    # ---- the 3-D edge model of a graph3d (include/eg3d/edges.h, K17) ----
+    def _edge_chains(self, call, what, max_dist, simplify, to_host):
+        ch, dv, st = D.EdgeChains(), D.DeviceEdgeChains(), D.EdgesStats()
+        st.struct_size = C.sizeof(D.EdgesStats)
+        _check(call(float(max_dist), 1 if simplify else 0, C.byref(dv), C.byref(ch) if to_host else None, C.byref(st)), what)
+        if not to_host:
+            return {"device": dv, "stats": D.edge_chains_to_dict(D.EdgeChains(), st)["stats"]}
+        d = D.edge_chains_to_dict(ch, st)
+        lib().eg3d_free_edge_chains(C.byref(ch))
+        d["device"] = dv
+        return d
+
+    def edge_chains_device(self, graph=None, max_dist=0.01, simplify=True, to_host=True):
+        """eg3d_edge_chains_device on `graph` (a DeviceGraph3D on this context's device; None = the result of this context's
+        last replay_device): the graph's polylines traced into maximal chains, simplified with the reference's
+        simplify_polyline at tolerance max_dist (scene units) and measured, on the device. Returns a dict of numpy arrays —
+        chain_off, chain_node, flags, s_off, s_node, length — with "stats" and "device" (the DeviceEdgeChains, buffers of
+        this context valid until its next edge-chains call); to_host=False leaves the arrays out."""
+        L = lib()
+        return self._edge_chains(lambda *a: L.eg3d_edge_chains_device(self._h, C.byref(graph) if graph is not None else None, *a),
+                                 "eg3d_edge_chains_device", max_dist, simplify, to_host)
+
+    def edge_chains(self, graph, max_dist=0.01, simplify=True, to_host=True):
+        """eg3d_edge_chains: the same on a host graph (a dict as replay_device or host.replay_matches return it; only n_nodes,
+        n_polylines, node_X, pl_start, pl_end, conn_off and conn_pl are read), uploaded for the call."""
+        ga, L = D.EdgesGraphArrays(graph), lib()
+        return self._edge_chains(lambda *a: L.eg3d_edge_chains(self._h, C.byref(ga.c), *a), "eg3d_edge_chains", max_dist, simplify,
+                                 to_host)
+
     def fetch_device_graph(self, dv):
         """Test/bench plumbing: the graph a DeviceGraph3D views (HBM), copied into the dict graph3d_to_dict gives."""
         def fetch(ptr, n, dtype):

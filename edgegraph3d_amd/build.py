@@ -255,6 +255,10 @@ RESOURCE_BOUNDS = {
     # the transform of a cloud's points (eg3d_transform_device, eg3d_transform_points): one kernel, the matrix in scalar
     # registers, the lanes' exchange through cross-lane reads — no spilled register, no scratch, no LDS
     "k16_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    # the 3-D edge model (eg3d_edge_chains_device, eg3d_edge_chains): no spilled register and no scratch in any of them (a
+    # substring: checks, trace, simplify, compact, length); LDS only in k17_simplify — the staged vertices of one chain,
+    # K17_LDS_VERTICES (1024) x 12 B, as the build reports it
+    "k17_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 12288},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},

@@ -25,6 +25,7 @@
 #include "eg3d_k14_triangulate.h"
 #include "eg3d_k15_colour.h"
 #include "eg3d_k16_transform.h"
+#include "eg3d_k17_edges.h"
 
 // (hidden: what the drivers share is not part of the library's dynamic symbol table)
 #define EG3D_API_BEGIN namespace eg3d { namespace api __attribute__((visibility("hidden"))) {
@@ -223,6 +224,15 @@ enum K11Buf { K11B_OFF0, K11B_OFF1, K11B_NBR0, K11B_NBR1, K11B_EROW0, K11B_EROW1
               K11B_A0, K11B_A1, K11B_SIZE0, K11B_SIZE1, K11B_MEMBER, K11B_MINM, K11B_FLAG, K11B_RANK, K11B_CN, K11B_OVF, K11B_OCNT,
               K11B_OOFF, K11B_KEY0, K11B_KEY1, K11B_VAL0, K11B_VAL1, K11B_IDS, K11B_CTR, K11B_COUNT };
 
+// the device buffers of eg3d_edge_chains_device / eg3d_edge_chains (eg3d_ctx::k17). Work: the counters, the claimed
+// (polyline, end) flags, the degrees, the successors, the cut nodes, the two buffers of the pointer jumping (five arrays
+// each: K17State), the chain heads and their scan, the chain sizes, the simplification's regions and counts. U*: the host
+// graph of eg3d_edge_chains. Result (valid until the next call of either entry point): CHAINOFF .. LENGTH.
+enum K17Buf { K17B_CTR, K17B_SEEN, K17B_DEG, K17B_SUCC, K17B_CUT, K17B_STATE0, K17B_STATE1 = K17B_STATE0 + 5, K17B_HEADFLAG = K17B_STATE1 + 5,
+              K17B_CHAINID, K17B_HEADOF, K17B_CHAINOFHEAD, K17B_NVTX, K17B_REGION, K17B_NF, K17B_NB, K17B_NKEPT, K17B_UX, K17B_UPS,
+              K17B_UPE, K17B_UCOFF, K17B_UCPL, K17B_CHAINOFF, K17B_CHAINNODE, K17B_CHAINFLAGS, K17B_SOFF, K17B_SNODE, K17B_LENGTH,
+              K17B_COUNT };
+
 // What the scene fixes, as plain values and device addresses (no ownership). Scene holds the original; every context
 // carries a copy (share_scene), so that the drivers read c->V, c->ds, ... without a second indirection.
 struct SceneFacts {
@@ -407,6 +417,11 @@ struct eg3d_ctx : SceneFacts {
   // include/eg3d_transform.h (K16). k16_ctr: the two counts; k16_X: the caller's points of eg3d_transform_points, transformed
   // in place (the device entry point works in the caller's own arrays).
   DevBuf k16_ctr, k16_X;
+  // include/eg3d/edges.h (K17): K17Buf names the buffers. g_last: the view eg3d_replay_device last handed out (g_valid: there
+  // is one), which eg3d_edge_chains_device reads when it is given no graph.
+  DevBuf k17[K17B_COUNT];
+  bool g_valid = false;
+  eg3d_device_graph3d g_last{};
   DevBuf b_fscratch, b_queue, b_items;  // K3a following: per-lane staging lists, work-queue heads, the lists to follow
   // K3b: working slices of the resident chains (b_cscratch: 8 XCDs x slots_per_xcd slices), the slot pools,
   // and the staging area finished chains are packed into (sized from the previous launches; grow-only)

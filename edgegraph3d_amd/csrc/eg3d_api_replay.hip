@@ -73,6 +73,7 @@ extern "C" int eg3d_replay_device(eg3d_ctx* c, const eg3d_device_edgepoints* clo
   uint64_t n_nodes = 0, n_pl = 0, n_conn = 0, n_iv = 0, slots = 0;
   float ms_graph = 0, ms_iv = 0, ms_copy = 0;
   K8Graph g{};
+  c->g_valid = false;  // (the result buffers are rewritten from here on; set again with the new view at the end)
   BUF_TRY(c->g_ivoff.ensure(8 * (NP + 1)));
   g.iv_off = c->g_ivoff.as<unsigned long long>();
   if (!n_pairs) {  // an empty cloud, or one-point chains only: the all-zero graph
@@ -192,21 +193,24 @@ extern "C" int eg3d_replay_device(eg3d_ctx* c, const eg3d_device_edgepoints* clo
   } else {
     HIP_TRY(hipStreamSynchronize(st));
   }
-  if (out_dev) {
-    out_dev->n_nodes = out_dev->n_real_nodes = n_nodes;
-    out_dev->n_polylines = n_pl;
-    out_dev->n_scene_polylines = NP;
-    out_dev->node_X = g.node_X;
-    out_dev->node_point = (const uint64_t*)g.node_point;
-    out_dev->pl_start = g.pl_start;
-    out_dev->pl_end = g.pl_end;
-    out_dev->conn_off = (const uint64_t*)g.conn_off;
-    out_dev->conn_pl = g.conn_pl;
-    out_dev->iv_off = (const uint64_t*)g.iv_off;
-    out_dev->iv_start_seg = g.iv_start_seg;
-    out_dev->iv_start_xy = g.iv_start_xy;
-    out_dev->iv_end_seg = g.iv_end_seg;
-    out_dev->iv_end_xy = g.iv_end_xy;
+  {  // the view of the result: the caller's, and the context's own for eg3d_edge_chains_device(graph == NULL)
+    eg3d_device_graph3d& v = c->g_last;
+    v.n_nodes = v.n_real_nodes = n_nodes;
+    v.n_polylines = n_pl;
+    v.n_scene_polylines = NP;
+    v.node_X = g.node_X;
+    v.node_point = (const uint64_t*)g.node_point;
+    v.pl_start = g.pl_start;
+    v.pl_end = g.pl_end;
+    v.conn_off = (const uint64_t*)g.conn_off;
+    v.conn_pl = g.conn_pl;
+    v.iv_off = (const uint64_t*)g.iv_off;
+    v.iv_start_seg = g.iv_start_seg;
+    v.iv_start_xy = g.iv_start_xy;
+    v.iv_end_seg = g.iv_end_seg;
+    v.iv_end_xy = g.iv_end_xy;
+    c->g_valid = true;
+    if (out_dev) *out_dev = v;
   }
   if (stats) {
     stats->struct_size = (uint32_t)sizeof(eg3d_replay_stats);

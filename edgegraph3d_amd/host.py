@@ -416,6 +416,35 @@ def write_ply(path, X, rgb=None, keep=None):
         raise OSError("eg3d_host_write_ply failed (rc=%d): %s" % (rc, path))
 
 
+def edge_chains(graph, max_dist, simplify=True):
+    """eg3d_host_edge_chains (include/eg3d/host_edges.h): the sequential statement of the 3-D edge model. `graph`: a dict as
+    replay_matches returns it (only its geometric half is read). Returns a dict of numpy arrays: chain_off, chain_node,
+    flags, s_off, s_node, length, stats. Raises ValueError when the graph or max_dist is refused; .code holds the C code."""
+    ga = D.EdgesGraphArrays(graph)
+    ch, st = D.EdgeChains(), D.EdgesStats()
+    st.struct_size = C.sizeof(D.EdgesStats)
+    rc = lib().eg3d_host_edge_chains(C.byref(ga.c), float(max_dist), 1 if simplify else 0, C.byref(ch), C.byref(st))
+    if rc != 0:
+        err = ValueError("eg3d_host_edge_chains refused its input (%d)" % rc)
+        err.code = rc
+        raise err
+    d = D.edge_chains_to_dict(ch, st)
+    lib().eg3d_host_free_edge_chains(C.byref(ch))
+    return d
+
+
+def write_ply_edges(path, chains, node_X):
+    """eg3d_host_write_ply_edges: the kept vertices of `chains` (a dict as edge_chains returns it) as an ASCII PLY line model
+    with `element vertex` and `element edge`. node_X [n_nodes, 3]: the positions the chains' node ids index."""
+    ca = D.EdgeChainsArrays(chains)
+    X = np.ascontiguousarray(node_X, np.float32).reshape(-1, 3)
+    if len(ca.a["s_node"]) and int(ca.a["s_node"].max()) >= len(X):
+        raise ValueError("write_ply_edges: a node id lies outside node_X")
+    rc = lib().eg3d_host_write_ply_edges(os.fsencode(path), C.byref(ca.c), D.np_ptr(X, C.c_float) if len(X) else None)
+    if rc != 0:
+        raise OSError("eg3d_host_write_ply_edges failed (rc=%d): %s" % (rc, path))
+
+
 def read_png_rgb(path):
     """eg3d_host_png_read_rgb: a non-interlaced PNG of any colour type and bit depth as an [H, W, 3] uint8 RGB array."""
     w, h, p = C.c_int(0), C.c_int(0), D.u8p()

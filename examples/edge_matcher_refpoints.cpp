@@ -43,6 +43,13 @@
 //                                                 on the final cloud — a similarity fitted to the target camera centres, one
 //                                                 "x y z" per camera; the cameras on the host, the points through
 //                                                 eg3d_transform_points. The PLY file is then in the target frame)
+//                          [--edges FILE [--edges-tol T]]   (the 3-D edge model of pipeline 3's cloud as an ASCII PLY line file that
+//                                                 MeshLab or CloudCompare opens: the reference points matched once more, device
+//                                                 only, on the run's context; the cloud replayed into the 3-D polyline graph
+//                                                 there (eg3d_replay_device); the graph traced into chains, simplified with
+//                                                 tolerance T in scene units (default 0.01, the reference's 3-D constant) and
+//                                                 measured there (eg3d_edge_chains_device, K17); eg3d_host_write_ply_edges. With
+//                                                 --align the vertices are those of the aligned cloud)
 //                          [--ply FILE [--ply-images DIR/]]   (after the JSON: the final cloud as the reference's json_to_ply
 //                                                 writes it, eg3d_host_write_ply — white, or with --ply-images coloured on the
 //                                                 device from DIR/ + the base name of every view's path, PNG only. The final
@@ -70,6 +77,7 @@
 #include "eg3d_host_colour.h"
 #include "eg3d_host_transform.h"
 #include "eg3d_transform.h"
+#include "eg3d/edges.h"
 
 static int fail(const char* what) {
   std::fprintf(stderr, "edge_matcher_refpoints: %s (%s)\n", what, eg3d_last_error());
@@ -535,6 +543,41 @@ int main(int argc, char** argv) {
   }
   if (!refpoints_first && run_pipeline3() != 0) return 1;
   eg3d_host_free_graph3d(&held_host);
+
+  // ---- --edges: replay -> K17 on the run's context, while the reference points are still the SfM data's only points. The
+  // model and the positions of the graph's nodes are kept; the file is written after --align, in the frame that gives.
+  const char* edges_path = nullptr;
+  float edges_tol = 0.01f;
+  for (int a = 4; a + 1 < argc; a++) {
+    if (std::strcmp(argv[a], "--edges") == 0) edges_path = argv[a + 1];
+    if (std::strcmp(argv[a], "--edges-tol") == 0) edges_tol = (float)std::atof(argv[a + 1]);
+  }
+  eg3d_edge_chain_set edge_model;
+  std::memset(&edge_model, 0, sizeof(edge_model));
+  std::vector<float> edge_node_X;
+  if (edges_path) {
+    eg3d_edgepoints none;
+    if (eg3d_match_refpoints(ctx, &seeds, 0, seeds.n_seeds, 1, &none, &tm) != EG3D_OK) return fail("eg3d_match_refpoints (--edges)");
+    eg3d_free_edgepoints(&none);
+    eg3d_graph3d g3;
+    if (eg3d_replay_device(ctx, nullptr, nullptr, &g3, nullptr) != EG3D_OK) return fail("eg3d_replay_device (--edges)");
+    edge_node_X.assign(g3.node_X, g3.node_X + 3 * g3.n_nodes);
+    const unsigned long long n_nodes = g3.n_nodes, n_pl = g3.n_polylines;
+    eg3d_free_graph3d(&g3);
+    eg3d_edges_stats es;
+    std::memset(&es, 0, sizeof(es));
+    es.struct_size = (uint32_t)sizeof(es);
+    if (eg3d_edge_chains_device(ctx, nullptr, edges_tol, 1, nullptr, &edge_model, &es) != EG3D_OK) {
+      std::fprintf(stderr, "edge_matcher_refpoints: %s\n", eg3d_last_error());
+      return fail("eg3d_edge_chains_device (--edges)");
+    }
+    std::printf("edge model: %llu nodes, %llu polylines -> %llu chains (%llu rings, %llu loops dropped), longest %llu vertices; %llu "
+                "vertices -> %llu kept at tolerance %g (trace %.3f ms, simplify %.3f ms, copy %.3f ms)\n", n_nodes, n_pl,
+                (unsigned long long)es.n_chains, (unsigned long long)es.n_rings, (unsigned long long)es.n_loops_dropped,
+                (unsigned long long)es.longest_chain, (unsigned long long)es.n_vertices_in, (unsigned long long)es.n_vertices_kept,
+                edges_tol, es.ms_trace, es.ms_simplify, es.ms_copy);
+    lap("3-D edge model (match, replay and K17 on the GPU)");
+  }
   eg3d_edgepoints pts = all_stages.view_as_edgepoints();
 
   // ---- filter_3d_points_close_2d_array + add_3dpoints_to_sfmd (pipelines.cpp:236-239; edge_matcher.cpp:150-158)
@@ -581,6 +624,7 @@ int main(int argc, char** argv) {
   // is the SfM data on the host; a cloud that stays resident takes eg3d_transform_device). The JSON above is written in
   // the reconstruction's own frame; what follows — the PLY file — is in the target frame.
   const char* align_path = nullptr;
+  std::vector<double> align_T;  // (kept for --edges)
   for (int a = 4; a + 1 < argc; a++)
     if (std::strcmp(argv[a], "--align") == 0) align_path = argv[a + 1];
   if (align_path) {
@@ -600,6 +644,7 @@ int main(int argc, char** argv) {
       eg3d_host_camera_errors(V, c32.data(), null_mask.data(), target.data(), &e);
       return e;
     };
+    align_T = T;
     const float before = error();
     const uint64_t n = eg3d_sfm_n_points(sfm);
     std::vector<float> Xa(3 * (size_t)n);
@@ -612,6 +657,18 @@ int main(int argc, char** argv) {
                 fit.scale, fit.reflection ? " (mirrored target)" : "", before, error(), (unsigned long long)ts.n_transformed,
                 (unsigned long long)ts.n_nonfinite);
     lap("align to the target camera centres (fit on the host, points on the GPU)");
+  }
+
+  // ---- --edges: the line model, its vertices in the aligned frame when there is one (a node's position is its point's)
+  if (edges_path) {
+    if (!align_T.empty() && !edge_node_X.empty() &&
+        eg3d_transform_points(ctx, align_T.data(), edge_node_X.data(), edge_node_X.size() / 3, edge_node_X.data(), nullptr) != EG3D_OK)
+      return fail("eg3d_transform_points (--edges)");
+    if (eg3d_host_write_ply_edges(edges_path, &edge_model, edge_node_X.data()) != 0) return fail("writing the PLY edge file");
+    std::printf("wrote %s (%llu chains, %llu vertices kept%s)\n", edges_path, (unsigned long long)edge_model.n_chains,
+                (unsigned long long)edge_model.n_kept, align_T.empty() ? "" : ", aligned");
+    eg3d_free_edge_chains(&edge_model);
+    lap("write the PLY edge file");
   }
 
   // ---- json_to_ply (src/utils/json_to_ply.cpp) on the final cloud
