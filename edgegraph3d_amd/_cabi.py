@@ -284,6 +284,34 @@ EXT_HEADERS = {
 }
 
 
+# include/eg3d/nearest.hpp (libeg3d.so, libeg3d_dlt4x4.so): a uniform-grid index over a point set and the nearest distances
+# of a second point set against it, K18; the index handle (eg3d_cloud_index*) is a void pointer here
+NEAREST = {
+    "eg3d_cloud_index_build": (i32, [vp, f32p, u64, u8p, f32, P(vp), P(D.CloudIndexStats)]),
+    "eg3d_cloud_index_build_device": (i32, [vp, P(D.DeviceEdgePoints), vp, f32, P(vp), P(D.CloudIndexStats)]),
+    "eg3d_cloud_index_free": (None, [vp]),
+    "eg3d_cloud_nearest_device": (i32, [vp, P(D.DeviceEdgePoints), vp, vp, f32, vp, vp, P(D.NearestStats)]),
+    "eg3d_cloud_nearest_points": (i32, [vp, f32p, u64, u8p, vp, f32, f32p, u32p, P(D.NearestStats)]),
+}
+
+# include/eg3d/host_nearest.hpp (libeg3d_host.so): its sequential statement and the PLY point reader
+HOST_NEAREST = {
+    "eg3d_host_nearest_last_error": (cstr, []),
+    "eg3d_host_cloud_nearest": (i32, [f32p, u64, u8p, f32p, u64, u8p, f32, f32, f32p, u32p, P(D.NearestStats)]),
+    "eg3d_host_cloud_index_stats": (i32, [f32p, u64, u8p, f32, P(D.CloudIndexStats)]),
+    "eg3d_host_read_ply_points": (i32, [cstr, P(f32p), u64p]),
+    "eg3d_host_free_points": (None, [f32p]),
+}
+
+# The .hpp ABI headers (C text under another suffix: the two tests above pin the set of .h files), as HEADERS: header ->
+# (library, table). bind_library declares these as well; tests/test_abi_nearest.py holds them to their headers, mirrors
+# (_cdefs.MIRRORS_HPP) and exports.
+HPP_HEADERS = {
+    "eg3d/nearest.hpp": ("eg3d", NEAREST),
+    "eg3d/host_nearest.hpp": ("host", HOST_NEAREST),
+}
+
+
 def bind(lib, table):
     """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""
     for name, (restype, argtypes) in table.items():
@@ -293,8 +321,9 @@ def bind(lib, table):
 
 
 def bind_library(lib, library):
-    """Declare on the CDLL `lib` every table HEADERS and EXT_HEADERS give to `library` ("eg3d", "host" or "rccl"). Returns `lib`."""
-    for owner, table in list(HEADERS.values()) + list(EXT_HEADERS.values()):
+    """Declare on the CDLL `lib` every table HEADERS, EXT_HEADERS and HPP_HEADERS give to `library` ("eg3d", "host" or "rccl").
+    Returns `lib`."""
+    for owner, table in list(HEADERS.values()) + list(EXT_HEADERS.values()) + list(HPP_HEADERS.values()):
         if owner == library:
             bind(lib, table)
     return lib

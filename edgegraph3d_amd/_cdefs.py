@@ -90,6 +90,57 @@ class EdgesStats(C.Structure):
                 ("reserved2", C.c_float)]
 
 
+class CloudIndexStats(C.Structure):
+    """eg3d_cloud_index_stats (include/eg3d/host_nearest.hpp): struct_size is set to the size of this mirror by its user."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_points", C.c_uint64), ("n_dropped", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("n_indexed", C.c_uint64), ("n_cells", C.c_uint64), ("max_cell_points", C.c_uint64),
+                ("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_uint32 * 3), ("reserved2", C.c_uint32),
+                ("ms_build", C.c_float), ("ms_copy", C.c_float)]
+
+
+class NearestStats(C.Structure):
+    """eg3d_nearest_stats (include/eg3d/host_nearest.hpp): the thresholds in, the figures out."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_thresholds", C.c_uint32), ("thresholds", C.c_float * 8), ("n_queries", C.c_uint64),
+                ("n_dropped", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_within", C.c_uint64), ("n_below", C.c_uint64 * 8),
+                ("sum_q32", C.c_uint64), ("min_d2", C.c_float), ("max_d2", C.c_float), ("median_d2", C.c_float),
+                ("ms_kernel", C.c_float), ("ms_copy", C.c_float), ("reserved", C.c_float)]
+
+
+def cloud_index_stats_to_dict(st):
+    """The figures of a CloudIndexStats: counts as ints, origin float32 [3], dims [3] ints, cell, the times."""
+    d = {f: int(getattr(st, f)) for f in ("n_points", "n_dropped", "n_nonfinite", "n_indexed", "n_cells", "max_cell_points")}
+    d.update(origin=np.array(st.origin[:], np.float32), dims=[int(v) for v in st.dims[:]], cell=np.float32(st.cell),
+             ms_build=st.ms_build, ms_copy=st.ms_copy)
+    return d
+
+
+def nearest_stats_new(thresholds=()):
+    """A NearestStats that carries `thresholds` in (as float32). Of more than 8 only the count travels, which the library
+    refuses."""
+    t = np.asarray(thresholds, np.float32).reshape(-1)
+    st = NearestStats(struct_size=C.sizeof(NearestStats), n_thresholds=len(t))
+    for k in range(min(len(t), 8)):
+        st.thresholds[k] = float(t[k])
+    return st
+
+
+def nearest_stats_to_dict(st, max_dist):
+    """The figures of a NearestStats: the counts and sum_q32 as ints, n_below for the thresholds given, min_d2 / max_d2 /
+    median_d2 as float32, and — distances — mean (FP64, sum_q32 * max_dist / 2^32 / n_within) and median (sqrt of
+    median_d2 in FP64); both nan for an empty within set."""
+    nt = min(int(st.n_thresholds), 8)
+    d = {f: int(getattr(st, f)) for f in ("n_queries", "n_dropped", "n_nonfinite", "n_within", "sum_q32")}
+    d["n_below"] = [int(v) for v in st.n_below[:nt]]
+    d["thresholds"] = np.array(st.thresholds[:nt], np.float32)
+    for f in ("min_d2", "max_d2", "median_d2"):
+        d[f] = np.float32(getattr(st, f))
+    w = d["n_within"]
+    d["mean"] = d["sum_q32"] * float(np.float32(max_dist)) / 4294967296.0 / w if w else float("nan")
+    d["median"] = float(np.sqrt(np.float64(d["median_d2"]))) if w else float("nan")
+    d["ms_kernel"], d["ms_copy"] = st.ms_kernel, st.ms_copy
+    return d
+
+
 def edge_chains_to_dict(c, stats=None):
     """The arrays of an EdgeChains as numpy copies: chain_off, chain_node, flags, s_off, s_node, length (+ stats)."""
     n = int(c.n_chains)
@@ -569,4 +620,8 @@ MIRRORS = {
 MIRRORS_EXT = {
     "eg3d/edges.h": {"eg3d_device_edge_chains": DeviceEdgeChains},
     "eg3d/host_edges.h": {"eg3d_edge_chain_set": EdgeChains, "eg3d_edges_stats": EdgesStats},
+}
+# ... and for the .hpp ABI headers (_cabi.HPP_HEADERS); tests/test_abi_nearest.py holds these
+MIRRORS_HPP = {
+    "eg3d/host_nearest.hpp": {"eg3d_cloud_index_stats": CloudIndexStats, "eg3d_nearest_stats": NearestStats},
 }

@@ -52,7 +52,9 @@ ERR_TRANSFORM_NONFINITE, ERR_TRANSFORM_OVERLAP = -16, -17
 
 def _check(rc, what):
     if rc != 0:
-        raise Eg3dError("%s failed (rc=%d): %s" % (what, rc, lib().eg3d_last_error().decode()))
+        err = Eg3dError("%s failed (rc=%d): %s" % (what, rc, lib().eg3d_last_error().decode()))
+        err.code = rc   # (the C code: EG3D_ERR_*, and the codes of the later headers)
+        raise err
 
 
 def check_polyline_sets(n_sets, row_off, pl_ids, n_views):
@@ -148,6 +150,49 @@ def _dev_ptr(x):
     if x is None:
         return None
     return C.c_void_p(x.ptr if isinstance(x, DeviceArray) else int(x))
+
+
+def points_cloud(X_dev, n_points):
+    """A DeviceEdgePoints that views a bare [n_points, 3] float32 array on the device (a DeviceArray or a device address) as a
+    whole cloud without observations: what the entry points of include/eg3d/nearest.hpp, which read only X, take
+    (cloud_index, nearest_device). Keep the DeviceArray alive for as long as the view is used."""
+    if isinstance(X_dev, DeviceArray) and X_dev.nbytes < 12 * int(n_points):
+        raise ValueError("points_cloud: the array holds %d bytes, %d points need %d" % (X_dev.nbytes, n_points, 12 * int(n_points)))
+    return D.DeviceEdgePoints(n_points=int(n_points), n_obs=0, X=_dev_ptr(X_dev), complete=1)
+
+
+class CloudIndex:
+    """A uniform-grid index over a reference point set on the device (include/eg3d/nearest.hpp), made by
+    Context.cloud_index. `stats`: the figures of the build (n_indexed, n_cells, origin, dims, max_cell_points, ...). It
+    holds device memory and works on its context's stream: close() it — or use it as a context manager — before the
+    context is closed; it keeps the context alive until then."""
+
+    def __init__(self, ctx, handle, stats):
+        self._ctx, self._h, self.stats = ctx, handle, stats
+        self.n_indexed, self.n_cells, self.cell = stats["n_indexed"], stats["n_cells"], stats["cell"]
+
+    def close(self):
+        if self._h:
+            lib().eg3d_cloud_index_free(self._h)
+            self._h, self._ctx = C.c_void_p(), None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# include/eg3d/host_nearest.hpp
+NEAREST_NONE = 0xFFFFFFFF
+ERR_NEAREST_CELL, ERR_NEAREST_MAXDIST, ERR_NEAREST_THRESHOLD, ERR_NEAREST_EXTENT, ERR_NEAREST_FOREIGN = -18, -19, -20, -21, -22
 
 
 class Context:
@@ -882,6 +927,82 @@ class Context:
         ga, L = D.EdgesGraphArrays(graph), lib()
         return self._edge_chains(lambda *a: L.eg3d_edge_chains(self._h, C.byref(ga.c), *a), "eg3d_edge_chains", max_dist, simplify,
                                  to_host)
+
+    # ---- cloud-to-cloud nearest distances (include/eg3d/nearest.hpp, K18) ----
+    def cloud_index(self, X=None, cloud=None, keep=None, cell=None):
+        """A CloudIndex over a reference point set: X, a host array [n, 3] (eg3d_cloud_index_build; keep: a host array [n]
+        or None), or — X is None — `cloud`, a DeviceEdgePoints on this context's device, None = this context's last device
+        output (eg3d_cloud_index_build_device; keep: DeviceArray or device address of [n] uint8, or None). cell: the grid's
+        edge, the largest max_dist a query may ask for. Free the index (close(), or `with`) before the context is closed."""
+        if cell is None:
+            raise ValueError("cloud_index: cell is required")
+        h, st = C.c_void_p(), D.CloudIndexStats(struct_size=C.sizeof(D.CloudIndexStats))
+        if X is not None:
+            if cloud is not None:
+                raise ValueError("cloud_index: X or cloud, not both")
+            X = np.ascontiguousarray(X, np.float32).reshape(-1, 3)
+            k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
+            if k is not None and len(k) != len(X):
+                raise ValueError("cloud_index: X and keep differ in length")
+            _check(lib().eg3d_cloud_index_build(self._h, D.np_ptr(X, C.c_float) if len(X) else None, len(X),
+                                                D.np_ptr(k, C.c_uint8) if k is not None and len(X) else None, float(cell),
+                                                C.byref(h), C.byref(st)), "eg3d_cloud_index_build")
+        else:
+            n = int((cloud if cloud is not None else self.last_device_output()).n_points)
+            if isinstance(keep, DeviceArray) and keep.nbytes != n:
+                raise ValueError("cloud_index: keep holds %d bytes, the cloud %d points" % (keep.nbytes, n))
+            _check(lib().eg3d_cloud_index_build_device(self._h, C.byref(cloud) if cloud is not None else None, _dev_ptr(keep),
+                                                       float(cell), C.byref(h), C.byref(st)), "eg3d_cloud_index_build_device")
+        return CloudIndex(self, h, D.cloud_index_stats_to_dict(st))
+
+    def nearest_device(self, index, max_dist, cloud=None, keep=None, thresholds=(), to_host=True, d2=None, nn=None):
+        """eg3d_cloud_nearest_device: every point of `cloud` (None = this context's last device output) against `index`.
+        keep, d2 ([n] float32), nn ([n] uint32): DeviceArray or device address; d2 and nn are allocated when not given. A
+        DeviceArray of another size than the cloud's is refused here with ValueError. Returns a dict: "d2_dev", "nn_dev"
+        (the device arrays), "stats" (the figures, with mean and median as distances) and, with to_host, "d2" and "nn" as
+        numpy arrays."""
+        n = int((cloud if cloud is not None else self.last_device_output()).n_points)
+        for name, a, size in (("keep", keep, n), ("d2", d2, 4 * n), ("nn", nn, 4 * n)):
+            if isinstance(a, DeviceArray) and a.nbytes != size:
+                raise ValueError("nearest_device: %s holds %d bytes, the cloud needs %d" % (name, a.nbytes, size))
+        d2 = d2 if d2 is not None else DeviceArray(4 * n, self.device)
+        nn = nn if nn is not None else DeviceArray(4 * n, self.device)
+        st = D.nearest_stats_new(thresholds)
+        _check(lib().eg3d_cloud_nearest_device(self._h, C.byref(cloud) if cloud is not None else None, _dev_ptr(keep), index._h,
+                                               float(max_dist), _dev_ptr(d2), _dev_ptr(nn), C.byref(st)), "eg3d_cloud_nearest_device")
+        out = {"d2_dev": d2, "nn_dev": nn, "stats": D.nearest_stats_to_dict(st, max_dist)}
+        if to_host:
+            if not (isinstance(d2, DeviceArray) and isinstance(nn, DeviceArray)):
+                raise ValueError("nearest_device: to_host needs d2 and nn as DeviceArray")
+            out["d2"], out["nn"] = d2.numpy(np.float32), nn.numpy(np.uint32)
+        return out
+
+    def nearest_points(self, index, X, max_dist, keep=None, thresholds=()):
+        """eg3d_cloud_nearest_points: the host array X [n, 3] against `index`. Returns (d2 [n] float32, nn [n] uint32, stats
+        dict) — bit for bit what host.cloud_nearest returns."""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1, 3)
+        k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
+        if k is not None and len(k) != len(X):
+            raise ValueError("nearest_points: X and keep differ in length")
+        n = len(X)
+        d2, nn = np.empty(n, np.float32), np.empty(n, np.uint32)
+        st = D.nearest_stats_new(thresholds)
+        _check(lib().eg3d_cloud_nearest_points(self._h, D.np_ptr(X, C.c_float) if n else None, n,
+                                               D.np_ptr(k, C.c_uint8) if k is not None and n else None, index._h, float(max_dist),
+                                               D.np_ptr(d2, C.c_float) if n else None, D.np_ptr(nn, C.c_uint32) if n else None,
+                                               C.byref(st)), "eg3d_cloud_nearest_points")
+        return d2, nn, D.nearest_stats_to_dict(st, max_dist)
+
+    def compare_clouds(self, ref_X, max_dist, thresholds=(), cloud=None, keep=None, ref_keep=None):
+        """Both directions of a comparison of a resident cloud (None = the last device output; keep: device mask) with the
+        host array ref_X [m, 3] (ref_keep: host mask), the cell being max_dist: {"accuracy": the cloud's points against an
+        index over ref_X, "completeness": ref_X against an index over the cloud}, each a figures dict with `mean` and
+        `median` as distances — what host.compare_clouds gives on the fetched cloud."""
+        with self.cloud_index(X=ref_X, keep=ref_keep, cell=max_dist) as ref_index:
+            acc = self.nearest_device(ref_index, max_dist, cloud=cloud, keep=keep, thresholds=thresholds, to_host=False)["stats"]
+        with self.cloud_index(cloud=cloud, keep=keep, cell=max_dist) as own_index:
+            comp = self.nearest_points(own_index, ref_X, max_dist, keep=ref_keep, thresholds=thresholds)[2]
+        return {"accuracy": acc, "completeness": comp}
 
     def fetch_device_graph(self, dv):
         """Test/bench plumbing: the graph a DeviceGraph3D views (HBM), copied into the dict graph3d_to_dict gives."""

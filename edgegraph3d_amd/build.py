@@ -57,7 +57,7 @@ def _run(cmd):
 
 def build_host(force=False):
     srcs = _all_sources(HOST_DIR, (".cpp",))
-    deps = (srcs + _all_sources(HOST_DIR, (".hpp", ".h")) + _all_sources(INC_DIR, (".h",)) + _all_sources(CSRC_DIR, (".h", ".hpp"))
+    deps = (srcs + _all_sources(HOST_DIR, (".hpp", ".h")) + _all_sources(INC_DIR, (".h", ".hpp")) + _all_sources(CSRC_DIR, (".h", ".hpp"))
             + _all_sources(os.path.join(PKG, "rccl"), (".h",)))
     if force or _newer(HOST_LIB, deps):
         _run(["g++"] + HOST_FLAGS + ["-I", INC_DIR, "-I", CSRC_DIR, "-o", HOST_LIB] + srcs + ["-lz"])  # libz: PNG inflate
@@ -89,7 +89,7 @@ def build_hip(force=False, out=None, defines=()):
     out = out or HIP_LIB
     srcs = _all_sources(CSRC_DIR, (".hip",))
     host_srcs = [os.path.join(HOST_DIR, "grid_build.cpp")]
-    deps = srcs + host_srcs + _all_sources(CSRC_DIR, (".h", ".hpp")) + _all_sources(INC_DIR, (".h",)) + [os.path.abspath(__file__)]  # (the flags live here)
+    deps = srcs + host_srcs + _all_sources(CSRC_DIR, (".h", ".hpp")) + _all_sources(INC_DIR, (".h", ".hpp")) + [os.path.abspath(__file__)]  # (the flags live here)
     if not (force or _newer(out, deps)):
         return out
     import concurrent.futures
@@ -259,6 +259,10 @@ RESOURCE_BOUNDS = {
     # substring: checks, trace, simplify, compact, length); LDS only in k17_simplify — the staged vertices of one chain,
     # K17_LDS_VERTICES (1024) x 12 B, as the build reports it
     "k17_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 12288},
+    # cloud-to-cloud nearest distances (eg3d_cloud_index_build*, eg3d_cloud_nearest_*): no spilled register, no scratch and no
+    # LDS in any of them (a substring: init, minmax, keys, gather, cells, max_cell, the three query forms, median) — the
+    # figures travel through cross-lane reads and integer atomics
+    "k18_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},

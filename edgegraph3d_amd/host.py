@@ -445,6 +445,82 @@ def write_ply_edges(path, chains, node_X):
         raise OSError("eg3d_host_write_ply_edges failed (rc=%d): %s" % (rc, path))
 
 
+# ---- include/eg3d/host_nearest.hpp: cloud-to-cloud nearest distances (K18's sequential statement), the PLY point reader ----
+class NearestError(ValueError):
+    """A refusal of include/eg3d/host_nearest.hpp; `code` is its EG3D_NEAREST_ERR_* code, the text the library's."""
+
+    def __init__(self, what, code):
+        ValueError.__init__(self, "%s refused (rc=%d): %s" % (what, code, lib().eg3d_host_nearest_last_error().decode()))
+        self.code = code
+
+
+NEAREST_ERR_ARG, NEAREST_ERR_CAPACITY, NEAREST_ERR_CELL, NEAREST_ERR_MAXDIST = -1, -3, -18, -19
+NEAREST_ERR_THRESHOLD, NEAREST_ERR_EXTENT, NEAREST_ERR_FOREIGN, NEAREST_ERR_FILE, NEAREST_ERR_PLY = -20, -21, -22, -23, -24
+NEAREST_NONE = 0xFFFFFFFF
+
+
+def _points_and_keep(what, X, keep):
+    X = np.ascontiguousarray(X, np.float32).reshape(-1, 3)
+    k = None if keep is None else np.ascontiguousarray(keep, np.uint8).reshape(-1)
+    if k is not None and len(k) != len(X):
+        raise ValueError("%s: the points and their keep mask differ in length" % what)
+    return X, k
+
+
+def _opt_ptr(a, ctype):
+    return D.np_ptr(a, ctype) if a is not None and len(a) else None
+
+
+def cloud_nearest(ref_X, X, max_dist, cell=None, ref_keep=None, keep=None, thresholds=(), d2=None, nn=None):
+    """eg3d_host_cloud_nearest: for every query X[i] the squared distance (float32; +inf = none) to the nearest reference
+    point within max_dist and that point's index (uint32; 0xFFFFFFFF = none). cell: the grid's edge, None = max_dist.
+    d2 / nn: arrays to fill (contiguous, [n] float32 / uint32), allocated when not given. Returns (d2, nn, stats dict as
+    _cdefs.nearest_stats_to_dict gives it). NearestError when the library refuses."""
+    R, rk = _points_and_keep("cloud_nearest", ref_X, ref_keep)
+    Q, qk = _points_and_keep("cloud_nearest", X, keep)
+    d2 = np.empty(len(Q), np.float32) if d2 is None else d2
+    nn = np.empty(len(Q), np.uint32) if nn is None else nn
+    if d2.dtype != np.float32 or nn.dtype != np.uint32 or d2.shape != (len(Q),) or nn.shape != (len(Q),):
+        raise ValueError("cloud_nearest: d2 / nn must be [n] float32 / uint32")
+    st = D.nearest_stats_new(thresholds)
+    rc = lib().eg3d_host_cloud_nearest(_opt_ptr(R, C.c_float), len(R), _opt_ptr(rk, C.c_uint8), _opt_ptr(Q, C.c_float), len(Q),
+                                       _opt_ptr(qk, C.c_uint8), float(max_dist if cell is None else cell), float(max_dist),
+                                       _opt_ptr(d2, C.c_float), _opt_ptr(nn, C.c_uint32), C.byref(st))
+    if rc != 0:
+        raise NearestError("eg3d_host_cloud_nearest", rc)
+    return d2, nn, D.nearest_stats_to_dict(st, max_dist)
+
+
+def cloud_index_stats(ref_X, cell, ref_keep=None):
+    """eg3d_host_cloud_index_stats: what the statement's grid over ref_X looks like (n_indexed, n_cells, origin, dims,
+    max_cell_points, ...) — the figures Context.cloud_index reports."""
+    R, rk = _points_and_keep("cloud_index_stats", ref_X, ref_keep)
+    st = D.CloudIndexStats(struct_size=C.sizeof(D.CloudIndexStats))
+    rc = lib().eg3d_host_cloud_index_stats(_opt_ptr(R, C.c_float), len(R), _opt_ptr(rk, C.c_uint8), float(cell), C.byref(st))
+    if rc != 0:
+        raise NearestError("eg3d_host_cloud_index_stats", rc)
+    return D.cloud_index_stats_to_dict(st)
+
+
+def compare_clouds(X, ref_X, max_dist, thresholds=(), keep=None, ref_keep=None):
+    """Both directions of a comparison on the host: {"accuracy": figures of X against ref_X, "completeness": figures of
+    ref_X against X}, each a stats dict with `mean` and `median` as distances. The cell is max_dist."""
+    return {"accuracy": cloud_nearest(ref_X, X, max_dist, ref_keep=ref_keep, keep=keep, thresholds=thresholds)[2],
+            "completeness": cloud_nearest(X, ref_X, max_dist, ref_keep=keep, keep=ref_keep, thresholds=thresholds)[2]}
+
+
+def read_ply_points(path):
+    """eg3d_host_read_ply_points: the `element vertex` of an ASCII or binary little-endian PLY file as [n, 3] float32.
+    NearestError (code -23: the file cannot be read; -24: the file is refused, the text says why)."""
+    X, n = D.f32p(), C.c_uint64(0)
+    rc = lib().eg3d_host_read_ply_points(os.fsencode(path), C.byref(X), C.byref(n))
+    if rc != 0:
+        raise NearestError("eg3d_host_read_ply_points", rc)
+    out = D.as_np(X, 3 * n.value, np.float32).reshape(-1, 3)
+    lib().eg3d_host_free_points(X)
+    return out
+
+
 def read_png_rgb(path):
     """eg3d_host_png_read_rgb: a non-interlaced PNG of any colour type and bit depth as an [H, W, 3] uint8 RGB array."""
     w, h, p = C.c_int(0), C.c_int(0), D.u8p()

@@ -50,6 +50,11 @@
 //                                                 tolerance T in scene units (default 0.01, the reference's 3-D constant) and
 //                                                 measured there (eg3d_edge_chains_device, K17); eg3d_host_write_ply_edges. With
 //                                                 --align the vertices are those of the aligned cloud)
+//                          [--compare FILE --compare-max-dist D]   (the final cloud — after --align when both are given — against the
+//                                                 reference cloud in FILE, a PLY file or an OpenMVG JSON: accuracy (cloud ->
+//                                                 FILE) and completeness (FILE -> cloud) as mean and median nearest distance
+//                                                 within D, on the run's context: eg3d_cloud_index_build,
+//                                                 eg3d_cloud_nearest_points, K18)
 //                          [--ply FILE [--ply-images DIR/]]   (after the JSON: the final cloud as the reference's json_to_ply
 //                                                 writes it, eg3d_host_write_ply — white, or with --ply-images coloured on the
 //                                                 device from DIR/ + the base name of every view's path, PNG only. The final
@@ -63,6 +68,7 @@
 // edge images (--make-plgs) is separate from the matching run. Build (see tests/test_gpu_edge_cases.py):
 //   g++ -std=c++17 -I include examples/edge_matcher_refpoints.cpp -Ledgegraph3d_amd -leg3d -leg3d_host ...
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -78,6 +84,7 @@
 #include "eg3d_host_transform.h"
 #include "eg3d_transform.h"
 #include "eg3d/edges.h"
+#include "eg3d/nearest.hpp"
 
 static int fail(const char* what) {
   std::fprintf(stderr, "edge_matcher_refpoints: %s (%s)\n", what, eg3d_last_error());
@@ -669,6 +676,56 @@ int main(int argc, char** argv) {
                 (unsigned long long)edge_model.n_kept, align_T.empty() ? "" : ", aligned");
     eg3d_free_edge_chains(&edge_model);
     lap("write the PLY edge file");
+  }
+
+  // ---- --compare: the final cloud against a reference cloud, both directions, on the run's context (K18)
+  const char* compare_path = nullptr;
+  float compare_md = 0.f;
+  for (int a = 4; a + 1 < argc; a++) {
+    if (std::strcmp(argv[a], "--compare") == 0) compare_path = argv[a + 1];
+    if (std::strcmp(argv[a], "--compare-max-dist") == 0) compare_md = (float)std::atof(argv[a + 1]);
+  }
+  if (compare_path) {
+    if (!(compare_md > 0.f)) return fail("--compare needs --compare-max-dist D with D > 0");
+    std::vector<float> ref;
+    const size_t len = std::strlen(compare_path);
+    if (len > 5 && std::strcmp(compare_path + len - 5, ".json") == 0) {
+      eg3d_sfm* other = eg3d_sfm_read_json(compare_path);
+      if (!other) return fail("reading the reference cloud (--compare)");
+      if (eg3d_sfm_n_points(other)) ref.assign(eg3d_sfm_points(other), eg3d_sfm_points(other) + 3 * eg3d_sfm_n_points(other));
+      eg3d_sfm_destroy(other);
+    } else {
+      float* p = nullptr;
+      uint64_t np = 0;
+      if (eg3d_host_read_ply_points(compare_path, &p, &np) != 0) {
+        std::fprintf(stderr, "%s\n", eg3d_host_nearest_last_error());
+        return fail("reading the reference cloud (--compare)");
+      }
+      ref.assign(p, p + 3 * np);
+      eg3d_host_free_points(p);
+    }
+    const uint64_t n = eg3d_sfm_n_points(sfm), m = ref.size() / 3;
+    eg3d_nearest_stats side[2];
+    eg3d_cloud_index* index[2] = {nullptr, nullptr};
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; k++) {  // 0: accuracy (cloud -> reference), 1: completeness (reference -> cloud)
+      std::memset(&side[k], 0, sizeof(side[k]));
+      side[k].struct_size = sizeof(side[k]);
+      const float* R = k == 0 ? ref.data() : eg3d_sfm_points(sfm);
+      const float* Q = k == 0 ? eg3d_sfm_points(sfm) : ref.data();
+      ok = eg3d_cloud_index_build(ctx, R, k == 0 ? m : n, nullptr, compare_md, &index[k], nullptr) == EG3D_OK &&
+           eg3d_cloud_nearest_points(ctx, Q, k == 0 ? n : m, nullptr, index[k], compare_md, nullptr, nullptr, &side[k]) == EG3D_OK;
+    }
+    eg3d_cloud_index_free(index[0]);
+    eg3d_cloud_index_free(index[1]);
+    if (!ok) return fail("eg3d_cloud_nearest_points (--compare)");
+    for (int k = 0; k < 2; k++) {
+      const double w = (double)side[k].n_within;
+      std::printf("compare: %s: %llu points, %llu within %g, mean %.9g, median %.9g\n", k == 0 ? "accuracy" : "completeness",
+                  (unsigned long long)side[k].n_queries, (unsigned long long)side[k].n_within, (double)compare_md,
+                  w ? (double)side[k].sum_q32 * (double)compare_md / 4294967296.0 / w : 0.0, w ? std::sqrt((double)side[k].median_d2) : 0.0);
+    }
+    lap("compare with the reference cloud (K18, both directions)");
   }
 
   // ---- json_to_ply (src/utils/json_to_ply.cpp) on the final cloud
