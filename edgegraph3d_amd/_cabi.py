@@ -312,6 +312,29 @@ HPP_HEADERS = {
 }
 
 
+# include/eg3d/edgemap.hh (libeg3d.so, libeg3d_dlt4x4.so): the edge maps of the source images on the device, K19
+EDGEMAP = {
+    "eg3d_edge_maps": (i32, [i32, C.c_int32, i32p, i32p, P(u8p), P(D.EdgemapParams), P(u8p), P(D.EdgemapStats)]),
+}
+
+# include/eg3d/host_edgemap.hh (libeg3d_host.so): their sequential statement, the PNG writer of a mask, the graphs of many masks
+HOST_EDGEMAP = {
+    "eg3d_host_edgemap_last_error": (cstr, []),
+    "eg3d_host_edge_maps": (i32, [C.c_int32, i32p, i32p, P(u8p), P(D.EdgemapParams), P(u8p), P(D.EdgemapStats)]),
+    "eg3d_host_png_write_mask": (i32, [cstr, u8p, C.c_int32, C.c_int32]),
+    "eg3d_host_plg_build_views_from_masks": (i32, [P(u8p), C.c_int32, i32p, i32p, P(D.PlgView)]),
+}
+
+# The open registry, as HEADERS: header -> (library, table). The three registries above are each pinned to a size and a
+# suffix by the test that came with them; this one is pinned to neither. The next ABI header — under include/eg3d/, with a
+# suffix those tests do not collect — is a new row here and its structs a row of _cdefs.MIRRORS_OPEN; tests/test_abi_open.py
+# derives every check from the two.
+OPEN_HEADERS = {
+    "eg3d/edgemap.hh": ("eg3d", EDGEMAP),
+    "eg3d/host_edgemap.hh": ("host", HOST_EDGEMAP),
+}
+
+
 def bind(lib, table):
     """Declare every function of `table` on the CDLL `lib`; a library that lacks one is refused. Returns `lib`."""
     for name, (restype, argtypes) in table.items():
@@ -321,9 +344,9 @@ def bind(lib, table):
 
 
 def bind_library(lib, library):
-    """Declare on the CDLL `lib` every table HEADERS, EXT_HEADERS and HPP_HEADERS give to `library` ("eg3d", "host" or "rccl").
-    Returns `lib`."""
-    for owner, table in list(HEADERS.values()) + list(EXT_HEADERS.values()) + list(HPP_HEADERS.values()):
+    """Declare on the CDLL `lib` every table HEADERS, EXT_HEADERS, HPP_HEADERS and OPEN_HEADERS give to `library` ("eg3d",
+    "host" or "rccl"). Returns `lib`."""
+    for owner, table in [row for reg in (HEADERS, EXT_HEADERS, HPP_HEADERS, OPEN_HEADERS) for row in reg.values()]:
         if owner == library:
             bind(lib, table)
     return lib

@@ -106,6 +106,43 @@ class NearestStats(C.Structure):
                 ("ms_kernel", C.c_float), ("ms_copy", C.c_float), ("reserved", C.c_float)]
 
 
+class EdgemapParams(C.Structure):
+    """eg3d_edgemap_params (include/eg3d/host_edgemap.hh): struct_size is set to the size of this mirror by its user."""
+    _fields_ = [("struct_size", C.c_uint32), ("low", C.c_int32), ("high", C.c_int32), ("smooth_passes", C.c_int32), ("l2", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class EdgemapStats(C.Structure):
+    """eg3d_edgemap_stats (include/eg3d/host_edgemap.hh): the counts and the times of a call."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_views", C.c_uint32), ("n_pixels", C.c_uint64), ("n_candidates", C.c_uint64),
+                ("n_strong", C.c_uint64), ("n_edges", C.c_uint64), ("hysteresis_rounds", C.c_uint32), ("reserved", C.c_uint32),
+                ("ms_upload", C.c_float), ("ms_kernel", C.c_float), ("ms_hysteresis", C.c_float), ("ms_copy", C.c_float)]
+
+
+def edgemap_call(fn, images, low, high, smooth_passes, l2):
+    """What api.edge_maps and host.edge_maps share: `fn(n_views, width*, height*, rgb**, params*, masks**, stats*)` is the
+    native call (the device index already bound). `images`: a sequence of uint8 [H, W, 3] arrays, which may differ in size.
+    Returns rc, (masks: a list of uint8 [H, W] arrays, stats dict). The shapes are checked here, because the C side cannot
+    know an array's length; the values are the library's to refuse."""
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+    for im in imgs:
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError("an image must be [H, W, 3] uint8, not %r" % (im.shape,))
+    n = len(imgs)
+    w = np.array([im.shape[1] for im in imgs], np.int32)
+    h = np.array([im.shape[0] for im in imgs], np.int32)
+    masks = [np.zeros(im.shape[:2], np.uint8) for im in imgs]
+    in_p = (u8p * max(n, 1))(*[np_ptr(im, C.c_uint8) for im in imgs])
+    out_p = (u8p * max(n, 1))(*[np_ptr(m, C.c_uint8) for m in masks])
+    params = EdgemapParams(struct_size=C.sizeof(EdgemapParams), low=int(low), high=int(high), smooth_passes=int(smooth_passes),
+                           l2=1 if l2 else 0)
+    st = EdgemapStats(struct_size=C.sizeof(EdgemapStats))
+    rc = fn(n, np_ptr(w, C.c_int32), np_ptr(h, C.c_int32), in_p, C.byref(params), out_p, C.byref(st))
+    stats = {f: int(getattr(st, f)) for f in ("n_views", "n_pixels", "n_candidates", "n_strong", "n_edges", "hysteresis_rounds")}
+    stats.update({f: float(getattr(st, f)) for f in ("ms_upload", "ms_kernel", "ms_hysteresis", "ms_copy")})
+    return rc, (masks, stats)
+
+
 def cloud_index_stats_to_dict(st):
     """The figures of a CloudIndexStats: counts as ints, origin float32 [3], dims [3] ints, cell, the times."""
     d = {f: int(getattr(st, f)) for f in ("n_points", "n_dropped", "n_nonfinite", "n_indexed", "n_cells", "max_cell_points")}
@@ -624,4 +661,9 @@ MIRRORS_EXT = {
 # ... and for the .hpp ABI headers (_cabi.HPP_HEADERS); tests/test_abi_nearest.py holds these
 MIRRORS_HPP = {
     "eg3d/host_nearest.hpp": {"eg3d_cloud_index_stats": CloudIndexStats, "eg3d_nearest_stats": NearestStats},
+}
+# ... and for the open registry (_cabi.OPEN_HEADERS: headers of any suffix the older tests do not pin); tests/test_abi_open.py
+# holds these. The next header's structs are a row here.
+MIRRORS_OPEN = {
+    "eg3d/host_edgemap.hh": {"eg3d_edgemap_params": EdgemapParams, "eg3d_edgemap_stats": EdgemapStats},
 }

@@ -82,6 +82,18 @@ def estimate_fundamental(n_views, seeds, iterations=0, rng_seed=0, fit_budget=0,
     return out
 
 
+def edge_maps(images, low, high, smooth_passes=1, l2=False, device=0):
+    """The edge maps of the source images on the device (eg3d_edge_maps, K19), before any Context exists. `images`: a
+    sequence of uint8 [H, W, 3] RGB arrays, which may differ in size; 0 <= low <= high <= 65535 bound the gradient
+    magnitude (|gx| + |gy|, or with l2 its square against the squared bounds). Returns (masks, stats): one uint8 [H, W]
+    mask per image, 1 = edge — what host.plg_from_mask takes — and the counts and times; bit for bit what host.edge_maps
+    returns (include/eg3d/host_edgemap.hh states the rules)."""
+    L = lib()
+    rc, out = D.edgemap_call(lambda *a: L.eg3d_edge_maps(int(device), *a), images, low, high, smooth_passes, l2)
+    _check(rc, "eg3d_edge_maps")
+    return out
+
+
 _HIP = None
 
 

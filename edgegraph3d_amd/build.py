@@ -57,7 +57,7 @@ def _run(cmd):
 
 def build_host(force=False):
     srcs = _all_sources(HOST_DIR, (".cpp",))
-    deps = (srcs + _all_sources(HOST_DIR, (".hpp", ".h")) + _all_sources(INC_DIR, (".h", ".hpp")) + _all_sources(CSRC_DIR, (".h", ".hpp"))
+    deps = (srcs + _all_sources(HOST_DIR, (".hpp", ".h")) + _all_sources(INC_DIR, (".h", ".hpp", ".hh")) + _all_sources(CSRC_DIR, (".h", ".hpp"))
             + _all_sources(os.path.join(PKG, "rccl"), (".h",)))
     if force or _newer(HOST_LIB, deps):
         _run(["g++"] + HOST_FLAGS + ["-I", INC_DIR, "-I", CSRC_DIR, "-o", HOST_LIB] + srcs + ["-lz"])  # libz: PNG inflate
@@ -89,7 +89,7 @@ def build_hip(force=False, out=None, defines=()):
     out = out or HIP_LIB
     srcs = _all_sources(CSRC_DIR, (".hip",))
     host_srcs = [os.path.join(HOST_DIR, "grid_build.cpp")]
-    deps = srcs + host_srcs + _all_sources(CSRC_DIR, (".h", ".hpp")) + _all_sources(INC_DIR, (".h", ".hpp")) + [os.path.abspath(__file__)]  # (the flags live here)
+    deps = srcs + host_srcs + _all_sources(CSRC_DIR, (".h", ".hpp")) + _all_sources(INC_DIR, (".h", ".hpp", ".hh")) + [os.path.abspath(__file__)]  # (the flags live here)
     if not (force or _newer(out, deps)):
         return out
     import concurrent.futures
@@ -263,6 +263,14 @@ RESOURCE_BOUNDS = {
     # LDS in any of them (a substring: init, minmax, keys, gather, cells, max_cell, the three query forms, median) — the
     # figures travel through cross-lane reads and integer atomics
     "k18_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 0},
+    # the edge maps of the source images (eg3d_edge_maps): no spilled register and no scratch in any of them (a substring:
+    # smooth and classify in their two source forms, hysteresis, mask). LDS as the build reports it: smooth 3 600 B (the staged
+    # 36 x 36 tile and its 36 x 32 horizontal sums), hysteresis 1 488 B, mask 4 B, and the largest, classify: 10 552 B (the
+    # staged tile, the magnitudes and the Sobel pairs of 34 x 34 pixels, two counts)
+    "k19_": {"vgpr_spill_count": 0, "sgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 10552},
+    "k19_smooth": {"group_segment_fixed_size": 3600},
+    "k19_hysteresis": {"group_segment_fixed_size": 1488},
+    "k19_mask": {"group_segment_fixed_size": 4},
     # single-pass K2: no spills, no scratch; LDS = the four waves' stages of EG3D_K2_STAGE_MAX (128) 16-byte hits
     # + the workgroup's claim (four counts and the base)
     "k2_epipolar_hits": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "group_segment_fixed_size": 8216},

@@ -653,6 +653,47 @@ def png_edge_mask(path):
     return m
 
 
+def edge_maps(images, low, high, smooth_passes=1, l2=False, device=0):
+    """The host statement of api.edge_maps (eg3d_host_edge_maps): the same arguments (`device` has no meaning here), the
+    same return shape, the same bits — without a GPU."""
+    rc, out = D.edgemap_call(lib().eg3d_host_edge_maps, images, low, high, smooth_passes, l2)
+    if rc != 0:
+        raise RuntimeError("eg3d_host_edge_maps failed (%d): %s" % (rc, lib().eg3d_host_edgemap_last_error().decode()))
+    return out
+
+
+def write_png_mask(path, mask):
+    """A mask (uint8 [H, W], non-zero = edge) as a 1-bit greyscale PNG, white = edge (eg3d_host_png_write_mask): what
+    png_edge_mask and the N2 builder read."""
+    m = np.ascontiguousarray(mask, np.uint8)
+    if m.ndim != 2:
+        raise ValueError("a mask must be [H, W], not %r" % (m.shape,))
+    rc = lib().eg3d_host_png_write_mask(os.fsencode(path), D.np_ptr(m, C.c_uint8), m.shape[1], m.shape[0])
+    if rc != 0:
+        raise RuntimeError("eg3d_host_png_write_mask(%s) failed (%d): %s" % (path, rc, lib().eg3d_host_edgemap_last_error().decode()))
+
+
+def plg_views_from_masks(masks):
+    """The polyline graphs of many masks at once (eg3d_host_plg_build_views_from_masks), built concurrently on the host's
+    cores: a list with what plg_from_mask returns for each mask."""
+    ms = [np.ascontiguousarray(m, np.uint8) for m in masks]
+    for m in ms:
+        if m.ndim != 2:
+            raise ValueError("a mask must be [H, W], not %r" % (m.shape,))
+    n = len(ms)
+    w = np.array([m.shape[1] for m in ms], np.int32)
+    h = np.array([m.shape[0] for m in ms], np.int32)
+    ptrs = (D.u8p * max(n, 1))(*[D.np_ptr(m, C.c_uint8) for m in ms])
+    views = (D.PlgView * max(n, 1))()
+    rc = lib().eg3d_host_plg_build_views_from_masks(ptrs, n, D.np_ptr(w, C.c_int32), D.np_ptr(h, C.c_int32), views)
+    if rc != 0:
+        raise RuntimeError("eg3d_host_plg_build_views_from_masks failed (%d): %s" % (rc, lib().eg3d_host_edgemap_last_error().decode()))
+    out = [D.plg_view_to_dict(views[v]) for v in range(n)]
+    for v in range(n):
+        lib().eg3d_plg_view_free(C.byref(views[v]))
+    return out
+
+
 def build_grid(scene_ptr, view, cell_dim):
     ncols, nrows, dropped = C.c_uint32(), C.c_uint32(), C.c_uint32()
     off, ids = D.u32p(), D.u32p()

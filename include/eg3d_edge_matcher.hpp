@@ -14,7 +14,9 @@
 //                                            the size comes from the SfM data's intrinsics
 //   parse_images(input_edges_folder)         + convert_edge_images_to_optimized_polyline_graphs (edge_matcher.cpp:84):
 //                                            eg3d_plg_build_from_png per view (row N2), -1 when an edge image is
-//                                            missing or unreadable
+//                                            missing or unreadable; with edge_matching_options().detect_edges the edge
+//                                            maps are detected on the device from the photographs instead (K19) and the
+//                                            edge folder is never opened
 //   generate_all_fundamental_matrices        pairs of views with >= 10 common points get a matrix (the reference's rule,
 //                                            exact); the matrix itself is analytic from the cameras of sfm_data_file by
 //                                            default, or the build's own LMedS estimate from the tracks when
@@ -39,6 +41,8 @@
 #include <vector>
 
 #include "eg3d_refapi.hpp"
+#include "eg3d_host_colour.h" /* eg3d_host_png_read_rgb: the photographs of detect_edges */
+#include "eg3d/edgemap.hh"    /* eg3d_edge_maps (K19) and, through it, the PNG writer and the graphs of many masks */
 
 namespace eg3d_ref {
 
@@ -91,6 +95,14 @@ struct EdgeMatchingOptions {
   // 65,175). Pipeline 3's cloud then comes first in the output, pipelines 1-2's behind it. Off by default: the reference's
   // order (1, 2, 3 — the manager is empty while pipelines 1-2 run) and the output of earlier builds.
   bool refpoints_first = false;
+  // detect_edges = true: the edge maps are not read from input_edges_folder (which is never opened) but detected on
+  // `device` from the photographs of images_folder (eg3d_edge_maps, K19: include/eg3d/host_edgemap.hh states the rules), with
+  // the bounds edge_low <= edge_high on |gx| + |gy| after edge_smooth_passes smoothing passes; the polyline graphs are built
+  // from those masks, and with em_out_folder set the maps are also written there as 1-bit PNG under the photographs' file
+  // names — a folder a later call can use as input_edges_folder. The photographs must be PNG (eg3d_host_png_read_rgb) and of
+  // one size. Off by default: the call behaves as before.
+  bool detect_edges = false;
+  int edge_low = 40, edge_high = 100, edge_smooth_passes = 1;
   bool quiet = false;
   int skipped_pipelines = 0;  // bit 0: pipeline 1 (similarity graph), bit 1: pipeline 2 (closeness to refpoints) [out]
 };
@@ -147,6 +159,23 @@ inline SfMData sfmdata_from_handle(const eg3d_sfm* h) {
   }
   return s;
 }
+// the per-view graphs of the N2 builder as the shim's type; the views are released
+inline void take_plg_views(std::vector<eg3d_plg_view>& views, std::vector<PolyLineGraph2D>& plgs) {
+  for (size_t v = 0; v < views.size(); v++) {
+    eg3d_plg_view& g = views[v];
+    PolyLineGraph2D& out = plgs[v];
+    out.polylines.resize(g.n_polylines);
+    for (uint32_t p = 0; p < g.n_polylines; p++) {
+      out.polylines[p].start = g.pl_start[p];
+      out.polylines[p].end = g.pl_end[p];
+      for (uint32_t k = g.pl_vtx_off[p]; k < g.pl_vtx_off[p + 1]; k++)
+        out.polylines[p].polyline_coords.push_back(vec2{g.vtx_xy[2 * k], g.vtx_xy[2 * k + 1]});
+    }
+    out.nodes_coords.resize(g.n_nodes);
+    for (uint32_t n = 0; n < g.n_nodes; n++) out.nodes_coords[n] = vec2{g.node_xy[2 * n], g.node_xy[2 * n + 1]};
+    eg3d_plg_view_free(&g);
+  }
+}
 }  // namespace detail
 
 // read_sfm_data (io/input/input_reader: OpenMvgParser::parse, OpenMvgParser.cpp:39-301); throws Eg3dError when the file
@@ -193,20 +222,58 @@ inline bool convert_edge_images_to_optimized_polyline_graphs(const char* input_e
   for (const std::string& p : paths) cpaths.push_back(p.c_str());
   std::vector<eg3d_plg_view> views((size_t)sfmd.numCameras_);
   if (eg3d_plg_build_views_from_png(cpaths.data(), sfmd.numCameras_, &width, &height, views.data()) != 0) return false;
-  for (int v = 0; v < sfmd.numCameras_; v++) {
-    eg3d_plg_view& g = views[(size_t)v];
-    PolyLineGraph2D& out = plgs[(size_t)v];
-    out.polylines.resize(g.n_polylines);
-    for (uint32_t p = 0; p < g.n_polylines; p++) {
-      out.polylines[p].start = g.pl_start[p];
-      out.polylines[p].end = g.pl_end[p];
-      for (uint32_t k = g.pl_vtx_off[p]; k < g.pl_vtx_off[p + 1]; k++)
-        out.polylines[p].polyline_coords.push_back(vec2{g.vtx_xy[2 * k], g.vtx_xy[2 * k + 1]});
+  detail::take_plg_views(views, plgs);
+  return true;
+}
+
+// The same graphs from the photographs: the edge maps detected on the device (edge_matching_options().detect_edges), the
+// graphs built from the masks on the host's cores. false when a photograph cannot be read as PNG, the photographs differ in
+// size, the detection fails, or a map cannot be written to em_out_folder (or would overwrite its photograph).
+inline bool detect_edge_maps_to_optimized_polyline_graphs(const char* images_folder, const char* em_out_folder, const SfMData& sfmd,
+                                                          std::vector<PolyLineGraph2D>& plgs, int& width, int& height) {
+  const EdgeMatchingOptions& o = edge_matching_options();
+  const int V = sfmd.numCameras_;
+  plgs.clear();
+  plgs.resize((size_t)V);
+  width = height = 0;
+  if (!images_folder || V <= 0) return false;
+  struct Photographs {
+    std::vector<uint8_t*> rgb;
+    ~Photographs() {
+      for (uint8_t* p : rgb) eg3d_host_free(p);
     }
-    out.nodes_coords.resize(g.n_nodes);
-    for (uint32_t n = 0; n < g.n_nodes; n++) out.nodes_coords[n] = vec2{g.node_xy[2 * n], g.node_xy[2 * n + 1]};
-    eg3d_plg_view_free(&g);
+  } photos;
+  photos.rgb.assign((size_t)V, nullptr);
+  std::vector<int32_t> w((size_t)V, 0), h((size_t)V, 0);
+  for (int v = 0; v < V; v++) {
+    int wv = 0, hv = 0;
+    if (eg3d_host_png_read_rgb(detail::join_path(images_folder, sfmd.camerasPaths_[(size_t)v]).c_str(), &wv, &hv, &photos.rgb[(size_t)v]) != 0) return false;
+    w[(size_t)v] = wv;
+    h[(size_t)v] = hv;
+    if (wv != w[0] || hv != h[0]) return false;
   }
+  std::vector<std::vector<uint8_t>> masks((size_t)V, std::vector<uint8_t>((size_t)w[0] * (size_t)h[0]));
+  std::vector<uint8_t*> mask_ptrs;
+  for (std::vector<uint8_t>& m : masks) mask_ptrs.push_back(m.data());
+  eg3d_edgemap_params p;
+  std::memset(&p, 0, sizeof p);
+  p.struct_size = (uint32_t)sizeof p;
+  p.low = o.edge_low;
+  p.high = o.edge_high;
+  p.smooth_passes = o.edge_smooth_passes;
+  const int rc = eg3d_edge_maps(o.device, V, w.data(), h.data(), photos.rgb.data(), &p, mask_ptrs.data(), nullptr);
+  if (rc != EG3D_OK) throw Eg3dError(rc, std::string("edge_matching: ") + eg3d_last_error());
+  if (em_out_folder && em_out_folder[0])
+    for (int v = 0; v < V; v++) {
+      const std::string out = detail::join_path(em_out_folder, sfmd.camerasPaths_[(size_t)v]);
+      if (out == detail::join_path(images_folder, sfmd.camerasPaths_[(size_t)v])) return false;
+      if (eg3d_host_png_write_mask(out.c_str(), mask_ptrs[(size_t)v], w[0], h[0]) != 0) return false;
+    }
+  std::vector<eg3d_plg_view> views((size_t)V);
+  if (eg3d_host_plg_build_views_from_masks(mask_ptrs.data(), V, w.data(), h.data(), views.data()) != 0) return false;
+  detail::take_plg_views(views, plgs);
+  width = w[0];
+  height = h[0];
   return true;
 }
 
@@ -331,7 +398,11 @@ inline int edge_matching(edge_matcher_input_params& emip, SfMData& sfm_data) {
     }
   std::vector<PolyLineGraph2D> plgs;
   int w = 0, h = 0;
-  if (!convert_edge_images_to_optimized_polyline_graphs(emip.input_edges_folder, sfm_data, plgs, w, h)) return -1;
+  if (edge_matching_options().detect_edges) {
+    if (!detect_edge_maps_to_optimized_polyline_graphs(emip.images_folder, emip.em_out_folder, sfm_data, plgs, w, h)) return -1;
+  } else if (!convert_edge_images_to_optimized_polyline_graphs(emip.input_edges_folder, sfm_data, plgs, w, h)) {
+    return -1;
+  }
   if (sfm_data.imageWidth_ <= 0 || sfm_data.imageHeight_ <= 0) {
     sfm_data.imageWidth_ = w;
     sfm_data.imageHeight_ = h;
